@@ -1,7 +1,12 @@
 """bench.py — BASELINE.json metric: training images/sec, DDPM UNet 32x32, global batch 128.
 
-    python bench.py --gpus N --steps K --warmup W [--workload ddpm32|ddpm64|wgan_gp64|vqvae] [--only]
+    python bench.py --gpus N --steps K --warmup W [--workload ddpm32|ddpm64|wgan_gp64|vqvae] [--only] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+``--dump-outputs DIR``: right after the timed region, rank 0 writes what the timed path computed in its last step - the
+loss (logs) a caller of the step receives and the model state the step left behind (``state_dict()`` order and shapes,
+flattened; a fixed, seeded sample of a larger one) - as DIR/<name>.npy in float32, at most 64 MiB.  Inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 
 Without a launcher in the environment ``--gpus N`` (N > 1) makes this process the parent of N ranks (lgm_hip/launch.py:
 one torch.distributed.run child, started before any GPU call; rank 0's line is relayed, the exit code is the ranks').
@@ -70,6 +75,33 @@ def mfma_factor(kernel_name: str) -> float:
         return WINO_FACTOR
     return 1.0
 HBM_PEAK = 8.0e12               # bytes / s (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: everything written, at most
+DUMP_SAMPLE = 1 << 22           # ... elements kept of a larger state vector (a fixed, seeded sample)
+
+
+def _state_vector(module):
+    """A module's floating-point state as its caller sees it (state_dict order, logical shapes) as one flat vector."""
+    return torch.cat([v.detach().reshape(-1).float() for v in module.state_dict().values() if v.is_floating_point()])
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy (float32); a vector longer than DUMP_SAMPLE is replaced by the same seeded
+    sample of its elements (sorted indices, seed 0) in every run."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            t = t.reshape(-1)
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t[idx.to(t.device)]
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    print(f"[bench] --dump-outputs: {len(host)} arrays, {total / 2**20:.1f} MiB -> {path}", file=sys.stderr, flush=True)
 
 
 def _conv_work(module, batch):
@@ -258,7 +290,10 @@ def setup_ddpm(args, dev, world, rank, img, global_batch):
         return eager.step((x, y), i)
     def work():     # forward x 3; bytes per image + (weights x 3, Adam 28 B/param, EMA / 10) per step
         return {32: 10.95e9, 64: 43.8e9}[img], (69.6e6 if img == 32 else 278e6), 1.472e9, {}
-    info = dict(per_gpu=per_gpu, fast=fast, work=work, n_instr=1, model=model,
+    def outputs(loss):
+        return {"loss": loss, "params": _state_vector(model.ema.online_model.model),
+                "ema_params": _state_vector(model.ema.ema_model.model)}
+    info = dict(per_gpu=per_gpu, fast=fast, work=work, n_instr=1, model=model, outputs=outputs,
                 workload=f"configs/diffusion/{'ddpm' if img == 32 else 'ddpm_64'}.json UNet dim=64, 3x{img}x{img} synthetic "
                          "NCHW fp32, training_step+backward+Adam+EMA")
     return step, eager_step, info
@@ -282,9 +317,10 @@ def setup_wgan(args, dev):
         # which `--warmup 5` would put - with its capture - inside the timed region
         for key in ("d", "g"):
             fast._capture(key, x)
+    last = {}
 
     def step(i):
-        ld = fast.step((x, None), i)
+        ld = last["logs"] = fast.step((x, None), i)
         return ld.get("d_loss", ld.get("g_loss"))
 
     def eager_step(i):
@@ -316,7 +352,10 @@ def setup_wgan(args, dev):
         return flop, byts, per_step, dict(G_fwd_gflop=round(2 * G / 1e9, 4), D_fwd_gflop=round(2 * D / 1e9, 4),
                                           critic_update_gflop=round(2 * critic / 1e9, 4),
                                           generator_update_gflop=round(2 * gen / 1e9, 4))
-    info = dict(per_gpu=B, fast=fast, work=work, n_instr=6,
+    def outputs(loss):      # the update's logs (critic OR generator losses), then both networks
+        return {**{k: v for k, v in last["logs"].items() if torch.is_tensor(v)},
+                "generator": _state_vector(m.G), "critic": _state_vector(m.D)}
+    info = dict(per_gpu=B, fast=fast, work=work, n_instr=6, outputs=outputs,
                 workload="configs/gan/wgan_gp_celeba.json WGAN-GP DCGAN G/D, 3x64x64 synthetic, training_step "
                          "(n_critic = 5: one critic OR generator update incl. GP double backward) + fused Adam")
     return step, eager_step, info
@@ -355,15 +394,18 @@ def setup_vqvae(args, dev, ema):
         return 2.0 * macs, byts, n_params * (4 * 3 + 28.0), dict(
             encoder_fwd_mflop=round(2 * sum(a for a, _ in el) / 1e6, 3), decoder_fwd_mflop=round(2 * sum(a for a, _ in dl) / 1e6, 3),
             quantiser_mflop_per_step=round(2 * 2 * B * n_lat * K * D / 1e6, 1))
-    info = dict(per_gpu=B, fast=fast, work=work, n_instr=1,
+    def outputs(loss):
+        return {"loss": loss, "params": _state_vector(v)}
+    info = dict(per_gpu=B, fast=fast, work=work, n_instr=1, outputs=outputs,
                 workload=f"configs/vae/vqvae{'_ema' if ema else ''}.json VQ-VAE 3x32x32, K=512 D=64, "
                          "training_step+backward+Adam")
     return step, eager_step, info
 
 
-def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, roofline=True, cpu=True):
+def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, roofline=True, cpu=True, dump=None):
     """Warm-up, the timed region (barrier + synchronize on both sides, max over ranks), the instrumented roofline
-    step and the CPU baseline of ONE workload.  Returns the workload's JSON object (rank 0) or None."""
+    step and the CPU baseline of ONE workload.  Returns the workload's JSON object (rank 0) or None.
+    ``dump``: directory for the outputs of the last timed step (dump_outputs), written before any further step."""
     from lgm_hip import ops
     torch.manual_seed(10)                         # reference train.py:20 seeds every rank identically
     if wl in ("ddpm32", "ddpm64"):
@@ -403,6 +445,8 @@ def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, roofline
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     final_loss = float(loss.item()) if loss is not None else float("nan")
+    if dump is not None and rank == 0:
+        dump_outputs(dump, info["outputs"](loss))
     ms = elapsed / steps * 1e3
     value = gb * steps / elapsed
     # N > 1: a few more steps (outside the timed region) with HIP events around the waits for the gradient exchange - how
@@ -671,7 +715,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="global batch (default: the workload's config value)")
     ap.add_argument("--torch-gpu-baseline", action="store_true",
                     help="also time the oracle's plain torch ops on the GPU (PyTorch-ROCm eager) as a comparison point")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, model state) as DIR/<name>.npy, float32, <= 64 MiB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.vq_ema and args.workload == "vqvae":
         args.workload = "vqvae_ema"
 
@@ -730,7 +778,8 @@ def main():
             os._exit(3)
 
     single = world == 1 and not args.only and args.workload == "ddpm32" and args.batch is None
-    line = run_workload(args.workload, args, dev, world, rank, args.steps, args.warmup, batch=args.batch)
+    line = run_workload(args.workload, args, dev, world, rank, args.steps, args.warmup, batch=args.batch,
+                        dump=args.dump_outputs)
     rc = 0
     if single and rank == 0:
         # The headline exists now: put it on record (stderr + gpurun_out/) BEFORE any secondary leg runs, so that a hard

@@ -632,3 +632,37 @@ def test_counter_summary_counts_steady_state_steps_only(tmp_path):
     assert k["fetch_bytes_per_launch"] == 1000 * 2048 and k["write_bytes_per_launch"] == 400 * 1024
     assert not any("fill_kernel" in n for n in d["kernels"])
     assert d["step_total"]["fetch_bytes"] == (2 * 1000 + 100) * 2048 and d["step_total"]["write_bytes"] == (2 * 400 + 100) * 1024
+
+
+_DUMP_WORKER = r'''
+import sys
+import torch
+sys.path.insert(0, sys.argv[1])
+import bench
+v = torch.arange(bench.DUMP_SAMPLE + 12345, dtype=torch.float64)
+for d in ("a", "b"):
+    bench.dump_outputs(sys.argv[2] + "/" + d, {"loss": torch.tensor([0.25]), "params": v})
+print(bench.DUMP_SAMPLE, bench.DUMP_MAX_BYTES)
+try:    # more than the cap in all: refused before anything is written
+    bench.dump_outputs(sys.argv[2] + "/big", {f"v{i}": v for i in range(5)})
+except AssertionError:
+    print("refused")
+'''
+
+
+def test_bench_dump_outputs_and_step_count_checks(tmp_path):
+    """bench.py --dump-outputs writes float32 .npy files, at most 64 MiB in all; a longer vector is replaced by the same
+    seeded sample of its elements (sorted, distinct) in every run.  --steps below 1 is refused before any GPU work."""
+    import numpy as np
+    r = subprocess.run([sys.executable, "-c", _DUMP_WORKER, ROOT, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    sample, cap = map(int, r.stdout.split()[:2])
+    assert cap == 64 << 20 and "refused" in r.stdout and not (tmp_path / "big").exists()
+    a, b = (np.load(str(tmp_path / d / "params.npy")) for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (sample,) and np.array_equal(a, b)
+    assert (np.diff(a) > 0).all() and a[-1] < sample + 12345          # elements of the vector, in order, no repeats
+    loss = np.load(str(tmp_path / "a" / "loss.npy"))
+    assert loss.dtype == np.float32 and loss.tolist() == [0.25]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
