@@ -1577,6 +1577,11 @@ static bool wgradn_supported(int n, const LgmConvGeom* const* gs) {
     for (int k = 0; k < n; ++k) all4 = all4 && gs[k] && lgm_wino4_wgrad_use(gs[k]);
     if (all4) return false;
   }
+  // a 4 x 4 layer on the F(4x4) kernel (groups of four images' tiles) shares that launch with layers of any map size: the
+  // F(2x2) map-class rule below is for the F(2x2) grouped launch
+  if (wgradn_use4(n, gs))
+    for (int k = 0; k < n; ++k)
+      if (gs[k]->H == 4 && gs[k]->W == 4) return true;
   for (int k = 0; k < n; ++k) {
     if (!gs[k] || !lgm_wino_wgrad_supported(gs[k])) return false;
     int G, ipc;

@@ -9,7 +9,7 @@
 // arithmetic fp32 with fp32 accumulation (error against float64 a few 1e-6 of the output scale: tests/test_hip_winograd.py).
 //
 // Work decomposition.  UNIT = 32 tiles (4 x 8 tiles = 16 x 32 output pixels of one image; on 16 x 16 maps 4 x 4 tiles of two
-// images) x 64 output channels x one split of the reduction; PHASE = 8 reduction channels.  512 threads = 8 waves, two
+// images, on 8 x 8 maps 2 x 2 tiles of eight, on 4 x 4 maps the one tile of each of 32 images) x 64 output channels x one split of the reduction; PHASE = 8 reduction channels.  512 threads = 8 waves, two
 // per SIMD, 144 accumulator registers each:
 //   * transform role: thread = (tile, reduction channel, half of the 6 rows of V): reads its 6x6 raw values from the
 //     channel-planar LDS patch (plane stride = 1 mod 32 floats: conflict-free), computes 18 elements of V = B^T d B and
@@ -76,6 +76,12 @@ template <>
 struct Geo<2> {   // 8 x 8 maps: 2 x 2 tiles of eight images; 4 RS = 8, IMG = 16 (mod 32): a wave's 2 x 2 x 2 (tx, ty, image)
   static constexpr int NI = 8, TTH = 2, TTW = 2, PH = 10, PW = 10, RS = 10, IMG = 112, PLANE = 897;   // tiles on 8 banks apart
 };
+template <>
+struct Geo<3> {   // 4 x 4 maps: one tile per image, 32 images.  The 6 x 6 patch IS the zero-padded image: only its 4 x 4
+  // interior is stored (PH = PW = 4, no halo) and the transform supplies the zero ring itself.  IMG = 20 = 4 x odd (mod 32):
+  // a half-wave's eight images start 4 banks apart (0, 20, 8, 28, 16, 4, 24, 12), its four channels fill the gaps
+  static constexpr int NI = 32, TTH = 1, TTW = 1, PH = 4, PW = 4, RS = 4, IMG = 20, PLANE = 641;
+};
 
 struct Args {
   const float* a;      // gathered activations, NHWC
@@ -138,6 +144,7 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
   constexpr int RBUF = 8 * PLANE;
   constexpr int NPIX = NI * PH * PW;
   constexpr int NJ = (2 * NPIX + 511) / 512;
+  constexpr int HALO = CLS == 3 ? 0 : 1;      // class 3 stores the interior only (Geo<3>)
   extern __shared__ __align__(16) float smem[];
   float* const Rb = smem;                   // [2][8 planes][PLANE]
   float* const Vb = smem + 2 * RBUF;        // [2][VBUF]
@@ -207,7 +214,7 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
       const int img = pix / (PH * PW);
       const int rem = pix - img * (PH * PW);
       const int py = rem / PW, px = rem - py * PW;
-      const int gy = h0 - 1 + py, gx = w0 - 1 + px;
+      const int gy = h0 - HALO + py, gx = w0 - HALO + px;
       l = (unsigned)(q * 4 * PLANE + img * IMG + py * RS + px);
       if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
         g = (unsigned)((((long)(b0 + img) * p.H + gy) * p.W + gx) * p.a_pitch + q * 4) * 4u;
@@ -252,11 +259,16 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
     t_ty = 2 * (wid & 1) + ((lane >> 4) & 1);
     t_tx = (lane >> 2) & 3;
     t_tile = t_img * 16 + t_ty * 4 + t_tx;
-  } else {
+  } else if (CLS == 2) {
     t_img = 2 * (wid & 3) + ((lane >> 4) & 1);
     t_ty = (lane >> 3) & 1;
     t_tx = (lane >> 2) & 1;
     t_tile = t_img * 4 + t_ty * 2 + t_tx;
+  } else {
+    t_img = 8 * (wid & 3) + ((lane >> 2) & 7);
+    t_ty = 0;
+    t_tx = 0;
+    t_tile = t_img;
   }
   const int trd = tk * PLANE + t_img * IMG + 4 * t_ty * RS + 4 * t_tx;
   const int vwr = (tk >> 2) * 128 + t_tile * 4 + (tk & 3) + half * (18 * 256);
@@ -319,6 +331,29 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
     asm volatile("" : "+v"(roff1));
     auto stage1 = [&](int nxt, int cp) {
       const float* r = smem + (nxt ? roff1 : roff0);
+      if constexpr (CLS == 3) {
+        // patch rows 0 and 5 and columns 0 and 5 are the padding: zeros, never stored.  Patch (row rr, column c) is the
+        // interior value (rr - 1, c - 1); the column pairs (0, 1) and (4, 5) carry a zero lane that stage 2 never reads.
+        // Each expression is the general one below with the zero terms dropped (fma(4, 0, z) = z): same values.
+        f32x2 d[5];
+#pragma unroll
+        for (int rr = 1; rr < 5; ++rr) {
+          const float* q = r + (rr - 1) * RS;
+          d[rr] = cp == 0 ? f32x2{0.f, q[0]} : cp == 1 ? f32x2{q[1], q[2]} : f32x2{q[3], 0.f};
+        }
+        if (HALF == 0) {
+          T[0][cp] = fma2(-5.f, d[2], d[4]);
+          const f32x2 a = fma2(-4.f, d[2], d[4]), b = fma2(-4.f, d[1], d[3]);
+          T[1][cp] = a + b;
+          T[2][cp] = a - b;
+        } else {
+          const f32x2 c = d[4] - d[2], f = d[3] - d[1];
+          T[0][cp] = fma2(2.f, f, c);
+          T[1][cp] = fma2(-2.f, f, c);
+          T[2][cp] = fma2(4.f, d[1], d[3] * -5.f);
+        }
+        return;
+      }
       f32x2 d[6];
 #pragma unroll
       for (int rr = 0; rr < 6; ++rr)
@@ -340,6 +375,20 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
     auto stage2 = [&](float* vbuf, int i, int part) {  // row i of the half, columns 0-2 (part 0) / 3-5 (part 1)
       float* v = vbuf + vwr + i * (6 * 256);
       const float t0 = T[i][0][0], t1 = T[i][0][1], t2 = T[i][1][0], t3 = T[i][1][1], t4 = T[i][2][0], t5 = T[i][2][1];
+      if constexpr (CLS == 3) {                      // columns 0 and 5 are the padding (t0 = t5 = 0)
+        if (part == 0) {
+          const float a = __builtin_fmaf(-4.f, t2, t4), b = __builtin_fmaf(-4.f, t1, t3);
+          v[0 * 256] = __builtin_fmaf(-5.f, t2, t4);
+          v[1 * 256] = a + b;
+          v[2 * 256] = a - b;
+        } else {
+          const float c = t4 - t2, f = t3 - t1;
+          v[3 * 256] = __builtin_fmaf(2.f, f, c);
+          v[4 * 256] = __builtin_fmaf(-2.f, f, c);
+          v[5 * 256] = __builtin_fmaf(4.f, t1, t3 * -5.f);
+        }
+        return;
+      }
       if (part == 0) {
         const float a = __builtin_fmaf(-4.f, t2, t4), b = __builtin_fmaf(-4.f, t1, t3);
         v[0 * 256] = __builtin_fmaf(4.f, t0, __builtin_fmaf(-5.f, t2, t4));
@@ -436,10 +485,14 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
       e_img = et >> 4;
       e_ty = (et >> 2) & 3;
       e_tx = et & 3;
-    } else {
+    } else if (CLS == 2) {
       e_img = et >> 2;
       e_ty = (et >> 1) & 1;
       e_tx = et & 1;
+    } else {
+      e_img = et;
+      e_ty = 0;
+      e_tx = 0;
     }
     const long opix = ((long)(b0 + e_img) * p.H + h0 + 4 * e_ty) * p.W + w0 + 4 * e_tx;
     const bool partial = p.splits > 1;
@@ -644,10 +697,11 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float* __restr
 }
 
 static long unit_count(int cls, int B, int H, int W) {     // units per 64 produced channels, before split-K
-  return cls == 1 ? B / 2 : cls == 2 ? B / 8 : (long)B * (H / 16) * (W / 32);
+  return cls == 1 ? B / 2 : cls == 2 ? B / 8 : cls == 3 ? B / 32 : (long)B * (H / 16) * (W / 32);
 }
 
 static int unit_class(int H, int W) {
+  if (H == 4 && W == 4) return 3;
   if (H == 8 && W == 8) return 2;
   if (H == 16 && W == 16) return 1;
   if (H >= 16 && W >= 32 && H % 16 == 0 && W % 32 == 0) return 0;
@@ -676,6 +730,12 @@ static std::atomic<int> lgm_wino4_light_override{-1};   // lgm_wino4_set_light: 
 extern "C" int lgm_wino4_set_light(int mode) {
   lgm_wino4_light_override.store(mode, std::memory_order_relaxed);
   return LGM_OK;
+}
+static bool wino4_light_asked() {      // light workgroups requested for every launch they take (see wino4_use_light)
+  static const bool env_given = getenv("LGM_WINO4_LIGHT") != nullptr;
+  static const int env_mode = env_given ? atoi(getenv("LGM_WINO4_LIGHT")) : 0;
+  const int ov = lgm_wino4_light_override.load(std::memory_order_relaxed);
+  return (ov >= 0 ? ov : env_mode) != 0;
 }
 static bool wino4_use_light(const LgmConvGeom* g, int gather_channels, int out_channels) {
   // The environment is read ONCE.  No rule reads WORLD_SIZE any more (round 6): being one rank of several does
@@ -720,7 +780,7 @@ static bool wino4_big_supported(const LgmConvGeom* g, int gather_channels, int o
   const long pix = (long)g->B * g->H * g->W + g->W + 1;
   if (pix * gather_channels >= (1L << 29) || pix * out_channels >= (1L << 29)) return false;
   if ((long)gather_channels * out_channels * 36 >= (1L << 29)) return false;
-  return g->B % (cls == 1 ? 2 : cls == 2 ? 8 : 1) == 0;
+  return g->B % (cls == 1 ? 2 : cls == 2 ? 8 : cls == 3 ? 32 : 1) == 0;
 }
 
 // Split count of an F(4x4) launch with `base` workgroups per split on `slots` workgroup slots.  A workgroup has the CU to
@@ -791,7 +851,7 @@ int lgm_wino4_launch(const LgmConvGeom* g, int yx, const float* a, long a_pitch,
   const int cls = unit_class(g->H, g->W);
   p.tb_h = cls == 0 ? g->H / 16 : 1;
   p.tb_w = cls == 0 ? g->W / 32 : 1;
-  p.nbg = cls == 1 ? g->B / 2 : cls == 2 ? g->B / 8 : g->B;
+  p.nbg = cls == 1 ? g->B / 2 : cls == 2 ? g->B / 8 : cls == 3 ? g->B / 32 : g->B;
   p.tiles_n = p.N / 64;
   const long M = (long)g->B * g->H * g->W;
   p.splits = lgm_wino4_splits(g, p.C, p.N);
@@ -831,11 +891,12 @@ int lgm_wino4_launch(const LgmConvGeom* g, int yx, const float* a, long a_pitch,
     hipLaunchKernelGGL(kern, dim3((unsigned)p.units), dim3(512), smem, s, p);                                   \
   } while (0)
   lgm_note_kernel(cls == 0 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<0, false, 0, false>") : cls == 1 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<1, false, 0, false>")
-                                                                                    : LGM_KNAME("lgmwino4::wino4_conv_kernel<2, false, 0, false>"));
+                  : cls == 2 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<2, false, 0, false>") : LGM_KNAME("lgmwino4::wino4_conv_kernel<3, false, 0, false>"));
   if (p.dbg) {
     const int e = lgm_wino4_debug_exp;
     if (cls == 1) LGM_W4LAUNCH(1, true, 0);
     else if (cls == 2) LGM_W4LAUNCH(2, true, 0);
+    else if (cls == 3) LGM_W4LAUNCH(3, true, 0);
     else if (e == 0) LGM_W4LAUNCH(0, true, 0);
     else if (e == 1) LGM_W4LAUNCH(0, true, 1);
     else if (e == 2) LGM_W4LAUNCH(0, true, 2);
@@ -859,7 +920,8 @@ int lgm_wino4_launch(const LgmConvGeom* g, int yx, const float* a, long a_pitch,
     hipLaunchKernelGGL(kern, dim3((unsigned)p.units), dim3(512), smem, s, p);
   } else if (cls == 0) LGM_W4LAUNCH(0, false, 0);
   else if (cls == 1) LGM_W4LAUNCH(1, false, 0);
-  else LGM_W4LAUNCH(2, false, 0);
+  else if (cls == 2) LGM_W4LAUNCH(2, false, 0);
+  else LGM_W4LAUNCH(3, false, 0);
 #undef LGM_W4LAUNCH
   if (partial) {
     partial[0] = p.splits;
@@ -921,7 +983,18 @@ extern "C" int64_t lgm_conv3x3_wino4_preferred(const LgmConvGeom* g, int yx) {
   const long min_units0 = min_units0_env >= 0 ? min_units0_env : (wino4_use_light(g, gc, oc) ? 32 : 128);
   const long min_units1 = min_units1_env >= 0 ? min_units1_env : (wino4_use_light(g, gc, oc) ? 32 : 128);
   const bool light = wino4_use_light(g, gc, oc);
-  const int cls = g->H == 8 && g->W == 8 ? 2 : g->H == 16 && g->W == 16 ? 1 : 0;
+  const int cls = g->H == 4 && g->W == 4 ? 3 : g->H == 8 && g->W == 8 ? 2 : g->H == 16 && g->W == 16 ? 1 : 0;
+  if (cls == 3) {
+    // 4 x 4 maps (one tile per image, 32 images per unit): the layer's two directions and its weight gradient switch
+    // together, so the rule reads the NARROWER side of the layer, the same in both directions.  From 32 units of that side
+    // (B = 128 with 512 channels: 8 splits of 8 phases at 512 -> 512, the shape of the 8 x 8 256 -> 256 launches); the
+    // 256-channel layers (16 units) stay on the F(2x2) pair.  No light workgroups on 4 x 4 maps: when they are asked for
+    // (a collective resident beside the launches) the F(2x2) pair keeps these layers.  LGM_WINO4_NO4=1: A/B switch.
+    static const bool no4 = getenv("LGM_WINO4_NO4") != nullptr;
+    const int narrow = gc < oc ? gc : oc;
+    const long units = lgmwino4::unit_count(3, g->B, g->H, g->W) * (narrow / 64);
+    return (!no4 && !wino4_light_asked() && narrow >= 256 && units >= 32) ? 1 : 0;
+  }
   // counted in 32-tile units whichever workgroup size runs: the thresholds keep their meaning
   const long base = light ? lgm_wino4l_units(g, oc) / 2 : lgmwino4::unit_count(cls, g->B, g->H, g->W) * (oc / 64);
   // forward with the light workgroups: LGM_WINO4_FWD_ALL=1 takes every layer they support (tuning knob)

@@ -54,7 +54,8 @@ struct WArgs {
   int grow;            // groups per group row (W / 16, or W / 8 for square groups)
   int trows;           // group rows per image (H / 4, or H / 8)
   int xcd_order;       // 1: sharers of a pixel range on one XCD (see the block decode)
-  int sq;              // group shape: 0 = four tiles in a row (4 x 16 output pixels), 1 = 2 x 2 tiles (8 x 8: the 8 x 8 maps)
+  int sq;              // group shape: 0 = four tiles in a row (4 x 16 output pixels), 1 = 2 x 2 tiles (8 x 8: the 8 x 8 maps),
+                       // 2 = the single tiles of four images (the 4 x 4 maps)
 };
 
 __device__ __forceinline__ f32x4 add4(const f32x4 a, const f32x4 b) { return a + b; }
@@ -145,10 +146,14 @@ __device__ __forceinline__ void wino4_wgrad_body(const WArgs& p, const int bidx)
       }
     }
   };
-  const int gh = p.sq ? 8 : 4, gw = p.sq ? 8 : 16;                          // output pixels of a group
-  auto gpix = [&](const GPos& q) -> long { return ((long)q.b * p.H + gh * q.ty) * p.W + gw * q.gx; };   // the group's first pixel
-  auto tile_row = [&](int tl) { return p.sq ? (tl >> 1) : 0; };             // tile position inside the group, in tiles
-  auto tile_col = [&](int tl) { return p.sq ? (tl & 1) : tl; };
+  const int gh = p.sq == 1 ? 8 : 4, gw = p.sq == 1 ? 8 : p.sq == 2 ? 4 : 16;   // output pixels of a group (per image)
+  // the group's first pixel (4 x 4 maps: group = images 4 b .. 4 b + 3, grow = trows = 1)
+  auto gpix = [&](const GPos& q) -> long {
+    return ((long)(p.sq == 2 ? 4 * q.b : q.b) * p.H + gh * q.ty) * p.W + gw * q.gx;
+  };
+  auto tile_row = [&](int tl) { return p.sq == 1 ? (tl >> 1) : 0; };        // tile position inside the group, in tiles
+  auto tile_col = [&](int tl) { return p.sq == 1 ? (tl & 1) : p.sq == 2 ? 0 : tl; };
+  auto tile_img = [&](int tl) { return p.sq == 2 ? tl : 0; };               // ... and its image (4 x 4 maps)
 
   f32x16 acc[9];
 #pragma unroll
@@ -173,7 +178,8 @@ __device__ __forceinline__ void wino4_wgrad_body(const WArgs& p, const int bidx)
   // =================================== waves 0-3: Yt = A dY A^T ===================================
   auto body_y = [&]() {
     const int tl = wid;                                  // tile of the group
-    const unsigned ylane = (unsigned)((((long)(4 * tile_row(tl)) * p.W + 4 * tile_col(tl)) * p.y_pitch + n0 + lane) * 4);
+    const unsigned ylane =
+        (unsigned)(((((long)tile_img(tl) * p.H + 4 * tile_row(tl)) * p.W + 4 * tile_col(tl)) * p.y_pitch + n0 + lane) * 4);
     const int ywr = (tl >> 1) * 128 + lane * 2 + (tl & 1);
     // two register sets: group ph + 2 is requested at the START of phase ph into the set phase ph - 1 emptied - a whole
     // phase ahead of its use (requested at step 2 of the same set, six steps ahead, the next phase still opened with a wait)
@@ -266,8 +272,9 @@ __device__ __forceinline__ void wino4_wgrad_body(const WArgs& p, const int bidx)
     const int tl = 2 * ((wid >> 1) & 1) + lh;            // tile of the group
     const int c = lr;
     const int trow = tile_row(tl), tcol = tile_col(tl);  // (trow is wave-uniform: tl >> 1 comes from the wave id)
-    const int tlast = p.sq ? 1 : 3;
-    const unsigned xlane = (unsigned)((((long)(4 * trow) * p.W + 4 * tcol) * p.x_pitch + c0 + c) * 4);
+    const int tlast = p.sq == 1 ? 1 : p.sq == 2 ? 0 : 3;
+    const unsigned xlane =
+        (unsigned)(((((long)tile_img(tl) * p.H + 4 * trow) * p.W + 4 * tcol) * p.x_pitch + c0 + c) * 4);
     const int xwr = YB + (tl >> 1) * 64 + c * 2 + (tl & 1) + HALF * (18 * 128);
     constexpr int R0 = HALF ? 1 : 0;                     // the five raw rows this half needs: R0 .. R0 + 4
     float d[5][6];
@@ -470,7 +477,8 @@ bool lgm_wino4_wgrad_supported(const LgmConvGeom* g) {
   if (!(g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1)) return false;
   if (g->Nw % 64 != 0 || g->Cw % 32 != 0) return false;
   const bool row_groups = g->W % 16 == 0 && g->H % 4 == 0, square_groups = g->W % 8 == 0 && g->H % 8 == 0;
-  if (!row_groups && !square_groups) return false;
+  const bool image_groups = g->H == 4 && g->W == 4 && g->B % 4 == 0;
+  if (!row_groups && !square_groups && !image_groups) return false;
   const long groups = (long)g->B * g->H * g->W / 64;
   return groups >= 4;
 }
@@ -513,11 +521,11 @@ static void wino4_wgrad_prepare(const LgmConvGeom* g, const float* y, long y_pit
   p.B = g->B; p.H = g->H; p.W = g->W; p.Nw = g->Nw; p.Cw = g->Cw;
   p.tiles_c = g->Cw / 32;
   p.splits = splits; p.gps = gps; p.total_groups = total;
-  p.sq = (g->W % 16 != 0) ? 1 : 0;
+  p.sq = (g->H == 4 && g->W == 4) ? 2 : (g->W % 16 != 0) ? 1 : 0;
   static const int xcd_order = getenv("LGM_W4W_XCD") ? atoi(getenv("LGM_W4W_XCD")) : 1;
   p.xcd_order = xcd_order;
-  p.grow = p.sq ? g->W / 8 : g->W / 16;
-  p.trows = p.sq ? g->H / 8 : g->H / 4;
+  p.grow = p.sq == 2 ? 1 : p.sq ? g->W / 8 : g->W / 16;
+  p.trows = p.sq == 2 ? 1 : p.sq ? g->H / 8 : g->H / 4;
 }
 
 static constexpr size_t kW4Smem = (size_t)(2 * lgmwino4w::MH + 256) * sizeof(float);
