@@ -1,7 +1,12 @@
 """bench.py — BASELINE.json metric: training images/sec, DDPM UNet 32x32, global batch 128.
 
-    python bench.py --gpus N --steps K --warmup W [--workload ddpm32|ddpm64|wgan_gp64|vqvae] [--only] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload ddpm32|ddpm64|wgan_gp64|vqvae] [--dump-outputs DIR] [--full [--only]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing more: set-up, warm-up, the timed steps, ``--dump-outputs`` if given,
+and the JSON line (metric, value, unit, ms_per_step, dtype, config).  ``--full`` adds everything else measured below
+(secondary configs, per-rank proxy, roofline, cpu_baseline, the exchange's exposed time on N > 1); ``--only`` then limits
+it to the named workload.
 
 ``--dump-outputs DIR``: right after the timed region, rank 0 writes what the timed path computed in its last step - the
 loss (logs) a caller of the step receives and the model state the step left behind (``state_dict()`` order and shapes,
@@ -18,7 +23,7 @@ noise ~ randn on device, q_sample, UNet fwd, weighted MSE) -> hand-written HIP b
 over RCCL when N > 1 -> fused Adam -> EMA update (every 10th step), replayed as HIP graphs.  Strong
 scaling: the global batch stays 128 (reference DataModule divides the config batch by the GPU count).
 
-Rank 0 prints ONE JSON line.  Its top level is the headline; on one GPU (and without --only) the same line carries
+Rank 0 prints ONE JSON line.  Its top level is the headline; with --full on one GPU (and without --only) the same line carries
   "secondary"       BASELINE's other configs measured the same way right after the headline leg, each with its own
                     "roofline" and "cpu_baseline":
                       ddpm64     config 5's network: DDPM UNet 64x64, B = 64 per GPU
@@ -28,7 +33,7 @@ Rank 0 prints ONE JSON line.  Its top level is the headline; on one GPU (and wit
                       ddpm64_sampling_1000  the same at its stated length: sample() -> 1000-step ancestral chain (p_sample_loop)
   "per_rank_proxy"  ms per step of the headline workload at the per-rank batches of 2 / 4 / 8 GPUs (64 / 32 / 16
                     images) on this one GPU: what a rank computes between its gradient exchanges under strong scaling.
-Objects of every workload:
+Objects of every workload with --full:
   "roofline"      the dominant SINGLE kernel of the convolution family (name with template arguments, as rocprofv3
                   prints it), timed live with HIP events on the launch stream in one extra instrumented step after the
                   timed region.  frac = EXECUTED MFMA FLOPs / event time / 157.3 TFLOP/s (<= 1 by construction): a
@@ -402,9 +407,10 @@ def setup_vqvae(args, dev, ema):
     return step, eager_step, info
 
 
-def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, roofline=True, cpu=True, dump=None):
-    """Warm-up, the timed region (barrier + synchronize on both sides, max over ranks), the instrumented roofline
-    step and the CPU baseline of ONE workload.  Returns the workload's JSON object (rank 0) or None.
+def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, full=False, dump=None):
+    """Warm-up and the timed region (barrier + synchronize on both sides, max over ranks) of ONE workload; ``full``
+    adds the exchange measurement (N > 1), the instrumented roofline step and the CPU baseline.  Returns the
+    workload's JSON object (rank 0) or None.
     ``dump``: directory for the outputs of the last timed step (dump_outputs), written before any further step."""
     from lgm_hip import ops
     torch.manual_seed(10)                         # reference train.py:20 seeds every rank identically
@@ -449,11 +455,11 @@ def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, roofline
         dump_outputs(dump, info["outputs"](loss))
     ms = elapsed / steps * 1e3
     value = gb * steps / elapsed
-    # N > 1: a few more steps (outside the timed region) with HIP events around the waits for the gradient exchange - how
-    # much of the communication the backward did NOT hide - and the collectives one step issues, for the line's `config`
+    # --full, N > 1: a few more steps (outside the timed region) with HIP events around the waits for the gradient exchange -
+    # how much of the communication the backward did NOT hide - and the collectives one step issues, for the line's `config`
     comm = None
     sync = getattr(info.get("fast"), "sync", None)
-    if sync is not None and not isinstance(sync, dict) and sync.active:
+    if full and sync is not None and not isinstance(sync, dict) and sync.active:
         sync.measure = True
         for i in range(min(5, steps)):
             step(warmup + steps + i)
@@ -471,8 +477,36 @@ def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, roofline
     if rank == 0:
         print(f"[bench] {wl}: timed region: {steps} steps in {elapsed:.3f}s ({value:.1f} img/s)", file=sys.stderr, flush=True)
     launch = info["fast"].mode if info["fast"] is not None else "eager"
-    if not roofline or args.no_roofline:
-        return {"ms_per_step": round(ms, 3), "value": round(value, 2), "launch": launch, "steps": steps, "warmup": warmup}
+    conv_mode = "bf16x3 (LGM_CONV_MODE)" if ops.B3 else (
+        ("fp32 MFMA, Winograd for the 3x3 layers: F(4x4,3x3) forward / input gradient on the large maps, F(2x2,3x3) elsewhere"
+         if ops.WINO4 else "fp32 MFMA, Winograd F(2x2,3x3) for the 3x3 layers") if ops.WINO else "fp32 MFMA, direct")
+    line = {"metric": metric, "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": steps,
+            "warmup": warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "f32" if not ops.B3 else "f32 (3x3 conv fwd/dgrad: opt-in bf16x3 split MFMA, fp32-level error)",
+            "data": "synthetic",
+            "config": {"workload": info["workload"], "global_batch": gb, "per_gpu_batch": per_gpu,
+                       "parallelism": f"dp{world}", "final_loss": round(final_loss, 5), "launch": launch,
+                       "conv_mode": conv_mode}}
+    if world > 1 or comm:
+        line["config"]["grad_exchange"] = ("bucketed all-reduce overlapped with the backward (RCCL)"
+                                           if os.environ.get("LGM_DDP_OVERLAP", "1") != "0"
+                                           else "one all-reduce after the backward (LGM_DDP_OVERLAP=0)")
+        from lgm_hip import ops as _ops
+        # which rule chose the kernels (lgm_hip.lightning.FlatGradSync._select_kernels): margin + light workgroups only
+        # while the exchange really overlaps the backward on RCCL; the environment's LGM_CU_MARGIN / LGM_WINO4_LIGHT win
+        sel = dict(getattr(sync, "selection", None) or {}) if sync is not None and not isinstance(sync, dict) else {}
+        sel.setdefault("cu_margin", int(_ops.lib().lgm_cu_margin()))
+        sel["note"] = ("launch plans sized for 256 - cu_margin CUs (a collective's workgroups hold the rest); "
+                       "LGM_CU_MARGIN / LGM_WINO4_LIGHT override the rule")
+        line["config"]["kernel_selection"] = sel
+        if comm:
+            line["config"].update({k: comm[k] for k in ("bucket_bytes", "collectives_per_step", "backend", "rccl_ranks")})
+            line["comm_exposed_ms"] = comm["comm_exposed_ms"]
+            line["comm_host_wait_ms"] = comm["comm_host_wait_ms"]
+            line["comm_exposed_frac_of_step"] = round(comm["comm_exposed_ms"] / ms, 4) if ms else None
+    if not full or args.no_roofline:
+        return line
 
     # ---- roofline leg: one extra instrumented step (a whole 5 D : 1 G cycle for the WGAN), per-launch HIP events on
     # the launch stream.  One un-instrumented eager pass first: the timed region replayed graphs, and the first launches
@@ -581,36 +615,8 @@ def run_workload(wl, args, dev, world, rank, steps, warmup, batch=None, roofline
                                             if step_counter_bytes else None)
     if detail:
         roof["work"] = detail
-    conv_mode = "bf16x3 (LGM_CONV_MODE)" if ops.B3 else (
-        ("fp32 MFMA, Winograd for the 3x3 layers: F(4x4,3x3) forward / input gradient on the large maps, F(2x2,3x3) elsewhere"
-         if ops.WINO4 else "fp32 MFMA, Winograd F(2x2,3x3) for the 3x3 layers") if ops.WINO else "fp32 MFMA, direct")
-    line = {"metric": metric, "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": steps,
-            "warmup": warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f32" if not ops.B3 else "f32 (3x3 conv fwd/dgrad: opt-in bf16x3 split MFMA, fp32-level error)",
-            "data": "synthetic",
-            "config": {"workload": info["workload"], "global_batch": gb, "per_gpu_batch": per_gpu,
-                       "parallelism": f"dp{world}", "final_loss": round(final_loss, 5), "launch": launch,
-                       "conv_mode": conv_mode},
-            "roofline": roof}
-    if world > 1 or comm:
-        line["config"]["grad_exchange"] = ("bucketed all-reduce overlapped with the backward (RCCL)"
-                                           if os.environ.get("LGM_DDP_OVERLAP", "1") != "0"
-                                           else "one all-reduce after the backward (LGM_DDP_OVERLAP=0)")
-        from lgm_hip import ops as _ops
-        # which rule chose the kernels (lgm_hip.lightning.FlatGradSync._select_kernels): margin + light workgroups only
-        # while the exchange really overlaps the backward on RCCL; the environment's LGM_CU_MARGIN / LGM_WINO4_LIGHT win
-        sel = dict(getattr(sync, "selection", None) or {}) if sync is not None and not isinstance(sync, dict) else {}
-        sel.setdefault("cu_margin", int(_ops.lib().lgm_cu_margin()))
-        sel["note"] = ("launch plans sized for 256 - cu_margin CUs (a collective's workgroups hold the rest); "
-                       "LGM_CU_MARGIN / LGM_WINO4_LIGHT override the rule")
-        line["config"]["kernel_selection"] = sel
-        if comm:
-            line["config"].update({k: comm[k] for k in ("bucket_bytes", "collectives_per_step", "backend", "rccl_ranks")})
-            line["comm_exposed_ms"] = comm["comm_exposed_ms"]
-            line["comm_host_wait_ms"] = comm["comm_host_wait_ms"]
-            line["comm_exposed_frac_of_step"] = round(comm["comm_exposed_ms"] / ms, 4) if ms else None
-    if world == 1 and cpu and not args.no_cpu_baseline:
+    line["roofline"] = roof
+    if world == 1 and not args.no_cpu_baseline:
         secs = args.cpu_seconds
         if wl == "ddpm32":
             line["cpu_baseline"] = cpu_baseline_ddpm(32, min_seconds=secs)
@@ -705,11 +711,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)     # ... after >= 10 warm-up steps
     ap.add_argument("--workload", default="ddpm32", choices=["ddpm32", "ddpm64", "wgan_gp64", "vqvae", "vqvae_ema"])
     ap.add_argument("--vq-ema", action="store_true", help="vqvae workload: EMA codebook (= --workload vqvae_ema)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: secondary configs, per-rank proxy, roofline, "
+                         "cpu_baseline, the gradient exchange's exposed time (N > 1); the options below shape it")
     ap.add_argument("--only", action="store_true", help="only the named workload: no secondary configs, no per-rank proxy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="profiling runs (rocprofv3 --kernel-trace / --pmc around this command): only warm-up + the timed "
-                         "steps, no instrumented step and none of the stream filler it queues behind")
+                    help="no instrumented step and none of the stream filler it queues behind (a plain run has neither)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="timed CPU work per cpu_baseline leg")
     ap.add_argument("--no-graph", action="store_true", help="issue every launch from Python (no HIP-graph replay)")
     ap.add_argument("--batch", type=int, default=None, help="global batch (default: the workload's config value)")
@@ -720,6 +728,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.torch_gpu_baseline and not args.full:
+        ap.error("--torch-gpu-baseline is part of a --full run")
     if args.vq_ema and args.workload == "vqvae":
         args.workload = "vqvae_ema"
 
@@ -777,9 +787,9 @@ def main():
                   file=sys.stderr, flush=True)
             os._exit(3)
 
-    single = world == 1 and not args.only and args.workload == "ddpm32" and args.batch is None
+    single = args.full and world == 1 and not args.only and args.workload == "ddpm32" and args.batch is None
     line = run_workload(args.workload, args, dev, world, rank, args.steps, args.warmup, batch=args.batch,
-                        dump=args.dump_outputs)
+                        full=args.full, dump=args.dump_outputs)
     rc = 0
     if single and rank == 0:
         # The headline exists now: put it on record (stderr + gpurun_out/) BEFORE any secondary leg runs, so that a hard
@@ -815,7 +825,7 @@ def main():
         sec = {}
         for wl, st, wu in (("ddpm64", 15, 3), ("wgan_gp64", 60, 12), ("vqvae", 100, 10), ("vqvae_ema", 100, 10)):
             def run(wl=wl, st=st, wu=wu):
-                r = run_workload(wl, args, dev, 1, 0, st, wu)
+                r = run_workload(wl, args, dev, 1, 0, st, wu, full=True)
                 return {k: r[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config",
                                           "roofline", "cpu_baseline") if k in r}
             sec[wl] = leg(wl, run)
@@ -831,8 +841,7 @@ def main():
         _ops.lib().lgm_set_cu_margin(16)
         try:
             for b in (64, 32, 16):
-                r = leg(f"proxy_b{b}", lambda b=b: run_workload("ddpm32", args, dev, 1, 0, 20, 5, batch=b, roofline=False,
-                                                                 cpu=False))
+                r = leg(f"proxy_b{b}", lambda b=b: run_workload("ddpm32", args, dev, 1, 0, 20, 5, batch=b))
                 proxy[f"b{b}"] = r.get("ms_per_step") if isinstance(r, dict) else None
         finally:
             _ops.lib().lgm_wino4_set_light(-1)

@@ -666,3 +666,10 @@ def test_bench_dump_outputs_and_step_count_checks(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+def test_bench_torch_gpu_baseline_needs_full():
+    """The PyTorch-eager comparison leg belongs to a --full run: a plain run refuses it before any GPU work."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--torch-gpu-baseline"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 2 and "--torch-gpu-baseline is part of a --full run" in r.stderr

@@ -130,9 +130,9 @@ def test_one_rank_rccl_exchange_between_graph_replays_is_the_identity(tmp_path):
 
 
 def test_bench_line_of_a_one_rank_rccl_run_describes_its_exchange():
-    """``bench.py --gpus 1 --only`` under a launcher with LGM_DDP_FORCE=1: the line carries backend nccl, rccl_ranks 1, the
-    buckets FlatGradSync issued, the rule that chose the kernels and comm_exposed_ms measured with HIP events."""
-    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--only", "--steps", "6", "--warmup", "3",
+    """``bench.py --gpus 1 --full --only`` under a launcher with LGM_DDP_FORCE=1: the line carries backend nccl, rccl_ranks 1,
+    the buckets FlatGradSync issued, the rule that chose the kernels and comm_exposed_ms measured with HIP events."""
+    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--only", "--steps", "6", "--warmup", "3",
                  "--no-cpu-baseline", "--batch", "64"], {"_PORT": "29573", "LGM_DDP_FORCE": "1"})
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -604,8 +604,8 @@ def test_bench_starts_its_own_ranks(tmp_path):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LGM_DIST_BACKEND="gloo", LGM_DIST_TIMEOUT="240")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--only", "--steps", "3", "--warmup", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--only", "--steps", "3",
+                        "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -627,3 +627,21 @@ def test_bench_starts_its_own_ranks(tmp_path):
     r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--only", "--steps", "1", "--warmup", "0",
                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, env=env2)
     assert r2.returncode != 0 and not [ln for ln in r2.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_plain_bench_run_is_the_headline_alone(tmp_path):
+    """``python bench.py --gpus 1 --steps 3 --warmup 2 --dump-outputs DIR`` without --full: the timed steps, the dumped
+    outputs and ONE line with the headline's fields; no roofline step, CPU baseline, secondary config or per-rank proxy."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "training images/sec (DDPM UNet 32x32, bs=128)" and rec["unit"] == "images/s"
+    assert rec["higher_is_better"] is True and rec["dtype"].startswith("f32") and rec["n_gpus"] == 1
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["ms_per_step"] > 0
+    assert rec["value"] == pytest.approx(128 * 1e3 / rec["ms_per_step"], rel=1e-3)
+    assert not {"roofline", "cpu_baseline", "secondary", "per_rank_proxy"} & rec.keys(), sorted(rec)
+    assert "cpu_baseline step" not in r.stderr
+    assert sorted(os.listdir(tmp_path)) == ["ema_params.npy", "loss.npy", "params.npy"]

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 out=$PWD/gpurun_out
 # STAGE=1: bench line + kernel traces; STAGE=2: counter passes + engine numbers; unset: everything (may exceed one gpurun call)
 if [ "${STAGE:-1}" = "1" ]; then
-python3 bench.py 2> $out/${R}_bench.err | tail -1 > $out/${R}_bench.json
+python3 bench.py --full 2> $out/${R}_bench.err | tail -1 > $out/${R}_bench.json
 echo "bench line done"
 GRAPH=1 bash tools/prof_workload.sh ddpm32 ${R}_bench_b128 > /dev/null
 # the per-rank batches run the kernel selection of an N > 1 job (light F(4x4) workgroups, launch plans for 240 CUs), as
