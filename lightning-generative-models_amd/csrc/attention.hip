@@ -29,6 +29,12 @@ int lgm_linattn_bwd_launch(const float* qkv, long pitch, const float* mem_kv, co
                            const float* ctx, const float* gctx, const float* kmax, const float* ksum,
                            const float* rvec, int B, int n, int heads, int M, float scale, float* gqkv,
                            long gq_pitch, float* gmem_partial, hipStream_t s);
+// tiled full attention for n > 128 query pixels (attention_tiled.hip)
+int lgm_attn_tiled_fwd_launch(const float* qkv, long pitch, const float* mem_kv, int B, int n, int heads, int M,
+                              float scale, float* out, long out_pitch, float* lse, hipStream_t s);
+int lgm_attn_tiled_bwd_launch(const float* qkv, long pitch, const float* mem_kv, const float* out, long out_pitch,
+                              const float* gout, long gout_pitch, const float* lse, int B, int n, int heads, int M,
+                              float scale, float* gqkv, long gq_pitch, float* gmem_partial, hipStream_t s);
 
 namespace {
 
@@ -107,7 +113,8 @@ __global__ __launch_bounds__(256) void linattn_out_kernel(const float* __restric
 }
 
 // =====================================================================================
-// Full softmax attention, n <= 128 query pixels, one block per (batch, head), one thread per row.
+// Full softmax attention, n <= 128 query pixels, one block per (batch, head), one thread per row (larger maps:
+// attention_tiled.hip).
 // =====================================================================================
 constexpr int FA_MAXN = 128;
 constexpr int FA_LD = DH + 1;
@@ -463,6 +470,12 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const float* __rest
   }
 }
 
+// n > FA_MAXN takes the tiled kernels (attention_tiled.hip); LGM_TILED_ATTN=1 forces them at every n (test switch)
+bool attn_tiled(int n) {
+  static const bool forced = getenv("LGM_TILED_ATTN") != nullptr;
+  return forced || n > FA_MAXN;
+}
+
 int attn_check(int B, int n, int heads, int dim_head, int M) {
   LGM_REQUIRE(B > 0 && n > 0 && heads > 0 && M >= 0 && M <= 16, "attention: bad sizes B=%d n=%d heads=%d M=%d", B, n, heads, M);
   LGM_REQUIRE(dim_head == DH, "attention: dim_head=%d unsupported (kernels are built for 32)", dim_head);
@@ -655,8 +668,10 @@ extern "C" int lgm_linattn_bwd_fused(const float* qkv, int64_t qkv_pitch, const 
 extern "C" int lgm_attn_fwd(const float* qkv, int64_t qkv_pitch, const float* mem_kv, int B, int n, int heads,
                             int dim_head, int M, float* out, int64_t out_pitch, float* lse, void* stream) {
   if (int rc = attn_check(B, n, heads, dim_head, M)) return rc;
-  LGM_REQUIRE(n <= FA_MAXN, "attn_fwd: n=%d > %d query pixels unsupported", n, FA_MAXN);
   LGM_REQUIRE(qkv && mem_kv && out && lse, "attn_fwd: null pointer");
+  if (attn_tiled(n))
+    return lgm_attn_tiled_fwd_launch(qkv, (long)qkv_pitch, mem_kv, B, n, heads, M, 1.f / sqrtf((float)dim_head), out,
+                                     (long)out_pitch, lse, (hipStream_t)stream);
   const size_t smem = (size_t)2 * (n + M) * FA_LD * sizeof(float);
   static const bool no_small = getenv("LGM_NO_SMALL_ATTN") != nullptr;          // A/B switch
   if (!no_small && n <= SA_MAXN && M <= 16 && qkv_pitch % 4 == 0 && out_pitch % 4 == 0 && lgm_aligned16(qkv) &&
@@ -685,13 +700,34 @@ extern "C" int64_t lgm_attn_bwd_workspace(int B, int heads, int dim_head, int M)
 }
 
 namespace {
+// the memory rows' gradient: per-image rows in `part`, summed now in a fixed order or described for the deferred reducer
+int attn_bwd_mem_reduce(float* part, long ncols, int B, float* gmem_kv, float gmem_beta, int64_t* gmem_desc, void* stream) {
+  if (gmem_desc) gmem_desc[6] = 0;
+  if (ncols <= 0) return LGM_OK;
+  if (gmem_desc) {
+    union { float f; int64_t i; } bb;
+    bb.i = 0; bb.f = gmem_beta;
+    gmem_desc[0] = (int64_t)(uintptr_t)part; gmem_desc[1] = ncols; gmem_desc[2] = (int64_t)(uintptr_t)gmem_kv;
+    gmem_desc[3] = ncols; gmem_desc[4] = 0; gmem_desc[5] = 0; gmem_desc[6] = B; gmem_desc[7] = bb.i;
+    return LGM_OK;
+  }
+  return lgm_colsum(part, ncols, B, ncols, gmem_kv, gmem_beta, part + (long)B * ncols, stream);
+}
+
 int attn_bwd_impl(const float* qkv, int64_t qkv_pitch, const float* mem_kv, const float* out, int64_t out_pitch,
                   const float* gout, int64_t gout_pitch, const float* lse, int B, int n, int heads, int dim_head, int M,
                   float* gqkv, int64_t gqkv_pitch, float* gmem_kv, float gmem_beta, float* part, int64_t* gmem_desc,
                   void* stream) {
   if (int rc = attn_check(B, n, heads, dim_head, M)) return rc;
-  LGM_REQUIRE(n <= FA_MAXN, "attn_bwd: n=%d > %d query pixels unsupported", n, FA_MAXN);
   LGM_REQUIRE(qkv && mem_kv && out && gout && lse && gqkv && gmem_kv && part, "attn_bwd: null pointer");
+  const long ncols = 2L * heads * M * DH;
+  if (attn_tiled(n)) {
+    if (int rc = lgm_attn_tiled_bwd_launch(qkv, (long)qkv_pitch, mem_kv, out, (long)out_pitch, gout, (long)gout_pitch, lse,
+                                           B, n, heads, M, 1.f / sqrtf((float)dim_head), gqkv, (long)gqkv_pitch, part,
+                                           (hipStream_t)stream))
+      return rc;
+    return attn_bwd_mem_reduce(part, ncols, B, gmem_kv, gmem_beta, gmem_desc, stream);
+  }
   const size_t smem = ((size_t)2 * (n + M) * FA_LD + (size_t)2 * n * FA_LD + 2 * n) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
@@ -699,7 +735,6 @@ int attn_bwd_impl(const float* qkv, int64_t qkv_pitch, const float* mem_kv, cons
                         (int)(((size_t)4 * (FA_MAXN + 16) * FA_LD + 2 * FA_MAXN) * sizeof(float)));
     attr_set = true;
   }
-  const long ncols = 2L * heads * M * DH;
   static const bool no_small = getenv("LGM_NO_SMALL_ATTN") != nullptr;          // A/B switch
   if (!no_small && n <= SA_MAXN && M <= 16 && qkv_pitch % 4 == 0 && out_pitch % 4 == 0 && gout_pitch % 4 == 0 &&
       gqkv_pitch % 4 == 0 && lgm_aligned16(qkv) && lgm_aligned16(out) && lgm_aligned16(gout) && lgm_aligned16(gqkv) &&
@@ -720,16 +755,7 @@ int attn_bwd_impl(const float* qkv, int64_t qkv_pitch, const float* mem_kv, cons
                        mem_kv, out, (long)out_pitch, gout, (long)gout_pitch, lse, n, heads, M,
                        1.f / sqrtf((float)dim_head), gqkv, (long)gqkv_pitch, part);
   LGM_LAUNCH_CHECK();
-  if (gmem_desc) gmem_desc[6] = 0;
-  if (M <= 0) return LGM_OK;
-  if (gmem_desc) {
-    union { float f; int64_t i; } bb;
-    bb.i = 0; bb.f = gmem_beta;
-    gmem_desc[0] = (int64_t)(uintptr_t)part; gmem_desc[1] = ncols; gmem_desc[2] = (int64_t)(uintptr_t)gmem_kv;
-    gmem_desc[3] = ncols; gmem_desc[4] = 0; gmem_desc[5] = 0; gmem_desc[6] = B; gmem_desc[7] = bb.i;
-    return LGM_OK;
-  }
-  return lgm_colsum(part, ncols, B, ncols, gmem_kv, gmem_beta, part + (long)B * ncols, stream);
+  return attn_bwd_mem_reduce(part, ncols, B, gmem_kv, gmem_beta, gmem_desc, stream);
 }
 }  // namespace
 

@@ -5,8 +5,9 @@ Inside the UNet the attention core runs fused with its memory key/values straigh
 kernel behind the reference's stand-alone call ``Attend()(q, k, v)`` with q ``[b, h, n, d]`` and k, v
 ``[b, h, n + M, d]`` (the reference concatenates M memory rows in front, ddpm.py:262-265).
 
-Limits of the kernel, raised as NotImplementedError: d == 32, n <= 128, M <= 16, the M leading key/value rows equal
-for every batch element (they are a broadcast parameter upstream), CUDA tensors.  Gradients flow for M == 0.
+Limits of the kernel, raised as NotImplementedError: d == 32, M <= 16, the M leading key/value rows equal
+for every batch element (they are a broadcast parameter upstream), CUDA tensors.  Gradients flow for M == 0.  Any
+number of query pixels n: n > 128 runs the tiled kernels (csrc/attention_tiled.hip).
 """
 from __future__ import annotations
 
@@ -50,7 +51,7 @@ class Attend(nn.Module):
     def forward(self, q, k, v):
         b, h, n, d = q.shape
         M = k.shape[-2] - n
-        if not q.is_cuda or d != 32 or n > 128 or M < 0 or M > 16 or k.shape != v.shape:
+        if not q.is_cuda or d != 32 or M < 0 or M > 16 or k.shape != v.shape:
             raise NotImplementedError(f"HIP Attend: unsupported call q{tuple(q.shape)} k{tuple(k.shape)}")
         q, k, v = (t.float() for t in (q, k, v))
         if M == 0:
