@@ -199,15 +199,17 @@ class Conv2d(nn.Module):
                 gb = fp.gptr(self.bias)              # bias gradient fused into the wgrad kernel
             else:
                 ops.colsum(gy, fp.gptr(self.bias), bb)
-        if need_gx and self.k == 3 and mask is None and bn_sums is None:
-            # 3x3 layers: input gradient and weight gradient side by side in ONE launch (ops.conv_bwd_pair)
+        if need_gx:
             if gx is None:
                 gx = ops.new(x.shape, x)
                 accumulate = False
-            pres = gx if accumulate else res
             assert not (accumulate and res is not None)
-            ok_pl = bool(planes_for_groups) and pres is None and ops.gn_planes_ok(B, H * W, x.shape[-1], planes_for_groups)
-            r = ops.conv_bwd_pair(g, gy, x, fp.ptr(self.weight), fp.gptr(self.weight), bw, gb, dfr, pres, gx, partial=ok_pl)
+            if accumulate:
+                res = gx                         # the residual the input gradient adds: gx itself
+        if need_gx and self.k == 3 and mask is None and bn_sums is None:
+            # 3x3 layers: input gradient and weight gradient side by side in ONE launch (ops.conv_bwd_pair)
+            ok_pl = bool(planes_for_groups) and res is None and ops.gn_planes_ok(B, H * W, x.shape[-1], planes_for_groups)
+            r = ops.conv_bwd_pair(g, gy, x, fp.ptr(self.weight), fp.gptr(self.weight), bw, gb, dfr, res, gx, partial=ok_pl)
             if r is not False:
                 return (gx, r) if planes_for_groups else gx
         if (need_gx and self.k == 1 and mask is None and bn_sums is None and not planes_for_groups and dfr is not None
@@ -215,21 +217,13 @@ class Conv2d(nn.Module):
             # a 1x1 layer whose weight gradient runs the streaming kernel on a launch of its own: it waits for up to three
             # partners (GradCtx.queue_wgrad1x1: one launch for four); the input gradient as before
             gc.queue_wgrad1x1(g, gy, x, fp.gptr(self.weight), bw, gb)
-            if gx is None:
-                gx = ops.new(x.shape, x)
-                accumulate = False
-            assert not (accumulate and res is not None)
-            ops.conv_yx(g, gy, fp.ptr(self.weight), None, gx if accumulate else res, gx, fp.tptr(self.weight))
+            ops.conv_yx(g, gy, fp.ptr(self.weight), None, res, gx, fp.tptr(self.weight))
             return gx
         if need_gx and (self.k != 3 or mask is not None or bn_sums is not None) and not planes_for_groups and not ops.B3:
             # the other layers (1x1, 4x4 / stride 2, 7x7; a 3x3 layer the pair above did not take keeps its Winograd /
             # direct input gradient below): both gradients through lgm_conv_bwd_pair - one launch when the kernels can
             # share a grid
-            if gx is None:
-                gx = ops.new(x.shape, x)
-                accumulate = False
-            assert not (accumulate and res is not None)
-            if ops._weng_take(g, fp.ptr(self.weight), gx if accumulate else res, False) is not None:
+            if ops._weng_take(g, fp.ptr(self.weight), res, False) is not None:
                 # 4x4 / stride-2 layer registered with the non-fused Winograd engine: its input gradient runs there, the
                 # weight gradient keeps the implicit-GEMM kernel (the one-launch pair would bypass the engine)
                 ops.conv_wgrad(g, gy, x, fp.gptr(self.weight), bw, gb, defer=dfr)
@@ -239,7 +233,7 @@ class Conv2d(nn.Module):
             if dfr is not None:
                 gc._keep.append((gy, x))       # a stand-alone weight-gradient launch may wait in the library's queue
             ops.conv_bwd_generic(g, gy, x, fp.ptr(self.weight), fp.tptr(self.weight), fp.gptr(self.weight), bw, gb, dfr,
-                                 gx if accumulate else res, gx, post=ops.make_post(0, 0.0, mask, mask_slope, bn=bn_sums),
+                                 res, gx, post=ops.make_post(0, 0.0, mask, mask_slope, bn=bn_sums),
                                  post_mask=mask, queue=dfr is not None)
             return gx
         if dfr is not None and self.k == 3 and ops.wgrad_queueable(g, gy, x):
@@ -250,12 +244,6 @@ class Conv2d(nn.Module):
             ops.conv_wgrad(g, gy, x, fp.gptr(self.weight), bw, gb, defer=dfr, queue=dfr is not None)
         if not need_gx:
             return None
-        if gx is None:
-            gx = ops.new(x.shape, x)
-            accumulate = False
-        if accumulate:
-            assert res is None
-            res = gx
         if planes_for_groups:
             ok = self.k == 3 and res is None and ops.gn_planes_ok(B, H * W, x.shape[-1], planes_for_groups)
             return gx, ops.conv_yx(g, gy, fp.ptr(self.weight), None, res, gx, fp.tptr(self.weight), partial=ok)

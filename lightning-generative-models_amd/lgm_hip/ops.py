@@ -53,19 +53,40 @@ _WS = {}
 _WS_RETIRED = []     # superseded buffers are NEVER freed: a captured HIP graph may have their address baked in
 
 
-def workspace(nbytes: int, device) -> torch.Tensor:
+def _grown(bufs: dict, device, nbytes: int, nfloats: int) -> torch.Tensor:
+    """The device's buffer in ``bufs``, first replaced by a new one of ``nfloats`` floats when it holds fewer than
+    ``nbytes``.  A graph replay after this point still writes its scratch data into the OLD buffer: returning it to the
+    caching allocator would let that land in a live tensor (graph and eager launches run in stream order, so the two
+    buffers are never used concurrently) - it goes to _WS_RETIRED instead."""
     key = torch.device(device).index or 0
-    ws = _WS.get(key)
+    ws = bufs.get(key)
     if ws is None or ws.numel() * 4 < nbytes:
-        n = max(int(nbytes * 1.25) // 4 + 64, 1 << 20)
         if ws is not None:
-            # a graph replay after this point still writes its scratch data into the OLD buffer: returning
-            # it to the caching allocator would let that land in a live tensor (graph and eager launches
-            # run in stream order, so the two buffers are never used concurrently)
             _WS_RETIRED.append(ws)
-        ws = torch.empty(n, dtype=torch.float32, device=device)
-        _WS[key] = ws
+        ws = bufs[key] = torch.empty(nfloats, dtype=torch.float32, device=device)
     return ws
+
+
+def workspace(nbytes: int, device) -> torch.Tensor:
+    return _grown(_WS, device, nbytes, max(int(nbytes * 1.25) // 4 + 64, 1 << 20))
+
+
+_PLAN_CACHES = []
+
+
+def _plan_cache() -> dict:
+    """A new dict of per-geometry planner answers (kernel choice, split counts, workspace sizes): clear_plan_caches()
+    empties every dict made here.  Never for buffers - captured graphs have their addresses baked in."""
+    d = {}
+    _PLAN_CACHES.append(d)
+    return d
+
+
+def _memo(cache: dict, key, compute):
+    v = cache.get(key)
+    if v is None:
+        v = cache[key] = compute()
+    return v
 
 
 def new(shape, like: torch.Tensor) -> torch.Tensor:
@@ -126,7 +147,26 @@ def _conv_bytes(g: ConvGeom) -> float:
     return 4.0 * (g.B * g.H * g.W * g.Cw + g.B * g.Ho * g.Wo * g.Nw + g.Nw * g.KH * g.KW * g.Cw)
 
 
-_CONV_WS_BYTES = {}
+class _timed:
+    """``with _timed(family, geoms, k):`` the launches inside are ONE KernelTimer record of k x the work of ``geoms`` (a
+    ConvGeom or a list of them; None: no work).  Nothing is recorded while TIMER is None."""
+    __slots__ = ("t",)
+
+    def __init__(self, fam: str, geoms=None, k: float = 1.0):
+        self.t = TIMER
+        if self.t is not None:
+            gs = [] if geoms is None else [geoms] if isinstance(geoms, ConvGeom) else geoms
+            self.t.begin(fam, k * sum(_conv_flops(g) for g in gs), k * sum(_conv_bytes(g) for g in gs))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.t is not None:
+            self.t.end()
+
+
+_CONV_WS_BYTES = _plan_cache()
 
 # OPT-IN split-precision 3x3 convolutions (SURVEY.md: "bf16x3 ... behind a flag"): LGM_CONV_MODE=bf16x3.
 # Only flats that called enable_b3() take part; everything else, and the default, is exact fp32 MFMA.
@@ -134,7 +174,7 @@ import os as _os
 
 B3 = _os.environ.get("LGM_CONV_MODE", "fp32") == "bf16x3"
 _B3_FLATS = []
-_B3_OK = {}
+_B3_OK = _plan_cache()
 
 
 def register_b3_flat(fp):
@@ -182,19 +222,17 @@ def _b3_planes(ptr: Optional[int], transposed: bool):
 
 def _b3_supported(g: ConvGeom, mode: int, a_pitch: int) -> bool:
     key = (g.B, g.H, g.W, g.Cw, g.Nw, g.KH, g.stride, g.pad, mode, a_pitch)
-    v = _B3_OK.get(key)
-    if v is None:
-        v = bool(g.KH == 3 and g.KW == 3 and lib().lgm_conv3x3_bf16x3_supported(ctypes.byref(g), mode, a_pitch))
-        _B3_OK[key] = v
-    return v
+    return _memo(_B3_OK, key, lambda: bool(g.KH == 3 and g.KW == 3 and
+                                           lib().lgm_conv3x3_bf16x3_supported(ctypes.byref(g), mode, a_pitch)))
 
 
 # Winograd F(2x2,3x3) for the 3x3 / stride 1 / pad 1 layers (exact fp32 arithmetic, 2.25x fewer MFMA FLOPs): the
 # default for flats that called enable_wino(); LGM_NO_WINO=1 routes them through the direct fp32 MFMA kernels.
 WINO = _os.environ.get("LGM_NO_WINO", "0") != "1"
 _WINO_FLATS = []
-_WINO_OK = {}
-_WINO_WS = {}
+_WINO_OK = _plan_cache()
+_WINO_WS = _plan_cache()
+_WINO_FITS = _plan_cache()
 
 
 def register_wino_flat(fp):
@@ -203,8 +241,9 @@ def register_wino_flat(fp):
     _WINO_FLATS.append(_wr.ref(fp))
 
 
-def _wino_u(w_ptr: Optional[int], backward: bool):
-    """-> address of the transformed copy of the 3x3 weight slot at ``w_ptr`` (a registered flat buffer), or None"""
+def _wino_u(w_ptr: Optional[int], backward: bool, f4: bool = False):
+    """-> address of the transformed copy of the 3x3 weight slot at ``w_ptr`` (a registered flat buffer) for the F(2x2)
+    kernels, or with ``f4`` its F(4x4) operand (registered on first use), or None"""
     if w_ptr is None:
         return None
     for ref in _WINO_FLATS:
@@ -213,74 +252,69 @@ def _wino_u(w_ptr: Optional[int], backward: bool):
             continue
         off = w_ptr - fp.data.data_ptr()
         if 0 <= off < 4 * fp.total:
-            return fp.wino_u(off // 4, backward) if off % 4 == 0 else None
+            return (fp.wino4_u if f4 else fp.wino_u)(off // 4, backward) if off % 4 == 0 else None
     return None
+
+
+def _wino_supported(g: ConvGeom, yx: int) -> bool:
+    key = (g.B, g.H, g.W, g.Cw, g.Nw, g.KH, g.KW, g.stride, g.pad, yx)
+    return _memo(_WINO_OK, key, lambda: bool(g.KH == 3 and g.KW == 3 and
+                                             lib().lgm_conv3x3_wino_supported(ctypes.byref(g), yx)))
 
 
 # Winograd F(4x4,3x3) on the large maps (csrc/winograd4.hip): taken before the F(2x2) kernel where the library's
 # measured table prefers it (lgm_conv3x3_wino4_preferred); LGM_NO_WINO4=1 switches it off.
 WINO4 = _os.environ.get("LGM_NO_WINO4", "0") != "1"
-_WINO4_OK = {}
+_WINO4_OK = _plan_cache()
 
 
 def _wino4_preferred(g: ConvGeom, yx: int) -> bool:
     key = (g.B, g.H, g.W, g.Cw, g.Nw, g.KH, g.KW, g.stride, g.pad, yx)
-    v = _WINO4_OK.get(key)
-    if v is None:
-        v = bool(WINO4 and g.KH == 3 and g.KW == 3 and lib().lgm_conv3x3_wino4_preferred(ctypes.byref(g), yx))
-        _WINO4_OK[key] = v
-    return v
+    return _memo(_WINO4_OK, key, lambda: bool(WINO4 and g.KH == 3 and g.KW == 3 and
+                                              lib().lgm_conv3x3_wino4_preferred(ctypes.byref(g), yx)))
 
 
-def _wino4_u(w_ptr: Optional[int], backward: bool):
-    """-> address of the F(4x4) operand of the 3x3 weight slot at ``w_ptr`` (registered on first use), or None"""
-    if w_ptr is None:
-        return None
-    for ref in _WINO_FLATS:
-        fp = ref()
-        if fp is None:
-            continue
-        off = w_ptr - fp.data.data_ptr()
-        if 0 <= off < 4 * fp.total:
-            return fp.wino4_u(off // 4, backward) if off % 4 == 0 else None
-    return None
-
-
-def _wino4_call(yx: int, g: ConvGeom, a, u_ptr: int, bias_ptr, res, out, partial: bool = False):
-    """As _wino_call, through lgm_conv3x3_wino4[_partial]."""
+def _wino_fits(g: ConvGeom, a, out, res, bias_ptr) -> bool:
+    """The operands of a Winograd launch qualify: 16-byte aligned, pitch % 4, 32-bit offsets (lgm_conv3x3_wino_fits)."""
     if a.data_ptr() % 16 or out.data_ptr() % 16 or pitch(a) % 4 or pitch(out) % 4 or (bias_ptr or 0) % 16:
         return False
     if res is not None and (res.data_ptr() % 16 or pitch(res) % 4):
         return False
-    fkey = (g.B, g.H, g.W, pitch(a), pitch(out), pitch(res) if res is not None else 0)
-    fits = _WINO_FITS.get(fkey)
-    if fits is None:
-        fits = bool(lib().lgm_conv3x3_wino_fits(ctypes.byref(g), fkey[3], fkey[4], fkey[5]))
-        _WINO_FITS[fkey] = fits
-    if not fits:
+    key = (g.B, g.H, g.W, pitch(a), pitch(out), pitch(res) if res is not None else 0)
+    return _memo(_WINO_FITS, key, lambda: bool(lib().lgm_conv3x3_wino_fits(ctypes.byref(g), *key[3:])))
+
+
+# entry points of the two Winograd kernels: (launch, workspace query, workspace query of the launch that leaves planes)
+_F22 = ("lgm_conv3x3_wino", "lgm_conv3x3_wino_workspace", "lgm_conv3x3_wino_workspace_partial")
+_F44 = ("lgm_conv3x3_wino4", "lgm_conv3x3_wino4_workspace", "lgm_conv3x3_wino4_workspace")
+
+
+def _wino_call(kind, yx: int, g: ConvGeom, a, u_ptr: int, bias_ptr, res, out, partial: bool = False):
+    """Launch the Winograd kernel ``kind`` (_F22 / _F44) when the operands qualify (_wino_fits); False = not taken (the
+    caller falls back to the next route).  ``partial``: the split-K planes are left for the consumer (GroupNorm) to sum -
+    returns (planes address, plane stride in floats, planes) or, when the launch did not split, True (``out`` complete)."""
+    if not _wino_fits(g, a, out, res, bias_ptr):
         return False
-    key = (g.B, g.H, g.W, g.Cw, g.Nw, yx, "w4")
-    n = _WINO_WS.get(key)
-    if n is None:
-        n = lib().lgm_conv3x3_wino4_workspace(ctypes.byref(g), yx)
-        _WINO_WS[key] = n
+    L = lib()
+    launch, ws_query, ws_query_partial = kind
+    n = _memo(_WINO_WS, (g.B, g.H, g.W, g.Cw, g.Nw, yx, launch, partial),
+              lambda: getattr(L, ws_query_partial if partial else ws_query)(ctypes.byref(g), yx))
     ws = workspace(n, a.device) if n > 0 else None
+    wsa = (None, 0) if ws is None else (ws.data_ptr(), ws.numel() * 4)
     if partial:
         assert res is None
         part = (ctypes.c_int64 * 2)()
-        lib().lgm_conv3x3_wino4_partial(yx, ctypes.byref(g), a.data_ptr(), pitch(a), u_ptr, bias_ptr, out.data_ptr(),
-                                        pitch(out), None if ws is None else ws.data_ptr(),
-                                        0 if ws is None else ws.numel() * 4, ctypes.addressof(part), stream())
+        getattr(L, launch + "_partial")(yx, ctypes.byref(g), a.data_ptr(), pitch(a), u_ptr, bias_ptr, out.data_ptr(),
+                                        pitch(out), *wsa, ctypes.addressof(part), stream())
         return (ws.data_ptr(), int(part[1]), int(part[0])) if part[0] > 1 else True
-    lib().lgm_conv3x3_wino4(yx, ctypes.byref(g), a.data_ptr(), pitch(a), u_ptr, bias_ptr, _p(res),
-                            pitch(res) if res is not None else 0, out.data_ptr(), pitch(out),
-                            None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
+    getattr(L, launch)(yx, ctypes.byref(g), a.data_ptr(), pitch(a), u_ptr, bias_ptr, _p(res),
+                       pitch(res) if res is not None else 0, out.data_ptr(), pitch(out), *wsa, stream())
     return True
 
 
 # GroupNorm statistics from the convolution's epilogue (lgm_conv3x3_wino4_stats + lgm_gn_fwd_stats): only where the
 # GroupNorm forward would otherwise need two passes over x (the 64 x 64 maps); LGM_NO_GN_EPI_STATS=1 switches it off.
-_EPI_STATS = {}
+_EPI_STATS = _plan_cache()
 
 
 def conv_xy_stats(g: ConvGeom, x, w_ptr: Optional[int], bias_ptr, y, groups: int):
@@ -288,93 +322,30 @@ def conv_xy_stats(g: ConvGeom, x, w_ptr: Optional[int], bias_ptr, y, groups: int
     gn_fwd(planes=...), or None when this layer does not take the path (the caller runs conv_xy)."""
     if not (WINO and WINO4 and _WINO_FLATS and not B3) or g.KH != 3 or g.KW != 3 or w_ptr is None:
         return None
-    key = (g.B, g.H, g.W, g.Cw, g.Nw, groups)
-    ent = _EPI_STATS.get(key)
-    if ent is None:
+
+    def plan():
         n, per = 0, ctypes.c_int(0)
         C = g.Nw
         if (_wino4_preferred(g, 0) and C % groups == 0 and 64 % (C // groups) == 0
                 and not lib().lgm_gn_fwd_fused_supported(g.B, g.H * g.W, C, groups)):
             n = int(lib().lgm_conv3x3_wino4_stats_floats(ctypes.byref(g), ctypes.addressof(per)))
-        ent = (n, int(per.value))
-        _EPI_STATS[key] = ent
-    if ent[0] <= 0:
+        return (n, int(per.value))
+    n, per = _memo(_EPI_STATS, (g.B, g.H, g.W, g.Cw, g.Nw, groups), plan)
+    if n <= 0 or not _wino_fits(g, x, y, None, bias_ptr):
         return None
-    if x.data_ptr() % 16 or y.data_ptr() % 16 or pitch(x) % 4 or pitch(y) % 4 or (bias_ptr or 0) % 16:
-        return None
-    fkey = (g.B, g.H, g.W, pitch(x), pitch(y), 0)
-    fits = _WINO_FITS.get(fkey)
-    if fits is None:
-        fits = bool(lib().lgm_conv3x3_wino_fits(ctypes.byref(g), fkey[3], fkey[4], fkey[5]))
-        _WINO_FITS[fkey] = fits
-    if not fits:
-        return None
-    u = _wino4_u(w_ptr, False)
+    u = _wino_u(w_ptr, False, f4=True)
     if u is None:
         return None
-    st = torch.empty(ent[0], dtype=torch.float32, device=x.device)
-    if TIMER is not None:
-        TIMER.begin("igemm_xy", _conv_flops(g), _conv_bytes(g))
-    lib().lgm_conv3x3_wino4_stats(ctypes.byref(g), x.data_ptr(), pitch(x), u, bias_ptr, y.data_ptr(), pitch(y),
-                                  st.data_ptr(), ent[0], stream())
-    if TIMER is not None:
-        TIMER.end()
-    return ("stats", st, ent[1], bias_ptr)
-
-
-def _wino_supported(g: ConvGeom, yx: int) -> bool:
-    key = (g.B, g.H, g.W, g.Cw, g.Nw, g.KH, g.KW, g.stride, g.pad, yx)
-    v = _WINO_OK.get(key)
-    if v is None:
-        v = bool(g.KH == 3 and g.KW == 3 and lib().lgm_conv3x3_wino_supported(ctypes.byref(g), yx))
-        _WINO_OK[key] = v
-    return v
-
-
-_WINO_FITS = {}
-
-
-def _wino_call(yx: int, g: ConvGeom, a, u_ptr: int, bias_ptr, res, out, partial: bool = False):
-    """Launch the Winograd kernel when the operands qualify (16-byte aligned, pitch % 4, 32-bit offsets); False = not
-    taken (the caller falls back to the direct kernel).  ``partial``: the split-K planes are left for the consumer
-    (GroupNorm) to sum - returns (planes address, plane stride in floats, planes) or, when the launch did not split,
-    True (``out`` complete)."""
-    if a.data_ptr() % 16 or out.data_ptr() % 16 or pitch(a) % 4 or pitch(out) % 4 or (bias_ptr or 0) % 16:
-        return False
-    if res is not None and (res.data_ptr() % 16 or pitch(res) % 4):
-        return False
-    fkey = (g.B, g.H, g.W, pitch(a), pitch(out), pitch(res) if res is not None else 0)
-    fits = _WINO_FITS.get(fkey)
-    if fits is None:
-        fits = bool(lib().lgm_conv3x3_wino_fits(ctypes.byref(g), fkey[3], fkey[4], fkey[5]))
-        _WINO_FITS[fkey] = fits
-    if not fits:
-        return False
-    key = (g.B, g.H, g.W, g.Cw, g.Nw, yx, partial)
-    n = _WINO_WS.get(key)
-    if n is None:
-        n = (lib().lgm_conv3x3_wino_workspace_partial if partial else lib().lgm_conv3x3_wino_workspace)(ctypes.byref(g), yx)
-        _WINO_WS[key] = n
-    ws = workspace(n, a.device) if n > 0 else None
-    if partial:
-        assert res is None
-        part = (ctypes.c_int64 * 2)()
-        lib().lgm_conv3x3_wino_partial(yx, ctypes.byref(g), a.data_ptr(), pitch(a), u_ptr, bias_ptr, out.data_ptr(),
-                                       pitch(out), None if ws is None else ws.data_ptr(),
-                                       0 if ws is None else ws.numel() * 4, ctypes.addressof(part), stream())
-        return (ws.data_ptr(), int(part[1]), int(part[0])) if part[0] > 1 else True
-    lib().lgm_conv3x3_wino(yx, ctypes.byref(g), a.data_ptr(), pitch(a), u_ptr, bias_ptr, _p(res),
-                           pitch(res) if res is not None else 0, out.data_ptr(), pitch(out),
-                           None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
-    return True
+    st = torch.empty(n, dtype=torch.float32, device=x.device)
+    with _timed("igemm_xy", g):
+        lib().lgm_conv3x3_wino4_stats(ctypes.byref(g), x.data_ptr(), pitch(x), u, bias_ptr, y.data_ptr(), pitch(y),
+                                      st.data_ptr(), n, stream())
+    return ("stats", st, per, bias_ptr)
 
 
 def _conv_ws(g: ConvGeom, yx: int, device):
     key = (g.B, g.H, g.W, g.Cw, g.Nw, g.KH, g.stride, g.pad, yx)
-    n = _CONV_WS_BYTES.get(key)
-    if n is None:
-        n = lib().lgm_conv_workspace(ctypes.byref(g), yx)
-        _CONV_WS_BYTES[key] = n
+    n = _memo(_CONV_WS_BYTES, key, lambda: lib().lgm_conv_workspace(ctypes.byref(g), yx))
     return workspace(n, device) if n > 0 else None
 
 
@@ -536,65 +507,57 @@ def conv_xy(g: ConvGeom, x, w_ptr: int, bias_ptr: Optional[int], res, y, partial
     (planes address, plane stride, planes, bias address) when the convolution left its result in pieces - ``y`` is then
     NOT written and the bias NOT applied - else None (``y`` complete).
     ``post`` (make_post): activation / backward mask applied by the convolution's epilogue (lgm_conv_xy_post)."""
-    if TIMER is not None:
-        TIMER.begin("igemm_xy", _conv_flops(g), _conv_bytes(g))
-    if GEMM1X1 and post is None and not partial and _gemm1x1_take(g, x, y, res, w_ptr, bias_ptr):
+    with _timed("igemm_xy", g):
+        return _conv(0, g, x, w_ptr, None, bias_ptr, res, y, partial, post, post_mask)
+
+
+def conv_yx(g: ConvGeom, y, w_ptr: int, bias_ptr: Optional[int], res, x, wt_ptr: Optional[int] = None,
+            partial: bool = False, post: Optional[PostOp] = None, post_mask=None):
+    """``partial`` / ``post``: as conv_xy."""
+    with _timed("igemm_yx", g):
+        return _conv(1, g, y, w_ptr, wt_ptr, bias_ptr, res, x, partial, post, post_mask)
+
+
+def _conv(yx: int, g: ConvGeom, a, w_ptr, wt_ptr, bias_ptr, res, out, partial, post, post_mask):
+    """conv_xy (yx = 0: ``a`` = X side, ``out`` = Y side) / conv_yx (yx = 1: ``a`` = Y side, ``out`` = X side): the first
+    route that takes the layer launches it."""
+    if not yx and GEMM1X1 and post is None and not partial and _gemm1x1_take(g, a, out, res, w_ptr, bias_ptr):
         # mid-sized 1x1 convolutions as ONE un-split GEMM launch of the engine's kernel (no split-K planes, no reducer)
-        M = g.B * g.H * g.W
-        lib().lgm_weng_gemm_epi(x.data_ptr(), w_ptr, y.data_ptr(), M, g.Nw, g.Cw, pitch(x), g.Cw, pitch(y), bias_ptr,
-                                _p(res), pitch(res) if res is not None else 0, stream())
-        if TIMER is not None:
-            TIMER.end()
+        lib().lgm_weng_gemm_epi(a.data_ptr(), w_ptr, out.data_ptr(), g.B * g.H * g.W, g.Nw, g.Cw, pitch(a), g.Cw,
+                                pitch(out), bias_ptr, _p(res), pitch(res) if res is not None else 0, stream())
         return None
     ent = _weng_take(g, w_ptr, res, partial)
     if ent is not None:          # (a BatchNorm-sums request in ``post`` is not served here: its tile count stays 0)
-        _weng_conv(0, g, x, ent, bias_ptr, y, post)
-        if TIMER is not None:
-            TIMER.end()
+        _weng_conv(yx, g, a, ent, bias_ptr, out, post)
         return None
+    if post is None and WINO and _WINO_FLATS and not B3:
+        for kind, taken in ((_F44, _wino4_preferred), (_F22, _wino_supported)):
+            if taken(g, yx):
+                u = _wino_u(w_ptr, bool(yx), f4=kind is _F44)
+                r = u is not None and _wino_call(kind, yx, g, a, u, bias_ptr, res, out, partial and PLANES and res is None)
+                if r:
+                    return None if r is True else r + (bias_ptr,)
+    ws = _conv_ws(g, yx, a.device)
+    # the direct kernels' arguments after the weights: bias, residual, output, workspace
+    tail = (bias_ptr, _p(res), pitch(res) if res is not None else 0, out.data_ptr(), pitch(out),
+            None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4)
+    direct = "lgm_conv_yx" if yx else "lgm_conv_xy"
+    w = (w_ptr, wt_ptr) if yx else (w_ptr,)
     if post is not None:
-        ws = _conv_ws(g, 0, x.device)
         if POSTOPS:
-            lib().lgm_conv_xy_post(ctypes.byref(g), x.data_ptr(), pitch(x), w_ptr, bias_ptr, _p(res),
-                                   pitch(res) if res is not None else 0, y.data_ptr(), pitch(y),
-                                   None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
-                                   ctypes.byref(post), stream())
+            getattr(lib(), direct + "_post")(ctypes.byref(g), a.data_ptr(), pitch(a), *w, *tail, ctypes.byref(post),
+                                             stream())
         else:
-            lib().lgm_conv_xy(ctypes.byref(g), x.data_ptr(), pitch(x), w_ptr, bias_ptr, _p(res),
-                              pitch(res) if res is not None else 0, y.data_ptr(), pitch(y),
-                              None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
-            _apply_post_separately(post, y, post_mask)
-        if TIMER is not None:
-            TIMER.end()
+            getattr(lib(), direct)(ctypes.byref(g), a.data_ptr(), pitch(a), *w, *tail, stream())
+            _apply_post_separately(post, out, post_mask)
         return None
-    if WINO and _WINO_FLATS and not B3 and _wino4_preferred(g, 0):
-        u = _wino4_u(w_ptr, False)
-        if u is not None:
-            r = _wino4_call(0, g, x, u, bias_ptr, res, y, partial and PLANES and res is None)
-            if r:
-                if TIMER is not None:
-                    TIMER.end()
-                return None if r is True else r + (bias_ptr,)
-    if WINO and _WINO_FLATS and not B3 and _wino_supported(g, 0):
-        u = _wino_u(w_ptr, False)
-        if u is not None:
-            r = _wino_call(0, g, x, u, bias_ptr, res, y, partial and PLANES and res is None)
-            if r:
-                if TIMER is not None:
-                    TIMER.end()
-                return None if r is True else r + (bias_ptr,)
-    ws = _conv_ws(g, 0, x.device)
-    pl = _b3_planes(w_ptr, False) if (B3 and _b3_supported(g, 0, pitch(x))) else None
+    pw = wt_ptr if yx else w_ptr         # the input gradient's planes belong to the transposed copy
+    pl = _b3_planes(pw, bool(yx)) if (B3 and pw is not None and _b3_supported(g, yx, pitch(a))) else None
     if pl is not None:
-        lib().lgm_conv3x3_bf16x3(0, ctypes.byref(g), x.data_ptr(), pitch(x), pl[0], pl[1], bias_ptr, _p(res),
-                                 pitch(res) if res is not None else 0, y.data_ptr(), pitch(y),
-                                 None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
+        lib().lgm_conv3x3_bf16x3(yx, ctypes.byref(g), a.data_ptr(), pitch(a), pl[0], pl[1], *tail, stream())
     else:
-        lib().lgm_conv_xy(ctypes.byref(g), x.data_ptr(), pitch(x), w_ptr, bias_ptr, _p(res),
-                          pitch(res) if res is not None else 0, y.data_ptr(), pitch(y),
-                          None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
-    if TIMER is not None:
-        TIMER.end()
+        getattr(lib(), direct)(ctypes.byref(g), a.data_ptr(), pitch(a), *w, *tail, stream())
+    return None
 
 
 def conv_stats(yx: int, g: ConvGeom, a, w_ptr: int, out, wt_ptr: Optional[int] = None):
@@ -602,91 +565,47 @@ def conv_stats(yx: int, g: ConvGeom, a, w_ptr: int, out, wt_ptr: Optional[int] =
     statistics of ``out`` per row tile.  Returns (partials tensor, tiles) - tiles == 0: this geometry could not,
     run lgm_bn_stats on ``out``.  Only the generic implicit-GEMM kernels do this (the DCGAN 4x4 / stride-2 layers)."""
     L = lib()
-    if TIMER is not None:
-        TIMER.begin("igemm_yx" if yx else "igemm_xy", _conv_flops(g), _conv_bytes(g))
-    ent = _weng_take(g, w_ptr, None, False)
-    if ent is not None:          # the engine's output transform leaves no statistics: tiles = 0, the BatchNorm reduces itself
-        _weng_conv(yx, g, a, ent, None, out, None)
-        if TIMER is not None:
-            TIMER.end()
-        return None, 0
-    ws = _conv_ws(g, yx, a.device)
-    oc = g.Cw if yx else g.Nw
-    stats = torch.empty(L.lgm_conv_stats_floats(ctypes.byref(g), yx), dtype=torch.float32, device=a.device)
-    nt = ctypes.c_int(0)
-    wsp, wsb = (None, 0) if ws is None else (ws.data_ptr(), ws.numel() * 4)
-    if yx:
-        L.lgm_conv_yx_stats(ctypes.byref(g), a.data_ptr(), pitch(a), w_ptr, wt_ptr, out.data_ptr(), pitch(out), wsp, wsb,
-                            stats.data_ptr(), ctypes.addressof(nt), stream())
-    else:
-        L.lgm_conv_xy_stats(ctypes.byref(g), a.data_ptr(), pitch(a), w_ptr, out.data_ptr(), pitch(out), wsp, wsb,
-                            stats.data_ptr(), ctypes.addressof(nt), stream())
-    if TIMER is not None:
-        TIMER.end()
+    with _timed("igemm_yx" if yx else "igemm_xy", g):
+        ent = _weng_take(g, w_ptr, None, False)
+        if ent is not None:      # the engine's output transform leaves no statistics: tiles = 0, the BatchNorm reduces itself
+            _weng_conv(yx, g, a, ent, None, out, None)
+            return None, 0
+        ws = _conv_ws(g, yx, a.device)
+        oc = g.Cw if yx else g.Nw
+        stats = torch.empty(L.lgm_conv_stats_floats(ctypes.byref(g), yx), dtype=torch.float32, device=a.device)
+        nt = ctypes.c_int(0)
+        wsp, wsb = (None, 0) if ws is None else (ws.data_ptr(), ws.numel() * 4)
+        if yx:
+            L.lgm_conv_yx_stats(ctypes.byref(g), a.data_ptr(), pitch(a), w_ptr, wt_ptr, out.data_ptr(), pitch(out), wsp,
+                                wsb, stats.data_ptr(), ctypes.addressof(nt), stream())
+        else:
+            L.lgm_conv_xy_stats(ctypes.byref(g), a.data_ptr(), pitch(a), w_ptr, out.data_ptr(), pitch(out), wsp, wsb,
+                                stats.data_ptr(), ctypes.addressof(nt), stream())
     assert oc == out.shape[-1]
     return stats, int(nt.value)
 
 
-def conv_yx(g: ConvGeom, y, w_ptr: int, bias_ptr: Optional[int], res, x, wt_ptr: Optional[int] = None,
-            partial: bool = False, post: Optional[PostOp] = None, post_mask=None):
-    """``partial`` / ``post``: as conv_xy."""
-    if TIMER is not None:
-        TIMER.begin("igemm_yx", _conv_flops(g), _conv_bytes(g))
-    ent = _weng_take(g, w_ptr, res, partial)
-    if ent is not None:
-        _weng_conv(1, g, y, ent, bias_ptr, x, post)
-        if TIMER is not None:
-            TIMER.end()
-        return None
-    if post is not None:
-        ws = _conv_ws(g, 1, y.device)
-        if POSTOPS:
-            lib().lgm_conv_yx_post(ctypes.byref(g), y.data_ptr(), pitch(y), w_ptr, wt_ptr, bias_ptr, _p(res),
-                                   pitch(res) if res is not None else 0, x.data_ptr(), pitch(x),
-                                   None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
-                                   ctypes.byref(post), stream())
-        else:
-            lib().lgm_conv_yx(ctypes.byref(g), y.data_ptr(), pitch(y), w_ptr, wt_ptr, bias_ptr, _p(res),
-                              pitch(res) if res is not None else 0, x.data_ptr(), pitch(x),
-                              None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
-            _apply_post_separately(post, x, post_mask)
-        if TIMER is not None:
-            TIMER.end()
-        return None
-    if WINO and _WINO_FLATS and not B3 and _wino4_preferred(g, 1):
-        u = _wino4_u(w_ptr, True)
-        if u is not None:
-            r = _wino4_call(1, g, y, u, bias_ptr, res, x, partial and PLANES and res is None)
-            if r:
-                if TIMER is not None:
-                    TIMER.end()
-                return None if r is True else r + (bias_ptr,)
-    if WINO and _WINO_FLATS and not B3 and _wino_supported(g, 1):
-        u = _wino_u(w_ptr, True)
-        if u is not None:
-            r = _wino_call(1, g, y, u, bias_ptr, res, x, partial and PLANES and res is None)
-            if r:
-                if TIMER is not None:
-                    TIMER.end()
-                return None if r is True else r + (bias_ptr,)
-    ws = _conv_ws(g, 1, y.device)
-    pl = _b3_planes(wt_ptr, True) if (B3 and wt_ptr is not None and _b3_supported(g, 1, pitch(y))) else None
-    if pl is not None:
-        lib().lgm_conv3x3_bf16x3(1, ctypes.byref(g), y.data_ptr(), pitch(y), pl[0], pl[1], bias_ptr, _p(res),
-                                 pitch(res) if res is not None else 0, x.data_ptr(), pitch(x),
-                                 None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
-        if TIMER is not None:
-            TIMER.end()
-        return
-    lib().lgm_conv_yx(ctypes.byref(g), y.data_ptr(), pitch(y), w_ptr, wt_ptr, bias_ptr, _p(res),
-                      pitch(res) if res is not None else 0, x.data_ptr(), pitch(x),
-                      None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, stream())
-    if TIMER is not None:
-        TIMER.end()
-
-
 _WGRAD_WS = {}        # deferred mode: one persistent slab workspace per weight (keyed by its gradient address)
-_WGRAD_TABLES = {}    # tuple of descriptor rows -> (device table, blocks)
+_WGRAD_TABLES = {}    # tuple of descriptor rows -> (device table, rows, blocks)
+
+
+def _persistent(key, nbytes, device):
+    ws = _WGRAD_WS.get(key)
+    if ws is None:
+        ws = _WGRAD_WS[key] = torch.empty(max(nbytes // 4 + 4, 16), dtype=torch.float32, device=device)
+    return ws
+
+
+def _slabs(gw_ptr: int, nbytes: int, defer, device):
+    """The slab buffer of a weight gradient whose input gradient shares its launch, and its descriptor: the weight's
+    own persistent buffer when the reduction is deferred, else the shared pair buffer (the slabs must not share the
+    generic workspace with the input gradient's split-K planes) and None."""
+    if defer is None:
+        return _grown(_PAIR_SLABS, device, nbytes, nbytes // 4 + 64), None
+    return _persistent((gw_ptr, nbytes), nbytes, device), (ctypes.c_int64 * 8)()
+
+
+_PAIR_SLABS = {}
 
 
 WGRAD_QUEUE = _os.environ.get("LGM_NO_WGRAD_QUEUE", "0") != "1"       # A/B switch: generic weight gradients launch at once
@@ -694,11 +613,8 @@ WGRAD_QUEUE = _os.environ.get("LGM_NO_WGRAD_QUEUE", "0") != "1"       # A/B swit
 
 def wgrad_queue_flush():
     """Issue the generic weight-gradient launches still waiting for partners (lgm_wgrad_queue_*)."""
-    if TIMER is not None:            # (their FLOPs were counted where they were queued)
-        TIMER.begin("wgrad", 0.0, 0.0)
-    lib().lgm_wgrad_queue_flush()
-    if TIMER is not None:
-        TIMER.end()
+    with _timed("wgrad"):            # (their FLOPs were counted where they were queued)
+        lib().lgm_wgrad_queue_flush()
 
 
 def conv_wgrad(g: ConvGeom, y, x, gw_ptr: int, beta: float, gbias_ptr: Optional[int] = None, defer=None, queue: bool = False):
@@ -709,18 +625,13 @@ def conv_wgrad(g: ConvGeom, y, x, gw_ptr: int, beta: float, gbias_ptr: Optional[
     L = lib()
     queue = queue and defer is not None and WGRAD_QUEUE
     nbytes = L.lgm_conv_wgrad_workspace(ctypes.byref(g))
-    if TIMER is not None:
-        TIMER.begin("wgrad", _conv_flops(g), _conv_bytes(g))
-    if defer is None:
-        ws = workspace(nbytes, y.device)
-        L.lgm_conv_wgrad(ctypes.byref(g), y.data_ptr(), pitch(y), x.data_ptr(), pitch(x), gw_ptr, gbias_ptr, beta,
-                         ws.data_ptr(), ws.numel() * 4, stream())
-    else:
-        key = (gw_ptr, nbytes)
-        ws = _WGRAD_WS.get(key)
-        if ws is None:
-            ws = torch.empty(max(nbytes // 4 + 4, 16), dtype=torch.float32, device=y.device)
-            _WGRAD_WS[key] = ws
+    with _timed("wgrad", g):
+        if defer is None:
+            ws = workspace(nbytes, y.device)
+            L.lgm_conv_wgrad(ctypes.byref(g), y.data_ptr(), pitch(y), x.data_ptr(), pitch(x), gw_ptr, gbias_ptr, beta,
+                             ws.data_ptr(), ws.numel() * 4, stream())
+            return
+        ws = _persistent((gw_ptr, nbytes), nbytes, y.device)
         desc = (ctypes.c_int64 * 8)()
         if queue:
             L.lgm_wgrad_queue_enable(1)
@@ -732,11 +643,9 @@ def conv_wgrad(g: ConvGeom, y, x, gw_ptr: int, beta: float, gbias_ptr: Optional[
                 L.lgm_wgrad_queue_enable(0)
         if desc[6] > 1:
             defer.append(tuple(desc))
-    if TIMER is not None:
-        TIMER.end()
 
 
-_PAIR_OK = {}
+_PAIR_OK = _plan_cache()
 
 
 # Up to four large-map layers' weight gradients in one launch (lgm_conv3x3_wino_wgradn): LGM_NO_WGRAD2=1 issues them
@@ -746,8 +655,20 @@ _PAIR_OK = {}
 # group above two; with only the F(2x2) kernel grouping, n = 4 was 10.11 vs 10.08).
 WGRAD2 = _os.environ.get("LGM_NO_WGRAD2", "0") != "1"
 WGRAD_GROUP = max(2, min(8, int(_os.environ.get("LGM_WGRAD_GROUP", "4"))))
-_WG2_OK = {}
-_WG2_WS = {}
+_WG2_OK = _plan_cache()
+_WG2_WS = _plan_cache()
+
+# Up to four 1x1 layers' weight gradients in one launch of the streaming 1x1 kernel (lgm_wgrad1x1_group): a stand-alone
+# launch is ~13 us of prologue / epilogue / ramp around a K loop at the MFMA rate, and nothing reads a weight gradient
+# before the optimizer.  LGM_NO_WGRAD1X1_GROUP=1 issues them singly (A/B switch).
+WGRAD1X1_GROUP = _os.environ.get("LGM_NO_WGRAD1X1_GROUP", "0") != "1"
+_W1G_OK = _plan_cache()
+_W1G_WS = _plan_cache()
+
+# the grouped weight-gradient launches: (launch; its _supported and _workspaces queries take the same prefix, answer cache,
+# workspace-size cache)
+_WGRAD3X3 = ("lgm_conv3x3_wino_wgradn", _WG2_OK, _WG2_WS)
+_WGRAD1X1 = ("lgm_wgrad1x1_group", _W1G_OK, _W1G_WS)
 
 
 class WgradItem(ctypes.Structure):
@@ -768,19 +689,68 @@ def _geom_array(geoms):
     return arr
 
 
-def wgrad_group_supported(geoms) -> bool:
-    key = tuple(_gkey(g) for g in geoms)
-    v = _WG2_OK.get(key)
-    if v is None:
+def _group_supported(kind, geoms) -> bool:
+    launch, ok, _ = kind
+
+    def ask():
         arr = _geom_array(geoms)        # bound to a local: the C side reads it during the call
-        v = bool(lib().lgm_conv3x3_wino_wgradn_supported(len(geoms), ctypes.addressof(arr)))
-        del arr
-        _WG2_OK[key] = v
-    return v
+        return bool(getattr(lib(), launch + "_supported")(len(geoms), ctypes.addressof(arr)))
+    return _memo(ok, tuple(_gkey(g) for g in geoms), ask)
+
+
+def _wgrad_group(kind, entries, defer):
+    """entries = 2 ... 4 of (geometry, gy, x, gw address, beta, gbias address): all weight gradients in ONE launch of
+    ``kind`` (_WGRAD3X3 / _WGRAD1X1); slab descriptors of the layers that split join ``defer`` (the bucket's batched
+    reduction)."""
+    L = lib()
+    launch, _, sizes = kind
+    n = len(entries)
+    geoms = [e[0] for e in entries]
+
+    def plan():
+        out = (ctypes.c_int64 * n)()
+        arr = _geom_array(geoms)        # bound to a local: the C side reads it during the call
+        getattr(L, launch + "_workspaces")(n, ctypes.addressof(arr), ctypes.addressof(out))
+        # never smaller than the single-layer plan's need: the same slab buffer serves a layer whichever way it runs
+        return tuple(max(int(out[k]), int(L.lgm_conv_wgrad_workspace(ctypes.byref(g)))) for k, g in enumerate(geoms))
+    need = _memo(sizes, tuple(_gkey(g) for g in geoms), plan)
+    items = (WgradItem * n)()
+    descs = []
+    for k, (g, gy, x, gw_ptr, beta, gb_ptr) in enumerate(entries):
+        ws = _persistent((gw_ptr, need[k]), need[k], gy.device)
+        desc = (ctypes.c_int64 * 8)()
+        descs.append(desc)
+        items[k] = WgradItem(ctypes.addressof(g), gy.data_ptr(), pitch(gy), x.data_ptr(), pitch(x), gw_ptr, gb_ptr, beta,
+                             ws.data_ptr(), ws.numel() * 4, ctypes.addressof(desc))
+    with _timed("wgrad", geoms):
+        getattr(L, launch)(n, ctypes.addressof(items), stream())
+    for desc in descs:
+        if desc[6] > 1:
+            defer.append(tuple(desc))
+
+
+def wgrad_group_supported(geoms) -> bool:
+    return _group_supported(_WGRAD3X3, geoms)
+
+
+def wgrad1x1_group_supported(geoms) -> bool:
+    return _group_supported(_WGRAD1X1, geoms)
+
+
+def conv_wgrad_group(entries, defer):
+    _wgrad_group(_WGRAD3X3, entries, defer)
+
+
+def conv_wgrad1x1_group(entries, defer):
+    _wgrad_group(_WGRAD1X1, entries, defer)
 
 
 def wgrad2_supported(ga: ConvGeom, gb: ConvGeom) -> bool:
     return wgrad_group_supported([ga, gb])
+
+
+def conv_wgrad2(a, b, defer):
+    conv_wgrad_group([a, b], defer)
 
 
 def wgrad_queueable(g: ConvGeom, gy, x) -> bool:
@@ -793,70 +763,6 @@ def wgrad_queueable(g: ConvGeom, gy, x) -> bool:
     return wgrad_group_supported([g, g])
 
 
-def conv_wgrad_group(entries, defer):
-    """entries = 2 ... 4 of (geometry, gy, x, gw address, beta, gbias address): all weight gradients in ONE launch; their
-    slab descriptors join ``defer`` (the bucket's batched reduction)."""
-    L = lib()
-    n = len(entries)
-    geoms = [e[0] for e in entries]
-    wkey = tuple(_gkey(g) for g in geoms)
-    need = _WG2_WS.get(wkey)
-    if need is None:
-        out = (ctypes.c_int64 * n)()
-        arr = _geom_array(geoms)        # bound to a local: the C side reads it during the call
-        L.lgm_conv3x3_wino_wgradn_workspaces(n, ctypes.addressof(arr), ctypes.addressof(out))
-        del arr
-        # never smaller than the single-layer plan's need: the same slab buffer serves a layer whichever way it runs
-        need = tuple(max(int(out[k]), int(L.lgm_conv_wgrad_workspace(ctypes.byref(g)))) for k, g in enumerate(geoms))
-        _WG2_WS[wkey] = need
-    items = (WgradItem * n)()
-    descs = []
-    flops = nbytes_alg = 0.0
-    for k, (g, gy, x, gw_ptr, beta, gb_ptr) in enumerate(entries):
-        key = (gw_ptr, need[k])
-        ws = _WGRAD_WS.get(key)
-        if ws is None:
-            ws = torch.empty(max(need[k] // 4 + 4, 16), dtype=torch.float32, device=gy.device)
-            _WGRAD_WS[key] = ws
-        desc = (ctypes.c_int64 * 8)()
-        descs.append(desc)
-        items[k] = WgradItem(ctypes.addressof(g), gy.data_ptr(), pitch(gy), x.data_ptr(), pitch(x), gw_ptr, gb_ptr, beta,
-                             ws.data_ptr(), ws.numel() * 4, ctypes.addressof(desc))
-        flops += _conv_flops(g)
-        nbytes_alg += _conv_bytes(g)
-    if TIMER is not None:
-        TIMER.begin("wgrad", flops, nbytes_alg)
-    L.lgm_conv3x3_wino_wgradn(n, ctypes.addressof(items), stream())
-    if TIMER is not None:
-        TIMER.end()
-    for desc in descs:
-        if desc[6] > 1:
-            defer.append(tuple(desc))
-
-
-def conv_wgrad2(a, b, defer):
-    conv_wgrad_group([a, b], defer)
-
-
-# Up to four 1x1 layers' weight gradients in one launch of the streaming 1x1 kernel (lgm_wgrad1x1_group): a stand-alone
-# launch is ~13 us of prologue / epilogue / ramp around a K loop at the MFMA rate, and nothing reads a weight gradient
-# before the optimizer.  LGM_NO_WGRAD1X1_GROUP=1 issues them singly (A/B switch).
-WGRAD1X1_GROUP = _os.environ.get("LGM_NO_WGRAD1X1_GROUP", "0") != "1"
-_W1G_OK = {}
-_W1G_WS = {}
-
-
-def wgrad1x1_group_supported(geoms) -> bool:
-    key = tuple(_gkey(g) for g in geoms)
-    v = _W1G_OK.get(key)
-    if v is None:
-        arr = _geom_array(geoms)        # bound to a local: the C side reads it during the call
-        v = bool(lib().lgm_wgrad1x1_group_supported(len(geoms), ctypes.addressof(arr)))
-        del arr
-        _W1G_OK[key] = v
-    return v
-
-
 def wgrad1x1_queueable(g: ConvGeom, gy, x) -> bool:
     """1x1 layers whose weight gradient takes the streaming kernel on its own launch today (never the one-launch
     gemm_bwd_pair): it can wait for partners."""
@@ -867,46 +773,6 @@ def wgrad1x1_queueable(g: ConvGeom, gy, x) -> bool:
     return wgrad1x1_group_supported([g, g])
 
 
-def conv_wgrad1x1_group(entries, defer):
-    """entries = 2 ... 4 of (geometry, gy, x, gw address, beta, gbias address), 1x1 layers: all weight gradients in ONE
-    launch; slab descriptors of the layers that split join ``defer``."""
-    L = lib()
-    n = len(entries)
-    geoms = [e[0] for e in entries]
-    wkey = tuple(_gkey(g) for g in geoms)
-    need = _W1G_WS.get(wkey)
-    if need is None:
-        out = (ctypes.c_int64 * n)()
-        arr = _geom_array(geoms)
-        L.lgm_wgrad1x1_group_workspaces(n, ctypes.addressof(arr), ctypes.addressof(out))
-        del arr
-        need = tuple(max(int(out[k]), int(L.lgm_conv_wgrad_workspace(ctypes.byref(g)))) for k, g in enumerate(geoms))
-        _W1G_WS[wkey] = need
-    items = (WgradItem * n)()
-    descs = []
-    flops = nbytes_alg = 0.0
-    for k, (g, gy, x, gw_ptr, beta, gb_ptr) in enumerate(entries):
-        key = (gw_ptr, need[k])
-        ws = _WGRAD_WS.get(key)
-        if ws is None:
-            ws = torch.empty(max(need[k] // 4 + 4, 16), dtype=torch.float32, device=gy.device)
-            _WGRAD_WS[key] = ws
-        desc = (ctypes.c_int64 * 8)()
-        descs.append(desc)
-        items[k] = WgradItem(ctypes.addressof(g), gy.data_ptr(), pitch(gy), x.data_ptr(), pitch(x), gw_ptr, gb_ptr, beta,
-                             ws.data_ptr(), ws.numel() * 4, ctypes.addressof(desc))
-        flops += _conv_flops(g)
-        nbytes_alg += _conv_bytes(g)
-    if TIMER is not None:
-        TIMER.begin("wgrad", flops, nbytes_alg)
-    L.lgm_wgrad1x1_group(n, ctypes.addressof(items), stream())
-    if TIMER is not None:
-        TIMER.end()
-    for desc in descs:
-        if desc[6] > 1:
-            defer.append(tuple(desc))
-
-
 def conv_bwd_pair(g: ConvGeom, gy, x, w_ptr: int, gw_ptr: int, beta: float, gbias_ptr: Optional[int], defer, res, gx,
                   partial: bool = False):
     """Input gradient AND weight gradient of a 3x3 layer in ONE launch (lgm_conv3x3_wino_bwd): at small per-GPU batches
@@ -915,7 +781,7 @@ def conv_bwd_pair(g: ConvGeom, gy, x, w_ptr: int, gw_ptr: int, beta: float, gbia
     or, with ``partial``, the planes tuple of conv_yx(partial=True)."""
     if not (WINO and _WINO_FLATS and not B3) or g.KH != 3 or g.KW != 3:
         return False
-    if _wino4_preferred(g, 1) and _wino4_u(w_ptr, True) is not None:
+    if _wino4_preferred(g, 1) and _wino_u(w_ptr, True, f4=True) is not None:
         return False        # large maps: F(4x4) input gradient (conv_yx) + the stand-alone Winograd weight gradient
     u = _wino_u(w_ptr, True)
     if u is None:
@@ -925,44 +791,25 @@ def conv_bwd_pair(g: ConvGeom, gy, x, w_ptr: int, gw_ptr: int, beta: float, gbia
     if res is not None and res.data_ptr() % 16:
         return False
     key = (g.B, g.H, g.W, g.Cw, g.Nw, pitch(gy), pitch(x), pitch(gx), pitch(res) if res is not None else 0)
-    ok = _PAIR_OK.get(key)
-    if ok is None:
-        ok = bool(lib().lgm_conv3x3_wino_bwd_supported(ctypes.byref(g), key[5], key[6], key[7], key[8]))
-        _PAIR_OK[key] = ok
-    if not ok:
+    if not _memo(_PAIR_OK, key, lambda: bool(lib().lgm_conv3x3_wino_bwd_supported(ctypes.byref(g), *key[5:]))):
         return False
     L = lib()
     partial = bool(partial and PLANES and res is None)
-    wkey = (g.B, g.H, g.W, g.Cw, g.Nw, "pair", partial)
-    sizes = _WINO_WS.get(wkey)
-    if sizes is None:
+
+    def plan():
         two = (ctypes.c_int64 * 2)()
         L.lgm_conv3x3_wino_bwd_workspaces(ctypes.byref(g), 1 if partial else 0, ctypes.addressof(two))
-        sizes = (int(two[0]), int(two[1]))
-        _WINO_WS[wkey] = sizes
-    n, nbytes = sizes
+        return (int(two[0]), int(two[1]))
+    n, nbytes = _memo(_WINO_WS, (g.B, g.H, g.W, g.Cw, g.Nw, "pair", partial), plan)
     dws = workspace(n, gy.device) if n > 0 else None
-    if TIMER is not None:
-        TIMER.begin("bwd_pair", 2.0 * _conv_flops(g), 2.0 * _conv_bytes(g))
-    if defer is None:
-        # the slabs must not share the generic workspace with the input gradient's split-K planes
-        wws = _pair_slabs(nbytes, gy.device)
-        desc = None
-    else:
-        k2 = (gw_ptr, nbytes)
-        wws = _WGRAD_WS.get(k2)
-        if wws is None:
-            wws = torch.empty(max(nbytes // 4 + 4, 16), dtype=torch.float32, device=gy.device)
-            _WGRAD_WS[k2] = wws
-        desc = (ctypes.c_int64 * 8)()
-    part = (ctypes.c_int64 * 2)() if partial else None
-    L.lgm_conv3x3_wino_bwd(ctypes.byref(g), gy.data_ptr(), pitch(gy), x.data_ptr(), pitch(x), u, _p(res),
-                           pitch(res) if res is not None else 0, gx.data_ptr(), pitch(gx),
-                           None if dws is None else dws.data_ptr(), 0 if dws is None else dws.numel() * 4,
-                           None if part is None else ctypes.addressof(part), gw_ptr, gbias_ptr, beta, wws.data_ptr(),
-                           wws.numel() * 4, None if desc is None else ctypes.addressof(desc), stream())
-    if TIMER is not None:
-        TIMER.end()
+    with _timed("bwd_pair", g, 2.0):
+        wws, desc = _slabs(gw_ptr, nbytes, defer, gy.device)
+        part = (ctypes.c_int64 * 2)() if partial else None
+        L.lgm_conv3x3_wino_bwd(ctypes.byref(g), gy.data_ptr(), pitch(gy), x.data_ptr(), pitch(x), u, _p(res),
+                               pitch(res) if res is not None else 0, gx.data_ptr(), pitch(gx),
+                               None if dws is None else dws.data_ptr(), 0 if dws is None else dws.numel() * 4,
+                               None if part is None else ctypes.addressof(part), gw_ptr, gbias_ptr, beta, wws.data_ptr(),
+                               wws.numel() * 4, None if desc is None else ctypes.addressof(desc), stream())
     if desc is not None and desc[6] > 1:
         defer.append(tuple(desc))
     if part is not None and part[0] > 1:
@@ -976,63 +823,37 @@ def conv_bwd_generic(g: ConvGeom, gy, x, w_ptr: int, wt_ptr: Optional[int], gw_p
     pick the two kernels that can share a grid (the 1x1 convolutions and linears at small row counts), else exactly
     conv_wgrad + conv_yx."""
     L = lib()
-    if TIMER is not None:
-        TIMER.begin("bwd_pair", 2.0 * _conv_flops(g), 2.0 * _conv_bytes(g))
-    dws = _conv_ws(g, 1, gy.device)
-    nbytes = L.lgm_conv_wgrad_workspace(ctypes.byref(g))
-    if defer is None:
-        wws, desc = _pair_slabs(nbytes, gy.device), None
-    else:
-        k2 = (gw_ptr, nbytes)
-        wws = _WGRAD_WS.get(k2)
-        if wws is None:
-            wws = torch.empty(max(nbytes // 4 + 4, 16), dtype=torch.float32, device=gy.device)
-            _WGRAD_WS[k2] = wws
-        desc = (ctypes.c_int64 * 8)()
-    args = (ctypes.byref(g), gy.data_ptr(), pitch(gy), x.data_ptr(), pitch(x), w_ptr, wt_ptr, _p(res),
-            pitch(res) if res is not None else 0, gx.data_ptr(), pitch(gx),
-            None if dws is None else dws.data_ptr(), 0 if dws is None else dws.numel() * 4, gw_ptr, gbias_ptr,
-            beta, wws.data_ptr(), wws.numel() * 4, None if desc is None else ctypes.addressof(desc))
-    queue = queue and desc is not None and WGRAD_QUEUE      # (see conv_wgrad: a stand-alone weight-gradient launch may wait)
-    if queue:
-        L.lgm_wgrad_queue_enable(1)
-    try:
-        if post is None or not POSTOPS:
-            L.lgm_conv_bwd_pair(*args, stream())
-            if post is not None:
-                _apply_post_separately(post, gx, post_mask)
-        else:                # ``post_mask`` only keeps the mask tensor alive for the duration of the call
-            L.lgm_conv_bwd_pair_post(*args, ctypes.byref(post), stream())
-    finally:
+    with _timed("bwd_pair", g, 2.0):
+        dws = _conv_ws(g, 1, gy.device)
+        nbytes = L.lgm_conv_wgrad_workspace(ctypes.byref(g))
+        wws, desc = _slabs(gw_ptr, nbytes, defer, gy.device)
+        args = (ctypes.byref(g), gy.data_ptr(), pitch(gy), x.data_ptr(), pitch(x), w_ptr, wt_ptr, _p(res),
+                pitch(res) if res is not None else 0, gx.data_ptr(), pitch(gx),
+                None if dws is None else dws.data_ptr(), 0 if dws is None else dws.numel() * 4, gw_ptr, gbias_ptr,
+                beta, wws.data_ptr(), wws.numel() * 4, None if desc is None else ctypes.addressof(desc))
+        queue = queue and desc is not None and WGRAD_QUEUE      # (see conv_wgrad: a stand-alone weight-gradient launch may wait)
         if queue:
-            L.lgm_wgrad_queue_enable(0)
-    if TIMER is not None:
-        TIMER.end()
+            L.lgm_wgrad_queue_enable(1)
+        try:
+            if post is None or not POSTOPS:
+                L.lgm_conv_bwd_pair(*args, stream())
+                if post is not None:
+                    _apply_post_separately(post, gx, post_mask)
+            else:                # ``post_mask`` only keeps the mask tensor alive for the duration of the call
+                L.lgm_conv_bwd_pair_post(*args, ctypes.byref(post), stream())
+        finally:
+            if queue:
+                L.lgm_wgrad_queue_enable(0)
     if desc is not None and desc[6] > 1:
         defer.append(tuple(desc))
 
 
-_PAIR_SLABS = {}
-
-
-def _pair_slabs(nbytes: int, device) -> torch.Tensor:
-    key = torch.device(device).index or 0
-    ws = _PAIR_SLABS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        if ws is not None:
-            _WS_RETIRED.append(ws)
-        ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=device)
-        _PAIR_SLABS[key] = ws
-    return ws
-
-
 def clear_plan_caches():
-    """Forget every per-geometry answer of the library's planners (kernel choice, split counts, workspace sizes, statistics
-    row counts).  Runs by itself after lgm_set_cu_margin / lgm_wino4_set_light (lgm_hip/_lib.py: on_selection_change):
-    those knobs change what the queries return.  Buffers are kept (captured graphs have their addresses baked in); they are
-    looked up by size, so a plan that now needs more gets a new one."""
-    for d in (_CONV_WS_BYTES, _WINO_OK, _WINO_WS, _WINO4_OK, _EPI_STATS, _WINO_FITS, _PAIR_OK, _WG2_OK, _WG2_WS,
-              _W1G_OK, _W1G_WS, _GN_PLANES_OK):
+    """Forget every per-geometry answer of the library's planners (every dict made by _plan_cache: kernel choice, split
+    counts, workspace sizes, statistics row counts).  Runs by itself after lgm_set_cu_margin / lgm_wino4_set_light
+    (lgm_hip/_lib.py: on_selection_change): those knobs change what the queries return.  Buffers are kept (captured
+    graphs have their addresses baked in); they are looked up by size, so a plan that now needs more gets a new one."""
+    for d in _PLAN_CACHES:
         d.clear()
 
 
@@ -1053,17 +874,9 @@ def wgrad_reduce_batch(rows, device):
     key = tuple(rows)
     ent = _WGRAD_TABLES.get(key)
     if ent is None:
-        tab, blk = [], 0
-        for r in rows:
-            tab.append(list(r) + [blk])
-            blk += (r[3] + r[5] + 255) // 256
-        ent = (torch.tensor(tab, dtype=torch.int64, device=device).contiguous(), blk)
-        _WGRAD_TABLES[key] = ent
-    if TIMER is not None:
-        TIMER.begin("wgrad", 0.0, 0.0)
-    lib().lgm_wgrad_reduce_batch(ent[0].data_ptr(), len(rows), ent[1], stream())
-    if TIMER is not None:
-        TIMER.end()
+        ent = _WGRAD_TABLES[key] = make_reducer(rows, device)
+    with _timed("wgrad"):
+        launch_reducer(ent)
     rows.clear()
 
 
@@ -1126,17 +939,12 @@ class GNSaved:
     __slots__ = ("mean", "rstd", "A", "Bc")
 
 
-_GN_PLANES_OK = {}
+_GN_PLANES_OK = _plan_cache()
 
 
 def gn_planes_ok(B, HW, C, G) -> bool:
     """The one-pass GroupNorm kernels (forward AND backward) exist for this shape: they can sum split-K planes."""
-    key = (B, HW, C, G)
-    v = _GN_PLANES_OK.get(key)
-    if v is None:
-        v = bool(lib().lgm_gn_planes_supported(B, HW, C, G))
-        _GN_PLANES_OK[key] = v
-    return v
+    return _memo(_GN_PLANES_OK, (B, HW, C, G), lambda: bool(lib().lgm_gn_planes_supported(B, HW, C, G)))
 
 
 _GN_WS = {}
@@ -1145,14 +953,7 @@ _GN_WS = {}
 def _gn_scratch(nfloats: int, device) -> torch.Tensor:
     """GroupNorm-backward scratch (S1, S2, P, Q, R rows).  NOT the shared workspace: the split-K planes of the
     producing convolution may still be sitting there when the backward kernel runs."""
-    key = torch.device(device).index or 0
-    ws = _GN_WS.get(key)
-    if ws is None or ws.numel() < nfloats:
-        if ws is not None:
-            _WS_RETIRED.append(ws)          # a captured graph may have its address baked in
-        ws = torch.empty(max(int(nfloats * 1.25) + 64, 1 << 16), dtype=torch.float32, device=device)
-        _GN_WS[key] = ws
-    return ws
+    return _grown(_GN_WS, device, 4 * nfloats, max(int(nfloats * 1.25) + 64, 1 << 16))
 
 
 def gn_fwd(x, G, eps, gamma_ptr, beta_ptr, ss, act: bool, res, y, planes=None) -> GNSaved:
@@ -1359,14 +1160,6 @@ def linattn_bwd(qkv, mem_ptr, gout, ctx, kstat, heads, dim_head, M, gqkv, gmem_p
         defer.append(tuple(desc))
 
 
-def _persistent(key, nbytes, device):
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        ws = torch.empty(max(nbytes // 4 + 4, 16), dtype=torch.float32, device=device)
-        _WGRAD_WS[key] = ws
-    return ws
-
-
 # The fused LinearAttention backward tail (csrc/linattn_fused.hip) for layers with at least this many (image, 128-pixel
 # tile) work items: one item is four heads in a row on ONE CU (55 us), so below a full round of the chip the three
 # separate launches - which spread over more workgroups - are faster (measured).  LGM_NO_LA_FUSED=1: off.
@@ -1477,16 +1270,13 @@ def posemb(t, dim, theta, out):
 # ds_bpermute butterfly per weight row, while the six separate launches it would replace are pipelined MFMA GEMMs of 5 - 6 us
 # each: 32.8 us fused vs 31.8 us for the six forward launches, 89 us vs 29 us backward.
 TIME_MLP = _os.environ.get("LGM_TIME_MLP", "0") == "1"
-_TIME_MLP_OK = {}
+_TIME_MLP_OK = _plan_cache()
 
 
 def time_mlp_ok(dim: int, time_dim: int, l1, l2) -> bool:
     """The fused time-embedding kernels take these widths (dense, unpadded Linear weights)."""
-    key = (dim, time_dim)
-    v = _TIME_MLP_OK.get(key)
-    if v is None:
-        v = bool(TIME_MLP and dim % 4 == 0 and time_dim % 4 == 0 and lib().lgm_time_mlp_supported(dim, time_dim))
-        _TIME_MLP_OK[key] = v
+    v = _memo(_TIME_MLP_OK, (dim, time_dim), lambda: bool(TIME_MLP and dim % 4 == 0 and time_dim % 4 == 0 and
+                                                          lib().lgm_time_mlp_supported(dim, time_dim)))
     return v and l1.bias is not None and l2.bias is not None
 
 
