@@ -9,32 +9,8 @@
 // Everything a (batch, head) pair needs lives in LDS/registers; reductions use fixed orders.
 #include "lgm_common.h"
 
-// MFMA kernels for the linear-attention contractions (linattn_mfma.hip)
-int lgm_linattn_ctx_launch(int mode, const float* qkv, long pitch, const float* mem_kv, const float* gout,
-                           long gout_pitch, const float* ctx_in, int B, int n, int heads, int M, float scale,
-                           float* ctx_out, float* kmax, float* ksum, float* r_out, hipStream_t s,
-                           const float* kmax_in = nullptr, const float* ksum_in = nullptr,
-                           float* gmem_partial = nullptr);
-// fused backward tail (linattn_fused.hip) and the single-layer slab reducer (conv_igemm.hip)
-int lgm_linattn_bwd_fused_launch(const float* qkv, long pitch, const float* gout, long gout_pitch, const float* ctx,
-                                 const float* gctx, const float* kmax, const float* ksum, const float* rvec,
-                                 const float* xn, long xn_pitch, const float* wt, int B, int n, float scale,
-                                 float* gxn, long gxn_pitch, float* slabs, int* blocks_out, hipStream_t s);
-int lgm_wgrad_reduce_launch(const float* ws, long slab, float* gw, long n_w, float* gb, long n_b, int splits, float beta,
-                            hipStream_t s);
-int lgm_linattn_out_fused_launch(const float* qkv, long pitch, const float* ctx, const float* wout, const float* bout,
-                                 const float* g, const float* x, long x_pitch, float* ao, long ao_pitch, float* o2,
-                                 long o2_pitch, float* y, long y_pitch, int B, int n, int Cout, float scale, hipStream_t s);
-int lgm_linattn_bwd_launch(const float* qkv, long pitch, const float* mem_kv, const float* gout, long gout_pitch,
-                           const float* ctx, const float* gctx, const float* kmax, const float* ksum,
-                           const float* rvec, int B, int n, int heads, int M, float scale, float* gqkv,
-                           long gq_pitch, float* gmem_partial, hipStream_t s);
-// tiled full attention for n > 128 query pixels (attention_tiled.hip)
-int lgm_attn_tiled_fwd_launch(const float* qkv, long pitch, const float* mem_kv, int B, int n, int heads, int M,
-                              float scale, float* out, long out_pitch, float* lse, hipStream_t s);
-int lgm_attn_tiled_bwd_launch(const float* qkv, long pitch, const float* mem_kv, const float* out, long out_pitch,
-                              const float* gout, long gout_pitch, const float* lse, int B, int n, int heads, int M,
-                              float scale, float* gqkv, long gq_pitch, float* gmem_partial, hipStream_t s);
+// launchers of the MFMA linear-attention kernels (linattn_mfma.hip), the fused backward tail (linattn_fused.hip), the tiled full
+// attention for n > 128 query pixels (attention_tiled.hip) and the slab reducer (conv_igemm.hip): lgm_internal.h
 
 namespace {
 
@@ -472,7 +448,7 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const float* __rest
 
 // n > FA_MAXN takes the tiled kernels (attention_tiled.hip); LGM_TILED_ATTN=1 forces them at every n (test switch)
 bool attn_tiled(int n) {
-  static const bool forced = getenv("LGM_TILED_ATTN") != nullptr;
+  static const bool forced = lgm_env_set("LGM_TILED_ATTN");
   return forced || n > FA_MAXN;
 }
 
@@ -673,7 +649,7 @@ extern "C" int lgm_attn_fwd(const float* qkv, int64_t qkv_pitch, const float* me
     return lgm_attn_tiled_fwd_launch(qkv, (long)qkv_pitch, mem_kv, B, n, heads, M, 1.f / sqrtf((float)dim_head), out,
                                      (long)out_pitch, lse, (hipStream_t)stream);
   const size_t smem = (size_t)2 * (n + M) * FA_LD * sizeof(float);
-  static const bool no_small = getenv("LGM_NO_SMALL_ATTN") != nullptr;          // A/B switch
+  static const bool no_small = lgm_env_set("LGM_NO_SMALL_ATTN");          // A/B switch
   if (!no_small && n <= SA_MAXN && M <= 16 && qkv_pitch % 4 == 0 && out_pitch % 4 == 0 && lgm_aligned16(qkv) &&
       lgm_aligned16(out) && lgm_aligned16(mem_kv))
   {
@@ -735,7 +711,7 @@ int attn_bwd_impl(const float* qkv, int64_t qkv_pitch, const float* mem_kv, cons
                         (int)(((size_t)4 * (FA_MAXN + 16) * FA_LD + 2 * FA_MAXN) * sizeof(float)));
     attr_set = true;
   }
-  static const bool no_small = getenv("LGM_NO_SMALL_ATTN") != nullptr;          // A/B switch
+  static const bool no_small = lgm_env_set("LGM_NO_SMALL_ATTN");          // A/B switch
   if (!no_small && n <= SA_MAXN && M <= 16 && qkv_pitch % 4 == 0 && out_pitch % 4 == 0 && gout_pitch % 4 == 0 &&
       gqkv_pitch % 4 == 0 && lgm_aligned16(qkv) && lgm_aligned16(out) && lgm_aligned16(gout) && lgm_aligned16(gqkv) &&
       lgm_aligned16(mem_kv) && lgm_aligned16(part))

@@ -17,51 +17,16 @@
 
 #include "lgm_common.h"
 
-// specialised 3x3 / stride 1 / pad 1 kernels (conv3x3.hip)
-bool lgm_conv3x3_supported(const LgmConvGeom* g, int gather_channels, int out_channels);
-int lgm_conv3x3_splits(const LgmConvGeom* g, int gather_channels, int out_channels);
-int lgm_splitk_reduce_launch(const float* ws, long ws_stride, int splits, const float* bias, const float* res,
-                             long res_pitch, float* out, long out_pitch, long M, int N, hipStream_t s);
-int lgm_conv3x3_launch(int mode, const LgmConvGeom* g, const float* a, long a_pitch, const float* w,
-                       const float* bias, const float* res, long res_pitch, float* out, long out_pitch,
-                       void* workspace, long workspace_bytes, hipStream_t s);
-bool lgm_wgrad3x3_supported(const LgmConvGeom* g);
-void lgm_wgrad3x3_plan(const LgmConvGeom* g, int* splits, int* tps, int* total_ts);
-bool lgm_wgrad1x1_supported(const LgmConvGeom* g, long y_pitch, long x_pitch);
-void lgm_wgrad1x1_plan(const LgmConvGeom* g, int* splits, int* chunks_per_split);
-int lgm_wgrad1x1_launch(const LgmConvGeom* g, const float* y, long y_pitch, const float* x, long x_pitch, float* out,
-                        float* bias_out, float beta, long slab, int splits, int chunks_per_split, hipStream_t s);
-int lgm_wgrad3x3_launch(const LgmConvGeom* g, const float* y, long y_pitch, const float* x, long x_pitch,
-                        float* out, float* bias_out, float beta, long slab, int splits, int tps, int total_ts,
-                        hipStream_t s);
-
-// Winograd F(2x2,3x3) weight gradient (winograd.hip): always through slabs + the fixed-order reducer
-bool lgm_wino_wgrad_supported(const LgmConvGeom* g);
-// F(4x4,3x3) weight gradient of the large-map layers (csrc/winograd4_wgrad.hip)
-bool lgm_wino4_wgrad_use(const LgmConvGeom* g);
-void lgm_wino4_wgrad_plan(const LgmConvGeom* g, long budget, int* splits, int* gps, int* total_groups);
-int lgm_wino4_wgrad_launch(const LgmConvGeom* g, const float* y, long y_pitch, const float* x, long x_pitch, float* out,
-                           int bias, long slab, int splits, int gps, int total, hipStream_t s);
-void lgm_wino_wgrad_plan(const LgmConvGeom* g, int* splits, int* cps, int* total_chunks);
-int lgm_wino_wgrad_launch(const LgmConvGeom* g, const float* y, long y_pitch, const float* x, long x_pitch, float* out,
-                          int bias, long slab, int splits, int cps, int total_chunks, hipStream_t s);
+// (the specialised kernels of the other translation units this file routes to: lgm_internal.h)
 static bool use_wino() {      // LGM_NO_WINO=1: direct fp32 MFMA kernels for the 3x3 layers (A/B comparisons)
   static const bool off = getenv("LGM_NO_WINO") != nullptr && getenv("LGM_NO_WINO")[0] == '1';
   return !off;
 }
 
-// 1x1 convolutions with a resident weight slice, X streamed (gemm_stream.hip)
-bool lgm_gemm_stream_supported(long M, int N, int K, long x_pitch, long out_pitch, long res_pitch);
-int lgm_gemm_stream_launch(const float* x, long x_pitch, const float* w, const float* bias, const float* res,
-                           long res_pitch, float* out, long out_pitch, long M, int N, int K, hipStream_t s);
 static bool use_gstream() {
-  static const bool off = getenv("LGM_NO_GSTREAM") != nullptr;   // A/B switch
+  static const bool off = lgm_env_set("LGM_NO_GSTREAM");   // A/B switch
   return !off;
 }
-// short-reduction 1x1 convolutions with a resident activation tile (gemm_rows.hip)
-bool lgm_gemm_rows_supported(long M, int N, int K);
-int lgm_gemm_rows_launch(const float* x, long x_pitch, const float* w, const float* bias, const float* res,
-                         long res_pitch, float* out, long out_pitch, long M, int N, int K, hipStream_t s);
 
 // the specialised kernels store 16 bytes per lane: outputs / residual / bias must allow it
 static bool wide_ok(const float* out, long out_pitch, const float* res, long res_pitch, const float* bias) {
@@ -91,7 +56,7 @@ __device__ __forceinline__ int lgm_xcd_swizzle(int bid, int nb) {
 // opt-in (LGM_XCD_SWZ=1): measured 0.3 % SLOWER on the WGAN-GP and DDPM steps - the N-siblings' A tiles are served by the
 // Infinity Cache already, and the contiguous ranges cost some balance at the tail
 static int swz_on() {
-  static const int on = getenv("LGM_XCD_SWZ") != nullptr;
+  static const int on = lgm_env_set("LGM_XCD_SWZ");
   return on;
 }
 
@@ -742,9 +707,9 @@ int igemm_splits(long M, int N, int K, int* kchunk) {
   // up to 256 tiles a launch leaves at most one wave per SIMD: nothing hides the load -> LDS -> barrier latency
   // of a chunk.  Split the reduction until ~4 workgroups share a CU (>= 8 chunks each).
   if (tiles > 256 || N % 4 != 0) return 1;
-  static const long t_big = getenv("LGM_IGEMM_TBIG") ? atol(getenv("LGM_IGEMM_TBIG")) : 1024;      // tuning knobs (A/B runs)
-  static const long t_small = getenv("LGM_IGEMM_TSMALL") ? atol(getenv("LGM_IGEMM_TSMALL")) : 256;
-  static const long c_min = getenv("LGM_IGEMM_CMIN") ? atol(getenv("LGM_IGEMM_CMIN")) : 0;          // 0: 8 / 4 chunks per split
+  static const long t_big = lgm_env_long("LGM_IGEMM_TBIG", 1024);      // tuning knobs (A/B runs)
+  static const long t_small = lgm_env_long("LGM_IGEMM_TSMALL", 256);
+  static const long c_min = lgm_env_long("LGM_IGEMM_CMIN", 0);          // 0: 8 / 4 chunks per split
   long s = tiles > 64 ? t_big / tiles : t_small / tiles;
   const long cmin = c_min > 0 ? c_min : (tiles > 64 ? 8 : 4);
   if (s > nk / cmin) s = nk / cmin;
@@ -998,7 +963,7 @@ __global__ __launch_bounds__(256) void narrow1x1_dgrad_kernel(const float* __res
 
 // the layers these two kernels take: 1x1 / stride 1 / unpadded, 64 channels on the wide side, 4 (padded) on the narrow one
 bool narrow1x1_geom(const LgmConvGeom* g) {
-  static const bool off = getenv("LGM_NO_NARROW1X1") != nullptr;        // A/B switch
+  static const bool off = lgm_env_set("LGM_NO_NARROW1X1");        // A/B switch
   return !off && g->KH == 1 && g->KW == 1 && g->stride == 1 && g->pad == 0 && g->Nw == 4 && g->Cw == 64;
 }
 unsigned narrow1x1_blocks(long P) {
@@ -1026,7 +991,7 @@ static int conv_xy_impl(const LgmConvGeom* g, const float* x, int64_t x_pitch, c
     LGM_LAUNCH_CHECK();
     return LGM_OK;
   }
-  static const bool post_3x3 = getenv("LGM_POST_VIA_3X3") != nullptr;   // A/B switch: direct 3x3 kernel + elementwise post-op
+  static const bool post_3x3 = lgm_env_set("LGM_POST_VIA_3X3");   // A/B switch: direct 3x3 kernel + elementwise post-op
   if (use_3x3() && (!t_post.post || post_3x3) && wide_ok(y, y_pitch, res, res_pitch, bias) && lgm_conv3x3_supported(g, g->Cw, g->Nw) &&
       ((long)g->B * g->H * g->W + g->W + 1) * x_pitch < (1L << 29))   // buffer offsets (bytes) below 2^31
     return lgm_conv3x3_launch(0, g, x, x_pitch, w, bias, res, res_pitch, y, y_pitch, workspace, workspace_bytes,
@@ -1375,7 +1340,7 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
     LGM_LAUNCH_CHECK();
     return LGM_OK;
   }
-  static const bool post_3x3 = getenv("LGM_POST_VIA_3X3") != nullptr;   // A/B switch (see conv_xy_impl)
+  static const bool post_3x3 = lgm_env_set("LGM_POST_VIA_3X3");   // A/B switch (see conv_xy_impl)
   if (use_3x3() && (!t_post.post || post_3x3) && wide_ok(x, x_pitch, res, res_pitch, bias) && lgm_conv3x3_supported(g, g->Nw, g->Cw) &&
       ((long)g->B * g->H * g->W + g->W + 1) * y_pitch < (1L << 29))
     return lgm_conv3x3_launch(w_t ? 2 : 1, g, y, y_pitch, w_t ? w_t : w, bias, res, res_pitch, x, x_pitch, workspace,
@@ -1398,7 +1363,7 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
     q.B = g->B; q.H = g->H; q.W = g->W; q.Ho = g->Ho; q.Wo = g->Wo; q.Nw = g->Nw;
     q.KH = g->KH; q.KW = g->KW; q.stride = g->stride; q.pad = g->pad;
     q.npix = (long)g->B * g->H * g->W;
-    static const bool no_lp = getenv("LGM_SMALLN_LANES") != nullptr;      // A/B switch: the lane-group form everywhere
+    static const bool no_lp = lgm_env_set("LGM_SMALLN_LANES");      // A/B switch: the lane-group form everywhere
     const int Hq = g->H / 2, Wq = g->W / 2;
     if (!no_lp && g->Nw % 32 == 0 && Hq >= 8 && Wq >= 16) {
       const int lgc = Wq >= 32 ? 5 : 4;                                  // 8 x 32 or 16 x 16 pixels of a class
@@ -1829,7 +1794,7 @@ void wgrad_plan(const LgmConvGeom* g, int* splits, int* chunk) {
   const long tiles = (long)lgm_cdiv(g->Nw, 64) * lgm_cdiv(Q, 64);
   // ~512 workgroups (two per CU): measured on the WGAN-GP step 256 / 512 / 1024 / 2048 / 4096 -> 24,550 / 25,100 /
   // 24,800 / 24,550 / 23,950 images/s (more splits = more slab traffic); no effect on the DDPM step
-  static const long target = getenv("LGM_WGRAD_TARGET") ? atol(getenv("LGM_WGRAD_TARGET")) : 512;   // tuning knob
+  static const long target = lgm_env_long("LGM_WGRAD_TARGET", 512);   // tuning knob
   long s = (target + tiles - 1) / tiles;
   const long max_s = (P + 255) / 256;            // at least 256 pixels per split
   if (s > max_s) s = max_s;
@@ -1890,7 +1855,7 @@ static int conv_wgrad_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch
   const bool fast3 = use_3x3() && lgm_wgrad3x3_supported(g) &&
                      ((long)g->B * g->H * g->W + g->W + 1) * x_pitch < (1L << 29) &&
                      (long)g->B * g->H * g->W * y_pitch < (1L << 29);
-  static const bool no_w1x1 = getenv("LGM_NO_W1X1") != nullptr;   // A/B switch
+  static const bool no_w1x1 = lgm_env_set("LGM_NO_W1X1");   // A/B switch
   const bool fast1 = !fast3 && !no_w1x1 && lgm_wgrad1x1_supported(g, y_pitch, x_pitch);
   // Winograd: same operand limits as the direct 3x3 kernel (the kernel always writes slabs, the reducer applies beta)
   const bool fastw = fast3 && use_wino() && lgm_wino_wgrad_supported(g);
@@ -1938,14 +1903,14 @@ static int conv_wgrad_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch
   } else {
     auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
     a.lWo = lg2(a.Wo); a.lHo = lg2(a.Ho); a.lW = lg2(a.W); a.lH = lg2(a.H);
-    static const bool no_fast = getenv("LGM_NO_WGRAD_FAST") != nullptr;   // A/B switch
+    static const bool no_fast = lgm_env_set("LGM_NO_WGRAD_FAST");   // A/B switch
     const bool fast = !no_fast && a.lWo >= 0 && a.lHo >= 0 && a.lW >= 0 && a.lH >= 0 &&
                       (long)a.B * a.H * a.W < (1L << 24) && x_pitch * 4 < (1L << 24) &&
                       (long)a.B * a.H * a.W * x_pitch * 4 < (1L << 31) && ((long)a.P + WBK) * y_pitch * 4 < (1L << 31);
     // Opt-in (LGM_WGRAD_BIG=1), measured SLOWER on the WGAN-GP step (24,150 vs 24,760 images/s): 128 output channels
     // per workgroup - two accumulators per wave, every gathered X fragment feeds two MFMAs - halves the workgroups,
     // and these layers need the parallelism more than the operand reuse.
-    static const bool want_big = getenv("LGM_WGRAD_BIG") != nullptr;
+    static const bool want_big = lgm_env_set("LGM_WGRAD_BIG");
     const bool big = fast && want_big && a.Nw % 128 == 0 && (long)(a.Nw / 128) * a.tiles_n * a.splits >= 512;
     lgm_note_kernel(big ? LGM_KNAME("wgrad_kernel<128, 64, 2, 1, true>")
                         : fast ? LGM_KNAME("wgrad_kernel<64, 64, 1, 1, true>") : LGM_KNAME("wgrad_kernel<64, 64, 1, 1, false>"));
@@ -2001,15 +1966,6 @@ int lgm_wgrad_reduce_launch(const float* ws, long slab, float* gw, long n_w, flo
 }
 
 // ---- backward pair of a 3x3 layer: input gradient + weight gradient in ONE launch (csrc/winograd.hip) -------------
-bool lgm_wino_supported(const LgmConvGeom* g, int gather_channels, int out_channels);
-struct WinoPairPlan {
-  int csplits, wsplits, cps, total_chunks;
-};
-WinoPairPlan lgm_wino_pair_plan(const LgmConvGeom* g, bool fused);
-int lgm_wino_pair_launch(const LgmConvGeom* g, const float* gy, long gy_pitch, const float* x, long x_pitch,
-                         const float* u_b, const float* res, long res_pitch, float* gx, long gx_pitch, void* dws,
-                         long dws_bytes, int64_t* partial, float* slabs, int bias, long slab, hipStream_t s);
-
 /* out[0] / out[1]: bytes of the input gradient's split-K workspace / of the weight gradient's slab workspace that
  * lgm_conv3x3_wino_bwd needs for this geometry (the pair plans its two split counts jointly) */
 extern "C" int lgm_conv3x3_wino_bwd_workspaces(const LgmConvGeom* g, int partial, int64_t* out) {
@@ -2023,7 +1979,7 @@ extern "C" int lgm_conv3x3_wino_bwd_workspaces(const LgmConvGeom* g, int partial
 extern "C" int64_t lgm_conv3x3_wino_bwd_supported(const LgmConvGeom* g, int64_t gy_pitch, int64_t x_pitch,
                                                   int64_t gx_pitch, int64_t res_pitch) {
   if (check_geom(g) != LGM_OK) return 0;
-  static const bool no_pair = getenv("LGM_NO_PAIR") != nullptr;   // A/B switch: separate launches
+  static const bool no_pair = lgm_env_set("LGM_NO_PAIR");   // A/B switch: separate launches
   if (no_pair || !use_3x3() || !use_wino()) return 0;
   const long pix = (long)g->B * g->H * g->W + g->W + 1;
   if (!(lgm_wgrad3x3_supported(g) && lgm_wino_wgrad_supported(g) && lgm_wino_supported(g, g->Nw, g->Cw))) return 0;
@@ -2081,7 +2037,7 @@ static int conv_bwd_pair_impl(const LgmConvGeom* g, const float* gy, int64_t gy_
                               float* gx, int64_t gx_pitch, void* dgrad_ws, int64_t dgrad_ws_bytes, float* gw,
                               float* gbias, float beta, void* wgrad_ws, int64_t wgrad_ws_bytes, int64_t* desc,
                               const LgmPostOp* post, void* stream) {
-  static const bool no_pair = getenv("LGM_NO_PAIR") != nullptr;   // A/B switch: separate launches
+  static const bool no_pair = lgm_env_set("LGM_NO_PAIR");   // A/B switch: separate launches
   hipStream_t s = (hipStream_t)stream;
   t_pair = PairCtx{};
   t_pair.active = !no_pair;
@@ -2105,7 +2061,7 @@ static int conv_bwd_pair_impl(const LgmConvGeom* g, const float* gy, int64_t gy_
   memcpy(&wa, c.wg, sizeof(WgradArgs));
   // one launch only while both grids fit the chip together (67 KB of LDS per workgroup: two per CU): large layers keep
   // their own launches, where the input-gradient kernel alone gets four workgroups per CU (B = 128: 1 % slower paired)
-  static const unsigned pair_max = getenv("LGM_PAIR_MAX") ? (unsigned)atoi(getenv("LGM_PAIR_MAX")) : 512u;
+  static const unsigned pair_max = (unsigned)lgm_env_int("LGM_PAIR_MAX", 512);
   const bool together = c.rec_i && c.rec_w && c.ig_blocks + c.wg_blocks <= pair_max;
   if (together) {
     static size_t attr = 0;

@@ -4,7 +4,10 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <stdlib.h>
+
 #include "../../include/lgm_hip.h"
+#include "lgm_internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -36,19 +39,54 @@ int lgm_cu_budget();
     }                                       \
   } while (0)
 
-// returns hipError_t (>0) through the C-ABI when a launch fails
-#define LGM_LAUNCH_CHECK()                                   \
+// returns hipError_t (>0) through the C-ABI when a launch fails; `who` names the launcher in lgm_last_error
+#define LGM_LAUNCH_CHECK_AS(who)                             \
   do {                                                       \
     hipError_t e__ = hipGetLastError();                      \
     if (e__ != hipSuccess) {                                 \
-      lgm_set_error("%s: %s", __func__, hipGetErrorString(e__)); \
+      lgm_set_error("%s: %s", who, hipGetErrorString(e__));  \
       return (int)e__;                                       \
     }                                                        \
   } while (0)
+#define LGM_LAUNCH_CHECK() LGM_LAUNCH_CHECK_AS(__func__)
 
 static inline int lgm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 static inline bool lgm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// Environment knobs (tuning values, A/B switches).  A call site keeps the result in a `static const` of its own: every knob
+// is read once per process, at first use.
+static inline bool lgm_env_set(const char* name) { return getenv(name) != nullptr; }
+static inline int lgm_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline long lgm_env_long(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e ? atol(e) : dflt;
+}
+static inline double lgm_env_double(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
+
+// bytes of the split-K partial output planes of a convolution launch (0: unsplit)
+static inline int64_t lgm_splitk_workspace(const LgmConvGeom* g, int out_channels, int splits) {
+  return splits > 1 ? (int64_t)splits * g->B * g->H * g->W * out_channels * (int64_t)sizeof(float) : 0;
+}
+
+// The operand contract of the Winograd convolution entry points (F(2x2) and F(4x4); `who` is the entry point lgm_last_error
+// names): 16-byte aligned operands, pitches in whole float4 that cover the channels (gc gathered, oc produced), and every
+// tensor inside the kernels' 32-bit byte offsets.  bias and res are optional.
+static inline int lgm_conv_operands_check(const char* who, const LgmConvGeom* g, int gc, int oc, const float* a, long a_pitch,
+                                          const float* u, const float* bias, const float* res, long res_pitch,
+                                          const float* out, long out_pitch) {
+  LGM_REQUIRE(a_pitch % 4 == 0 && a_pitch >= gc && lgm_aligned16(a) && lgm_aligned16(u) && lgm_aligned16(out) &&
+              out_pitch % 4 == 0 && out_pitch >= oc && (!res || (lgm_aligned16(res) && res_pitch % 4 == 0 && res_pitch >= oc)) &&
+              (!bias || lgm_aligned16(bias)), "%s: 16-byte aligned operands with pitch %% 4 == 0 expected", who);
+  LGM_REQUIRE(lgm_conv3x3_wino_fits(g, a_pitch, out_pitch, res ? res_pitch : 0), "%s: tensor too large for 32-bit offsets", who);
+  return LGM_OK;
+}
 __device__ __forceinline__ bool lgm_aligned16_dev(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // ---- device helpers -------------------------------------------------------------

@@ -18,9 +18,6 @@
 
 #include "lgm_common.h"
 
-int lgm_wgrad_reduce_launch(const float* ws, long slab, float* gw, long n_w, float* gb, long n_b, int splits, float beta,
-                            hipStream_t s);
-
 namespace {
 
 constexpr int DH = 32;

@@ -245,8 +245,6 @@ inline int tile_of(int dim) { return dim % 128 == 0 ? 128 : 64; }
 
 }  // namespace
 
-void lgm_wgrad1x1_plan(const LgmConvGeom* g, int* splits, int* chunks_per_split);
-
 // 1x1, stride 1, unpadded, channel counts in whole 64-blocks, whole 64-pixel chunks, 32-bit byte offsets
 bool lgm_wgrad1x1_supported(const LgmConvGeom* g, long y_pitch, long x_pitch) {
   if (!(g->KH == 1 && g->KW == 1 && g->stride == 1 && g->pad == 0)) return false;

@@ -36,9 +36,6 @@
 
 #include "lgm_common.h"
 
-int lgm_splitk_reduce_launch(const float* ws, long ws_stride, int splits, const float* bias, const float* res,
-                             long res_pitch, float* out, long out_pitch, long M, int N, hipStream_t s);
-
 // diagnostic: when set (lgm_wino_set_debug_buffer), the convolution runs its stamped build and writes, per
 // workgroup, 64 int64: [0] stamp count, [1] s_memrealtime at exit, [2..] s_memtime stamps (start, after the
 // prologue, after every phase, after every epilogue).  Never set on the product path.
@@ -780,7 +777,7 @@ bool lgm_wino_supported(const LgmConvGeom* g, int gather_channels, int out_chann
 
 // fused = the consumer sums the partial planes itself (lgm_gn_fwd_planes / lgm_gn_bwd_planes): no reducer launch, and
 // its read of the reduced tensor is replaced by a read of the planes
-int lgm_wino_splits(const LgmConvGeom* g, int gather_channels, int out_channels, bool fused = false) {
+int lgm_wino_splits(const LgmConvGeom* g, int gather_channels, int out_channels, bool fused) {
   using namespace lgmwino;
   int TTH, TTW, NI;
   if (!plan_unit(g->H, g->W, &TTH, &TTW, &NI)) return 1;
@@ -792,8 +789,8 @@ int lgm_wino_splits(const LgmConvGeom* g, int gather_channels, int out_channels,
   // cost in phase times (~2.1 us): rounds of 256 workgroups x (phases per unit + ~1.5 of prologue / epilogue) + the
   // partial sums every extra split writes and the reducer reads back (8 bytes per output element at ~3 TB/s) -
   // 1.3 phases per split on the 4x4 maps at B = 128, 0.16 at B = 16, where splitting deeper is what fills the chip
-  static const double k_ovh = getenv("LGM_FPLAN_OVH") ? atof(getenv("LGM_FPLAN_OVH")) : 1.5;       // tuning knobs (A/B runs)
-  static const double k_spl = getenv("LGM_FPLAN_SPLIT") ? atof(getenv("LGM_FPLAN_SPLIT")) : 1.0;
+  static const double k_ovh = lgm_env_double("LGM_FPLAN_OVH", 1.5);       // tuning knobs (A/B runs)
+  static const double k_spl = lgm_env_double("LGM_FPLAN_SPLIT", 1.0);
   const double per_split = k_spl * (fused ? 6.0 : 8.0) * (double)g->B * g->H * g->W * out_channels / 3.0e12 / 2.1e-6;
   long s = 1;
   double best = 1e30;
@@ -847,7 +844,7 @@ static void wino_prepare(const LgmConvGeom* g, int yx, const float* a, long a_pi
   // contiguous unit range, xcd_swizzle) work on ONE channel block and fetch its transformed weights into that XCD's L2
   // once - channel-block-fastest made every XCD read the whole table (128.8 MB per launch for 512 -> 512 at 4x4 against
   // 16.8 MB of weights).  Time-neutral (those layers are not bound by the weight fetch); it is HBM-side traffic.
-  static const bool tile_fastest = !(getenv("LGM_WINO_TN_FASTEST") != nullptr);   // A/B switch
+  static const bool tile_fastest = !(lgm_env_set("LGM_WINO_TN_FASTEST"));   // A/B switch
   p.tile_fastest = (tile_fastest && p.tb_h == 1 && p.tb_w == 1 && p.nbg > 1) ? 1 : 0;
   *nblocks_out = (unsigned)lgm_cdiv(p.units, p.per);
   *ttw_out = TTW;
@@ -855,7 +852,7 @@ static void wino_prepare(const LgmConvGeom* g, int yx, const float* a, long a_pi
 
 int lgm_wino_launch(const LgmConvGeom* g, int yx, const float* a, long a_pitch, const float* u, const float* bias,
                     const float* res, long res_pitch, float* out, long out_pitch, void* workspace,
-                    long workspace_bytes, hipStream_t s, int64_t* partial = nullptr) {
+                    long workspace_bytes, hipStream_t s, int64_t* partial) {
   using namespace lgmwino;
   Args p;
   unsigned nblocks;
@@ -927,16 +924,14 @@ extern "C" int64_t lgm_conv3x3_wino_workspace(const LgmConvGeom* g, int yx) {
   if (!g) return -1;
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   if (!lgm_wino_supported(g, gc, oc)) return 0;
-  const int s = lgm_wino_splits(g, gc, oc);
-  return s > 1 ? (int64_t)s * g->B * g->H * g->W * oc * (int64_t)sizeof(float) : 0;
+  return lgm_splitk_workspace(g, oc, lgm_wino_splits(g, gc, oc));
 }
 
 extern "C" int64_t lgm_conv3x3_wino_workspace_partial(const LgmConvGeom* g, int yx) {
   if (!g) return -1;
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   if (!lgm_wino_supported(g, gc, oc)) return 0;
-  const int s = lgm_wino_splits(g, gc, oc, true);
-  return s > 1 ? (int64_t)s * g->B * g->H * g->W * oc * (int64_t)sizeof(float) : 0;
+  return lgm_splitk_workspace(g, oc, lgm_wino_splits(g, gc, oc, true));
 }
 
 extern "C" int lgm_wino_weights(const float* src, float* dst_f, float* dst_b, const int64_t* table, int n_slots,
@@ -955,10 +950,9 @@ extern "C" int lgm_conv3x3_wino(int yx, const LgmConvGeom* g, const float* a, in
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   LGM_REQUIRE(lgm_wino_supported(g, gc, oc), "conv3x3_wino: unsupported geometry (3x3/s1/p1, H,W powers of two >= 4, "
               "reduction channels %% 8, produced channels %% 64, whole image groups)");
-  LGM_REQUIRE(a_pitch % 4 == 0 && a_pitch >= gc && lgm_aligned16(a) && lgm_aligned16(u) && lgm_aligned16(out) &&
-              out_pitch % 4 == 0 && out_pitch >= oc && (!res || (lgm_aligned16(res) && res_pitch % 4 == 0 && res_pitch >= oc)) &&
-              (!bias || lgm_aligned16(bias)), "conv3x3_wino: 16-byte aligned operands with pitch %% 4 == 0 expected");
-  LGM_REQUIRE(lgm_conv3x3_wino_fits(g, a_pitch, out_pitch, res ? res_pitch : 0), "conv3x3_wino: tensor too large for 32-bit offsets");
+  if (const int rc = lgm_conv_operands_check("conv3x3_wino", g, gc, oc, a, a_pitch,
+                                             u, bias, res, res_pitch, out, out_pitch))
+    return rc;
   return lgm_wino_launch(g, yx, a, a_pitch, u, bias, res, res_pitch, out, out_pitch, workspace, workspace_bytes,
                          (hipStream_t)stream);
 }
@@ -969,10 +963,9 @@ extern "C" int lgm_conv3x3_wino_partial(int yx, const LgmConvGeom* g, const floa
   LGM_REQUIRE(g && a && u && out && partial, "conv3x3_wino_partial: null pointer");
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   LGM_REQUIRE(lgm_wino_supported(g, gc, oc), "conv3x3_wino_partial: unsupported geometry");
-  LGM_REQUIRE(a_pitch % 4 == 0 && a_pitch >= gc && lgm_aligned16(a) && lgm_aligned16(u) && lgm_aligned16(out) &&
-              out_pitch % 4 == 0 && out_pitch >= oc && (!bias || lgm_aligned16(bias)),
-              "conv3x3_wino_partial: 16-byte aligned operands with pitch %% 4 == 0 expected");
-  LGM_REQUIRE(lgm_conv3x3_wino_fits(g, a_pitch, out_pitch, 0), "conv3x3_wino_partial: tensor too large for 32-bit offsets");
+  if (const int rc = lgm_conv_operands_check("conv3x3_wino_partial", g, gc, oc, a, a_pitch,
+                                             u, bias, nullptr, 0, out, out_pitch))
+    return rc;
   return lgm_wino_launch(g, yx, a, a_pitch, u, bias, nullptr, 0, out, out_pitch, workspace, workspace_bytes,
                          (hipStream_t)stream, partial);
 }
@@ -1508,16 +1501,11 @@ static bool wgrad2_operands_ok(const LgmConvGeom* g, const float* y, long y_pitc
 }
 
 // F(4x4,3x3) weight gradient (csrc/winograd4_wgrad.hip): pairs of layers that both take it share a launch of THAT kernel
-bool lgm_wino4_wgrad_use(const LgmConvGeom* g);
-void lgm_wino4_wgrad_plan(const LgmConvGeom* g, long budget, int* splits, int* gps, int* total_groups);
-int lgm_wino4_wgradn_launch(int n, const LgmConvGeom* const* gs, const float* const* ys, const long* yps,
-                            const float* const* xs, const long* xps, float* const* outs, const int* biases, const long* slabs,
-                            const int* splits, const int* gpss, const int* totals, hipStream_t s);
 // F(4x4) weight gradients of 2 ... 4 layers in one launch (LGM_W4W_GROUP bounds n, default 4): every layer takes the F(4x4)
 // kernel and still gets at least two slabs' worth of its 64 x 32-channel blocks out of the 256 workgroups (the 512-channel
 // layers of the 64 x 64 configuration do not fit side by side: they take the F(2x2) grouped launch or go alone)
 static bool wgradn_use4(int n, const LgmConvGeom* const* gs) {
-  static const int nmax = getenv("LGM_W4W_GROUP") ? atoi(getenv("LGM_W4W_GROUP")) : 8;
+  static const int nmax = lgm_env_int("LGM_W4W_GROUP", 8);
   if (n < 2 || n > 8 || n > nmax) return false;
   long need = 0;
   double phases = 0.0;                 // tile groups x channel blocks of the whole group = phases the chip's workgroups share
@@ -1531,7 +1519,7 @@ static bool wgradn_use4(int n, const LgmConvGeom* const* gs) {
   // prologue / epilogue / slab savings are used up and the longer tail costs more (32 x 32 maps at B = 128: four layers =
   // 64 phases, 10.03 -> 10.01 ms per step; 64 x 64 maps at B = 64: four layers = 128 phases, 16.78 -> 17.26 ms; eight layers
   // at 32 x 32 = 128 phases: 10.21 ms).  LGM_W4W_MAX_PHASES: tuning knob.
-  static const double max_phases = getenv("LGM_W4W_MAX_PHASES") ? atof(getenv("LGM_W4W_MAX_PHASES")) : 80.0;
+  static const double max_phases = lgm_env_double("LGM_W4W_MAX_PHASES", 80.0);
   if (n > 2 && phases / (double)lgm_cu_budget() > max_phases) return false;
   return need <= lgm_cu_budget();
 }
@@ -1571,7 +1559,7 @@ static bool wgradn_supported(int n, const LgmConvGeom* const* gs) {
   // layers that would each take the F(4x4) kernel but do not fit side by side (wgradn_use4: the 512-channel layers of the
   // 64 x 64 configuration) go alone on that kernel rather than together on the F(2x2) one: 17.24 -> 17.11 ms per step
   // (A/B: LGM_W4W_ALONE=0)
-  static const bool alone4 = getenv("LGM_W4W_ALONE") ? atoi(getenv("LGM_W4W_ALONE")) != 0 : true;
+  static const bool alone4 = lgm_env_int("LGM_W4W_ALONE", 1) != 0;
   if (alone4 && !wgradn_use4(n, gs)) {
     bool all4 = true;
     for (int k = 0; k < n; ++k) all4 = all4 && gs[k] && lgm_wino4_wgrad_use(gs[k]);
@@ -1762,9 +1750,6 @@ extern "C" int lgm_conv3x3_wino_wgrad2(const LgmConvGeom* ga, const float* ya, i
 // in units of one phase / chunk (64 MFMAs per wave, ~2.1 us), plus what the splits cost afterwards: the input
 // gradient's partial planes (written, then read by the reducer or the consuming GroupNorm) and the weight gradient's
 // slabs (written by the kernel, read by the batched slab reducer).
-struct WinoPairPlan {
-  int csplits, wsplits, cps, total_chunks;
-};
 static WinoPairPlan wino_pair_plan_search(const LgmConvGeom* g, bool fused);
 WinoPairPlan lgm_wino_pair_plan(const LgmConvGeom* g, bool fused) {
   // the search below costs ~1 ms: once per geometry and thread
@@ -1803,10 +1788,10 @@ static WinoPairPlan wino_pair_plan_search(const LgmConvGeom* g, bool fused) {
   long smax = chunks / 2 < 256 ? chunks / 2 : 256;
   if (smax < 2) smax = 2;
   // per slab: read back by the batched slab reducer at HBM rate (its write rides in the kernel's epilogue)
-  static const double k_slab = getenv("LGM_PLAN_SLAB") ? atof(getenv("LGM_PLAN_SLAB")) : 1.0;     // tuning knobs (A/B runs)
-  static const double k_tc = getenv("LGM_PLAN_TC") ? atof(getenv("LGM_PLAN_TC")) : 1.5;
-  static const double k_tw = getenv("LGM_PLAN_TW") ? atof(getenv("LGM_PLAN_TW")) : 3.0;
-  static const double k_wph = getenv("LGM_PLAN_WPH") ? atof(getenv("LGM_PLAN_WPH")) : 1.0;
+  static const double k_slab = lgm_env_double("LGM_PLAN_SLAB", 1.0);     // tuning knobs (A/B runs)
+  static const double k_tc = lgm_env_double("LGM_PLAN_TC", 1.5);
+  static const double k_tw = lgm_env_double("LGM_PLAN_TW", 3.0);
+  static const double k_wph = lgm_env_double("LGM_PLAN_WPH", 1.0);
   const double slab_cost = k_slab * 4.0 * ((double)g->Nw * 9 * g->Cw + g->Nw) / 4.5e12 / 2.1e-6;
   // makespan of n1 blocks of t1 followed by n2 blocks of t2 on 256 CUs, one block per CU, dispatched in order
   auto makespan = [](long n1, double t1, long n2, double t2) {

@@ -29,10 +29,7 @@
 
 #include <type_traits>
 
-#include "lgm_common.h"
-
-int lgm_splitk_reduce_launch(const float* ws, long ws_stride, int splits, const float* bias, const float* res,
-                             long res_pitch, float* out, long out_pitch, long M, int N, hipStream_t s);
+#include "wino4_host.h"
 
 // diagnostic: when set (lgm_wino4_set_debug_buffer), the convolution runs its stamped build and writes, per workgroup,
 // 32 int64: [0] stamp count, [1..] s_memtime (entry, set-up done, prologue done, every phase, both epilogue passes),
@@ -54,11 +51,8 @@ extern "C" int lgm_wino4_set_debug_buffer(void* buf, int exp) {
 #endif
 
 namespace lgmwino4 {
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace lgmwino4dev;
 
-constexpr int KC = 8;              // reduction channels per phase
-constexpr int NXI = 36;
 constexpr int VBUF = NXI * 256;    // floats per V buffer: [xi][k-half][tile 32][4]
 constexpr int MBUF = NXI * 32 * 32;   // floats of the epilogue exchange: two halves of [xi][tile 32][4 quads (swizzled)][4]
 
@@ -83,44 +77,10 @@ struct Geo<3> {   // 4 x 4 maps: one tile per image, 32 images.  The 6 x 6 patch
   static constexpr int NI = 32, TTH = 1, TTW = 1, PH = 4, PW = 4, RS = 4, IMG = 20, PLANE = 641;
 };
 
-struct Args {
-  const float* a;      // gathered activations, NHWC
-  const float* u;      // transformed weights [N/64][C/8][36][2][2][32][4]
-  const float* bias;
-  const float* res;
-  float* out;
-  long a_pitch, res_pitch, out_pitch;
-  int B, H, W;
-  int C;               // reduction channels
-  int N;               // produced channels
-  int tb_h, tb_w, tiles_n, nbg;
-  int splits, pps, units;
-  int tn_slowest;      // unit order, see the kernel
-  int xcd_ranges;      // 1: an XCD takes a contiguous unit range (default); 0: unit = blockIdx (LGM_WINO4_NO_XCD_RANGES=1, A/B)
-  float* ws;
-  long ws_stride;
+struct Args : ConvArgs {
   long long* dbg;      // diagnostic build only (wino4_conv_kernel<CLS, true>): per-workgroup cycle stamps
   float* stats;        // STATS build only: [spatial unit][4 parts][2: sum y, sum y^2][N] of the PRE-BIAS outputs
 };
-
-__device__ __forceinline__ f32x4 add4(const f32x4 a, const f32x4 b) { return a + b; }
-// hipcc emits four v_sub_f32 for a vector subtraction (the neg modifiers of v_pk_add_f32 are not selected)
-__device__ __forceinline__ f32x4 sub4(const f32x4 a, const f32x4 b) {
-  f32x2 lo, hi;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
-      : "=v"(lo)
-      : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(__builtin_shufflevector(b, b, 0, 1)));
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
-      : "=v"(hi)
-      : "v"(__builtin_shufflevector(a, a, 2, 3)), "v"(__builtin_shufflevector(b, b, 2, 3)));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
-__device__ __forceinline__ f32x4 fma4(const float c, const f32x4 a, const f32x4 b) {   // c * a + b
-  return __builtin_elementwise_fma(f32x4{c, c, c, c}, a, b);
-}
-__device__ __forceinline__ f32x2 fma2(const float c, const f32x2 a, const f32x2 b) {
-  return __builtin_elementwise_fma(f32x2{c, c}, a, b);
-}
 
 // EXP (diagnostic builds only): bit 0 drops the transform, bit 1 the patch fetch / commit, bit 2 the U loads, bit 3 the V
 // reads of the phase loop -- wrong results, used to attribute the phase time.
@@ -155,38 +115,8 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
   const int lr = lane & 31, lh = lane >> 5;
 
   // ---- unit ----
-  // Hardware deals consecutive workgroup ids to the eight XCDs round-robin, each with its own 4 MB 16-way L2.  With
-  // unit = blockIdx the 32 (64) workgroups an XCD runs together are units x, x + 8, ...: the same tile block of images
-  // four apart, i.e. patches whose addresses differ by multiples of 1 MB and fall on the SAME L2 sets - they evict each
-  // other between the four phases that share a 128-byte line (FETCH_SIZE 85 MB per launch for 33.5 MB of input at
-  // 64 -> 64 @ 32 x 32, B = 128; the F(2x2) kernel, which always walked XCD-contiguous unit ranges: 38 MB).  An XCD takes a
-  // CONTIGUOUS unit range instead: neighbouring tile blocks and images, addresses spread over all sets, halo rows and
-  // the channel blocks of one tile block shared in one L2.
-  int L = (p.xcd_ranges && (gridDim.x & 7) == 0) ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x;
-  // Two unit orders (host: wino4_unit_order): channel block fastest - the channel blocks and splits of one tile block sit in
-  // one L2 and share its patch (large maps: the input is the big operand) - or channel block SLOWEST - an XCD works on
-  // one or two (channel block, split) slices of U and streams the images past them (8 x 8 maps with hundreds of channels:
-  // U is the big operand, 9 ... 19 MB, and every XCD would otherwise stream all of it)
-  int tn, split, twi, thi, bg;
-  if (p.tn_slowest) {
-    twi = L % p.tb_w;
-    L /= p.tb_w;
-    thi = L % p.tb_h;
-    L /= p.tb_h;
-    bg = L % p.nbg;
-    L /= p.nbg;
-    split = L % p.splits;
-    tn = L / p.splits;
-  } else {
-    tn = L % p.tiles_n;
-    L /= p.tiles_n;
-    split = L % p.splits;
-    L /= p.splits;
-    twi = L % p.tb_w;
-    L /= p.tb_w;
-    thi = L % p.tb_h;
-    bg = L / p.tb_h;
-  }
+  const ConvUnit un = conv_unit(p);
+  const int tn = un.tn, split = un.split, twi = un.twi, thi = un.thi, bg = un.bg;
   const int n0 = tn * 64;
   const int h0 = thi * (4 * GE::TTH), w0 = twi * (4 * GE::TTW), b0 = bg * NI;
   const int ncc = p.C / KC;
@@ -196,14 +126,7 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
 
   // ---- raw patch slots: s = tid + 512 j -> pixel s >> 1 of the patch, channel quad s & 1 ----
   const unsigned nrec_a = (unsigned)((long)p.B * p.H * p.W * p.a_pitch * 4);
-  __amdgpu_buffer_rsrc_t rsrc_a;
-  {
-    const unsigned long long ab = reinterpret_cast<unsigned long long>(p.a);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ab);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(ab >> 32));
-    rsrc_a = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                               __builtin_amdgcn_readfirstlane(nrec_a), 0x00020000);
-  }
+  const __amdgpu_buffer_rsrc_t rsrc_a = wave_buffer_rsrc(p.a, nrec_a);
   unsigned goff[NJ], plds[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -276,15 +199,7 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const Args p) {
   // ---- MFMA role ----
   const int xg = wid & 3, ch = wid >> 2;
   const int vrd = xg * (9 * 256) + lh * 128 + lr * 4;
-  __amdgpu_buffer_rsrc_t rsrc_u;
-  {
-    const unsigned long long ub = reinterpret_cast<unsigned long long>(p.u);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ub);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(ub >> 32));
-    rsrc_u = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                               __builtin_amdgcn_readfirstlane((unsigned)((long)p.N * p.C * NXI * 4)),
-                                               0x00020000);
-  }
+  const __amdgpu_buffer_rsrc_t rsrc_u = wave_buffer_rsrc(p.u, (unsigned)((long)p.N * p.C * NXI * 4));
   const unsigned ulane = (unsigned)((ch * 64 + lane) * 16);
   const unsigned ubase = (unsigned)((tn * ncc + cc0) * NXI + xg * 9) * 2048u;
   // Warm this XCD's L2 with the unit's whole operand range.  Inside a training step every launch finds the caches cold
@@ -696,29 +611,64 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float* __restr
   }
 }
 
-static long unit_count(int cls, int B, int H, int W) {     // units per 64 produced channels, before split-K
-  return cls == 1 ? B / 2 : cls == 2 ? B / 8 : cls == 3 ? B / 32 : (long)B * (H / 16) * (W / 32);
-}
+// This form for the shared host half (wino4_host.h)
+namespace {
+struct Form {
+  using Args = lgmwino4::Args;
+  static constexpr int THREADS = 512, MBUF = lgmwino4::MBUF;
+  static constexpr int UH = 16, UW = 32;            // class 0: maps with H % 16 == 0 and W % 32 == 0
+  static constexpr int NCLS = 4;
+  static constexpr int NI[NCLS] = {1, 2, 8, 32};    // 16 x 16: two images, 8 x 8: eight, 4 x 4: 32 images to a unit
+  static constexpr const char* LAUNCHER = "lgm_wino4_launch";
+  static int splits(const LgmConvGeom* g, int gather_channels, int out_channels);
+  static int launch(Args& p, int cls, bool res, bool partial, bool stats, size_t smem, hipStream_t s);
+  template <int CLS, bool DBG = false, int EXP = 0, bool STATS = false>
+  static void go(const Args& p, size_t smem, hipStream_t s) {
+    lgmwino4host::launch_kernel<wino4_conv_kernel<CLS, DBG, EXP, STATS>, THREADS>(p, smem, s);
+  }
+};
 
-static int unit_class(int H, int W) {
-  if (H == 4 && W == 4) return 3;
-  if (H == 8 && W == 8) return 2;
-  if (H == 16 && W == 16) return 1;
-  if (H >= 16 && W >= 32 && H % 16 == 0 && W % 32 == 0) return 0;
-  return -1;
+int Form::launch(Args& p, int cls, bool res, bool partial, bool stats, size_t smem, hipStream_t s) {
+  p.dbg = (long long*)lgm_wino4_debug_buffer;
+  if (p.dbg && lgm_wino4_debug_slots > 0) {
+    if (lgm_wino4_debug_next >= lgm_wino4_debug_slots || p.units > 4095) p.dbg = nullptr;     // out of slots: the plain build
+    else p.dbg += (long)(lgm_wino4_debug_next++) * 4096 * 32;
+  }
+  lgm_note_kernel(cls == 0 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<0, false, 0, false>") : cls == 1 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<1, false, 0, false>")
+                  : cls == 2 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<2, false, 0, false>") : LGM_KNAME("lgmwino4::wino4_conv_kernel<3, false, 0, false>"));
+  if (p.dbg) {
+    const int e = lgm_wino4_debug_exp;
+    if (cls == 1) go<1, true>(p, smem, s);
+    else if (cls == 2) go<2, true>(p, smem, s);
+    else if (cls == 3) go<3, true>(p, smem, s);
+    else if (e == 0) go<0, true, 0>(p, smem, s);
+    else if (e == 1) go<0, true, 1>(p, smem, s);
+    else if (e == 2) go<0, true, 2>(p, smem, s);
+    else if (e == 3) go<0, true, 3>(p, smem, s);
+    else if (e == 4) go<0, true, 4>(p, smem, s);
+    else if (e == 7) go<0, true, 7>(p, smem, s);
+    else if (e == 8) go<0, true, 8>(p, smem, s);
+    else go<0, true, 15>(p, smem, s);
+  } else if (stats) {
+    if (cls != 0 || p.splits != 1 || res || partial) {
+      lgm_set_error("wino4 (stats): class-0 maps, an unsplit reduction and no residual expected");
+      return LGM_ERR_UNSUPPORTED;
+    }
+    lgm_note_kernel(LGM_KNAME("lgmwino4::wino4_conv_kernel<0, false, 0, true>"));
+    go<0, false, 0, true>(p, smem, s);
+  } else if (cls == 0) go<0>(p, smem, s);
+  else if (cls == 1) go<1>(p, smem, s);
+  else if (cls == 2) go<2>(p, smem, s);
+  else go<3>(p, smem, s);
+  return LGM_OK;
 }
+}  // namespace
 
 }  // namespace lgmwino4
 
-// ---- light workgroups (winograd4l.hip): same operands, 16-tile units, 256 threads ----
-bool lgm_wino4l_supported(const LgmConvGeom* g, int gather_channels, int out_channels);
-long lgm_wino4l_units(const LgmConvGeom* g, int out_channels);
-int lgm_wino4l_stats_parts(const LgmConvGeom* g);
-int lgm_wino4l_class(const LgmConvGeom* g);
-int lgm_wino4l_splits(const LgmConvGeom* g, int gather_channels, int out_channels);
-int lgm_wino4l_launch(const LgmConvGeom* g, int yx, const float* a, long a_pitch, const float* u, const float* bias,
-                      const float* res, long res_pitch, float* out, long out_pitch, void* workspace, long workspace_bytes,
-                      hipStream_t s, int64_t* partial, float* stats);
+using lgmwino4::Form;
+namespace w4h = lgmwino4host;
+
 // LGM_WINO4_LIGHT: 1 = the light workgroups wherever they take the geometry, 0 = the 32-tile workgroups only.  Unset: launch
 // by launch (below) unless lgm_wino4_set_light(1) was called - which lgm_hip.lightning.FlatGradSync does for a rank whose
 // gradient exchange overlaps its backward pass on RCCL (a resident collective shares the chip: with one foreign
@@ -731,23 +681,25 @@ extern "C" int lgm_wino4_set_light(int mode) {
   lgm_wino4_light_override.store(mode, std::memory_order_relaxed);
   return LGM_OK;
 }
-static bool wino4_light_asked() {      // light workgroups requested for every launch they take (see wino4_use_light)
-  static const bool env_given = getenv("LGM_WINO4_LIGHT") != nullptr;
-  static const int env_mode = env_given ? atoi(getenv("LGM_WINO4_LIGHT")) : 0;
+// What was asked for: lgm_wino4_set_light's mode if one is set, else LGM_WINO4_LIGHT.  The environment is read ONCE.  No rule
+// reads WORLD_SIZE any more (round 6): being one rank of several does not by itself mean that a collective is
+// resident beside the launches - lgm_hip.lightning.FlatGradSync switches the light workgroups (and the CU margin) on when its
+// exchange really overlaps the backward pass on RCCL.
+struct Wino4LightAsk {
+  bool given;      // false: nothing asked for, the library decides launch by launch
+  int mode;        // != 0: light workgroups for every launch they take
+};
+static Wino4LightAsk wino4_light_ask() {
+  static const bool env_given = lgm_env_set("LGM_WINO4_LIGHT");
+  static const int env_mode = lgm_env_int("LGM_WINO4_LIGHT", 0);
   const int ov = lgm_wino4_light_override.load(std::memory_order_relaxed);
-  return (ov >= 0 ? ov : env_mode) != 0;
+  return {env_given || ov >= 0, ov >= 0 ? ov : env_mode};
 }
 static bool wino4_use_light(const LgmConvGeom* g, int gather_channels, int out_channels) {
-  // The environment is read ONCE.  No rule reads WORLD_SIZE any more (round 6): being one rank of several does
-  // not by itself mean that a collective is resident beside the launches - lgm_hip.lightning.FlatGradSync switches the
-  // light workgroups (and the CU margin) on when its exchange really overlaps the backward pass on RCCL.
-  static const bool env_given = getenv("LGM_WINO4_LIGHT") != nullptr;
-  static const int env_mode = env_given ? atoi(getenv("LGM_WINO4_LIGHT")) : 0;
-  const int ov = lgm_wino4_light_override.load(std::memory_order_relaxed);
-  const int mode = ov >= 0 ? ov : env_mode;
   if (!lgm_wino4l_supported(g, gather_channels, out_channels)) return false;
-  if (mode != 0) return true;
-  if (env_given || ov >= 0) return false;   // 0 asked for: 32-tile only
+  const Wino4LightAsk ask = wino4_light_ask();
+  if (ask.mode != 0) return true;
+  if (ask.given) return false;   // 0 asked for: 32-tile only
   // One GPU, nothing asked for: the light workgroups for the launches the 32-tile kernel cannot fill the chip with -
   // fewer 32-tile units than the class's bound (LGM_WINO4_LIGHT_BELOW="a,b,c": W % 32 == 0 maps, 16x16, 8x8; 0 = never).
   // Measured per step (tools/step_ab.sh): B = 64 6.94 -> 6.73 ms, B = 32 5.37 -> 5.21; at B = 128 (256 / 128 / 64 units)
@@ -767,20 +719,8 @@ static bool wino4_use_light(const LgmConvGeom* g, int gather_channels, int out_c
   return cls >= 0 && lgm_wino4l_units(g, out_channels) / 2 < below[cls];
 }
 
-static bool wino4_big_supported(const LgmConvGeom* g, int gather_channels, int out_channels);
 bool lgm_wino4_supported(const LgmConvGeom* g, int gather_channels, int out_channels) {
-  return wino4_use_light(g, gather_channels, out_channels) || wino4_big_supported(g, gather_channels, out_channels);
-}
-static bool wino4_big_supported(const LgmConvGeom* g, int gather_channels, int out_channels) {
-  using namespace lgmwino4;
-  if (!(g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1)) return false;
-  if (gather_channels % 8 != 0 || out_channels % 64 != 0 || gather_channels % 32 != 0) return false;
-  const int cls = unit_class(g->H, g->W);
-  if (cls < 0) return false;
-  const long pix = (long)g->B * g->H * g->W + g->W + 1;
-  if (pix * gather_channels >= (1L << 29) || pix * out_channels >= (1L << 29)) return false;
-  if ((long)gather_channels * out_channels * 36 >= (1L << 29)) return false;
-  return g->B % (cls == 1 ? 2 : cls == 2 ? 8 : cls == 3 ? 32 : 1) == 0;
+  return wino4_use_light(g, gather_channels, out_channels) || w4h::supported<Form>(g, gather_channels, out_channels);
 }
 
 // Split count of an F(4x4) launch with `base` workgroups per split on `slots` workgroup slots.  A workgroup has the CU to
@@ -809,21 +749,17 @@ int lgm_wino4_pick_splits(long base, long slots, int phases, int smax, int min_p
   return best;
 }
 
-int lgm_wino4_splits(const LgmConvGeom* g, int gather_channels, int out_channels) {
-  using namespace lgmwino4;
-  if (wino4_use_light(g, gather_channels, out_channels)) return lgm_wino4l_splits(g, gather_channels, out_channels);
-  const int cls = unit_class(g->H, g->W);
+int Form::splits(const LgmConvGeom* g, int gather_channels, int out_channels) {
+  const int cls = w4h::unit_class<Form>(g->H, g->W);
   if (cls < 0) return 1;
-  const long base = unit_count(cls, g->B, g->H, g->W) * (out_channels / 64);
-  static const int forced = getenv("LGM_WINO4_SPLITS") ? atoi(getenv("LGM_WINO4_SPLITS")) : 0;
-  const int phases = gather_channels / KC;
-  int smax = phases / 2 < 16 ? phases / 2 : 16;
-  if (smax < 1) smax = 1;
-  if (forced > 0) return forced < smax ? forced : smax;
+  const long base = w4h::unit_count<Form>(cls, g->B, g->H, g->W) * (out_channels / 64);
+  static const int forced = lgm_env_int("LGM_WINO4_SPLITS", 0);
   const long slots = lgm_cu_budget();
-  if (base >= slots * 3 / 4) return 1;
-  static const int min_pps = getenv("LGM_WINO4_MIN_PPS") ? atoi(getenv("LGM_WINO4_MIN_PPS")) : 4;
-  static const bool old_rule = getenv("LGM_WINO4_SPLITS_CEIL") != nullptr;      // A/B switch: the former rule
+  const int phases = gather_channels / lgmwino4dev::KC;
+  int smax;
+  if (const int s = w4h::split_front(base, slots, phases, forced, &smax)) return s;
+  static const int min_pps = lgm_env_int("LGM_WINO4_MIN_PPS", 4);
+  static const bool old_rule = lgm_env_set("LGM_WINO4_SPLITS_CEIL");      // A/B switch: the former rule
   if (old_rule) {
     int s = (int)((slots + base - 1) / base);
     if (s > smax) s = smax;
@@ -833,106 +769,20 @@ int lgm_wino4_splits(const LgmConvGeom* g, int gather_channels, int out_channels
   return lgm_wino4_pick_splits(base, slots, phases, smax, min_pps);
 }
 
-// partial (optional, int64 x 2): as lgm_wino_launch - the caller's consumer sums the split-K planes itself
+int lgm_wino4_splits(const LgmConvGeom* g, int gather_channels, int out_channels) {
+  return wino4_use_light(g, gather_channels, out_channels) ? lgm_wino4l_splits(g, gather_channels, out_channels)
+                                                           : Form::splits(g, gather_channels, out_channels);
+}
+
+// picks the workgroup form of this launch
 int lgm_wino4_launch(const LgmConvGeom* g, int yx, const float* a, long a_pitch, const float* u, const float* bias,
                      const float* res, long res_pitch, float* out, long out_pitch, void* workspace, long workspace_bytes,
-                     hipStream_t s, int64_t* partial = nullptr, float* stats = nullptr) {
-  using namespace lgmwino4;
+                     hipStream_t s, int64_t* partial, float* stats) {
   if (wino4_use_light(g, yx ? g->Nw : g->Cw, yx ? g->Cw : g->Nw))
     return lgm_wino4l_launch(g, yx, a, a_pitch, u, bias, res, res_pitch, out, out_pitch, workspace, workspace_bytes, s, partial,
                              stats);
-  Args p{};
-  p.stats = stats;
-  p.a = a; p.u = u; p.bias = bias; p.res = res; p.out = out;
-  p.a_pitch = a_pitch; p.res_pitch = res_pitch; p.out_pitch = out_pitch;
-  p.B = g->B; p.H = g->H; p.W = g->W;
-  p.C = yx ? g->Nw : g->Cw;
-  p.N = yx ? g->Cw : g->Nw;
-  const int cls = unit_class(g->H, g->W);
-  p.tb_h = cls == 0 ? g->H / 16 : 1;
-  p.tb_w = cls == 0 ? g->W / 32 : 1;
-  p.nbg = cls == 1 ? g->B / 2 : cls == 2 ? g->B / 8 : cls == 3 ? g->B / 32 : g->B;
-  p.tiles_n = p.N / 64;
-  const long M = (long)g->B * g->H * g->W;
-  p.splits = lgm_wino4_splits(g, p.C, p.N);
-  if (p.splits > 1) {
-    const long need = (long)p.splits * M * p.N * (long)sizeof(float);
-    if (!workspace || workspace_bytes < need || !lgm_aligned16(workspace)) p.splits = 1;
-  }
-  p.ws = (float*)workspace;
-  p.ws_stride = M * p.N;
-  p.pps = lgm_cdiv(p.C / KC, p.splits);
-  p.splits = lgm_cdiv(p.C / KC, p.pps);
-  p.units = (int)((long)p.nbg * p.tb_h * p.tb_w * p.tiles_n * p.splits);
-  {
-    // bytes the chip's eight L2s fetch under either order: patches once (x 1.2 halo) and all of U per XCD, or patches once per
-    // channel block and U once
-    static const bool no_ranges = getenv("LGM_WINO4_NO_XCD_RANGES") != nullptr;
-    p.xcd_ranges = no_ranges ? 0 : 1;
-    static const int forced = getenv("LGM_WINO4_TN_SLOWEST") ? atoi(getenv("LGM_WINO4_TN_SLOWEST")) : -1;
-    const double in_b = 1.2 * (double)M * p.C * 4.0, u_b = 36.0 * p.C * p.N * 4.0;
-    p.tn_slowest = forced >= 0 ? forced : ((in_b + 8.0 * u_b > in_b * p.tiles_n + u_b) ? 1 : 0);
-  }
-  const size_t smem = (size_t)MBUF * sizeof(float);
-  p.dbg = (long long*)lgm_wino4_debug_buffer;
-  if (p.dbg && lgm_wino4_debug_slots > 0) {
-    if (lgm_wino4_debug_next >= lgm_wino4_debug_slots || p.units > 4095) p.dbg = nullptr;     // out of slots: the plain build
-    else p.dbg += (long)(lgm_wino4_debug_next++) * 4096 * 32;
-  }
-#define LGM_W4LAUNCH(CC, DD, EE)                                                                                \
-  do {                                                                                                          \
-    auto kern = wino4_conv_kernel<CC, DD, EE>;                                                                        \
-    static bool attr = false;                                                                                   \
-    if (!attr) {                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)smem);                                                                     \
-      attr = true;                                                                                              \
-    }                                                                                                           \
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.units), dim3(512), smem, s, p);                                   \
-  } while (0)
-  lgm_note_kernel(cls == 0 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<0, false, 0, false>") : cls == 1 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<1, false, 0, false>")
-                  : cls == 2 ? LGM_KNAME("lgmwino4::wino4_conv_kernel<2, false, 0, false>") : LGM_KNAME("lgmwino4::wino4_conv_kernel<3, false, 0, false>"));
-  if (p.dbg) {
-    const int e = lgm_wino4_debug_exp;
-    if (cls == 1) LGM_W4LAUNCH(1, true, 0);
-    else if (cls == 2) LGM_W4LAUNCH(2, true, 0);
-    else if (cls == 3) LGM_W4LAUNCH(3, true, 0);
-    else if (e == 0) LGM_W4LAUNCH(0, true, 0);
-    else if (e == 1) LGM_W4LAUNCH(0, true, 1);
-    else if (e == 2) LGM_W4LAUNCH(0, true, 2);
-    else if (e == 3) LGM_W4LAUNCH(0, true, 3);
-    else if (e == 4) LGM_W4LAUNCH(0, true, 4);
-    else if (e == 7) LGM_W4LAUNCH(0, true, 7);
-    else if (e == 8) LGM_W4LAUNCH(0, true, 8);
-    else LGM_W4LAUNCH(0, true, 15);
-  } else if (stats) {
-    if (cls != 0 || p.splits != 1 || res || partial) {
-      lgm_set_error("wino4 (stats): class-0 maps, an unsplit reduction and no residual expected");
-      return LGM_ERR_UNSUPPORTED;
-    }
-    auto kern = wino4_conv_kernel<0, false, 0, true>;
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      attr = true;
-    }
-    lgm_note_kernel(LGM_KNAME("lgmwino4::wino4_conv_kernel<0, false, 0, true>"));
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.units), dim3(512), smem, s, p);
-  } else if (cls == 0) LGM_W4LAUNCH(0, false, 0);
-  else if (cls == 1) LGM_W4LAUNCH(1, false, 0);
-  else if (cls == 2) LGM_W4LAUNCH(2, false, 0);
-  else LGM_W4LAUNCH(3, false, 0);
-#undef LGM_W4LAUNCH
-  if (partial) {
-    partial[0] = p.splits;
-    partial[1] = p.ws_stride;
-    LGM_LAUNCH_CHECK();
-    return LGM_OK;
-  }
-  if (p.splits > 1)
-    return lgm_splitk_reduce_launch(p.ws, p.ws_stride, p.splits, bias, res, res_pitch, out, out_pitch, M, p.N, s);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
+  return w4h::conv_launch<Form>(g, yx, a, a_pitch, u, bias, res, res_pitch, out, out_pitch, workspace, workspace_bytes, s,
+                                partial, stats);
 }
 
 // ---- C-ABI ------------------------------------------------------------------------------------
@@ -947,12 +797,11 @@ extern "C" int64_t lgm_conv3x3_wino4_supported(const LgmConvGeom* g, int yx) {
 extern "C" int64_t lgm_conv3x3_wino4_stats_floats(const LgmConvGeom* g, int* parts_per_image) {
   if (parts_per_image) *parts_per_image = 0;
   if (!g || !lgm_wino4_supported(g, g->Cw, g->Nw)) return 0;
-  const bool light = wino4_use_light(g, g->Cw, g->Nw);
-  if (light ? lgm_wino4l_stats_parts(g) == 0 : lgmwino4::unit_class(g->H, g->W) != 0) return 0;
+  const int per = wino4_use_light(g, g->Cw, g->Nw) ? lgm_wino4l_stats_parts(g) : w4h::stats_parts<Form>(g);
+  if (per == 0) return 0;
   if (lgm_wino4_splits(g, g->Cw, g->Nw) != 1) return 0;
-  static const bool off = getenv("LGM_NO_GN_EPI_STATS") != nullptr;      // A/B switch
+  static const bool off = lgm_env_set("LGM_NO_GN_EPI_STATS");      // A/B switch
   if (off) return 0;
-  const int per = light ? lgm_wino4l_stats_parts(g) : (g->H / 16) * (g->W / 32) * 4;
   if (parts_per_image) *parts_per_image = per;
   return (int64_t)g->B * per * 2 * g->Nw;
 }
@@ -961,8 +810,7 @@ extern "C" int64_t lgm_conv3x3_wino4_workspace(const LgmConvGeom* g, int yx) {
   if (!g) return -1;
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   if (!lgm_wino4_supported(g, gc, oc)) return 0;
-  const int s = lgm_wino4_splits(g, gc, oc);
-  return s > 1 ? (int64_t)s * g->B * g->H * g->W * oc * (int64_t)sizeof(float) : 0;
+  return lgm_splitk_workspace(g, oc, lgm_wino4_splits(g, gc, oc));
 }
 
 // 1 when the F(4x4) kernel is expected to beat the F(2x2) kernel on this layer (measured on the MI355X, B = 128,
@@ -971,51 +819,51 @@ extern "C" int64_t lgm_conv3x3_wino4_preferred(const LgmConvGeom* g, int yx) {
   if (!g) return 0;
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   if (!lgm_wino4_supported(g, gc, oc)) return 0;
-  static const int force = getenv("LGM_WINO4_FORCE") ? atoi(getenv("LGM_WINO4_FORCE")) : 0;
+  static const int force = lgm_env_int("LGM_WINO4_FORCE", 0);
   if (force) return 1;
+  const bool light = wino4_use_light(g, gc, oc);
+  const int cls = light ? lgm_wino4l_class(g) : w4h::unit_class<Form>(g->H, g->W);
   // maps >= 16 x 32: from 128 units (B = 64 at 32 x 32: the reduction is split in two, 4 phases per workgroup: 7.28 vs
   // 7.35 ms per step against the F(2x2) pair on its joint plan; without the split 7.44); 256 units: 10.9 vs 11.4 ms;
   // 16 x 16 maps (more phases per unit) likewise from 128 units
   // with the light workgroups (16-tile units: twice the workgroups, one wave per SIMD each) already from 32 such units -
   // the per-rank batches 32 and 16 at 32 x 32: 5.35 -> 5.27 and 4.54 -> 4.52 ms per step, nothing changes at 64 and 128
-  static const long min_units0_env = getenv("LGM_WINO4_MIN_UNITS") ? atol(getenv("LGM_WINO4_MIN_UNITS")) : -1;
-  static const long min_units1_env = getenv("LGM_WINO4_MIN_UNITS1") ? atol(getenv("LGM_WINO4_MIN_UNITS1")) : -1;
-  const long min_units0 = min_units0_env >= 0 ? min_units0_env : (wino4_use_light(g, gc, oc) ? 32 : 128);
-  const long min_units1 = min_units1_env >= 0 ? min_units1_env : (wino4_use_light(g, gc, oc) ? 32 : 128);
-  const bool light = wino4_use_light(g, gc, oc);
-  const int cls = g->H == 4 && g->W == 4 ? 3 : g->H == 8 && g->W == 8 ? 2 : g->H == 16 && g->W == 16 ? 1 : 0;
+  static const long min_units0_env = lgm_env_long("LGM_WINO4_MIN_UNITS", -1);
+  static const long min_units1_env = lgm_env_long("LGM_WINO4_MIN_UNITS1", -1);
+  const long min_units0 = min_units0_env >= 0 ? min_units0_env : (light ? 32 : 128);
+  const long min_units1 = min_units1_env >= 0 ? min_units1_env : (light ? 32 : 128);
   if (cls == 3) {
     // 4 x 4 maps (one tile per image, 32 images per unit): the layer's two directions and its weight gradient switch
     // together, so the rule reads the NARROWER side of the layer, the same in both directions.  From 32 units of that side
     // (B = 128 with 512 channels: 8 splits of 8 phases at 512 -> 512, the shape of the 8 x 8 256 -> 256 launches); the
     // 256-channel layers (16 units) stay on the F(2x2) pair.  No light workgroups on 4 x 4 maps: when they are asked for
     // (a collective resident beside the launches) the F(2x2) pair keeps these layers.  LGM_WINO4_NO4=1: A/B switch.
-    static const bool no4 = getenv("LGM_WINO4_NO4") != nullptr;
+    static const bool no4 = lgm_env_set("LGM_WINO4_NO4");
     const int narrow = gc < oc ? gc : oc;
-    const long units = lgmwino4::unit_count(3, g->B, g->H, g->W) * (narrow / 64);
-    return (!no4 && !wino4_light_asked() && narrow >= 256 && units >= 32) ? 1 : 0;
+    const long units = w4h::unit_count<Form>(3, g->B, g->H, g->W) * (narrow / 64);
+    return (!no4 && wino4_light_ask().mode == 0 && narrow >= 256 && units >= 32) ? 1 : 0;
   }
   // counted in 32-tile units whichever workgroup size runs: the thresholds keep their meaning
-  const long base = light ? lgm_wino4l_units(g, oc) / 2 : lgmwino4::unit_count(cls, g->B, g->H, g->W) * (oc / 64);
+  const long base = light ? lgm_wino4l_units(g, oc) / 2 : w4h::unit_count<Form>(cls, g->B, g->H, g->W) * (oc / 64);
   // forward with the light workgroups: LGM_WINO4_FWD_ALL=1 takes every layer they support (tuning knob)
-  static const int fwd_all = getenv("LGM_WINO4_FWD_ALL") ? atoi(getenv("LGM_WINO4_FWD_ALL")) : 0;
+  static const int fwd_all = lgm_env_int("LGM_WINO4_FWD_ALL", 0);
   if (light && yx == 0 && fwd_all) return 1;
-  static const int bwd_all = getenv("LGM_WINO4_BWD_ALL") ? atoi(getenv("LGM_WINO4_BWD_ALL")) : 0;
+  static const int bwd_all = lgm_env_int("LGM_WINO4_BWD_ALL", 0);
   if (light && yx == 1 && bwd_all) return 1;
   // 8 x 8 maps: few units (8 images each), so the reduction is split; worth it when a split still has >= 8 phases
-  static const bool no8 = getenv("LGM_WINO4_NO8") != nullptr;           // A/B switch
+  static const bool no8 = lgm_env_set("LGM_WINO4_NO8");           // A/B switch
   // Forward and backward: the heavy 8 x 8 layers leave the F(2x2) pair (input gradient + weight gradient in one launch) for
   // the F(4x4) input gradient + the F(4x4) weight gradient on 2 x 2-tile groups (winograd4_wgrad.hip), two layers per
   // launch: 10.28 -> 10.16 ms per step.  (With the F(2x2) weight gradient left standing alone the same move cost what it
   // gained: 10.97 vs 10.95, later 10.66 vs 10.66.)  LGM_WINO4_NOYX8=1: forward only.
-  static const bool noyx8 = getenv("LGM_WINO4_NOYX8") != nullptr;
-  static const int c2_minc = getenv("LGM_WINO4_C2_MINC") ? atoi(getenv("LGM_WINO4_C2_MINC")) : 256;
+  static const bool noyx8 = lgm_env_set("LGM_WINO4_NOYX8");
+  static const int c2_minc = lgm_env_int("LGM_WINO4_C2_MINC", 256);
   if (cls == 2) return (!no8 && (yx == 0 || !noyx8) && base >= 32 && gc >= c2_minc) ? 1 : 0;
-  static const int c1_minc = getenv("LGM_WINO4_C1_MINC") ? atoi(getenv("LGM_WINO4_C1_MINC")) : 0;
+  static const int c1_minc = lgm_env_int("LGM_WINO4_C1_MINC", 0);
   if (cls == 1 && gc < c1_minc) return 0;
   // 16 x 16 maps with a reduction of >= 128 channels (>= 16 phases: two splits of >= 8) already from 64 units - the
   // per-rank batch of two GPUs: 6.98 -> 6.94 ms per step at B = 64, nothing changes at B = 128 (LGM_WINO4_MIN_UNITS1W)
-  static const long min_units1w_env = getenv("LGM_WINO4_MIN_UNITS1W") ? atol(getenv("LGM_WINO4_MIN_UNITS1W")) : -1;
+  static const long min_units1w_env = lgm_env_long("LGM_WINO4_MIN_UNITS1W", -1);
   const long min_units1w = min_units1w_env >= 0 ? min_units1w_env : (light ? 32 : 64);
   if (cls == 1 && gc >= 128 && base >= min_units1w) return 1;
   return base >= (cls == 1 ? min_units1 : min_units0) ? 1 : 0;
@@ -1037,12 +885,9 @@ extern "C" int lgm_conv3x3_wino4(int yx, const LgmConvGeom* g, const float* a, i
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   LGM_REQUIRE(lgm_wino4_supported(g, gc, oc), "conv3x3_wino4: unsupported geometry (3x3/s1/p1, maps 16x16 or H %% 16 == 0 "
               "and W %% 32 == 0, reduction channels %% 32, produced channels %% 64)");
-  LGM_REQUIRE(a_pitch % 4 == 0 && a_pitch >= gc && lgm_aligned16(a) && lgm_aligned16(u) && lgm_aligned16(out) &&
-              out_pitch % 4 == 0 && out_pitch >= oc && (!res || (lgm_aligned16(res) && res_pitch % 4 == 0 && res_pitch >= oc)) &&
-              (!bias || lgm_aligned16(bias)), "conv3x3_wino4: 16-byte aligned operands with pitch %% 4 == 0 expected");
-  const long pix = (long)g->B * g->H * g->W + g->W + 1;
-  LGM_REQUIRE(pix * a_pitch < (1L << 29) && pix * out_pitch < (1L << 29) && pix * (res ? res_pitch : 0) < (1L << 29),
-              "conv3x3_wino4: tensor too large for 32-bit offsets");
+  if (const int rc = lgm_conv_operands_check("conv3x3_wino4", g, gc, oc, a, a_pitch,
+                                             u, bias, res, res_pitch, out, out_pitch))
+    return rc;
   return lgm_wino4_launch(g, yx, a, a_pitch, u, bias, res, res_pitch, out, out_pitch, workspace, workspace_bytes,
                           (hipStream_t)stream);
 }
@@ -1060,11 +905,9 @@ extern "C" int lgm_conv3x3_wino4_stats(const LgmConvGeom* g, const float* x, int
               "conv3x3_wino4_stats: geometry not taken, or the statistics buffer (%ld floats) is not what THIS kernel selection "
               "writes (%ld: ask lgm_conv3x3_wino4_stats_floats again after lgm_wino4_set_light / lgm_set_cu_margin)",
               (long)stats_floats, (long)need);
-  LGM_REQUIRE(x_pitch % 4 == 0 && x_pitch >= g->Cw && lgm_aligned16(x) && lgm_aligned16(u) && lgm_aligned16(y) &&
-              y_pitch % 4 == 0 && y_pitch >= g->Nw && (!bias || lgm_aligned16(bias)),
-              "conv3x3_wino4_stats: 16-byte aligned operands with pitch %% 4 == 0 expected");
-  const long pix = (long)g->B * g->H * g->W + g->W + 1;
-  LGM_REQUIRE(pix * x_pitch < (1L << 29) && pix * y_pitch < (1L << 29), "conv3x3_wino4_stats: tensor too large for 32-bit offsets");
+  if (const int rc = lgm_conv_operands_check("conv3x3_wino4_stats", g, g->Cw, g->Nw, x, x_pitch,
+                                             u, bias, nullptr, 0, y, y_pitch))
+    return rc;
   return lgm_wino4_launch(g, 0, x, x_pitch, u, bias, nullptr, 0, y, y_pitch, nullptr, 0, (hipStream_t)stream, nullptr, stats);
 }
 
@@ -1074,11 +917,9 @@ extern "C" int lgm_conv3x3_wino4_partial(int yx, const LgmConvGeom* g, const flo
   LGM_REQUIRE(g && a && u && out && partial, "conv3x3_wino4_partial: null pointer");
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   LGM_REQUIRE(lgm_wino4_supported(g, gc, oc), "conv3x3_wino4_partial: unsupported geometry");
-  LGM_REQUIRE(a_pitch % 4 == 0 && a_pitch >= gc && lgm_aligned16(a) && lgm_aligned16(u) && lgm_aligned16(out) &&
-              out_pitch % 4 == 0 && out_pitch >= oc && (!bias || lgm_aligned16(bias)),
-              "conv3x3_wino4_partial: 16-byte aligned operands with pitch %% 4 == 0 expected");
-  const long pix = (long)g->B * g->H * g->W + g->W + 1;
-  LGM_REQUIRE(pix * a_pitch < (1L << 29) && pix * out_pitch < (1L << 29), "conv3x3_wino4_partial: tensor too large for 32-bit offsets");
+  if (const int rc = lgm_conv_operands_check("conv3x3_wino4_partial", g, gc, oc, a, a_pitch,
+                                             u, bias, nullptr, 0, out, out_pitch))
+    return rc;
   return lgm_wino4_launch(g, yx, a, a_pitch, u, bias, nullptr, 0, out, out_pitch, workspace, workspace_bytes,
                           (hipStream_t)stream, partial);
 }

@@ -24,7 +24,7 @@
 
 #include <type_traits>
 
-#include "lgm_common.h"
+#include "wino4_device.h"
 
 // W4W_EXP (attribution builds only, -DW4W_EXP=n into a separate library, LGM_LIB=<path>): bit 0 drops the Yt transform,
 // bit 1 the Xt transform, bit 2 the raw loads, bit 3 the operand reads of the MFMA steps -- wrong results, timing valid.
@@ -33,10 +33,8 @@
 #endif
 
 namespace lgmwino4w {
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace lgmwino4dev;
 
-constexpr int NXI = 36;
 constexpr int YB = NXI * 256;      // floats of a Yt buffer: [xi][tile pair][n 64][2]
 constexpr int XB = NXI * 128;      // floats of an Xt buffer: [xi][tile pair][c 32][2]
 constexpr int OPB = YB + XB;       // one operand buffer
@@ -57,24 +55,6 @@ struct WArgs {
   int sq;              // group shape: 0 = four tiles in a row (4 x 16 output pixels), 1 = 2 x 2 tiles (8 x 8: the 8 x 8 maps),
                        // 2 = the single tiles of four images (the 4 x 4 maps)
 };
-
-__device__ __forceinline__ f32x4 add4(const f32x4 a, const f32x4 b) { return a + b; }
-__device__ __forceinline__ f32x4 sub4(const f32x4 a, const f32x4 b) {
-  f32x2 lo, hi;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
-      : "=v"(lo)
-      : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(__builtin_shufflevector(b, b, 0, 1)));
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
-      : "=v"(hi)
-      : "v"(__builtin_shufflevector(a, a, 2, 3)), "v"(__builtin_shufflevector(b, b, 2, 3)));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
-__device__ __forceinline__ f32x4 fma4(const float c, const f32x4 a, const f32x4 b) {   // c * a + b
-  return __builtin_elementwise_fma(f32x4{c, c, c, c}, a, b);
-}
-__device__ __forceinline__ f32x2 fma2(const float c, const f32x2 a, const f32x2 b) {
-  return __builtin_elementwise_fma(f32x2{c, c}, a, b);
-}
 
 // The kernel body as a device function of (arguments, logical block id): runs as its own launch or as a block range of a
 // grouped launch (several layers' weight gradients in one grid).
@@ -114,15 +94,8 @@ __device__ __forceinline__ void wino4_wgrad_body(const WArgs& p, const int bidx)
   // the X descriptor starts one row and one column BEFORE the tensor (offsets of halo pixels stay non-negative; the W + 1
   // pixels in front of the allocation are never requested: every padding position gets an out-of-range offset)
   const unsigned nrec_x = (unsigned)(((long)p.B * p.H * p.W + p.W + 1) * p.x_pitch * 4);
-  auto rsrc = [&](const float* ptr, unsigned nrec) {
-    const unsigned long long ab = reinterpret_cast<unsigned long long>(ptr);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ab);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(ab >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(nrec), 0x00020000);
-  };
-  const __amdgpu_buffer_rsrc_t rsrc_y = rsrc(p.y, nrec_y);
-  const __amdgpu_buffer_rsrc_t rsrc_x = rsrc(p.x - (long)(p.W + 1) * p.x_pitch, nrec_x);
+  const __amdgpu_buffer_rsrc_t rsrc_y = wave_buffer_rsrc(p.y, nrec_y);
+  const __amdgpu_buffer_rsrc_t rsrc_x = wave_buffer_rsrc(p.x - (long)(p.W + 1) * p.x_pitch, nrec_x);
 
   // group g -> (image, tile row, group of the row).  Decoded ONCE (three integer divisions cost ~60 instructions, and a phase
   // has only 18 MFMAs per wave to hide them under); every later group is the previous one advanced like an odometer.
@@ -485,9 +458,8 @@ bool lgm_wino4_wgrad_supported(const LgmConvGeom* g) {
 
 // The layers that take this kernel: where the F(4x4) input gradient is preferred (lgm_conv3x3_wino4_preferred: the large
 // maps at batches that fill the chip), so that a layer's two gradients switch together; LGM_NO_WINO4_WGRAD=1: never.
-extern "C" int64_t lgm_conv3x3_wino4_preferred(const LgmConvGeom* g, int yx);
 bool lgm_wino4_wgrad_use(const LgmConvGeom* g) {
-  static const bool off = getenv("LGM_NO_WINO4_WGRAD") != nullptr || getenv("LGM_NO_WINO4") != nullptr;
+  static const bool off = lgm_env_set("LGM_NO_WINO4_WGRAD") || lgm_env_set("LGM_NO_WINO4");
   return !off && lgm_wino4_wgrad_supported(g) && lgm_conv3x3_wino4_preferred(g, 1) != 0;
 }
 
@@ -522,7 +494,7 @@ static void wino4_wgrad_prepare(const LgmConvGeom* g, const float* y, long y_pit
   p.tiles_c = g->Cw / 32;
   p.splits = splits; p.gps = gps; p.total_groups = total;
   p.sq = (g->H == 4 && g->W == 4) ? 2 : (g->W % 16 != 0) ? 1 : 0;
-  static const int xcd_order = getenv("LGM_W4W_XCD") ? atoi(getenv("LGM_W4W_XCD")) : 1;
+  static const int xcd_order = lgm_env_int("LGM_W4W_XCD", 1);
   p.xcd_order = xcd_order;
   p.grow = p.sq == 2 ? 1 : p.sq ? g->W / 8 : g->W / 16;
   p.trows = p.sq == 2 ? 1 : p.sq ? g->H / 8 : g->H / 4;

@@ -28,18 +28,11 @@
 
 #include <type_traits>
 
-#include "lgm_common.h"
-
-int lgm_splitk_reduce_launch(const float* ws, long ws_stride, int splits, const float* bias, const float* res,
-                             long res_pitch, float* out, long out_pitch, long M, int N, hipStream_t s);
+#include "wino4_host.h"
 
 namespace lgmwino4l {
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace lgmwino4dev;
 
-constexpr int KC = 8;              // reduction channels per phase
-constexpr int NXI = 36;
 constexpr int NT = 16;             // tiles per unit
 constexpr int VBUF = NXI * 128;    // floats per V buffer: [xi][kq 2][tile 16][4]
 constexpr int MBUF = NXI * NT * 32;   // floats of the epilogue exchange: [xi][tile 16][8 quads (swizzled)][4]
@@ -59,43 +52,9 @@ struct Geo<2> {   // 8 x 8 maps: 2 x 2 tiles of four images; 4 RS = 8, IMG = 16 
   static constexpr int NI = 4, TTH = 2, TTW = 2, PH = 10, PW = 10, RS = 10, IMG = 112, PLANE = 449;   // tiles 8 banks apart
 };
 
-struct Args {
-  const float* a;      // gathered activations, NHWC
-  const float* u;      // transformed weights [N/64][C/8][36][2][2][32][4] (wino4_weights_kernel)
-  const float* bias;
-  const float* res;
-  float* out;
-  long a_pitch, res_pitch, out_pitch;
-  int B, H, W;
-  int C;               // reduction channels
-  int N;               // produced channels
-  int tb_h, tb_w, tiles_n, nbg;
-  int splits, pps, units;
-  int tn_slowest;      // unit order, see the kernel
-  int xcd_ranges;      // 1: an XCD takes a contiguous unit range (default); 0: unit = blockIdx (LGM_WINO4_NO_XCD_RANGES=1, A/B)
-  float* ws;
-  long ws_stride;
+struct Args : ConvArgs {
   float* stats;        // STATS build only: [spatial unit][4 parts][2: sum y, sum y^2][N] of the PRE-BIAS outputs
 };
-
-__device__ __forceinline__ f32x4 add4(const f32x4 a, const f32x4 b) { return a + b; }
-// hipcc emits four v_sub_f32 for a vector subtraction (the neg modifiers of v_pk_add_f32 are not selected)
-__device__ __forceinline__ f32x4 sub4(const f32x4 a, const f32x4 b) {
-  f32x2 lo, hi;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
-      : "=v"(lo)
-      : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(__builtin_shufflevector(b, b, 0, 1)));
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
-      : "=v"(hi)
-      : "v"(__builtin_shufflevector(a, a, 2, 3)), "v"(__builtin_shufflevector(b, b, 2, 3)));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
-__device__ __forceinline__ f32x4 fma4(const float c, const f32x4 a, const f32x4 b) {   // c * a + b
-  return __builtin_elementwise_fma(f32x4{c, c, c, c}, a, b);
-}
-__device__ __forceinline__ f32x2 fma2(const float c, const f32x2 a, const f32x2 b) {
-  return __builtin_elementwise_fma(f32x2{c, c}, a, b);
-}
 
 template <int CLS, bool STATS = false>
 __global__ __launch_bounds__(256, 2) void wino4l_conv_kernel(const Args p) {
@@ -115,38 +74,8 @@ __global__ __launch_bounds__(256, 2) void wino4l_conv_kernel(const Args p) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   // ---- unit ----
-  // Hardware deals consecutive workgroup ids to the eight XCDs round-robin, each with its own 4 MB 16-way L2.  With
-  // unit = blockIdx the 32 (64) workgroups an XCD runs together are units x, x + 8, ...: the same tile block of images
-  // four apart, i.e. patches whose addresses differ by multiples of 1 MB and fall on the SAME L2 sets - they evict each
-  // other between the four phases that share a 128-byte line (FETCH_SIZE 85 MB per launch for 33.5 MB of input at
-  // 64 -> 64 @ 32 x 32, B = 128; the F(2x2) kernel, which always walked XCD-contiguous unit ranges: 38 MB).  An XCD takes a
-  // CONTIGUOUS unit range instead: neighbouring tile blocks and images, addresses spread over all sets, halo rows and
-  // the channel blocks of one tile block shared in one L2.
-  int L = (p.xcd_ranges && (gridDim.x & 7) == 0) ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x;
-  // Two unit orders (host: wino4_unit_order): channel block fastest - the channel blocks and splits of one tile block sit in
-  // one L2 and share its patch (large maps: the input is the big operand) - or channel block SLOWEST - an XCD works on
-  // one or two (channel block, split) slices of U and streams the images past them (8 x 8 maps with hundreds of channels:
-  // U is the big operand, 9 ... 19 MB, and every XCD would otherwise stream all of it)
-  int tn, split, twi, thi, bg;
-  if (p.tn_slowest) {
-    twi = L % p.tb_w;
-    L /= p.tb_w;
-    thi = L % p.tb_h;
-    L /= p.tb_h;
-    bg = L % p.nbg;
-    L /= p.nbg;
-    split = L % p.splits;
-    tn = L / p.splits;
-  } else {
-    tn = L % p.tiles_n;
-    L /= p.tiles_n;
-    split = L % p.splits;
-    L /= p.splits;
-    twi = L % p.tb_w;
-    L /= p.tb_w;
-    thi = L % p.tb_h;
-    bg = L / p.tb_h;
-  }
+  const ConvUnit un = conv_unit(p);
+  const int tn = un.tn, split = un.split, twi = un.twi, thi = un.thi, bg = un.bg;
   const int n0 = tn * 64;
   const int h0 = thi * (4 * GE::TTH), w0 = twi * (4 * GE::TTW), b0 = bg * NI;
   const int ncc = p.C / KC;
@@ -156,14 +85,7 @@ __global__ __launch_bounds__(256, 2) void wino4l_conv_kernel(const Args p) {
 
   // ---- raw patch slots: s = tid + 256 j -> pixel s >> 1 of the patch, channel quad s & 1 ----
   const unsigned nrec_a = (unsigned)((long)p.B * p.H * p.W * p.a_pitch * 4);
-  __amdgpu_buffer_rsrc_t rsrc_a;
-  {
-    const unsigned long long ab = reinterpret_cast<unsigned long long>(p.a);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ab);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(ab >> 32));
-    rsrc_a = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                               __builtin_amdgcn_readfirstlane(nrec_a), 0x00020000);
-  }
+  const __amdgpu_buffer_rsrc_t rsrc_a = wave_buffer_rsrc(p.a, nrec_a);
   unsigned goff[NJ], plds[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -229,15 +151,7 @@ __global__ __launch_bounds__(256, 2) void wino4l_conv_kernel(const Args p) {
   const int xg = wid;
   const int mt = lane & 15, kk = lane >> 4;
   const int vrd = xg * (9 * 128) + (kk >> 1) * 64 + mt * 4 + 2 * (kk & 1);
-  __amdgpu_buffer_rsrc_t rsrc_u;
-  {
-    const unsigned long long ub = reinterpret_cast<unsigned long long>(p.u);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)ub);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(ub >> 32));
-    rsrc_u = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                               __builtin_amdgcn_readfirstlane((unsigned)((long)p.N * p.C * NXI * 4)),
-                                               0x00020000);
-  }
+  const __amdgpu_buffer_rsrc_t rsrc_u = wave_buffer_rsrc(p.u, (unsigned)((long)p.N * p.C * NXI * 4));
   // channel block cb (16 channels) of the operand: half = cb & 1, rows 16 (cb >> 1) + channel; this lane's two k are the
   // floats 2 (kk & 1), 2 (kk & 1) + 1 of the row's k-quad kq = kk >> 1
   const unsigned ulane = (unsigned)((((kk >> 1) * 32 + mt) * 4 + 2 * (kk & 1)) * 4);
@@ -481,63 +395,75 @@ __global__ __launch_bounds__(256, 2) void wino4l_conv_kernel(const Args p) {
   else body(std::integral_constant<int, 1>{});
 }
 
-static long unit_count(int cls, int B, int H, int W) {     // units per 64 produced channels, before split-K
-  return cls == 1 ? B : cls == 2 ? B / 4 : (long)B * (H / 8) * (W / 32);
-}
-
-static int unit_class(int H, int W) {
-  if (H == 8 && W == 8) return 2;
-  if (H == 16 && W == 16) return 1;
-  if (H >= 8 && W >= 32 && H % 8 == 0 && W % 32 == 0) return 0;
-  return -1;
-}
+// This form for the shared host half (wino4_host.h)
+namespace {
+struct Form {
+  using Args = lgmwino4l::Args;
+  static constexpr int THREADS = 256, MBUF = lgmwino4l::MBUF;
+  static constexpr int UH = 8, UW = 32;          // class 0: maps with H % 8 == 0 and W % 32 == 0
+  static constexpr int NCLS = 3;                 // no 4 x 4 maps
+  static constexpr int NI[NCLS] = {1, 1, 4};     // 16 x 16: one image, 8 x 8: four images to a unit
+  static constexpr const char* LAUNCHER = "lgm_wino4l_launch";
+  static int splits(const LgmConvGeom* g, int gather_channels, int out_channels) {
+    return lgm_wino4l_splits(g, gather_channels, out_channels);
+  }
+  static int launch(const Args& p, int cls, bool res, bool partial, bool stats, size_t smem, hipStream_t s) {
+    if (stats) {
+      if (cls != 0 || p.splits != 1 || res || partial) {
+        lgm_set_error("wino4l (stats): class-0 maps, an unsplit reduction and no residual expected");
+        return LGM_ERR_UNSUPPORTED;
+      }
+      lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<0, true>"));
+      lgmwino4host::launch_kernel<wino4l_conv_kernel<0, true>, THREADS>(p, smem, s);
+    } else if (cls == 0) {
+      lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<0, false>"));
+      lgmwino4host::launch_kernel<wino4l_conv_kernel<0, false>, THREADS>(p, smem, s);
+    } else if (cls == 1) {
+      lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<1, false>"));
+      lgmwino4host::launch_kernel<wino4l_conv_kernel<1, false>, THREADS>(p, smem, s);
+    } else {
+      lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<2, false>"));
+      lgmwino4host::launch_kernel<wino4l_conv_kernel<2, false>, THREADS>(p, smem, s);
+    }
+    return LGM_OK;
+  }
+};
+}  // namespace
 
 }  // namespace lgmwino4l
 
+using lgmwino4l::Form;
+namespace w4h = lgmwino4host;
+
 bool lgm_wino4l_supported(const LgmConvGeom* g, int gather_channels, int out_channels) {
-  using namespace lgmwino4l;
-  if (!(g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1)) return false;
-  if (gather_channels % 32 != 0 || out_channels % 64 != 0) return false;
-  const int cls = unit_class(g->H, g->W);
-  if (cls < 0) return false;
-  const long pix = (long)g->B * g->H * g->W + g->W + 1;
-  if (pix * gather_channels >= (1L << 29) || pix * out_channels >= (1L << 29)) return false;
-  if ((long)gather_channels * out_channels * 36 >= (1L << 29)) return false;
-  return g->B % (cls == 2 ? 4 : 1) == 0;
+  return w4h::supported<Form>(g, gather_channels, out_channels);
 }
 
 long lgm_wino4l_units(const LgmConvGeom* g, int out_channels) {
-  using namespace lgmwino4l;
-  const int cls = unit_class(g->H, g->W);
-  return cls < 0 ? 0 : unit_count(cls, g->B, g->H, g->W) * (out_channels / 64);
+  const int cls = w4h::unit_class<Form>(g->H, g->W);
+  return cls < 0 ? 0 : w4h::unit_count<Form>(cls, g->B, g->H, g->W) * (out_channels / 64);
 }
 
 // 0: maps with H % 8 == 0 and W % 32 == 0, 1: 16x16, 2: 8x8 (four images to a unit); -1: not taken
-int lgm_wino4l_class(const LgmConvGeom* g) { return lgmwino4l::unit_class(g->H, g->W); }
+int lgm_wino4l_class(const LgmConvGeom* g) { return w4h::unit_class<Form>(g->H, g->W); }
 
 // rows of GroupNorm statistics one image contributes per channel (STATS build: one row per wave of a unit)
-int lgm_wino4l_stats_parts(const LgmConvGeom* g) {
-  using namespace lgmwino4l;
-  return unit_class(g->H, g->W) == 0 ? (g->H / 8) * (g->W / 32) * 4 : 0;
-}
+int lgm_wino4l_stats_parts(const LgmConvGeom* g) { return w4h::stats_parts<Form>(g); }
 
 // Split-K plan.  Light workgroups come two to a CU (512 slots, two waves per SIMD - what hides a cold launch's memory
 // latency): a launch is split until it fills them, while every split keeps >= min_pps phases.
 int lgm_wino4l_splits(const LgmConvGeom* g, int gather_channels, int out_channels) {
-  using namespace lgmwino4l;
   const long base = lgm_wino4l_units(g, out_channels);
   if (base <= 0) return 1;
-  static const int forced = getenv("LGM_WINO4L_SPLITS") ? atoi(getenv("LGM_WINO4L_SPLITS")) : 0;
-  const int phases = gather_channels / KC;
-  int smax = phases / 2 < 16 ? phases / 2 : 16;
-  if (smax < 1) smax = 1;
-  if (forced > 0) return forced < smax ? forced : smax;
+  static const int forced = lgm_env_int("LGM_WINO4L_SPLITS", 0);
   // 256 = one light workgroup per CU: 6.89 vs 6.99 ms per step at B = 64 and 5.38 vs 5.41 at B = 32 against 512 (two per CU),
   // which only wins at B = 128 (10.22 vs 10.27), where the 32-tile kernel is the default anyway
-  static const int target_env = getenv("LGM_WINO4L_TARGET") ? atoi(getenv("LGM_WINO4L_TARGET")) : 0;
+  static const int target_env = lgm_env_int("LGM_WINO4L_TARGET", 0);
   const int target = target_env > 0 ? target_env : lgm_cu_budget();
-  if (base >= target * 3 / 4) return 1;
-  static const int min_pps = getenv("LGM_WINO4L_MIN_PPS") ? atoi(getenv("LGM_WINO4L_MIN_PPS")) : 4;
+  const int phases = gather_channels / lgmwino4dev::KC;
+  int smax;
+  if (const int s = w4h::split_front(base, target, phases, forced, &smax)) return s;
+  static const int min_pps = lgm_env_int("LGM_WINO4L_MIN_PPS", 4);
   // (two light workgroups fit a CU: a grid a little above `target` does not run a second round, so the 32-tile kernel's
   // lgm_wino4_pick_splits does not apply - with it B = 64 on a rank's plans went 6.74 -> 6.84 ms)
   int s = (int)((target + base - 1) / base);
@@ -549,79 +475,8 @@ int lgm_wino4l_splits(const LgmConvGeom* g, int gather_channels, int out_channel
 int lgm_wino4l_launch(const LgmConvGeom* g, int yx, const float* a, long a_pitch, const float* u, const float* bias,
                       const float* res, long res_pitch, float* out, long out_pitch, void* workspace, long workspace_bytes,
                       hipStream_t s, int64_t* partial, float* stats) {
-  using namespace lgmwino4l;
-  Args p{};
-  p.stats = stats;
-  p.a = a; p.u = u; p.bias = bias; p.res = res; p.out = out;
-  p.a_pitch = a_pitch; p.res_pitch = res_pitch; p.out_pitch = out_pitch;
-  p.B = g->B; p.H = g->H; p.W = g->W;
-  p.C = yx ? g->Nw : g->Cw;
-  p.N = yx ? g->Cw : g->Nw;
-  const int cls = unit_class(g->H, g->W);
-  p.tb_h = cls == 0 ? g->H / 8 : 1;
-  p.tb_w = cls == 0 ? g->W / 32 : 1;
-  p.nbg = cls == 2 ? g->B / 4 : g->B;
-  p.tiles_n = p.N / 64;
-  const long M = (long)g->B * g->H * g->W;
-  p.splits = lgm_wino4l_splits(g, p.C, p.N);
-  if (p.splits > 1) {
-    const long need = (long)p.splits * M * p.N * (long)sizeof(float);
-    if (!workspace || workspace_bytes < need || !lgm_aligned16(workspace)) p.splits = 1;
-  }
-  p.ws = (float*)workspace;
-  p.ws_stride = M * p.N;
-  p.pps = lgm_cdiv(p.C / KC, p.splits);
-  p.splits = lgm_cdiv(p.C / KC, p.pps);
-  p.units = (int)((long)p.nbg * p.tb_h * p.tb_w * p.tiles_n * p.splits);
-  {
-    // bytes the chip's eight L2s fetch under either order: patches once (x 1.2 halo) and all of U per XCD, or patches once per
-    // channel block and U once
-    static const bool no_ranges = getenv("LGM_WINO4_NO_XCD_RANGES") != nullptr;
-    p.xcd_ranges = no_ranges ? 0 : 1;
-    static const int forced = getenv("LGM_WINO4_TN_SLOWEST") ? atoi(getenv("LGM_WINO4_TN_SLOWEST")) : -1;
-    const double in_b = 1.2 * (double)M * p.C * 4.0, u_b = 36.0 * p.C * p.N * 4.0;
-    p.tn_slowest = forced >= 0 ? forced : ((in_b + 8.0 * u_b > in_b * p.tiles_n + u_b) ? 1 : 0);
-  }
-  const size_t smem = (size_t)MBUF * sizeof(float);
-#define LGM_W4L(KERN)                                                                                             \
-  do {                                                                                                            \
-    auto kern = KERN;                                                                                             \
-    static bool attr = false;                                                                                     \
-    if (!attr) {                                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)smem);                                                                       \
-      attr = true;                                                                                                \
-    }                                                                                                             \
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.units), dim3(256), smem, s, p);                                     \
-  } while (0)
-  if (stats) {
-    if (cls != 0 || p.splits != 1 || res || partial) {
-      lgm_set_error("wino4l (stats): class-0 maps, an unsplit reduction and no residual expected");
-      return LGM_ERR_UNSUPPORTED;
-    }
-    lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<0, true>"));
-    LGM_W4L((wino4l_conv_kernel<0, true>));
-  } else if (cls == 0) {
-    lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<0, false>"));
-    LGM_W4L((wino4l_conv_kernel<0, false>));
-  } else if (cls == 1) {
-    lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<1, false>"));
-    LGM_W4L((wino4l_conv_kernel<1, false>));
-  } else {
-    lgm_note_kernel(LGM_KNAME("lgmwino4l::wino4l_conv_kernel<2, false>"));
-    LGM_W4L((wino4l_conv_kernel<2, false>));
-  }
-#undef LGM_W4L
-  if (partial) {
-    partial[0] = p.splits;
-    partial[1] = p.ws_stride;
-    LGM_LAUNCH_CHECK();
-    return LGM_OK;
-  }
-  if (p.splits > 1)
-    return lgm_splitk_reduce_launch(p.ws, p.ws_stride, p.splits, bias, res, res_pitch, out, out_pitch, M, p.N, s);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
+  return w4h::conv_launch<Form>(g, yx, a, a_pitch, u, bias, res, res_pitch, out, out_pitch, workspace, workspace_bytes, s,
+                                partial, stats);
 }
 
 // ---- C-ABI (direct entry points: tests and tools; the product path reaches this kernel through lgm_conv3x3_wino4*, whose
@@ -635,8 +490,7 @@ extern "C" int64_t lgm_conv3x3_wino4l_workspace(const LgmConvGeom* g, int yx) {
   if (!g) return -1;
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   if (!lgm_wino4l_supported(g, gc, oc)) return 0;
-  const int s = lgm_wino4l_splits(g, gc, oc);
-  return s > 1 ? (int64_t)s * g->B * g->H * g->W * oc * (int64_t)sizeof(float) : 0;
+  return lgm_splitk_workspace(g, oc, lgm_wino4l_splits(g, gc, oc));
 }
 
 extern "C" int lgm_conv3x3_wino4l(int yx, const LgmConvGeom* g, const float* a, int64_t a_pitch, const float* u,
@@ -646,12 +500,9 @@ extern "C" int lgm_conv3x3_wino4l(int yx, const LgmConvGeom* g, const float* a, 
   const int gc = yx ? g->Nw : g->Cw, oc = yx ? g->Cw : g->Nw;
   LGM_REQUIRE(lgm_wino4l_supported(g, gc, oc), "conv3x3_wino4l: unsupported geometry (3x3/s1/p1, maps 8x8, 16x16 or H %% 8 == 0 "
               "and W %% 32 == 0, reduction channels %% 32, produced channels %% 64)");
-  LGM_REQUIRE(a_pitch % 4 == 0 && a_pitch >= gc && lgm_aligned16(a) && lgm_aligned16(u) && lgm_aligned16(out) &&
-              out_pitch % 4 == 0 && out_pitch >= oc && (!res || (lgm_aligned16(res) && res_pitch % 4 == 0 && res_pitch >= oc)) &&
-              (!bias || lgm_aligned16(bias)), "conv3x3_wino4l: 16-byte aligned operands with pitch %% 4 == 0 expected");
-  const long pix = (long)g->B * g->H * g->W + g->W + 1;
-  LGM_REQUIRE(pix * a_pitch < (1L << 29) && pix * out_pitch < (1L << 29) && pix * (res ? res_pitch : 0) < (1L << 29),
-              "conv3x3_wino4l: tensor too large for 32-bit offsets");
+  if (const int rc = lgm_conv_operands_check("conv3x3_wino4l", g, gc, oc, a, a_pitch,
+                                             u, bias, res, res_pitch, out, out_pitch))
+    return rc;
   return lgm_wino4l_launch(g, yx, a, a_pitch, u, bias, res, res_pitch, out, out_pitch, workspace, workspace_bytes,
                            (hipStream_t)stream, nullptr, nullptr);
 }
