@@ -442,6 +442,35 @@ int lgm_sample_step_table(float* x, const float* v, const float* noise, float* x
                           int Cpad, const float* table, const int32_t* counter, int clip, int advance,
                           void* stream);
 
+/* The four diffusion entry points above for every objective GaussianDiffusion accepts (ddpm.py:562):
+ * objective 0 = pred_noise, 1 = pred_x0, 2 = pred_v (same bits as the entry points above; the pred_v configuration keeps
+ * calling those).  `out` / `v` is the raw network output.
+ *
+ * lgm_qsample_target_obj: lgm_qsample_target with the objective's target (ddpm.py:911-917: the noise, the normalised
+ * x_start, or v) and offset noise (:889-891): offset [B*C] or NULL, n = noise + strength * offset[b*C+c], used for x_t AND
+ * for the target. */
+int lgm_qsample_target_obj(const float* img, const float* noise, const float* offset, float strength,
+                           const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
+                           int objective, float* xt, float* target, int64_t pitch, int B, int C, int HW, int Cpad,
+                           void* stream);
+/* model_predictions ddpm.py:707-734, all three branches:
+ *   pred_noise: x_start = maybe_clip(sqrt_recip[t] * x - sqrt_recipm1[t] * out); pred_noise = out, or re-derived from the
+ *               clipped x_start as below when clip AND rederive are set (:720-721)
+ *   pred_x0   : x_start = maybe_clip(out);  pred_noise = (sqrt_recip[t] * x - x_start) / sqrt_recipm1[t]
+ *   pred_v    : as lgm_model_predictions (rederive has no effect) */
+int lgm_model_predictions_obj(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
+                              const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                              int objective, int clip, int rederive, float* pred_noise, float* x_start, int B,
+                              int64_t per_sample, int n_table, void* stream);
+/* lgm_sample_step / lgm_sample_step_table with (x0, eps) from the objective's branch of model_predictions; same scalars,
+ * same table layout [n_steps][8].  p_sample passes clip only, ddim_sample clip and rederive. */
+int lgm_sample_step_obj(const float* x, const float* v, const float* noise, float* out, float* x0_out, int B,
+                        int C, int HW, int Cpad, int objective, float A, float Bv, int clip, int rederive,
+                        float R, float Rm1, float C0, float C1, float C2, float C3, void* stream);
+int lgm_sample_step_table_obj(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
+                              int Cpad, const float* table, const int32_t* counter, int objective, int clip,
+                              int rederive, int advance, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM
  * -> output transform launch, for the layers the fused Winograd kernels' workgroup shapes cannot fill:

@@ -585,6 +585,150 @@ __global__ __launch_bounds__(256) void sample_step_table_kernel(float* __restric
 __global__ void sampler_advance_kernel(int* counter) { counter[0] += 1; }
 
 // ---------------------------------------------------------------------------------------
+// The same four kernels for every objective GaussianDiffusion accepts (ddpm.py:562): objective 0 = pred_noise (the network
+// predicts eps), 1 = pred_x0 (it predicts the image), 2 = pred_v.  The pred_v configuration keeps the kernels above; with
+// objective 2 these give the same bits (tests/test_hip_objectives.py).
+// ---------------------------------------------------------------------------------------
+// offset noise (ddpm.py:889-891, `noise += strength * offset[b, c]`): product and sum rounded separately, like the two
+// ATen operations of the reference
+__device__ __forceinline__ float offset_noise_one(float n, float strength, float off) {
+#pragma clang fp contract(off)
+  const float d = strength * off;
+  return n + d;
+}
+// x_t as the reference's q_sample rounds it (two products, one sum) and v with the one fused multiply-add qsample_kernel's
+// `a * n - bb * x0` compiles to, spelled out so that objective 2 gives that kernel's bits whatever the optimiser does here.
+// qsample_kernel has no contraction pragma, so that fusion is the compiler's choice: the bit-equality test of objective 2
+// (tests/test_hip_objectives.py) guards that choice; no product path depends on it, pred_v keeps calling qsample_kernel.
+__device__ __forceinline__ void qsample_one(float a, float bb, float x0, float n, float& xt, float& v) {
+#pragma clang fp contract(off)
+  xt = a * x0 + bb * n;
+  v = fmaf(a, n, -(bb * x0));
+}
+// qsample_kernel with the target of the objective (ddpm.py:911-917) and the optional offset noise; the offset noise goes
+// into x_t AND into the target, as in the reference (it is added before q_sample)
+__global__ __launch_bounds__(256) void qsample_obj_kernel(const float* __restrict__ img, const float* __restrict__ noise,
+                                                          const float* __restrict__ offset, float strength,
+                                                          const int64_t* __restrict__ t, const float* __restrict__ sa,
+                                                          const float* __restrict__ sb, int normalize, int objective,
+                                                          float* __restrict__ xt, float* __restrict__ target, long pitch,
+                                                          int B, int C, int HW, int Cpad) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)B * HW * Cpad;
+  if (i >= total) return;
+  const int c = (int)(i % Cpad);
+  const long pix = i / Cpad;
+  const int b = (int)(pix / HW);
+  const int p = (int)(pix % HW);
+  float xv = 0.f, tv = 0.f;
+  if (c < C) {
+    const long s = ((long)b * C + c) * HW + p;
+    float x0 = img[s];
+    if (normalize) x0 = x0 * 2.f - 1.f;
+    float n = noise[s];
+    if (offset) n = offset_noise_one(n, strength, offset[(long)b * C + c]);
+    const float a = sa[t[b]], bb = sb[t[b]];
+    float v;
+    qsample_one(a, bb, x0, n, xv, v);
+    tv = objective == 0 ? n : (objective == 1 ? x0 : v);
+  }
+  xt[pix * pitch + c] = xv;
+  if (target) target[pix * pitch + c] = tv;
+}
+
+// model_predictions ddpm.py:707-734, all three branches, from the network output `out` and the head (A, S, R, Rm1) =
+// (sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1)[t].  pred_noise keeps the RAW network output unless clip and rederive are
+// both set (:720-721).  Contraction off: the reference rounds every product and sum separately.  Written with selects on
+// the (wave-uniform) objective, not branches: one straight-line body for the three objectives.
+__device__ __forceinline__ void predictions_one(int objective, float xv, float ov, float A, float S, float R, float Rm1,
+                                                int clip, int rederive, float& pn, float& x0) {
+#pragma clang fp contract(off)
+  const float p = objective == 0 ? R : A, q = objective == 0 ? Rm1 : S;
+  const float lin = p * xv - q * ov;                 // predict_start_from_noise :673-677 / predict_start_from_v :690-694
+  x0 = objective == 1 ? ov : lin;
+  if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  const float derived = (R * xv - x0) / Rm1;         // predict_noise_from_start :679-682
+  pn = (objective == 0 && !(clip && rederive)) ? ov : derived;
+}
+__global__ __launch_bounds__(256) void model_predictions_obj_kernel(const float* __restrict__ x, const float* __restrict__ out,
+                                                                    const long* __restrict__ t, const float* __restrict__ sa,
+                                                                    const float* __restrict__ s1, const float* __restrict__ r,
+                                                                    const float* __restrict__ rm1, int objective, int clip,
+                                                                    int rederive, float* __restrict__ pn,
+                                                                    float* __restrict__ xs, long per, int n_table) {
+  const int b = blockIdx.y;
+  long ti = t[b];
+  ti = ti < 0 ? 0 : (ti >= n_table ? n_table - 1 : ti);
+  const float A = sa[ti], S = s1[ti], R = r[ti], Rm1 = rm1[ti];
+  const long base = (long)b * per;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (long)gridDim.x * blockDim.x) {
+    float e, x0;
+    predictions_one(objective, x[base + i], out[base + i], A, S, R, Rm1, clip, rederive, e, x0);
+    xs[base + i] = x0;
+    pn[base + i] = e;
+  }
+}
+
+// sample_update for the three objectives: the head (A, Bv, R, Rm1) of the coefficient row is the one the pred_v kernels
+// take (Bv = -sqrt_1mac[t]); pred_noise reads (R, Rm1), pred_x0 reads them for eps only
+__device__ __forceinline__ void sample_update_obj(int objective, float xv, float ov, float nz, float A, float Bv, int clip,
+                                                  int rederive, float R, float Rm1, float C0, float C1, float C2,
+                                                  float C3, float& o, float& x0) {
+#pragma clang fp contract(off)
+  float eps;
+  predictions_one(objective, xv, ov, A, -Bv, R, Rm1, clip, rederive, eps, x0);
+  o = C0 * x0 + C1 * xv + C2 * eps;
+  if (C3 != 0.f) o += C3 * nz;
+}
+__global__ __launch_bounds__(256) void sample_step_obj_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                              const float* __restrict__ noise, float* __restrict__ out,
+                                                              float* __restrict__ x0_out, int B, int C, int HW, int Cpad,
+                                                              int objective, float A, float Bv, int clip, int rederive,
+                                                              float R, float Rm1, float C0, float C1, float C2, float C3) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)B * HW * Cpad;
+  if (i >= total) return;
+  const int c = (int)(i % Cpad);
+  const long pix = i / Cpad;
+  float o = 0.f, x0 = 0.f;
+  if (c < C) {
+    float nz = 0.f;
+    if (noise && C3 != 0.f) {
+      const int b = (int)(pix / HW), p = (int)(pix % HW);
+      nz = noise[((long)b * C + c) * HW + p];
+    }
+    sample_update_obj(objective, x[i], v[i], nz, A, Bv, clip, rederive, R, Rm1, C0, C1, C2, noise ? C3 : 0.f, o, x0);
+  }
+  out[i] = o;
+  if (x0_out) x0_out[i] = x0;
+}
+__global__ __launch_bounds__(256) void sample_step_table_obj_kernel(float* __restrict__ x, const float* __restrict__ v,
+                                                                    const float* __restrict__ noise,
+                                                                    float* __restrict__ x0_out, int B, int C, int HW,
+                                                                    int Cpad, const float* __restrict__ table,
+                                                                    const int* __restrict__ counter, int objective,
+                                                                    int clip, int rederive) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)B * HW * Cpad;
+  if (i >= total) return;
+  const float* row = table + 8 * counter[0];
+  const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], C0 = row[4], C1 = row[5], C2 = row[6], C3 = row[7];
+  const int c = (int)(i % Cpad);
+  const long pix = i / Cpad;
+  float o = 0.f, x0 = 0.f;
+  if (c < C) {
+    float nz = 0.f;
+    if (noise && C3 != 0.f) {
+      const int b = (int)(pix / HW), p = (int)(pix % HW);
+      nz = noise[((long)b * C + c) * HW + p];
+    }
+    sample_update_obj(objective, x[i], v[i], nz, A, Bv, clip, rederive, R, Rm1, C0, C1, C2, noise ? C3 : 0.f, o, x0);
+  }
+  x[i] = o;
+  if (x0_out) x0_out[i] = x0;
+}
+
+// ---------------------------------------------------------------------------------------
 // The UNet's time embedding in ONE launch (reference ddpm.py:119-132 SinusoidalPosEmb, :328-333 time_mlp = Linear ->
 // GELU -> Linear, and the SiLU in front of every ResnetBlock.mlp's Linear :181-183).  It was six launches of 4 - 7 us that
 // no batch size shrinks (posemb, GEMM, GELU, split-K GEMM, reducer, SiLU): ~32 us of every training step and of every
@@ -1169,6 +1313,62 @@ extern "C" int lgm_sample_step(const float* x, const float* v, const float* nois
   LGM_REQUIRE(x && v && out && B > 0 && C > 0 && HW > 0 && Cpad >= C, "sample_step: bad arguments");
   hipLaunchKernelGGL(sample_step_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, x,
                      v, noise, out, x0_out, B, C, HW, Cpad, A, Bv, clip, R, Rm1, C0, C1, C2, C3);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+// The entry points above for every objective (0 = pred_noise, 1 = pred_x0, 2 = pred_v); see the kernels' comments.
+static bool objective_ok(int objective) { return objective >= 0 && objective <= 2; }
+
+extern "C" int lgm_qsample_target_obj(const float* img, const float* noise, const float* offset, float strength,
+                                      const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
+                                      int objective, float* xt, float* target, int64_t pitch, int B, int C, int HW,
+                                      int Cpad, void* stream) {
+  LGM_REQUIRE(img && noise && t && sqrt_ac && sqrt_1mac && xt && B > 0 && C > 0 && HW > 0 && Cpad >= C && pitch >= Cpad &&
+                  objective_ok(objective),
+              "qsample_target_obj: bad arguments");
+  hipLaunchKernelGGL(qsample_obj_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, img,
+                     noise, offset, strength, t, sqrt_ac, sqrt_1mac, normalize, objective, xt, target, (long)pitch, B, C, HW,
+                     Cpad);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+extern "C" int lgm_model_predictions_obj(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
+                                         const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                                         int objective, int clip, int rederive, float* pred_noise, float* x_start, int B,
+                                         int64_t per_sample, int n_table, void* stream) {
+  LGM_REQUIRE(x && out && t && sqrt_ac && sqrt_1mac && sqrt_recip && sqrt_recipm1 && pred_noise && x_start && B > 0 &&
+                  B <= 65535 && per_sample > 0 && n_table > 0 && objective_ok(objective),
+              "model_predictions_obj: bad arguments");
+  const int gx = (int)(per_sample < 256L * 4096 ? lgm_cdiv(per_sample, 256) : 4096);
+  hipLaunchKernelGGL(model_predictions_obj_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, out, (const long*)t,
+                     sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, objective, clip, rederive, pred_noise, x_start,
+                     (long)per_sample, n_table);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+extern "C" int lgm_sample_step_obj(const float* x, const float* v, const float* noise, float* out, float* x0_out, int B,
+                                   int C, int HW, int Cpad, int objective, float A, float Bv, int clip, int rederive,
+                                   float R, float Rm1, float C0, float C1, float C2, float C3, void* stream) {
+  LGM_REQUIRE(x && v && out && B > 0 && C > 0 && HW > 0 && Cpad >= C && objective_ok(objective),
+              "sample_step_obj: bad arguments");
+  hipLaunchKernelGGL(sample_step_obj_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream,
+                     x, v, noise, out, x0_out, B, C, HW, Cpad, objective, A, Bv, clip, rederive, R, Rm1, C0, C1, C2, C3);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+extern "C" int lgm_sample_step_table_obj(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
+                                         int Cpad, const float* table, const int32_t* counter, int objective, int clip,
+                                         int rederive, int advance, void* stream) {
+  LGM_REQUIRE(x && v && table && counter && B > 0 && C > 0 && HW > 0 && Cpad >= C && objective_ok(objective),
+              "sample_step_table_obj: bad arguments");
+  hipLaunchKernelGGL(sample_step_table_obj_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0,
+                     (hipStream_t)stream, x, v, noise, x0_out, B, C, HW, Cpad, table, (const int*)counter, objective, clip,
+                     rederive);
+  if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }

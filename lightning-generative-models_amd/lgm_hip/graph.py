@@ -4,7 +4,8 @@ At small per-GPU batches (strong scaling: 128 / N images per GPU) the ~400 kerne
 host-bound when issued from Python.  The step is therefore captured ONCE and replayed:
 
     one rank : ONE graph - t ~ randint, noise ~ randn, q_sample, UNet forward, loss, the whole backward -
-               then fused Adam (1 eager kernel) and EMA (every 10th step)
+               then fused Adam (1 eager kernel) and EMA (every 10th step); a diffusion with offset noise also
+               draws its [B, C] offsets inside the graph
     N ranks  : FOUR graphs, cut where an exchange bucket of the flat gradient buffer becomes final
                (GraphedDDPMStep), with the asynchronous all-reduce of each bucket issued between the replays
 
@@ -94,9 +95,9 @@ def _capture(fn, warmup: int, pool=None):
 
 
 class GraphedDDPMStep:
-    """``inject=True`` (parity tests): ``t`` / ``noise`` are static INPUT buffers the caller fills before each
-    step instead of being drawn inside graph 1.  Either way ``self.t`` / ``self.noise`` hold the values the
-    last replay used.
+    """``inject=True`` (parity tests): ``t`` / ``noise`` (and ``offset``, the [B, C] offset noise of a diffusion with
+    ``offset_noise_strength > 0``) are static INPUT buffers the caller fills before each step instead of being drawn
+    inside graph 1.  Either way ``self.t`` / ``self.noise`` / ``self.offset`` hold the values the last replay used.
 
     One rank: ONE graph for the whole forward + backward (``LGM_ONE_GRAPH=0``: two, forward + backward phase 1 | phase 2 -
     no measurable difference), one Adam launch.  With a gradient exchange
@@ -128,6 +129,8 @@ class GraphedDDPMStep:
         net = self.net
         self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device) if inject else None
         self.noise = torch.zeros_like(x) if inject else None
+        strength = float(self.gd.offset_noise_strength)
+        self.offset = torch.zeros(x.shape[:2], device=x.device) if inject and strength > 0.0 else None
         # (the pipelined variant applies a bucket's Adam slice right behind ITS all-reduce: only with the overlapped exchange)
         self.pipeline = _STEP_PIPELINE and (sync is None or getattr(sync, "overlap", True))
         split = sync is not None or self.pipeline
@@ -135,12 +138,13 @@ class GraphedDDPMStep:
         def part1a():
             gd = self.gd
             if inject:
-                t, noise = self.t, self.noise
-            else:
+                t, noise, offset = self.t, self.noise, self.offset
+            else:                                    # the draws of GaussianDiffusion.forward / p_losses, in their order
                 t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
                 noise = torch.randn_like(self.x)
-                self.t, self.noise = t, noise
-            loss, ctx = hip_loss_forward(gd, self.x, t, noise, gd.auto_normalize, True)
+                offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
+                self.t, self.noise, self.offset = t, noise, offset
+            loss, ctx = hip_loss_forward(gd, self.x, t, noise, gd.auto_normalize, True, offset, strength)
             fp.zero_grad()
             return loss, hip_loss_backward_phase1a(ctx, self.one)
 

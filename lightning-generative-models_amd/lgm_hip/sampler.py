@@ -12,6 +12,10 @@ Two ways to run a chain, bit-identical in their results (tests/test_hip_unet.py)
     the ~230 launches of a step, no host syncs, no per-step allocations (``lgm_sample_step_table``);
   * eager launches (``return_all_timesteps``, ``LGM_NO_SAMPLER_GRAPH=1``, or when capture fails): per-timestep
     scalars from host copies of the schedule buffers (``lgm_sample_step``).
+
+The pred_v configuration issues the launches above; pred_noise and pred_x0 take ``lgm_sample_step_obj`` /
+``lgm_sample_step_table_obj`` (same scalars and table, the objective's branch of model_predictions inside; the ancestral
+step clips x0 only, DDIM also re-derives the noise from the clipped x0, reference :720-721, 808-810).
 """
 from __future__ import annotations
 
@@ -34,6 +38,11 @@ def _host_schedule(gd):
         hs = {n: getattr(gd, n).detach().cpu() for n in names}
         gd._host_sched = hs
     return hs
+
+
+def _objective(gd) -> int:
+    from models.generative.diffusion.ddpm import OBJECTIVES
+    return OBJECTIVES[gd.objective]
 
 
 def _f32(x) -> float:
@@ -67,15 +76,20 @@ class _Chain:
                 self.tbuf[t] = tb
         return tb
 
-    def step(self, t: int, noise: Optional[torch.Tensor], clip: bool, C0, C1, C2, C3):
+    def step(self, t: int, noise: Optional[torch.Tensor], clip: bool, C0, C1, C2, C3, rederive: bool = False):
         hs = _host_schedule(self.gd)
         B, C, H, W = self.shape
         v, _ = self.net.forward_nhwc(self.x, self.times(t), False)
-        ops.lib().lgm_sample_step(self.x.data_ptr(), v.data_ptr(), None if noise is None else noise.data_ptr(),
-                                  self.x_next.data_ptr(), self.x0.data_ptr(), B, C, H * W, self.Cp,
-                                  _f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t]),
-                                  1 if clip else 0, _f32(hs["sqrt_recip_alphas_cumprod"][t]),
-                                  _f32(hs["sqrt_recipm1_alphas_cumprod"][t]), C0, C1, C2, C3, ops.stream())
+        nz = None if noise is None else noise.data_ptr()
+        A, Bv = _f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t])
+        R, Rm1 = _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t])
+        if self.gd.objective == "pred_v":
+            ops.lib().lgm_sample_step(self.x.data_ptr(), v.data_ptr(), nz, self.x_next.data_ptr(), self.x0.data_ptr(), B, C,
+                                      H * W, self.Cp, A, Bv, 1 if clip else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
+        else:
+            ops.lib().lgm_sample_step_obj(self.x.data_ptr(), v.data_ptr(), nz, self.x_next.data_ptr(), self.x0.data_ptr(),
+                                          B, C, H * W, self.Cp, _objective(self.gd), A, Bv, 1 if clip else 0,
+                                          1 if rederive else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
         self.x, self.x_next = self.x_next, self.x
 
     def image(self, unnormalize: bool) -> torch.Tensor:
@@ -121,8 +135,10 @@ _CAPTURE_RETRY_AFTER = 8      # a failed capture is retried after this many eage
 class _GraphedChain:
     """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it."""
 
-    def __init__(self, gd, shape, with_noise: bool, max_steps: int = 4096):
+    def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096):
         net = gd.model
+        objective = _objective(gd)
+        is_v = gd.objective == "pred_v"
         self._net = weakref.ref(net)                 # the cache is keyed weakly on the network: no strong reference here
         B, C, H, W = shape
         dev = gd.betas.device
@@ -150,8 +166,13 @@ class _GraphedChain:
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
-            L.lgm_sample_step_table(self.x.data_ptr(), v.data_ptr(), None if nz is None else nz.data_ptr(), None, B, C,
-                                    H * W, Cp, self.table.data_ptr(), self.counter.data_ptr(), 1, 1, ops.stream())
+            if is_v:
+                L.lgm_sample_step_table(self.x.data_ptr(), v.data_ptr(), None if nz is None else nz.data_ptr(), None, B, C,
+                                        H * W, Cp, self.table.data_ptr(), self.counter.data_ptr(), 1, 1, ops.stream())
+            else:
+                L.lgm_sample_step_table_obj(self.x.data_ptr(), v.data_ptr(), None if nz is None else nz.data_ptr(), None,
+                                            B, C, H * W, Cp, self.table.data_ptr(), self.counter.data_ptr(), objective, 1,
+                                            1 if rederive else 0, 1, ops.stream())
 
         net.refresh_derived_weights(False)
         rng_state = torch.cuda.get_rng_state(dev)
@@ -202,8 +223,9 @@ class _GraphedChain:
         return self.x
 
 
-def _graph_chain(gd, shape, with_noise: bool):
-    """-> a _GraphedChain for (network, shape), or None (graph replay disabled / capture failed: eager launches)"""
+def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False):
+    """-> a _GraphedChain for (network, shape, objective), or None (graph replay disabled / capture failed: eager launches).
+    ``rederive``: the DDIM chain's re-derived noise, part of the captured launch for pred_noise / pred_x0."""
     if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or gd.betas.device.type != "cuda":
         return None
     net = gd.model
@@ -213,6 +235,8 @@ def _graph_chain(gd, shape, with_noise: bool):
         per_net = {}
         _GRAPHS[net] = per_net
     key = (tuple(shape), bool(with_noise))
+    if gd.objective != "pred_v":                     # two diffusions of other objectives may share one network
+        key += (gd.objective, bool(rederive))
     ent = per_net.get(key)
     if isinstance(ent, _GraphedChain) and not ent.matches(net):
         ent = None                                   # captured against buffers the network no longer uses
@@ -224,7 +248,7 @@ def _graph_chain(gd, shape, with_noise: bool):
         ent = None
     if ent is None:
         try:
-            ent = _GraphedChain(gd, tuple(shape), with_noise)
+            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive)
         except Exception as e:  # capture is an optimisation
             import sys
             print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",
@@ -247,12 +271,12 @@ def ddim_step(chain: _Chain, t: int, t_next: int, noise: Optional[torch.Tensor],
     """One DDIM step (loop body :805-829)."""
     hs = _host_schedule(chain.gd)
     if t_next < 0:
-        chain.step(t, None, True, 1.0, 0.0, 0.0, 0.0)
+        chain.step(t, None, True, 1.0, 0.0, 0.0, 0.0, rederive=True)
         return
     a, an = hs["alphas_cumprod"][t], hs["alphas_cumprod"][t_next]
     sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()
     c = (1 - an - sigma ** 2).sqrt()
-    chain.step(t, noise if float(sigma) != 0.0 else None, True, _f32(an.sqrt()), 0.0, _f32(c), _f32(sigma))
+    chain.step(t, noise if float(sigma) != 0.0 else None, True, _f32(an.sqrt()), 0.0, _f32(c), _f32(sigma), rederive=True)
 
 
 @torch.no_grad()
@@ -301,7 +325,7 @@ def ddim_sample(gd, shape, return_all_timesteps=False, init_noise=None, noises: 
     dev = chain.x.device
     eta = gd.ddim_sampling_eta
     pairs = gd.ddim_time_pairs()
-    gc = None if return_all_timesteps else _graph_chain(gd, shape, eta != 0.0)
+    gc = None if return_all_timesteps else _graph_chain(gd, shape, eta != 0.0, rederive=True)
     if gc is not None:
         x = gc.run(chain.x, [a for a, _ in pairs], [_ddim_coeffs(gd, a, b, eta) for a, b in pairs],
                    noises if eta != 0.0 else None)

@@ -777,18 +777,22 @@ def _cosine_beta_schedule(timesteps, s=0.008):
     return torch.clip(1 - ac[1:] / ac[:-1], 0, 0.999)
 
 
+OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}     # the `objective` argument of the lgm_*_obj entry points
+
+
 class GaussianDiffusion(nn.Module):
     def __init__(self, model: Unet, *, img_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5):
         super().__init__()
-        if objective != "pred_v" or offset_noise_strength != 0.0:
-            raise NotImplementedError("HIP path implements the configuration DDPM constructs (pred_v, no offset noise)")
+        if objective not in OBJECTIVES:
+            raise ValueError(f"objective must be one of {sorted(OBJECTIVES)}, got {objective!r}")
         self.model = model
         self.channels = model.channels
         self.self_condition = False
         self.img_size = img_size
         self.objective = objective
+        self.offset_noise_strength = offset_noise_strength
         fn = {"linear": _linear_beta_schedule, "cosine": _cosine_beta_schedule, "sigmoid": _sigmoid_beta_schedule}
         if beta_schedule not in fn:
             raise ValueError(f"unknown beta schedule {beta_schedule}")
@@ -819,7 +823,7 @@ class GaussianDiffusion(nn.Module):
         reg("posterior_log_variance_clipped", torch.log(post_var.clamp(min=1e-20)))
         reg("posterior_mean_coef1", betas * torch.sqrt(ac_prev) / (1.0 - ac))
         reg("posterior_mean_coef2", (1.0 - ac_prev) * torch.sqrt(alphas) / (1.0 - ac))
-        reg("loss_weight", clipped / (snr + 1))
+        reg("loss_weight", {"pred_noise": clipped / snr, "pred_x0": clipped, "pred_v": clipped / (snr + 1)}[objective])
         self.auto_normalize = auto_normalize
 
     @property
@@ -832,12 +836,18 @@ class GaussianDiffusion(nn.Module):
         return list(zip(times[:-1], times[1:]))
 
     # -- training ---------------------------------------------------------------------------
-    def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, _normalize=False):
-        """x_start already normalised unless _normalize (reference :878-925)."""
+    def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, *, _offset_noise=None, _normalize=False):
+        """x_start already normalised unless _normalize (reference :878-925).  Offset noise (:885-891): one draw per
+        (sample, channel), added to the noise inside the q_sample kernel - the caller's ``noise`` is not written.
+        ``_offset_noise`` (extension, for parity tests): the [B, C] draw the reference takes from torch.randn."""
         if noise is None:
             noise = torch.randn_like(x_start)
+        strength = self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
+        offset = None
+        if strength > 0.0:
+            offset = _offset_noise if _offset_noise is not None else torch.randn(x_start.shape[:2], device=x_start.device)
         anchor = self.model._anchor(x_start.device)
-        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize)
+        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength))
 
     def forward(self, img, *args, **kwargs):
         b, c, h, w = img.shape
@@ -897,15 +907,25 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False):
-        """-> ModelPrediction(pred_noise, pred_x_start), reference :707-734 (pred_v branch: ``rederive_pred_noise`` has no
-        effect there, the noise is always derived from the possibly clipped x_start).  UNet forward on the HIP engine, then
-        ONE launch for both results."""
+        """-> ModelPrediction(pred_noise, pred_x_start), reference :707-734.  ``rederive_pred_noise`` takes effect for
+        pred_noise only (with ``clip_x_start``; otherwise pred_noise is the raw network output); for pred_x0 and pred_v the
+        noise is always derived from the possibly clipped x_start.  UNet forward on the HIP engine, then ONE launch for
+        both results."""
         assert x_self_cond is None, "the network DDPM constructs is not self-conditioned"
         v = self.model(x, t, x_self_cond)
         x = x.detach().float().contiguous()
         B = x.shape[0]
         t = t.to(device=x.device, dtype=torch.long).contiguous()
         pred_noise, x_start = torch.empty_like(x), torch.empty_like(x)
+        if self.objective != "pred_v":
+            ops.lib().lgm_model_predictions_obj(x.data_ptr(), v.data_ptr(), t.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
+                                                self.sqrt_one_minus_alphas_cumprod.data_ptr(),
+                                                self.sqrt_recip_alphas_cumprod.data_ptr(),
+                                                self.sqrt_recipm1_alphas_cumprod.data_ptr(), OBJECTIVES[self.objective],
+                                                1 if clip_x_start else 0, 1 if rederive_pred_noise else 0,
+                                                pred_noise.data_ptr(), x_start.data_ptr(), B, x.numel() // B,
+                                                self.num_timesteps, ops.stream())
+            return ModelPrediction(pred_noise, x_start)
         ops.lib().lgm_model_predictions(x.data_ptr(), v.data_ptr(), t.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
                                         self.sqrt_one_minus_alphas_cumprod.data_ptr(),
                                         self.sqrt_recip_alphas_cumprod.data_ptr(),
@@ -963,8 +983,10 @@ class GaussianDiffusion(nn.Module):
         return sampler.p_sample_loop(self, tuple(img.shape), init_noise=img, start=t, unnormalize=False)
 
 
-def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, save: bool):
-    """q_sample + UNet + v-target + weighted MSE on the HIP engine.  Returns (loss[1], ctx)."""
+def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, save: bool, offset=None,
+                     strength: float = 0.0):
+    """q_sample + UNet + the objective's target + weighted MSE on the HIP engine.  Returns (loss[1], ctx).
+    ``offset`` ([B, C] or None) / ``strength``: offset noise, added to ``noise`` inside the q_sample kernel."""
     net = gd.model
     B, C, H, W = img.shape
     Cp = _r4(C)
@@ -975,15 +997,24 @@ def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, sa
     target = ops.new((B, H, W, Cp), img)
     L = ops.lib()
     st = ops.stream()
-    L.lgm_qsample_target(img.data_ptr(), noise.data_ptr(), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
-                         gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0, xt.data_ptr(),
-                         target.data_ptr(), Cp, B, C, H * W, Cp, st)
+    if gd.objective == "pred_v" and offset is None:
+        L.lgm_qsample_target(img.data_ptr(), noise.data_ptr(), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
+                             gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0, xt.data_ptr(),
+                             target.data_ptr(), Cp, B, C, H * W, Cp, st)
+    else:
+        if offset is not None:
+            offset = offset.detach().float().contiguous()
+            assert offset.shape == (B, C), f"offset noise is one value per (sample, channel), got {tuple(offset.shape)}"
+        L.lgm_qsample_target_obj(img.data_ptr(), noise.data_ptr(), None if offset is None else offset.data_ptr(),
+                                 float(strength), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
+                                 gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
+                                 OBJECTIVES[gd.objective], xt.data_ptr(), target.data_ptr(), Cp, B, C, H * W, Cp, st)
     out, tape = net.forward_nhwc(xt, t, save)
     per = ops.new((B,), img)
     loss = ops.new((1,), img)
     L.lgm_weighted_mse_fwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
                            B, C, H * W, Cp, per.data_ptr(), loss.data_ptr(), st)
-    return loss, (gd, tape, out, target, t, (B, C, H, W), img, noise)
+    return loss, (gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
 
 
 def hip_loss_backward_phase1(ctx, gl):
@@ -1005,11 +1036,11 @@ def hip_loss_backward_phase1a(ctx, gl):
 
 
 class _PLossFn(torch.autograd.Function):
-    """q_sample + UNet + v-target + weighted MSE, forward and hand-written backward."""
+    """q_sample + UNet + the objective's target + weighted MSE, forward and hand-written backward."""
 
     @staticmethod
-    def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize):
-        loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]))
+    def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0):
+        loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]), offset, strength)
         return loss.view(())
 
     @staticmethod
@@ -1018,7 +1049,7 @@ class _PLossFn(torch.autograd.Function):
         st = hip_loss_backward_phase1(ctx.stuff, gl)
         ctx.stuff[0].model.backward_phase2(st)
         ctx.stuff = None
-        return None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -1027,12 +1058,16 @@ class _PLossFn(torch.autograd.Function):
 class DDPM(LightningModule):
     def __init__(self, img_channels: int = 3, img_size: int = 64, dim: int = 64, diffusion_timesteps: int = 1000,
                  sampling_timesteps: Optional[int] = None, lr: float = 2e-5, betas: Tuple[float, float] = (0.9, 0.99),
-                 ema_update_every: int = 10, ema_decay: float = 0.995):
+                 ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
+                 beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
+                 min_snr_gamma: float = 5):
         super().__init__()
         self.save_hyperparameters()
         model = Unet(dim=dim, channels=img_channels)
         diffusion_model = GaussianDiffusion(model, img_size=img_size, timesteps=diffusion_timesteps,
-                                            sampling_timesteps=sampling_timesteps)
+                                            sampling_timesteps=sampling_timesteps, objective=objective,
+                                            beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
+                                            min_snr_loss_weight=min_snr_loss_weight, min_snr_gamma=min_snr_gamma)
         self.channels = img_channels
         self.img_size = img_size
         self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
