@@ -45,7 +45,10 @@ extern "C" {
                              * 4: LgmPostOp carries the BatchNorm-backward sums (bn_*), lgm_bn_reduce3_coef_tiles;
                              * 5: lgm_set_cu_margin / lgm_cu_margin;
                              * 6: lgm_extract_axpby, lgm_model_predictions (GaussianDiffusion's per-sample-time algebra), lgm_time_mlp_*, lgm_weng_*;
-                             * 7: lgm_gn_bwd_add, lgm_wgrad1x1_group*, lgm_wgrad_queue_* */
+                             * 7: lgm_gn_bwd_add, lgm_wgrad1x1_group*, lgm_wgrad_queue_*
+                             * (entry points added since without a change to an existing one keep the number, as the
+                             *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
+                             *  lgm_sample_step_table_slice - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
 #define LGM_ERR_UNSUPPORTED (-2)
@@ -470,6 +473,35 @@ int lgm_sample_step_obj(const float* x, const float* v, const float* noise, floa
 int lgm_sample_step_table_obj(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
                               int Cpad, const float* table, const int32_t* counter, int objective, int clip,
                               int rederive, int advance, void* stream);
+
+/* Self-conditioning (ddpm.py:428-435, 899-909).  A self-conditioned UNet reads ONE NHWC input buffer [B, HW, pitch] with
+ * pitch = r4(2 C): lanes [sc_off, sc_off + C) = x_self_cond (sc_off = 0), lanes [x_off, x_off + C) = x (x_off = C) - the order
+ * of cat((x_self_cond, x), dim=1) - and zeros in the remaining lanes.  These entry points produce the two slices in place of
+ * a concat tensor; loads and stores are scalar, so the slices need no float4 alignment (C = 3: lanes 0 and 3 of 8).
+ * sc_off < 0 means "no self-conditioning slice": with pitch = r4(C) and x_off = 0 the *_slice entry points give the bits of
+ * the entry points above (objective 2: of the pred_v ones too).  `out` / `v` is the network output [B, HW, out_pitch].
+ *
+ * lgm_selfcond_estimate: xin[sc slice] = unclipped x_start of model_predictions (objective's branch) from xin[x slice] and
+ *   `out`, per-sample t.  The x slice and the padding are not written.
+ * lgm_qsample_target_slice: lgm_qsample_target_obj with x_t into the x slice, zeros into the self-conditioning slice and the
+ *   padding; target [B, HW, target_pitch] with Cpad lanes written, as before (may be NULL).
+ * lgm_sample_step_slice / lgm_sample_step_table_slice: lgm_sample_step_obj / lgm_sample_step_table_obj reading x from the x
+ *   slice of xin, writing the next x into the x slice of xout (xout may be xin; the table form is in place), the x0 the
+ *   reference hands to the next step (clipped when clip is set) into xout's self-conditioning slice, zeros into its padding. */
+int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int sc_off, const float* out, int64_t out_pitch,
+                          const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip,
+                          const float* sqrt_recipm1, int objective, int B, int C, int HW, int n_table, void* stream);
+int lgm_qsample_target_slice(const float* img, const float* noise, const float* offset, float strength,
+                             const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
+                             int objective, float* xin, int64_t pitch, int x_off, int sc_off, float* target,
+                             int64_t target_pitch, int B, int C, int HW, int Cpad, void* stream);
+int lgm_sample_step_slice(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                          int64_t v_pitch, const float* noise, int B, int C, int HW, int objective, float A, float Bv,
+                          int clip, int rederive, float R, float Rm1, float C0, float C1, float C2, float C3,
+                          void* stream);
+int lgm_sample_step_table_slice(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
+                                const float* noise, int B, int C, int HW, const float* table, const int32_t* counter,
+                                int objective, int clip, int rederive, int advance, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

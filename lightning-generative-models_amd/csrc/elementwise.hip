@@ -729,6 +729,101 @@ __global__ __launch_bounds__(256) void sample_step_table_obj_kernel(float* __res
 }
 
 // ---------------------------------------------------------------------------------------
+// Self-conditioning (ddpm.py:428-435, 899-909): the UNet reads ONE NHWC input buffer [B, HW, pitch] whose lanes
+// [sc_off, sc_off + C) hold x_self_cond and [x_off, x_off + C) hold x (cat((x_self_cond, x), dim=1): sc_off = 0, x_off = C,
+// pitch = r4(2 C)); every other lane is padding and stays zero.  The kernels below are the producers of those two slices.
+// With C = 3 the slices start at lanes 0 and 3 of a pitch of 8: scalar loads and stores only, nothing assumes float4
+// alignment.  One thread per (pixel, lane); the lanes c < C do the arithmetic of channel c and write BOTH slices, the others
+// write the zeros of the padding they sit on (or nothing).  sc_off < 0: no self-conditioning slice (pitch = r4(C), x_off = 0:
+// the layout and the bits of the kernels above).
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ bool slice_pad_lane(int lane, int x_off, int sc_off, int C) {
+  return !(lane >= x_off && lane < x_off + C) && !(sc_off >= 0 && lane >= sc_off && lane < sc_off + C);
+}
+// x_start estimate of the first pass (:901-903, model_predictions with clip_x_start=False): reads x_t from the x slice and the
+// network output, writes the self-conditioning slice; the x slice and the padding are not touched
+__global__ __launch_bounds__(256) void selfcond_estimate_kernel(float* __restrict__ xin, long pitch, int x_off, int sc_off,
+                                                                const float* __restrict__ out, long out_pitch,
+                                                                const long* __restrict__ t, const float* __restrict__ sa,
+                                                                const float* __restrict__ s1, const float* __restrict__ r,
+                                                                const float* __restrict__ rm1, int objective, int B, int C,
+                                                                int HW, int n_table) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * HW * C) return;
+  const int c = (int)(i % C);
+  const long pix = i / C;
+  long ti = t[pix / HW];
+  ti = ti < 0 ? 0 : (ti >= n_table ? n_table - 1 : ti);
+  float e, x0;
+  predictions_one(objective, xin[pix * pitch + x_off + c], out[pix * out_pitch + c], sa[ti], s1[ti], r[ti], rm1[ti], 0, 0, e,
+                  x0);
+  xin[pix * pitch + sc_off + c] = x0;
+}
+// qsample_obj_kernel writing x_t into the x slice and zeros into the self-conditioning slice and the padding; the target
+// buffer (pitch tpitch, tCpad lanes written) as before
+__global__ __launch_bounds__(256) void qsample_slice_kernel(const float* __restrict__ img, const float* __restrict__ noise,
+                                                            const float* __restrict__ offset, float strength,
+                                                            const int64_t* __restrict__ t, const float* __restrict__ sa,
+                                                            const float* __restrict__ sb, int normalize, int objective,
+                                                            float* __restrict__ xin, long pitch, int lanes, int x_off,
+                                                            int sc_off, float* __restrict__ target, long tpitch, int tCpad,
+                                                            int B, int C, int HW) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * HW * lanes) return;
+  const int c = (int)(i % lanes);
+  const long pix = i / lanes;
+  if (c < C) {
+    const int b = (int)(pix / HW);
+    const int p = (int)(pix % HW);
+    const long s = ((long)b * C + c) * HW + p;
+    float x0 = img[s];
+    if (normalize) x0 = x0 * 2.f - 1.f;
+    float n = noise[s];
+    if (offset) n = offset_noise_one(n, strength, offset[(long)b * C + c]);
+    const float a = sa[t[b]], bb = sb[t[b]];
+    float xv, v;
+    qsample_one(a, bb, x0, n, xv, v);
+    xin[pix * pitch + x_off + c] = xv;
+    if (sc_off >= 0) xin[pix * pitch + sc_off + c] = 0.f;
+    if (target) target[pix * tpitch + c] = objective == 0 ? n : (objective == 1 ? x0 : v);
+  } else if (target && c < tCpad) {
+    target[pix * tpitch + c] = 0.f;
+  }
+  if (slice_pad_lane(c, x_off, sc_off, C)) xin[pix * pitch + c] = 0.f;
+}
+// sample_step_obj_kernel / sample_step_table_obj_kernel over the slices: x from the x slice of `xin`, the next x into the x
+// slice of `xout` (xout == xin: in place - a thread reads and writes its own lanes only), x0 as the reference hands it on
+// (clipped where it clips) into the self-conditioning slice of `xout`, zeros into xout's padding.  table == null: the scalars
+// by value in `row`.
+struct SampleRow { float v[8]; };
+__global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin, float* xout, long pitch, int lanes, int x_off,
+                                                                int sc_off, const float* __restrict__ v, long v_pitch,
+                                                                const float* __restrict__ noise, int B, int C, int HW,
+                                                                SampleRow byval, const float* __restrict__ table,
+                                                                const int* __restrict__ counter, int objective, int clip,
+                                                                int rederive) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * HW * lanes) return;
+  const float* row = table ? table + 8 * counter[0] : byval.v;
+  const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], C0 = row[4], C1 = row[5], C2 = row[6], C3 = row[7];
+  const int c = (int)(i % lanes);
+  const long pix = i / lanes;
+  if (c < C) {
+    float nz = 0.f;
+    if (noise && C3 != 0.f) {
+      const int b = (int)(pix / HW), p = (int)(pix % HW);
+      nz = noise[((long)b * C + c) * HW + p];
+    }
+    float o, x0;
+    sample_update_obj(objective, xin[pix * pitch + x_off + c], v[pix * v_pitch + c], nz, A, Bv, clip, rederive, R, Rm1, C0,
+                      C1, C2, noise ? C3 : 0.f, o, x0);
+    xout[pix * pitch + x_off + c] = o;
+    if (sc_off >= 0) xout[pix * pitch + sc_off + c] = x0;
+  }
+  if (slice_pad_lane(c, x_off, sc_off, C)) xout[pix * pitch + c] = 0.f;
+}
+
+// ---------------------------------------------------------------------------------------
 // The UNet's time embedding in ONE launch (reference ddpm.py:119-132 SinusoidalPosEmb, :328-333 time_mlp = Linear ->
 // GELU -> Linear, and the SiLU in front of every ResnetBlock.mlp's Linear :181-183).  It was six launches of 4 - 7 us that
 // no batch size shrinks (posemb, GEMM, GELU, split-K GEMM, reducer, SiLU): ~32 us of every training step and of every
@@ -1371,6 +1466,80 @@ extern "C" int lgm_sample_step_table_obj(float* x, const float* v, const float* 
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK();
   return LGM_OK;
+}
+
+// The slice-aware entry points of a self-conditioned UNet's input buffer (see the kernels' comments).  The two slices lie
+// inside the pitch and do not overlap; sc_off < 0 = no self-conditioning slice.
+static bool slices_ok(int64_t pitch, int x_off, int sc_off, int C) {
+  if (C <= 0 || x_off < 0 || x_off + C > pitch) return false;
+  if (sc_off < 0) return true;
+  return sc_off + C <= pitch && (sc_off + C <= x_off || x_off + C <= sc_off);
+}
+
+extern "C" int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int sc_off, const float* out, int64_t out_pitch,
+                                     const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
+                                     const float* sqrt_recip, const float* sqrt_recipm1, int objective, int B, int C, int HW,
+                                     int n_table, void* stream) {
+  LGM_REQUIRE(xin && out && t && sqrt_ac && sqrt_1mac && sqrt_recip && sqrt_recipm1 && B > 0 && HW > 0 && n_table > 0 &&
+                  sc_off >= 0 && slices_ok(pitch, x_off, sc_off, C) && out_pitch >= C && objective_ok(objective),
+              "selfcond_estimate: bad arguments");
+  lgm_note_kernel(LGM_KNAME("selfcond_estimate_kernel"));
+  hipLaunchKernelGGL(selfcond_estimate_kernel, dim3(lgm_cdiv((long)B * HW * C, 256)), dim3(256), 0, (hipStream_t)stream, xin,
+                     (long)pitch, x_off, sc_off, out, (long)out_pitch, (const long*)t, sqrt_ac, sqrt_1mac, sqrt_recip,
+                     sqrt_recipm1, objective, B, C, HW, n_table);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+extern "C" int lgm_qsample_target_slice(const float* img, const float* noise, const float* offset, float strength,
+                                        const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
+                                        int objective, float* xin, int64_t pitch, int x_off, int sc_off, float* target,
+                                        int64_t target_pitch, int B, int C, int HW, int Cpad, void* stream) {
+  LGM_REQUIRE(img && noise && t && sqrt_ac && sqrt_1mac && xin && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) &&
+                  Cpad >= C && Cpad <= pitch && target_pitch >= Cpad && objective_ok(objective),
+              "qsample_target_slice: bad arguments");
+  lgm_note_kernel(LGM_KNAME("qsample_slice_kernel"));
+  hipLaunchKernelGGL(qsample_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, img,
+                     noise, offset, strength, t, sqrt_ac, sqrt_1mac, normalize, objective, xin, (long)pitch, (int)pitch,
+                     x_off, sc_off, target, (long)target_pitch, Cpad, B, C, HW);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+static int sample_step_slice_launch(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                                    int64_t v_pitch, const float* noise, int B, int C, int HW, const SampleRow& row,
+                                    const float* table, const int32_t* counter, int objective, int clip, int rederive,
+                                    int advance, void* stream) {
+  lgm_note_kernel(LGM_KNAME("sample_step_slice_kernel"));
+  hipLaunchKernelGGL(sample_step_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream,
+                     xin, xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, B, C, HW, row, table,
+                     (const int*)counter, objective, clip, rederive);
+  if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
+  LGM_LAUNCH_CHECK_AS("sample_step_slice");
+  return LGM_OK;
+}
+
+extern "C" int lgm_sample_step_slice(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                                     int64_t v_pitch, const float* noise, int B, int C, int HW, int objective, float A,
+                                     float Bv, int clip, int rederive, float R, float Rm1, float C0, float C1, float C2,
+                                     float C3, void* stream) {
+  LGM_REQUIRE(xin && xout && v && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) && v_pitch >= C &&
+                  objective_ok(objective),
+              "sample_step_slice: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, C0, C1, C2, C3}};
+  return sample_step_slice_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, B, C, HW, row, nullptr, nullptr,
+                                  objective, clip, rederive, 0, stream);
+}
+
+extern "C" int lgm_sample_step_table_slice(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
+                                           const float* noise, int B, int C, int HW, const float* table,
+                                           const int32_t* counter, int objective, int clip, int rederive, int advance,
+                                           void* stream) {
+  LGM_REQUIRE(x && v && table && counter && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) && v_pitch >= C &&
+                  objective_ok(objective),
+              "sample_step_table_slice: bad arguments");
+  return sample_step_slice_launch(x, x, pitch, x_off, sc_off, v, v_pitch, noise, B, C, HW, SampleRow{}, table, counter,
+                                  objective, clip, rederive, advance, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -25,6 +25,7 @@ from .lightning import multi_rank
 
 
 import os as _os
+import random
 
 _ONE_GRAPH = _os.environ.get("LGM_ONE_GRAPH", "1") == "1"           # one rank: the whole step in ONE graph (A/B switch)
 _STEP_PIPELINE = _os.environ.get("LGM_STEP_PIPELINE", "0") == "1"   # opt-in: weight passes of a bucket on a side stream
@@ -115,10 +116,17 @@ class GraphedDDPMStep:
     backward once its gradients are final).  Bit-identical to the default (tested), but the streaming kernels' workgroups
     delay the one-workgroup-per-CU convolutions more than the overlap returns, and two more graph boundaries plus five
     Adam slices cost 0.2 ms by themselves.  Kept for multi-GPU experiments, where the Adam slices would run beside the
-    later buckets' all-reduces."""
+    later buckets' all-reduces.
+
+    Self-conditioned model (reference :899-909): whether a step runs the estimate pass is a HOST coin, so the first graph is cut
+    behind the launch that draws t / noise and writes x_t (``pre``), the estimate pass - the network without saved
+    activations + the kernel that writes x_start into the self-conditioning slice of the input buffer - is a graph of its own
+    (``est``) replayed on the steps whose coin says so, and the saved forward pass opens the next graph.  ``pre`` zeroes the
+    self-conditioning slice on every step.  A model without self-conditioning captures exactly the graphs listed above."""
 
     def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, inject: bool = False):
-        from models.generative.diffusion.ddpm import hip_loss_backward_phase1a, hip_loss_forward
+        from models.generative.diffusion.ddpm import (hip_loss_backward_phase1a, hip_loss_estimate, hip_loss_forward,
+                                                      hip_loss_network, hip_loss_qsample)
         self.model, self.opt, self.sync = model, opt, sync
         self.gd = model.ema.online_model
         self.net = self.gd.model
@@ -135,21 +143,41 @@ class GraphedDDPMStep:
         self.pipeline = _STEP_PIPELINE and (sync is None or getattr(sync, "overlap", True))
         split = sync is not None or self.pipeline
 
-        def part1a():
+        self_cond = bool(self.net.self_condition)
+        self.pre = self.est = None                   # self-conditioned model only: see the class comment
+
+        def draws():
             gd = self.gd
             if inject:
-                t, noise, offset = self.t, self.noise, self.offset
-            else:                                    # the draws of GaussianDiffusion.forward / p_losses, in their order
-                t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
-                noise = torch.randn_like(self.x)
-                offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
-                self.t, self.noise, self.offset = t, noise, offset
-            loss, ctx = hip_loss_forward(gd, self.x, t, noise, gd.auto_normalize, True, offset, strength)
+                return self.t, self.noise, self.offset
+            # the draws of GaussianDiffusion.forward / p_losses, in their order
+            t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
+            noise = torch.randn_like(self.x)
+            offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
+            self.t, self.noise, self.offset = t, noise, offset
+            return t, noise, offset
+
+        def part0():                                 # self-conditioned: the draws and the q_sample launch
+            t, noise, offset = draws()
+            return hip_loss_qsample(self.gd, self.x, t, noise, self.gd.auto_normalize, offset, strength)
+
+        def part1a(q=None):
+            gd = self.gd
+            if self_cond:
+                xt, target, img, noise, t, offset = q
+                loss, ctx = hip_loss_network(gd, xt, target, img, t, noise, offset, True)
+            else:
+                t, noise, offset = draws()
+                loss, ctx = hip_loss_forward(gd, self.x, t, noise, gd.auto_normalize, True, offset, strength)
             fp.zero_grad()
             return loss, hip_loss_backward_phase1a(ctx, self.one)
 
         def whole():
-            _, st = part1a()
+            q = None
+            if self_cond:
+                q = part0()
+                hip_loss_estimate(self.gd, q[0], q[4])
+            _, st = part1a(q)
             net.backward_phase2(net.backward_phase1b(st))
 
         # warm-up and capture must not perturb the random stream: a run that captures at batch 0 and a run that
@@ -168,8 +196,14 @@ class GraphedDDPMStep:
             if self.pipeline:
                 net._flush_collect = {}              # the phases hand their reduction rows over instead of launching
             try:
+                q, pool0 = None, None
+                if self_cond:
+                    self.pre, q, _ = _capture(part0, 0)
+                    pool0 = self.pre.pool()
+                    self.est, _, _ = _capture(lambda: hip_loss_estimate(self.gd, q[0], q[4]), 0, pool0)
+                    self._q = q                      # keeps the input buffer and the target alive
                 if split:
-                    g1a, (self.loss, st), _ = _capture(part1a, 0)
+                    g1a, (self.loss, st), _ = _capture(lambda: part1a(q), 0, pool0)
                     pool = g1a.pool()
                     g1b, st, _ = _capture(lambda: net.backward_phase1b(st), 0, pool)
                     g2a, st, _ = _capture(lambda: net.backward_phase2a(st), 0, pool)
@@ -177,17 +211,17 @@ class GraphedDDPMStep:
                     self.graphs = [g1a, g1b, g2a, g2b]
                 elif _ONE_GRAPH:
                     def everything():                # one rank: nothing has to happen between the phases
-                        loss, st1 = part1a()
+                        loss, st1 = part1a(q)
                         st2 = net.backward_phase1b(st1)
                         net.backward_phase2(st2)
                         return loss, st2
-                    g1, (self.loss, st), _ = _capture(everything, 0)
+                    g1, (self.loss, st), _ = _capture(everything, 0, pool0)
                     self.graphs = [g1]
                 else:
                     def part1():
-                        loss, st1 = part1a()
+                        loss, st1 = part1a(q)
                         return loss, net.backward_phase1b(st1)
-                    g1, (self.loss, st), _ = _capture(part1, 0)
+                    g1, (self.loss, st), _ = _capture(part1, 0, pool0)
                     g2, _, _ = _capture(lambda: net.backward_phase2(st), 0, g1.pool())
                     self.graphs = [g1, g2]
                 rows = net._flush_collect if self.pipeline else {}
@@ -202,7 +236,16 @@ class GraphedDDPMStep:
         finally:
             torch.cuda.set_rng_state(rng_state, x.device)
 
-    def step(self, batch_idx: int = 0):
+    def _replay_pre(self, self_cond: bool):
+        """Self-conditioned model: draws + q_sample, then the estimate pass when this step's host coin says so."""
+        if self.pre is not None:
+            self.pre.replay()
+            if self_cond:
+                self.est.replay()
+
+    def step(self, batch_idx: int = 0, self_cond: bool = False):
+        """``self_cond``: this step's coin (read by a self-conditioned model only)."""
+        self._replay_pre(self_cond)
         if self.pipeline:
             return self._step_pipelined(batch_idx)
         sync = self.sync
@@ -268,12 +311,17 @@ class DDPMFastStep:
         self.use_graph = use_graph
         self.graphed: Optional[GraphedDDPMStep] = None
         self.mode = "eager"
+        # self-conditioned model: the coin of reference :902, drawn on the host once per step (tests inject a sequence here)
+        self.coin = lambda: random.random() < 0.5
 
     def _capture(self, x):
         try:
             self.graphed = GraphedDDPMStep(self.model, self.opt, x.clone(), self.sync)
+            n = len(self.graphed.graphs) + (1 if self.graphed.pre is not None else 0)
             self.mode = ("hipGraph replay (4 graphs/step, weight passes on a side stream)" if _STEP_PIPELINE else
-                         f"hipGraph replay ({len(self.graphed.graphs)} graph{'s' if len(self.graphed.graphs) > 1 else ''}/step)")
+                         f"hipGraph replay ({n} graph{'s' if n > 1 else ''}/step)")
+            if self.graphed.est is not None:
+                self.mode = self.mode[:-1] + ", + the estimate graph on self-conditioned steps)"
         except Exception as e:  # capture is an optimisation: fall back to eager launches
             import sys
             print(f"[lgm_hip] HIP-graph capture unavailable ({type(e).__name__}: {e}); eager launches",
@@ -289,13 +337,14 @@ class DDPMFastStep:
             m._log_sample()
         if self.use_graph and self.graphed is None:
             self._capture(x)
+        self_cond = bool(self.coin()) if self.net.self_condition else False
         if self.graphed is not None and x.shape == self.graphed.x.shape:
             self.graphed.x.copy_(x)
-            loss = self.graphed.step(batch_idx)
+            loss = self.graphed.step(batch_idx, self_cond)
         else:
             self.net.grad_sync = self.sync           # backward phases hand finished buckets to the exchange
             gd = m.ema.online_model
-            loss = gd(x)
+            loss = gd(x, _self_cond=self_cond) if self.net.self_condition else gd(x)
             loss.backward()
             if self.sync is not None:
                 self.sync.finish()

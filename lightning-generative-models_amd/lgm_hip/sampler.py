@@ -16,6 +16,11 @@ Two ways to run a chain, bit-identical in their results (tests/test_hip_unet.py)
 The pred_v configuration issues the launches above; pred_noise and pred_x0 take ``lgm_sample_step_obj`` /
 ``lgm_sample_step_table_obj`` (same scalars and table, the objective's branch of model_predictions inside; the ancestral
 step clips x0 only, DDIM also re-derives the noise from the clipped x0, reference :720-721, 808-810).
+
+A self-conditioned network (reference :773-774, 807-810, 864-865) reads ONE input buffer with two slices (Unet.input_buffer):
+``lgm_sample_step_slice`` / ``lgm_sample_step_table_slice`` read x from its slice, write the next x there and the x_start the
+reference hands on (clipped, as p_sample and ddim_sample clip it) into the self-conditioning slice the next step reads.  A
+chain starts with that slice zero: the reference's ``x_start = None``.
 """
 from __future__ import annotations
 
@@ -52,9 +57,9 @@ def _f32(x) -> float:
 class _Chain:
     """Device-resident state of one sampling run (NHWC, padded channels)."""
 
-    def __init__(self, gd, shape, init_noise: Optional[torch.Tensor]):
+    def __init__(self, gd, shape, init_noise: Optional[torch.Tensor], x_self_cond: Optional[torch.Tensor] = None):
         self.gd = gd
-        self.net = gd.model
+        self.net = net = gd.model
         B, C, H, W = shape
         self.shape = shape
         dev = gd.betas.device
@@ -62,10 +67,19 @@ class _Chain:
         self.Cp = _r4(C)
         if init_noise is None:
             init_noise = torch.randn(shape, device=dev)
-        self.x = torch.empty((B, H, W, self.Cp), device=dev)
-        ops.nchw_to_nhwc(init_noise.float().contiguous(), self.x)
-        self.x_next = torch.empty_like(self.x)
-        self.x0 = torch.empty_like(self.x)
+        if net.self_condition:
+            # both slices live in the input buffer; the update kernel writes the x_start of a step where the next step reads it
+            self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)
+            ops.nchw_to_nhwc(init_noise.float().contiguous(), net.x_slice(self.x, pad=True))
+            if x_self_cond is not None:
+                ops.nchw_to_nhwc(x_self_cond.float().contiguous(), net.sc_slice(self.x))
+            self.x_next = torch.zeros_like(self.x)
+            self.x0 = None                       # after a step: the self-conditioning slice of self.x
+        else:
+            self.x = torch.empty((B, H, W, self.Cp), device=dev)
+            ops.nchw_to_nhwc(init_noise.float().contiguous(), self.x)
+            self.x_next = torch.empty_like(self.x)
+            self.x0 = torch.empty_like(self.x)
         self.tbuf = {}
 
     def times(self, t: int) -> torch.Tensor:
@@ -83,7 +97,13 @@ class _Chain:
         nz = None if noise is None else noise.data_ptr()
         A, Bv = _f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t])
         R, Rm1 = _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t])
-        if self.gd.objective == "pred_v":
+        net = self.net
+        if net.self_condition:
+            ops.lib().lgm_sample_step_slice(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
+                                            v.data_ptr(), ops.pitch(v), nz, B, C, H * W, _objective(self.gd), A, Bv,
+                                            1 if clip else 0, 1 if rederive else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
+            self.x0 = net.sc_slice(self.x_next)
+        elif self.gd.objective == "pred_v":
             ops.lib().lgm_sample_step(self.x.data_ptr(), v.data_ptr(), nz, self.x_next.data_ptr(), self.x0.data_ptr(), B, C,
                                       H * W, self.Cp, A, Bv, 1 if clip else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
         else:
@@ -95,7 +115,7 @@ class _Chain:
     def image(self, unnormalize: bool) -> torch.Tensor:
         B, C, H, W = self.shape
         out = torch.empty(self.shape, device=self.x.device)
-        ops.nhwc_to_nchw(self.x, out)
+        ops.nhwc_to_nchw(self.net.x_slice(self.x), out)
         if unnormalize:
             out.mul_(0.5).add_(0.5)     # unnormalize_to_zero_to_one, once per sampling run
         return out
@@ -149,7 +169,8 @@ class _GraphedChain:
                        None if fp.data_uf is None else fp.data_uf.data_ptr(),
                        None if fp.data_t is None else fp.data_t.data_ptr())
         Cp = _r4(C)
-        self.x = torch.zeros((B, H, W, Cp), device=dev)
+        self_cond = net.self_condition
+        self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)     # static input buffer (both slices when self-conditioned)
         self.t = torch.zeros(B, dtype=torch.long, device=dev)
         self.noise = torch.zeros(shape, device=dev) if with_noise else None     # injected noise goes here
         self.table = torch.zeros((max_steps, 8), device=dev)
@@ -166,7 +187,12 @@ class _GraphedChain:
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
-            if is_v:
+            if self_cond:                        # x and the x_start handed on: both slices of the static buffer, in place
+                L.lgm_sample_step_table_slice(self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(),
+                                              ops.pitch(v), None if nz is None else nz.data_ptr(), B, C, H * W,
+                                              self.table.data_ptr(), self.counter.data_ptr(), objective, 1,
+                                              1 if rederive else 0, 1, ops.stream())
+            elif is_v:
                 L.lgm_sample_step_table(self.x.data_ptr(), v.data_ptr(), None if nz is None else nz.data_ptr(), None, B, C,
                                         H * W, Cp, self.table.data_ptr(), self.counter.data_ptr(), 1, 1, ops.stream())
             else:
@@ -208,6 +234,9 @@ class _GraphedChain:
         assert n <= self.max_steps
         self._net().refresh_derived_weights(False)   # the weights may have moved since the last chain (EMA updates)
         self.x.copy_(x0_nhwc)
+        net = self._net()
+        if net.self_condition:
+            net.sc_slice(self.x).zero_()             # a chain starts without an estimate (the reference's x_start = None)
         self.table[:n].copy_(torch.tensor(coeffs, dtype=torch.float32), non_blocking=False)
         self.ttable[:n].copy_(torch.tensor(times, dtype=torch.long))
         self.counter.zero_()

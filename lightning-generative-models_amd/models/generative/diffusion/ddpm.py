@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import math
 import os
+import random
 from collections import namedtuple
 from typing import List, Optional, Tuple
 
@@ -292,16 +293,21 @@ class Unet(nn.Module):
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32,
                  attn_heads=4, full_attn=None, flash_attn=False):
         super().__init__()
-        if self_condition or learned_variance or learned_sinusoidal_cond or random_fourier_features:
+        if learned_variance or learned_sinusoidal_cond or random_fourier_features:
             raise NotImplementedError("HIP UNet covers the configuration the reference DDPM constructs "
-                                      "(ddpm.py:984-987): no self-conditioning / learned variance / fourier features")
+                                      "(ddpm.py:984-987) and self-conditioning: no learned variance / fourier features")
         if init_dim not in (None, dim):
             raise NotImplementedError("init_dim != dim")
         self.dim, self.channels = dim, channels
-        self.self_condition = False
+        self.self_condition = bool(self_condition)
         self.random_or_learned_sinusoidal_cond = False
         self.theta = float(sinusoidal_pos_emb_theta)
-        self.init_conv = Conv2d(channels, dim, 7, padding=3)
+        # self-conditioned (:300-301, 435): the network reads cat((x_self_cond, x), dim=1) - ONE NHWC buffer of r4(2 C) lanes
+        # whose slices [sc_off, sc_off + C) and [x_off, x_off + C) their producers fill; nothing is concatenated
+        self.in_channels = channels * (2 if self.self_condition else 1)
+        self.in_pitch = _r4(self.in_channels)
+        self.x_off, self.sc_off = (channels, 0) if self.self_condition else (0, -1)
+        self.init_conv = Conv2d(self.in_channels, dim, 7, padding=3)
         dims = [dim, *[dim * m for m in dim_mults]]
         in_out = list(zip(dims[:-1], dims[1:]))
         self.in_out = in_out
@@ -478,7 +484,7 @@ class Unet(nn.Module):
 
     # ---- network ----------------------------------------------------------------------------
     def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True):
-        """x: [B, S, S, r4(channels)] NHWC (pad lanes zero), t: int64 [B].
+        """x: [B, S, S, in_pitch] NHWC (``input_buffer``; pad lanes zero), t: int64 [B].
         Returns (out [B,S,S,r4(out_dim)], tape).  ``refresh_weights=False``: the derived weight copies (Winograd /
         split-precision operands) are known to be current — a sampling chain refreshes them once, not per step."""
         B, S, _, _ = x.shape
@@ -711,8 +717,20 @@ class Unet(nn.Module):
         self._flat.bind_grad_views()
 
     def forward(self, x: torch.Tensor, time: torch.Tensor, x_self_cond=None) -> torch.Tensor:
-        """NCHW in / NCHW out, like the reference Unet.forward (:428-471)."""
-        return _UnetFn.apply(self._anchor(x.device), self, x, time)
+        """NCHW in / NCHW out, like the reference Unet.forward (:428-471); ``x_self_cond`` is a constant (no gradient
+        reaches it) and is read by a self-conditioned network only, ``None`` meaning zeros (:434)."""
+        return _UnetFn.apply(self._anchor(x.device), self, x, time, x_self_cond)
+
+    # ---- the input buffer and its two slices ------------------------------------------------------------
+    def input_buffer(self, B, H, W, like):
+        return ops.new((B, H, W, self.in_pitch), like)
+
+    def x_slice(self, xin, pad: bool = False):
+        """The lanes of ``x`` in an input buffer; ``pad``: and the padding behind them (a producer that zero-fills it)."""
+        return _chan(xin, self.x_off, self.in_pitch if pad else self.x_off + self.channels)
+
+    def sc_slice(self, xin):
+        return _chan(xin, self.sc_off, self.sc_off + self.channels)
 
     def _anchor(self, device):
         self.prepare_hip(device)
@@ -722,10 +740,14 @@ class Unet(nn.Module):
             self._anchor_t = a
         return a
 
-    def run_nchw(self, x, time, save):
+    def run_nchw(self, x, time, save, x_self_cond=None):
         B, C, H, W = x.shape
-        xin = ops.new((B, H, W, _r4(C)), x)
-        ops.nchw_to_nhwc(x.contiguous(), xin)
+        xin = self.input_buffer(B, H, W, x)
+        ops.nchw_to_nhwc(x.contiguous(), self.x_slice(xin, pad=True))
+        if self.self_condition:
+            sc = torch.zeros_like(x) if x_self_cond is None else x_self_cond.detach().float().contiguous()
+            assert sc.shape == x.shape, f"x_self_cond {tuple(sc.shape)} must have the shape of x {tuple(x.shape)}"
+            ops.nchw_to_nhwc(sc, self.sc_slice(xin))
         out, tape = self.forward_nhwc(xin, time, save)
         y = ops.new((B, self.out_dim, H, W), x)
         ops.nhwc_to_nchw(out, y)
@@ -734,9 +756,9 @@ class Unet(nn.Module):
 
 class _UnetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, net: Unet, x, time):
+    def forward(ctx, anchor, net: Unet, x, time, x_self_cond=None):
         save = bool(ctx.needs_input_grad[0])   # grad mode on at apply() time and anchor requires grad
-        y, tape, _ = net.run_nchw(x.detach().float(), time, save)
+        y, tape, _ = net.run_nchw(x.detach().float(), time, save, x_self_cond)
         ctx.net, ctx.tape = net, tape
         return y
 
@@ -750,7 +772,7 @@ class _UnetFn(torch.autograd.Function):
         ops.nchw_to_nhwc(gy.contiguous(), g)
         net.backward_nhwc(tape, g)
         ctx.tape = None
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -789,7 +811,7 @@ class GaussianDiffusion(nn.Module):
             raise ValueError(f"objective must be one of {sorted(OBJECTIVES)}, got {objective!r}")
         self.model = model
         self.channels = model.channels
-        self.self_condition = False
+        self.self_condition = model.self_condition
         self.img_size = img_size
         self.objective = objective
         self.offset_noise_strength = offset_noise_strength
@@ -836,18 +858,26 @@ class GaussianDiffusion(nn.Module):
         return list(zip(times[:-1], times[1:]))
 
     # -- training ---------------------------------------------------------------------------
-    def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, *, _offset_noise=None, _normalize=False):
+    def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, *, _offset_noise=None, _normalize=False,
+                 _self_cond=None):
         """x_start already normalised unless _normalize (reference :878-925).  Offset noise (:885-891): one draw per
         (sample, channel), added to the noise inside the q_sample kernel - the caller's ``noise`` is not written.
-        ``_offset_noise`` (extension, for parity tests): the [B, C] draw the reference takes from torch.randn."""
+        ``_offset_noise`` (extension, for parity tests): the [B, C] draw the reference takes from torch.randn.
+        Self-conditioned model (:899-909): with probability 0.5 (Python's ``random.random()``, as in the reference) the network
+        runs once without saved activations, its unclipped x_start becomes the self-conditioning input of the pass the
+        gradient is taken through; no gradient reaches the estimate.  ``_self_cond`` (extension, for parity tests):
+        ``True`` / ``False`` is the coin, an NCHW tensor is used as the estimate itself."""
         if noise is None:
             noise = torch.randn_like(x_start)
         strength = self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
         offset = None
         if strength > 0.0:
             offset = _offset_noise if _offset_noise is not None else torch.randn(x_start.shape[:2], device=x_start.device)
+        self_cond = False
+        if self.self_condition:
+            self_cond = (random.random() < 0.5) if _self_cond is None else _self_cond
         anchor = self.model._anchor(x_start.device)
-        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength))
+        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond)
 
     def forward(self, img, *args, **kwargs):
         b, c, h, w = img.shape
@@ -910,8 +940,7 @@ class GaussianDiffusion(nn.Module):
         """-> ModelPrediction(pred_noise, pred_x_start), reference :707-734.  ``rederive_pred_noise`` takes effect for
         pred_noise only (with ``clip_x_start``; otherwise pred_noise is the raw network output); for pred_x0 and pred_v the
         noise is always derived from the possibly clipped x_start.  UNet forward on the HIP engine, then ONE launch for
-        both results."""
-        assert x_self_cond is None, "the network DDPM constructs is not self-conditioned"
+        both results.  ``x_self_cond`` (NCHW, ``None`` = zeros) is read by a self-conditioned network only."""
         v = self.model(x, t, x_self_cond)
         x = x.detach().float().contiguous()
         B = x.shape[0]
@@ -944,10 +973,10 @@ class GaussianDiffusion(nn.Module):
     @torch.no_grad()
     def p_sample(self, x, t: int, x_self_cond=None, noise=None):
         """One ancestral step at the shared timestep ``t`` -> (pred_img, x_start), reference :748-757.  ``noise``
-        (extension, for parity tests): the draw the reference takes from randn_like."""
+        (extension, for parity tests): the draw the reference takes from randn_like.  ``x_self_cond`` (NCHW, ``None`` =
+        zeros): the x_start the previous step returned, for a self-conditioned network."""
         from lgm_hip import sampler
-        assert x_self_cond is None
-        chain = sampler._Chain(self, tuple(x.shape), x)
+        chain = sampler._Chain(self, tuple(x.shape), x, x_self_cond)
         if noise is None and t > 0:
             noise = torch.randn_like(x)
         sampler.p_sample_step(chain, int(t), noise)
@@ -984,31 +1013,75 @@ class GaussianDiffusion(nn.Module):
 
 
 def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, save: bool, offset=None,
-                     strength: float = 0.0):
+                     strength: float = 0.0, self_cond=False):
     """q_sample + UNet + the objective's target + weighted MSE on the HIP engine.  Returns (loss[1], ctx).
-    ``offset`` ([B, C] or None) / ``strength``: offset noise, added to ``noise`` inside the q_sample kernel."""
+    ``offset`` ([B, C] or None) / ``strength``: offset noise, added to ``noise`` inside the q_sample kernel.
+    ``self_cond`` (self-conditioned network only): ``True`` = estimate pass first (``hip_loss_estimate``), a tensor = that
+    NCHW estimate."""
+    xt, target, img, noise, t, offset = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength)
+    if gd.model.self_condition:
+        if torch.is_tensor(self_cond):
+            assert self_cond.shape == img.shape
+            ops.nchw_to_nhwc(self_cond.detach().float().contiguous(), gd.model.sc_slice(xt))
+        elif self_cond:
+            hip_loss_estimate(gd, xt, t)
+    return hip_loss_network(gd, xt, target, img, t, noise, offset, save)
+
+
+def hip_loss_estimate(gd: "GaussianDiffusion", xt, t):
+    """The estimate pass of a self-conditioned training step (:901-905): the network without saved activations on the input
+    buffer whose self-conditioning slice is zero, then ONE launch that writes the unclipped x_start into that slice."""
+    net = gd.model
+    B, H, W, _ = xt.shape
+    out, _ = net.forward_nhwc(xt, t, False)
+    ops.lib().lgm_selfcond_estimate(xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off, out.data_ptr(), ops.pitch(out),
+                                    t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
+                                    gd.sqrt_one_minus_alphas_cumprod.data_ptr(), gd.sqrt_recip_alphas_cumprod.data_ptr(),
+                                    gd.sqrt_recipm1_alphas_cumprod.data_ptr(), OBJECTIVES[gd.objective], B, net.channels,
+                                    H * W, gd.num_timesteps, ops.stream())
+
+
+def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, offset=None, strength: float = 0.0):
+    """x_t into the network's input buffer and the objective's target: one launch.  A self-conditioned network's buffer gets
+    x_t in its x slice and zeros in its self-conditioning slice."""
     net = gd.model
     B, C, H, W = img.shape
     Cp = _r4(C)
     img = img.detach().float().contiguous()
     noise = noise.detach().float().contiguous()
     t = t.contiguous()
-    xt = ops.new((B, H, W, Cp), img)
+    xt = net.input_buffer(B, H, W, img)
     target = ops.new((B, H, W, Cp), img)
     L = ops.lib()
     st = ops.stream()
-    if gd.objective == "pred_v" and offset is None:
+    if offset is not None:
+        offset = offset.detach().float().contiguous()
+        assert offset.shape == (B, C), f"offset noise is one value per (sample, channel), got {tuple(offset.shape)}"
+    if net.self_condition:
+        L.lgm_qsample_target_slice(img.data_ptr(), noise.data_ptr(), None if offset is None else offset.data_ptr(),
+                                   float(strength), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
+                                   gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
+                                   OBJECTIVES[gd.objective], xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
+                                   target.data_ptr(), Cp, B, C, H * W, Cp, st)
+    elif gd.objective == "pred_v" and offset is None:
         L.lgm_qsample_target(img.data_ptr(), noise.data_ptr(), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
                              gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0, xt.data_ptr(),
                              target.data_ptr(), Cp, B, C, H * W, Cp, st)
     else:
-        if offset is not None:
-            offset = offset.detach().float().contiguous()
-            assert offset.shape == (B, C), f"offset noise is one value per (sample, channel), got {tuple(offset.shape)}"
         L.lgm_qsample_target_obj(img.data_ptr(), noise.data_ptr(), None if offset is None else offset.data_ptr(),
                                  float(strength), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
                                  gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
                                  OBJECTIVES[gd.objective], xt.data_ptr(), target.data_ptr(), Cp, B, C, H * W, Cp, st)
+    return xt, target, img, noise, t, offset
+
+
+def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool):
+    """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx)."""
+    net = gd.model
+    B, C, H, W = img.shape
+    Cp = _r4(C)
+    L = ops.lib()
+    st = ops.stream()
     out, tape = net.forward_nhwc(xt, t, save)
     per = ops.new((B,), img)
     loss = ops.new((1,), img)
@@ -1039,8 +1112,9 @@ class _PLossFn(torch.autograd.Function):
     """q_sample + UNet + the objective's target + weighted MSE, forward and hand-written backward."""
 
     @staticmethod
-    def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0):
-        loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]), offset, strength)
+    def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0, self_cond=False):
+        loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]), offset, strength,
+                                           self_cond)
         return loss.view(())
 
     @staticmethod
@@ -1049,7 +1123,7 @@ class _PLossFn(torch.autograd.Function):
         st = hip_loss_backward_phase1(ctx.stuff, gl)
         ctx.stuff[0].model.backward_phase2(st)
         ctx.stuff = None
-        return None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -1060,10 +1134,10 @@ class DDPM(LightningModule):
                  sampling_timesteps: Optional[int] = None, lr: float = 2e-5, betas: Tuple[float, float] = (0.9, 0.99),
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
-                 min_snr_gamma: float = 5):
+                 min_snr_gamma: float = 5, self_condition: bool = False):
         super().__init__()
         self.save_hyperparameters()
-        model = Unet(dim=dim, channels=img_channels)
+        model = Unet(dim=dim, channels=img_channels, self_condition=self_condition)
         diffusion_model = GaussianDiffusion(model, img_size=img_size, timesteps=diffusion_timesteps,
                                             sampling_timesteps=sampling_timesteps, objective=objective,
                                             beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
