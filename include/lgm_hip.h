@@ -48,7 +48,8 @@ extern "C" {
                              * 7: lgm_gn_bwd_add, lgm_wgrad1x1_group*, lgm_wgrad_queue_*
                              * (entry points added since without a change to an existing one keep the number, as the
                              *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
-                             *  lgm_sample_step_table_slice - a library that lacks a declared symbol fails to load) */
+                             *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix - a library
+                             *  that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
 #define LGM_ERR_UNSUPPORTED (-2)
@@ -502,6 +503,24 @@ int lgm_sample_step_slice(const float* xin, float* xout, int64_t pitch, int x_of
 int lgm_sample_step_table_slice(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
                                 const float* noise, int B, int C, int HW, const float* table, const int32_t* counter,
                                 int objective, int clip, int rederive, int advance, void* stream);
+
+/* Class conditioning and classifier-free guidance (csrc/classcond.hip; an extension of the reference's Unet /
+ * GaussianDiffusion, like `objective` and `self_condition`).  emb is the label embedding [num_classes + 1][time_dim], row
+ * num_classes = the null label; y holds one int64 label per sample and is clamped to [0, num_classes] on the device (a
+ * caller that can see the labels rejects others beforehand).  time_dim % 4 == 0, 16-byte aligned rows.
+ *
+ * lgm_label_emb_fwd: temb[b] += emb[y[b]], st[b] = SiLU(temb[b]) - behind the time MLP (ddpm.py:430, 181-183), in place.
+ * lgm_label_emb_wgrad: gemb[k] = beta * gemb[k] + sum over the samples with y[b] = k of gtemb[b], in ascending b: every row
+ *   is written, a class no sample has gets beta * its old value.  No atomics: the same bits on every run.
+ * lgm_cfg_mix: out_cond[r][c] = out_null[r][c] + scale * (out_cond[r][c] - out_null[r][c]) for c < C, in place in out_cond
+ *   [rows][cond_pitch]; scale == 1 keeps out_cond and scale == 0 takes out_null, bit for bit; lanes >= C keep their value.
+ *   scale_dev != NULL: the scale is read from that device float instead (a captured sampling step).  Pitches % 4 == 0. */
+int lgm_label_emb_fwd(float* temb, float* st, const float* emb, const int64_t* y, int B, int time_dim, int num_classes,
+                      void* stream);
+int lgm_label_emb_wgrad(const float* gtemb, const int64_t* y, float* gemb, float beta, int B, int time_dim,
+                        int num_classes, void* stream);
+int lgm_cfg_mix(float* out_cond, int64_t cond_pitch, const float* out_null, int64_t null_pitch, float scale,
+                const float* scale_dev, int64_t rows, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

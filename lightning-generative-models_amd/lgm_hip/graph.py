@@ -122,9 +122,15 @@ class GraphedDDPMStep:
     behind the launch that draws t / noise and writes x_t (``pre``), the estimate pass - the network without saved
     activations + the kernel that writes x_start into the self-conditioning slice of the input buffer - is a graph of its own
     (``est``) replayed on the steps whose coin says so, and the saved forward pass opens the next graph.  ``pre`` zeroes the
-    self-conditioning slice on every step.  A model without self-conditioning captures exactly the graphs listed above."""
+    self-conditioning slice on every step.  A model without self-conditioning captures exactly the graphs listed above.
 
-    def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, inject: bool = False):
+    Class-conditional model: ``y`` is a second static input buffer (the batch's labels, copied beside ``x`` before replay).
+    The label drop of classifier-free guidance - rand(B) < cond_drop_prob - is drawn inside the graph behind t, noise and
+    offset, the order ``GaussianDiffusion.forward`` draws in; ``self.classes`` holds the labels the last replay used (with
+    ``inject`` it is the input buffer of already-dropped labels).  A model without classes draws nothing more."""
+
+    def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, inject: bool = False,
+                 y: Optional[torch.Tensor] = None):
         from models.generative.diffusion.ddpm import (hip_loss_backward_phase1a, hip_loss_estimate, hip_loss_forward,
                                                       hip_loss_network, hip_loss_qsample)
         self.model, self.opt, self.sync = model, opt, sync
@@ -139,6 +145,10 @@ class GraphedDDPMStep:
         self.noise = torch.zeros_like(x) if inject else None
         strength = float(self.gd.offset_noise_strength)
         self.offset = torch.zeros(x.shape[:2], device=x.device) if inject and strength > 0.0 else None
+        self.y = self.classes = None
+        if net.num_classes is not None:
+            self.y = net.labels(y, x.shape[0], x.device).clone()
+            self.classes = self.y.clone() if inject else None
         # (the pipelined variant applies a bucket's Adam slice right behind ITS all-reduce: only with the overlapped exchange)
         self.pipeline = _STEP_PIPELINE and (sync is None or getattr(sync, "overlap", True))
         split = sync is not None or self.pipeline
@@ -155,6 +165,8 @@ class GraphedDDPMStep:
             noise = torch.randn_like(self.x)
             offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
             self.t, self.noise, self.offset = t, noise, offset
+            if self.y is not None:
+                self.classes = gd.drop_labels(self.y)
             return t, noise, offset
 
         def part0():                                 # self-conditioned: the draws and the q_sample launch
@@ -165,10 +177,11 @@ class GraphedDDPMStep:
             gd = self.gd
             if self_cond:
                 xt, target, img, noise, t, offset = q
-                loss, ctx = hip_loss_network(gd, xt, target, img, t, noise, offset, True)
+                loss, ctx = hip_loss_network(gd, xt, target, img, t, noise, offset, True, self.classes)
             else:
                 t, noise, offset = draws()
-                loss, ctx = hip_loss_forward(gd, self.x, t, noise, gd.auto_normalize, True, offset, strength)
+                loss, ctx = hip_loss_forward(gd, self.x, t, noise, gd.auto_normalize, True, offset, strength,
+                                             classes=self.classes)
             fp.zero_grad()
             return loss, hip_loss_backward_phase1a(ctx, self.one)
 
@@ -176,7 +189,7 @@ class GraphedDDPMStep:
             q = None
             if self_cond:
                 q = part0()
-                hip_loss_estimate(self.gd, q[0], q[4])
+                hip_loss_estimate(self.gd, q[0], q[4], self.classes)
             _, st = part1a(q)
             net.backward_phase2(net.backward_phase1b(st))
 
@@ -200,7 +213,7 @@ class GraphedDDPMStep:
                 if self_cond:
                     self.pre, q, _ = _capture(part0, 0)
                     pool0 = self.pre.pool()
-                    self.est, _, _ = _capture(lambda: hip_loss_estimate(self.gd, q[0], q[4]), 0, pool0)
+                    self.est, _, _ = _capture(lambda: hip_loss_estimate(self.gd, q[0], q[4], self.classes), 0, pool0)
                     self._q = q                      # keeps the input buffer and the target alive
                 if split:
                     g1a, (self.loss, st), _ = _capture(lambda: part1a(q), 0, pool0)
@@ -314,9 +327,9 @@ class DDPMFastStep:
         # self-conditioned model: the coin of reference :902, drawn on the host once per step (tests inject a sequence here)
         self.coin = lambda: random.random() < 0.5
 
-    def _capture(self, x):
+    def _capture(self, x, y=None):
         try:
-            self.graphed = GraphedDDPMStep(self.model, self.opt, x.clone(), self.sync)
+            self.graphed = GraphedDDPMStep(self.model, self.opt, x.clone(), self.sync, y=y)
             n = len(self.graphed.graphs) + (1 if self.graphed.pre is not None else 0)
             self.mode = ("hipGraph replay (4 graphs/step, weight passes on a side stream)" if _STEP_PIPELINE else
                          f"hipGraph replay ({n} graph{'s' if n > 1 else ''}/step)")
@@ -333,18 +346,24 @@ class DDPMFastStep:
         from models.generative.diffusion.ddpm import _is_master
         m = self.model
         x = batch[0]
+        y = batch[1] if self.net.num_classes is not None else None      # the labels: read by a class-conditional model only
         if m.sample_every and m.global_step % m.sample_every == 0 and _is_master():
             m._log_sample()
         if self.use_graph and self.graphed is None:
-            self._capture(x)
+            self._capture(x, y)
         self_cond = bool(self.coin()) if self.net.self_condition else False
         if self.graphed is not None and x.shape == self.graphed.x.shape:
             self.graphed.x.copy_(x)
+            if y is not None:
+                self.graphed.y.copy_(y)
             loss = self.graphed.step(batch_idx, self_cond)
         else:
             self.net.grad_sync = self.sync           # backward phases hand finished buckets to the exchange
             gd = m.ema.online_model
-            loss = gd(x, _self_cond=self_cond) if self.net.self_condition else gd(x)
+            kw = dict(_self_cond=self_cond) if self.net.self_condition else {}
+            if y is not None:
+                kw["classes"] = y
+            loss = gd(x, **kw)
             loss.backward()
             if self.sync is not None:
                 self.sync.finish()

@@ -1290,6 +1290,26 @@ def time_mlp_bwd(gst, pe, a1, h, temb, w2, dim, time_dim, gtemb, ga1, gw1, gb1, 
                            dim, time_dim, gtemb.data_ptr(), ga1.data_ptr(), gw1, gb1, gw2, gb2, float(beta), stream())
 
 
+# Class conditioning (csrc/classcond.hip): the label embedding behind the time MLP and the classifier-free-guidance mix
+def label_emb_fwd(temb, st, emb_ptr, y, num_classes):
+    """temb[b] += emb[y[b]]; st = SiLU(temb).  temb, st: dense [B, time_dim]; y: int64 [B] on the device."""
+    lib().lgm_label_emb_fwd(temb.data_ptr(), st.data_ptr(), emb_ptr, y.data_ptr(), temb.shape[0], temb.shape[1],
+                            num_classes, stream())
+
+
+def label_emb_wgrad(gtemb, y, gemb_ptr, beta, num_classes):
+    """gemb[k] = beta * gemb[k] + sum_{b: y[b] = k} gtemb[b] (ascending b), every row k in [0, num_classes]."""
+    lib().lgm_label_emb_wgrad(gtemb.data_ptr(), y.data_ptr(), gemb_ptr, float(beta), gtemb.shape[0], gtemb.shape[1],
+                              num_classes, stream())
+
+
+def cfg_mix(out_cond, out_null, scale, C, scale_dev=None):
+    """out_cond <- out_null + scale * (out_cond - out_null) on the first C lanes of two NHWC network outputs, in place."""
+    assert out_cond.shape == out_null.shape
+    lib().lgm_cfg_mix(out_cond.data_ptr(), pitch(out_cond), out_null.data_ptr(), pitch(out_null), float(scale),
+                      _p(scale_dev), rows(out_cond), C, stream())
+
+
 def act_fwd(x, bias_ptr, res, y, act, slope=0.0):
     lib().lgm_act_fwd(x.data_ptr(), pitch(x), bias_ptr, _p(res), pitch(res) if res is not None else 0,
                       y.data_ptr(), pitch(y), rows(x), x.shape[-1], act, slope, stream())

@@ -21,6 +21,11 @@ A self-conditioned network (reference :773-774, 807-810, 864-865) reads ONE inpu
 ``lgm_sample_step_slice`` / ``lgm_sample_step_table_slice`` read x from its slice, write the next x there and the x_start the
 reference hands on (clipped, as p_sample and ddim_sample clip it) into the self-conditioning slice the next step reads.  A
 chain starts with that slice zero: the reference's ``x_start = None``.
+
+A class-conditional network (``Unet(num_classes=K)``) reads one label per sample, fixed for the run.  With a guidance scale
+other than 1 a step is two forwards over the SAME input buffer - the labels, then the null label - and ``lgm_cfg_mix``
+(out_null + scale * (out_cond - out_null), in place in the conditional output) in front of the update kernel, in the eager
+launches and in the captured step alike; labels and scale of a captured step live in static buffers.
 """
 from __future__ import annotations
 
@@ -57,13 +62,16 @@ def _f32(x) -> float:
 class _Chain:
     """Device-resident state of one sampling run (NHWC, padded channels)."""
 
-    def __init__(self, gd, shape, init_noise: Optional[torch.Tensor], x_self_cond: Optional[torch.Tensor] = None):
+    def __init__(self, gd, shape, init_noise: Optional[torch.Tensor], x_self_cond: Optional[torch.Tensor] = None,
+                 classes=None, cond_scale: float = 1.0):
         self.gd = gd
         self.net = net = gd.model
         B, C, H, W = shape
         self.shape = shape
         dev = gd.betas.device
         self.net.prepare_hip(dev)
+        # the run's labels on the device (None: a network without classes) and its guidance scale
+        self.classes, self.cond_scale = gd._guidance(classes, cond_scale, B, dev)
         self.Cp = _r4(C)
         if init_noise is None:
             init_noise = torch.randn(shape, device=dev)
@@ -93,7 +101,7 @@ class _Chain:
     def step(self, t: int, noise: Optional[torch.Tensor], clip: bool, C0, C1, C2, C3, rederive: bool = False):
         hs = _host_schedule(self.gd)
         B, C, H, W = self.shape
-        v, _ = self.net.forward_nhwc(self.x, self.times(t), False)
+        v = self.net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
         nz = None if noise is None else noise.data_ptr()
         A, Bv = _f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t])
         R, Rm1 = _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t])
@@ -155,7 +163,7 @@ _CAPTURE_RETRY_AFTER = 8      # a failed capture is retried after this many eage
 class _GraphedChain:
     """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it."""
 
-    def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096):
+    def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096, guided: bool = False):
         net = gd.model
         objective = _objective(gd)
         is_v = gd.objective == "pred_v"
@@ -176,6 +184,9 @@ class _GraphedChain:
         self.table = torch.zeros((max_steps, 8), device=dev)
         self.ttable = torch.zeros(max_steps, dtype=torch.long, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        # class-conditional network: the run's labels; guided step: its scale, read on the device by lgm_cfg_mix
+        self.classes = net.labels(None, B, dev).clone() if net.num_classes is not None else None
+        self.scale = torch.ones(1, device=dev) if guided else None
         self.inject = False
         self.max_steps = max_steps
         L = ops.lib()
@@ -183,7 +194,7 @@ class _GraphedChain:
         def one_step():
             st = ops.stream()
             L.lgm_sampler_time(self.ttable.data_ptr(), self.counter.data_ptr(), self.t.data_ptr(), B, st)
-            v, _ = net.forward_nhwc(self.x, self.t, False, refresh_weights=False)
+            v = net.forward_guided(self.x, self.t, self.classes, 1.0, refresh_weights=False, scale_dev=self.scale)
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
@@ -227,10 +238,15 @@ class _GraphedChain:
                 and (None if fp.data_uf is None else fp.data_uf.data_ptr()) == uf
                 and (None if fp.data_t is None else fp.data_t.data_ptr()) == dt)
 
-    def run(self, x0_nhwc, times, coeffs, noises):
+    def run(self, x0_nhwc, times, coeffs, noises, classes=None, cond_scale: float = 1.0):
         """times[i], coeffs[i] (8 floats) per step; noises: None (draw on device) or a list with one NCHW tensor or
-        None per step.  Returns the final NHWC image (a view of the static buffer)."""
+        None per step; classes: the run's device labels (class-conditional network).  Returns the final NHWC image (a view
+        of the static buffer)."""
         n = len(times)
+        if self.classes is not None:
+            self.classes.copy_(classes)
+        if self.scale is not None:
+            self.scale.fill_(float(cond_scale))
         assert n <= self.max_steps
         self._net().refresh_derived_weights(False)   # the weights may have moved since the last chain (EMA updates)
         self.x.copy_(x0_nhwc)
@@ -252,7 +268,7 @@ class _GraphedChain:
         return self.x
 
 
-def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False):
+def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bool = False):
     """-> a _GraphedChain for (network, shape, objective), or None (graph replay disabled / capture failed: eager launches).
     ``rederive``: the DDIM chain's re-derived noise, part of the captured launch for pred_noise / pred_x0."""
     if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or gd.betas.device.type != "cuda":
@@ -266,6 +282,8 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False):
     key = (tuple(shape), bool(with_noise))
     if gd.objective != "pred_v":                     # two diffusions of other objectives may share one network
         key += (gd.objective, bool(rederive))
+    if guided:                                       # two forwards and the mix per step: a graph of its own
+        key += ("guided",)
     ent = per_net.get(key)
     if isinstance(ent, _GraphedChain) and not ent.matches(net):
         ent = None                                   # captured against buffers the network no longer uses
@@ -277,7 +295,7 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False):
         ent = None
     if ent is None:
         try:
-            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive)
+            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided)
         except Exception as e:  # capture is an optimisation
             import sys
             print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",
@@ -316,22 +334,23 @@ def warm_chain(gd, shape, replays: int = 20) -> bool:
     if gc is None:
         return False
     ts = list(reversed(range(gd.num_timesteps)))[:replays]
-    gc.run(_Chain(gd, shape, None).x, ts, [_p_sample_coeffs(gd, t) for t in ts], None)
+    chain = _Chain(gd, shape, None)
+    gc.run(chain.x, ts, [_p_sample_coeffs(gd, t) for t in ts], None, chain.classes)
     return True
 
 
 @torch.no_grad()
 def p_sample_loop(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-                  start: Optional[int] = None, unnormalize: Optional[bool] = None):
+                  start: Optional[int] = None, unnormalize: Optional[bool] = None, classes=None, cond_scale: float = 1.0):
     """``start``: walk the chain from step start - 1 down to 0 (GaussianDiffusion.interpolate :861-865) instead of from
     T - 1; ``unnormalize``: default = the model's auto_normalize (p_sample_loop :779), False for interpolate."""
-    chain = _Chain(gd, shape, init_noise)
+    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale)
     dev = chain.x.device
     ts = list(reversed(range(gd.num_timesteps if start is None else int(start))))
     unn = gd.auto_normalize if unnormalize is None else bool(unnormalize)
-    gc = None if return_all_timesteps or not ts else _graph_chain(gd, shape, True)
+    gc = None if return_all_timesteps or not ts else _graph_chain(gd, shape, True, guided=chain.cond_scale != 1.0)
     if gc is not None:
-        x = gc.run(chain.x, ts, [_p_sample_coeffs(gd, t) for t in ts], noises)
+        x = gc.run(chain.x, ts, [_p_sample_coeffs(gd, t) for t in ts], noises, chain.classes, chain.cond_scale)
         chain.x = x
         return chain.image(unn)
     frames = [chain.image(False)] if return_all_timesteps else None
@@ -349,15 +368,17 @@ def p_sample_loop(gd, shape, return_all_timesteps=False, init_noise=None, noises
 
 
 @torch.no_grad()
-def ddim_sample(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None):
-    chain = _Chain(gd, shape, init_noise)
+def ddim_sample(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
+                classes=None, cond_scale: float = 1.0):
+    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale)
     dev = chain.x.device
     eta = gd.ddim_sampling_eta
     pairs = gd.ddim_time_pairs()
-    gc = None if return_all_timesteps else _graph_chain(gd, shape, eta != 0.0, rederive=True)
+    gc = None if return_all_timesteps else _graph_chain(gd, shape, eta != 0.0, rederive=True,
+                                                        guided=chain.cond_scale != 1.0)
     if gc is not None:
         x = gc.run(chain.x, [a for a, _ in pairs], [_ddim_coeffs(gd, a, b, eta) for a, b in pairs],
-                   noises if eta != 0.0 else None)
+                   noises if eta != 0.0 else None, chain.classes, chain.cond_scale)
         chain.x = x
         return chain.image(gd.auto_normalize)
     frames = [chain.image(False)] if return_all_timesteps else None

@@ -291,8 +291,10 @@ class Unet(nn.Module):
                  self_condition=False, resnet_block_groups=8, learned_variance=False,
                  learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32,
-                 attn_heads=4, full_attn=None, flash_attn=False):
+                 attn_heads=4, full_attn=None, flash_attn=False, num_classes=None):
         super().__init__()
+        if num_classes is not None and int(num_classes) < 1:
+            raise ValueError(f"num_classes must be a positive number of classes, got {num_classes!r}")
         if learned_variance or learned_sinusoidal_cond or random_fourier_features:
             raise NotImplementedError("HIP UNet covers the configuration the reference DDPM constructs "
                                       "(ddpm.py:984-987) and self-conditioning: no learned variance / fourier features")
@@ -314,6 +316,12 @@ class Unet(nn.Module):
         time_dim = dim * 4
         self.time_dim = time_dim
         self.time_mlp = nn.Sequential(nn.Identity(), Linear(dim, time_dim), nn.Identity(), Linear(time_dim, time_dim))
+        # class-conditional (extension): temb = time_mlp(t) + label_emb.weight[classes], row num_classes = the null label
+        # classifier-free guidance trains and samples with; N(0, 1) like nn.Embedding, dense under Adam and the EMA
+        self.num_classes = None if num_classes is None else int(num_classes)
+        if self.num_classes is not None:
+            self.label_emb = nn.Embedding(self.num_classes + 1, time_dim)
+        self._null_labels = {}
         n = len(in_out)
         if not full_attn:
             full_attn = (*((False,) * (n - 1)), True)
@@ -383,6 +391,8 @@ class Unet(nn.Module):
         for lin in (self.time_mlp[1], self.time_mlp[3]):      # their gradients are produced last, too
             first.append((names[id(lin.weight)], lin.weight, "weight"))
             first.append((names[id(lin.bias)], lin.bias, "vector"))
+        if self.num_classes is not None:                      # dense rows [K + 1, time_dim], final with the time MLP's
+            first.append((names[id(self.label_emb.weight)], self.label_emb.weight, "vector"))
         taken = {id(p) for _, p, _ in first}
         rest = [(n, p, param_kind(n, p)) for n, p in named.items() if id(p) not in taken]
         self._flat = FlatParams(first + rest, device)
@@ -420,7 +430,30 @@ class Unet(nn.Module):
         return self._flat
 
     # ---- time embedding -------------------------------------------------------------------
-    def _time_fwd(self, t, save):
+    def labels(self, classes, B, device):
+        """The int64 [B] device tensor of labels the kernels read, or None for a network without classes.  ``None`` on a
+        class-conditional network = the null label for every sample.  Labels the host can see (a CPU tensor, a list) are
+        checked against [0, num_classes]; labels already on the device are clamped by the kernels."""
+        K = self.num_classes
+        if K is None:
+            if classes is not None:
+                raise ValueError("classes were passed to a Unet built without num_classes")
+            return None
+        device = torch.device(device)
+        if classes is None:
+            key = (B, device)
+            y = self._null_labels.get(key)
+            if y is None:
+                y = self._null_labels[key] = torch.full((B,), K, dtype=torch.long, device=device)
+            return y
+        y = torch.as_tensor(classes)
+        if y.dtype.is_floating_point or y.dtype == torch.bool or tuple(y.shape) != (B,):
+            raise ValueError(f"classes must be {B} integer labels (one per sample), got {y.dtype} {tuple(y.shape)}")
+        if y.device.type == "cpu" and B > 0 and (int(y.min()) < 0 or int(y.max()) > K):
+            raise ValueError(f"classes must lie in [0, {K}] ({K} = the null label), got [{int(y.min())}, {int(y.max())}]")
+        return y.to(device=device, dtype=torch.long).contiguous()
+
+    def _time_fwd(self, t, save, classes=None):
         B = t.shape[0]
         fp = self._flat
         l1, l2 = self.time_mlp[1], self.time_mlp[3]
@@ -438,7 +471,12 @@ class Unet(nn.Module):
             ops.conv_xy(l1.geom(B), pe, fp.ptr(l1.weight), fp.ptr(l1.bias), None, a1)
             ops.act_fwd(a1, None, None, h, ops.ACT_GELU)
             ops.conv_xy(l2.geom(B), h, fp.ptr(l2.weight), fp.ptr(l2.bias), None, temb)
-            ops.act_fwd(temb, None, None, st, ops.ACT_SILU)
+            if self.num_classes is None:
+                ops.act_fwd(temb, None, None, st, ops.ACT_SILU)
+        if self.num_classes is not None:
+            # temb += label_emb[classes], st = SiLU(temb): one row-local launch behind the time MLP
+            classes = self.labels(None, B, t.device) if classes is None else classes
+            ops.label_emb_fwd(temb, st, fp.ptr(self.label_emb.weight), classes, self.num_classes)
         g = self._mlp_geoms.get(B)
         if g is None:
             g = ops.make_geom(B, 1, 1, self.time_dim, self._ss_total, 1, 1, 1, 0)
@@ -446,10 +484,10 @@ class Unet(nn.Module):
         rb0 = self.resblocks()[0]
         ss_all = ops.new((B, self._ss_total), t)
         ops.conv_xy(g, st, fp.ptr(rb0.mlp[1].weight), fp.ptr(rb0.mlp[1].bias), None, ss_all)
-        return ss_all, ((pe, a1, h, temb, st) if save else None)
+        return ss_all, ((pe, a1, h, temb, st, classes) if save else None)
 
     def _time_bwd(self, gc: GradCtx, saved, gss_all):
-        pe, a1, h, temb, st = saved
+        pe, a1, h, temb, st, classes = saved
         B = pe.shape[0]
         fp = gc.flat
         l1, l2 = self.time_mlp[1], self.time_mlp[3]
@@ -470,8 +508,10 @@ class Unet(nn.Module):
             ga1 = ops.new(a1.shape, a1)
             ops.time_mlp_bwd(gst, pe, a1, h, temb, fp.ptr(l2.weight), self.dim, self.time_dim, gtemb, ga1,
                              fp.gptr(l1.weight), fp.gptr(l1.bias), fp.gptr(l2.weight), fp.gptr(l2.bias), bw)
+            self._label_emb_bwd(gc, gtemb, classes)
             return
         ops.act_bwd(temb, None, gst, gtemb, False, ops.ACT_SILU)
+        self._label_emb_bwd(gc, gtemb, classes)
         gh = ops.new(h.shape, h)
         # weight gradient and input gradient of the second time-MLP linear in one launch (lgm_conv_bwd_pair)
         ops.conv_bwd_generic(l2.geom(B), gtemb, h, fp.ptr(l2.weight), fp.tptr(l2.weight), fp.gptr(l2.weight),
@@ -482,18 +522,38 @@ class Unet(nn.Module):
         ops.conv_wgrad(l1.geom(B), ga1, pe, fp.gptr(l1.weight), gc.beta(l1.weight), fp.gptr(l1.bias))
         gc.beta(l1.bias)
 
+    def _label_emb_bwd(self, gc: GradCtx, gtemb, classes):
+        """g label_emb.weight[k] = sum of g temb[b] over the samples of class k, in ascending b; other rows exactly zero"""
+        if self.num_classes is not None:
+            w = self.label_emb.weight
+            ops.label_emb_wgrad(gtemb, classes, gc.flat.gptr(w), gc.beta(w), self.num_classes)
+
     # ---- network ----------------------------------------------------------------------------
-    def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True):
+    def forward_guided(self, x, t, classes=None, cond_scale: float = 1.0, refresh_weights: bool = True, scale_dev=None):
+        """The network output a sampler reads (no saved activations).  ``cond_scale == 1``: one forward with ``classes``.
+        Otherwise classifier-free guidance: a second forward over the SAME input buffer with the null label, then
+        out = out_null + cond_scale * (out - out_null) in place (lgm_cfg_mix); the derived weights are refreshed once.
+        ``scale_dev``: a device float holding the scale (captured steps), which makes the step a guided one."""
+        out, _ = self.forward_nhwc(x, t, False, refresh_weights, classes)
+        if scale_dev is not None or float(cond_scale) != 1.0:
+            if self.num_classes is None:
+                raise ValueError("cond_scale != 1 needs a Unet built with num_classes")
+            null, _ = self.forward_nhwc(x, t, False, False, None)
+            ops.cfg_mix(out, null, cond_scale, self.out_dim, scale_dev)
+        return out
+
+    def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True, classes=None):
         """x: [B, S, S, in_pitch] NHWC (``input_buffer``; pad lanes zero), t: int64 [B].
         Returns (out [B,S,S,r4(out_dim)], tape).  ``refresh_weights=False``: the derived weight copies (Winograd /
-        split-precision operands) are known to be current — a sampling chain refreshes them once, not per step."""
+        split-precision operands) are known to be current — a sampling chain refreshes them once, not per step.
+        ``classes``: int64 [B] on the device (``Unet.labels``), read by a class-conditional network only; None = null labels."""
         B, S, _, _ = x.shape
         dim = self.dim
         n = len(self.in_out)
         assert S % (2 ** (n - 1)) == 0, f"input size {S} must be divisible by {2 ** (n - 1)}"
         if refresh_weights:
             self.refresh_derived_weights(save)
-        ss_all, time_saved = self._time_fwd(t, save)
+        ss_all, time_saved = self._time_fwd(t, save, classes)
         ssl = [ss_all[:, o:o + 2 * rb.dim_out] for o, rb in zip(self._ss_offsets, self.resblocks())]
         k = 0  # running resblock index
         tape = []
@@ -716,10 +776,13 @@ class Unet(nn.Module):
             sync.ready(0, self._head_end)
         self._flat.bind_grad_views()
 
-    def forward(self, x: torch.Tensor, time: torch.Tensor, x_self_cond=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, time: torch.Tensor, x_self_cond=None, classes=None) -> torch.Tensor:
         """NCHW in / NCHW out, like the reference Unet.forward (:428-471); ``x_self_cond`` is a constant (no gradient
-        reaches it) and is read by a self-conditioned network only, ``None`` meaning zeros (:434)."""
-        return _UnetFn.apply(self._anchor(x.device), self, x, time, x_self_cond)
+        reaches it) and is read by a self-conditioned network only, ``None`` meaning zeros (:434).  ``classes`` (extension):
+        one label in [0, num_classes] per sample for a class-conditional network, ``None`` meaning the null label; on a
+        network without classes it raises ValueError."""
+        classes = self.labels(classes, x.shape[0], x.device)
+        return _UnetFn.apply(self._anchor(x.device), self, x, time, x_self_cond, classes)
 
     # ---- the input buffer and its two slices ------------------------------------------------------------
     def input_buffer(self, B, H, W, like):
@@ -740,7 +803,8 @@ class Unet(nn.Module):
             self._anchor_t = a
         return a
 
-    def run_nchw(self, x, time, save, x_self_cond=None):
+    def run_nchw(self, x, time, save, x_self_cond=None, classes=None, cond_scale: float = 1.0):
+        """``classes``: device labels (``Unet.labels``); ``cond_scale != 1`` (without saved activations only): guided output"""
         B, C, H, W = x.shape
         xin = self.input_buffer(B, H, W, x)
         ops.nchw_to_nhwc(x.contiguous(), self.x_slice(xin, pad=True))
@@ -748,7 +812,11 @@ class Unet(nn.Module):
             sc = torch.zeros_like(x) if x_self_cond is None else x_self_cond.detach().float().contiguous()
             assert sc.shape == x.shape, f"x_self_cond {tuple(sc.shape)} must have the shape of x {tuple(x.shape)}"
             ops.nchw_to_nhwc(sc, self.sc_slice(xin))
-        out, tape = self.forward_nhwc(xin, time, save)
+        if save:
+            assert float(cond_scale) == 1.0, "guidance is a sampling-time mix: no gradient is taken through it"
+            out, tape = self.forward_nhwc(xin, time, True, True, classes)
+        else:
+            out, tape = self.forward_guided(xin, time, classes, cond_scale), None
         y = ops.new((B, self.out_dim, H, W), x)
         ops.nhwc_to_nchw(out, y)
         return y, tape, out
@@ -756,9 +824,9 @@ class Unet(nn.Module):
 
 class _UnetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, net: Unet, x, time, x_self_cond=None):
+    def forward(ctx, anchor, net: Unet, x, time, x_self_cond=None, classes=None):
         save = bool(ctx.needs_input_grad[0])   # grad mode on at apply() time and anchor requires grad
-        y, tape, _ = net.run_nchw(x.detach().float(), time, save, x_self_cond)
+        y, tape, _ = net.run_nchw(x.detach().float(), time, save, x_self_cond, classes)
         ctx.net, ctx.tape = net, tape
         return y
 
@@ -772,7 +840,7 @@ class _UnetFn(torch.autograd.Function):
         ops.nchw_to_nhwc(gy.contiguous(), g)
         net.backward_nhwc(tape, g)
         ctx.tape = None
-        return None, None, None, None, None
+        return None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -805,10 +873,22 @@ OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}     # the `objective` 
 class GaussianDiffusion(nn.Module):
     def __init__(self, model: Unet, *, img_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
-                 offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5):
+                 offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, cond_drop_prob=None,
+                 cond_scale=1.0):
+        """``cond_drop_prob`` / ``cond_scale`` (extension, class-conditional ``model`` only): the probability with which
+        ``forward`` replaces a training label by the null label, and the classifier-free-guidance scale ``sample`` uses.
+        ``cond_drop_prob=None`` is 0.1 on a class-conditional model and 0 on any other."""
         super().__init__()
         if objective not in OBJECTIVES:
             raise ValueError(f"objective must be one of {sorted(OBJECTIVES)}, got {objective!r}")
+        self.num_classes = getattr(model, "num_classes", None)
+        if cond_drop_prob is None:
+            cond_drop_prob = 0.1 if self.num_classes is not None else 0.0
+        if not 0.0 <= float(cond_drop_prob) <= 1.0:
+            raise ValueError(f"cond_drop_prob must lie in [0, 1], got {cond_drop_prob!r}")
+        if self.num_classes is None and (float(cond_drop_prob) > 0.0 or float(cond_scale) != 1.0):
+            raise ValueError("cond_drop_prob > 0 and cond_scale != 1 need a model built with num_classes")
+        self.cond_drop_prob, self.cond_scale = float(cond_drop_prob), float(cond_scale)
         self.model = model
         self.channels = model.channels
         self.self_condition = model.self_condition
@@ -858,15 +938,18 @@ class GaussianDiffusion(nn.Module):
         return list(zip(times[:-1], times[1:]))
 
     # -- training ---------------------------------------------------------------------------
-    def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, *, _offset_noise=None, _normalize=False,
-                 _self_cond=None):
+    def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, classes=None, *, _offset_noise=None,
+                 _normalize=False, _self_cond=None):
         """x_start already normalised unless _normalize (reference :878-925).  Offset noise (:885-891): one draw per
         (sample, channel), added to the noise inside the q_sample kernel - the caller's ``noise`` is not written.
         ``_offset_noise`` (extension, for parity tests): the [B, C] draw the reference takes from torch.randn.
         Self-conditioned model (:899-909): with probability 0.5 (Python's ``random.random()``, as in the reference) the network
         runs once without saved activations, its unclipped x_start becomes the self-conditioning input of the pass the
         gradient is taken through; no gradient reaches the estimate.  ``_self_cond`` (extension, for parity tests):
-        ``True`` / ``False`` is the coin, an NCHW tensor is used as the estimate itself."""
+        ``True`` / ``False`` is the coin, an NCHW tensor is used as the estimate itself.
+        ``classes`` (extension, class-conditional model): the labels as the network gets them - ``forward`` has already
+        replaced the dropped ones by the null label; the estimate pass and the main pass see the same labels."""
+        classes = self.model.labels(classes, x_start.shape[0], x_start.device)
         if noise is None:
             noise = torch.randn_like(x_start)
         strength = self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
@@ -877,13 +960,34 @@ class GaussianDiffusion(nn.Module):
         if self.self_condition:
             self_cond = (random.random() < 0.5) if _self_cond is None else _self_cond
         anchor = self.model._anchor(x_start.device)
-        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond)
+        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond, classes)
 
-    def forward(self, img, *args, **kwargs):
+    def drop_labels(self, classes):
+        """Classifier-free guidance training: every label becomes the null label with probability ``cond_drop_prob`` (one
+        ``torch.rand(B)`` on the labels' device; nothing is drawn when the probability is 0)."""
+        if self.cond_drop_prob <= 0.0:
+            return classes
+        drop = torch.rand(classes.shape[0], device=classes.device) < self.cond_drop_prob
+        return torch.where(drop, torch.full_like(classes, self.num_classes), classes)
+
+    def forward(self, img, *args, classes=None, **kwargs):
+        """``classes`` (keyword, class-conditional model): the batch's labels.  The draws are then taken here, in the order
+        the graph-replayed step takes them: t, noise, offset noise, label drop.  Without labels: t, then what p_losses
+        draws - the stream of a model without classes."""
         b, c, h, w = img.shape
         assert h == self.img_size and w == self.img_size, f"height and width of image must be {self.img_size}"
         t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()
-        return self.p_losses(img, t, *args, _normalize=self.auto_normalize, **kwargs)
+        if classes is None:
+            return self.p_losses(img, t, *args, _normalize=self.auto_normalize, **kwargs)
+        classes = self.model.labels(classes, b, img.device)
+        noise, strength = (list(args) + [None, None])[:2]
+        noise = kwargs.pop("noise", noise)
+        strength = kwargs.pop("offset_noise_strength", strength)
+        if noise is None:
+            noise = torch.randn_like(img)
+        if (self.offset_noise_strength if strength is None else strength) > 0.0 and kwargs.get("_offset_noise") is None:
+            kwargs["_offset_noise"] = torch.randn(img.shape[:2], device=img.device)
+        return self.p_losses(img, t, noise, strength, self.drop_labels(classes), _normalize=self.auto_normalize, **kwargs)
 
     # -- the reference's per-sample-timestep algebra (:673-705, 869-876): one lgm_extract_axpby launch each ---------
     def normalize(self, img):
@@ -936,12 +1040,28 @@ class GaussianDiffusion(nn.Module):
                 self._extract(self.posterior_log_variance_clipped, t, x_t.ndim))
 
     @torch.no_grad()
-    def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False):
+    def _guidance(self, classes, cond_scale, B, device):
+        """-> (device labels or None, scale) for a sampling call; ``cond_scale=None`` is the constructor's"""
+        scale = self.cond_scale if cond_scale is None else float(cond_scale)
+        if scale != 1.0 and self.num_classes is None:
+            raise ValueError("cond_scale != 1 needs a model built with num_classes")
+        return self.model.labels(classes, B, device), scale
+
+    @torch.no_grad()
+    def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, classes=None,
+                          cond_scale=1.0):
         """-> ModelPrediction(pred_noise, pred_x_start), reference :707-734.  ``rederive_pred_noise`` takes effect for
         pred_noise only (with ``clip_x_start``; otherwise pred_noise is the raw network output); for pred_x0 and pred_v the
         noise is always derived from the possibly clipped x_start.  UNet forward on the HIP engine, then ONE launch for
-        both results.  ``x_self_cond`` (NCHW, ``None`` = zeros) is read by a self-conditioned network only."""
-        v = self.model(x, t, x_self_cond)
+        both results.  ``x_self_cond`` (NCHW, ``None`` = zeros) is read by a self-conditioned network only.
+        ``classes`` / ``cond_scale`` (extension): the network output is out_null + cond_scale * (out_cond - out_null), mixed
+        before the objective's algebra; ``cond_scale == 1`` is one forward with the labels."""
+        classes, cond_scale = self._guidance(classes, cond_scale, x.shape[0], x.device)
+        if cond_scale == 1.0:
+            v = self.model(x, t, x_self_cond, classes)
+        else:
+            self.model._anchor(x.device)
+            v = self.model.run_nchw(x.detach().float(), t.to(x.device), False, x_self_cond, classes, cond_scale)[0]
         x = x.detach().float().contiguous()
         B = x.shape[0]
         t = t.to(device=x.device, dtype=torch.long).contiguous()
@@ -964,19 +1084,20 @@ class GaussianDiffusion(nn.Module):
         return ModelPrediction(pred_noise, x_start)
 
     @torch.no_grad()
-    def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True):
-        x_start = self.model_predictions(x, t, x_self_cond, clip_x_start=clip_denoised).pred_x_start
+    def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True, classes=None, cond_scale=1.0):
+        x_start = self.model_predictions(x, t, x_self_cond, clip_x_start=clip_denoised, classes=classes,
+                                         cond_scale=cond_scale).pred_x_start
         mean, var, logvar = self.q_posterior(x_start=x_start, x_t=x, t=t)
         return mean, var, logvar, x_start
 
     # -- sampling: lgm_hip/sampler.py (one fused update kernel per step, graph replay for whole chains) -------------
     @torch.no_grad()
-    def p_sample(self, x, t: int, x_self_cond=None, noise=None):
+    def p_sample(self, x, t: int, x_self_cond=None, noise=None, classes=None, cond_scale=1.0):
         """One ancestral step at the shared timestep ``t`` -> (pred_img, x_start), reference :748-757.  ``noise``
         (extension, for parity tests): the draw the reference takes from randn_like.  ``x_self_cond`` (NCHW, ``None`` =
         zeros): the x_start the previous step returned, for a self-conditioned network."""
         from lgm_hip import sampler
-        chain = sampler._Chain(self, tuple(x.shape), x, x_self_cond)
+        chain = sampler._Chain(self, tuple(x.shape), x, x_self_cond, classes, cond_scale)
         if noise is None and t > 0:
             noise = torch.randn_like(x)
         sampler.p_sample_step(chain, int(t), noise)
@@ -985,22 +1106,29 @@ class GaussianDiffusion(nn.Module):
         return chain.image(False), x0
 
     @torch.no_grad()
-    def p_sample_loop(self, shape, return_all_timesteps=False):
+    def p_sample_loop(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0):
         from lgm_hip import sampler
-        return sampler.p_sample_loop(self, tuple(shape), return_all_timesteps)
+        return sampler.p_sample_loop(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale)
 
     @torch.no_grad()
-    def ddim_sample(self, shape, return_all_timesteps=False):
+    def ddim_sample(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0):
         from lgm_hip import sampler
-        return sampler.ddim_sample(self, tuple(shape), return_all_timesteps)
+        return sampler.ddim_sample(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale)
 
     @torch.no_grad()
-    def sample(self, batch_size=16, return_all_timesteps=False):
+    def sample(self, batch_size=16, return_all_timesteps=False, classes=None, cond_scale=None):
+        """``classes`` (class-conditional model): one label per image, ``None`` = the null label, in one forward per step;
+        ``cond_scale=None`` takes the constructor's."""
         fn = self.ddim_sample if self.is_ddim_sampling else self.p_sample_loop
-        return fn((batch_size, self.channels, self.img_size, self.img_size), return_all_timesteps=return_all_timesteps)
+        scale = self.cond_scale if cond_scale is None else cond_scale
+        if classes is None:
+            scale = 1.0                              # out_null + s * (out_null - out_null): the null forward alone
+        classes, scale = self._guidance(classes, scale, batch_size, self.device)
+        return fn((batch_size, self.channels, self.img_size, self.img_size), return_all_timesteps=return_all_timesteps,
+                  classes=classes, cond_scale=scale)
 
     @torch.no_grad()
-    def interpolate(self, x1, x2, t=None, lam=0.5):
+    def interpolate(self, x1, x2, t=None, lam=0.5, classes=None, cond_scale=1.0):
         """reference :847-867: noise both images to step t, blend, walk the ancestral chain back to 0 (no unnormalise)."""
         from lgm_hip import sampler
         b = x1.shape[0]
@@ -1009,31 +1137,32 @@ class GaussianDiffusion(nn.Module):
         tb = torch.full((b,), t, device=x1.device, dtype=torch.long)
         xt1, xt2 = self.q_sample(x1, tb), self.q_sample(x2, tb)
         img = (1 - lam) * xt1 + lam * xt2
-        return sampler.p_sample_loop(self, tuple(img.shape), init_noise=img, start=t, unnormalize=False)
+        return sampler.p_sample_loop(self, tuple(img.shape), init_noise=img, start=t, unnormalize=False, classes=classes,
+                                     cond_scale=cond_scale)
 
 
 def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, save: bool, offset=None,
-                     strength: float = 0.0, self_cond=False):
+                     strength: float = 0.0, self_cond=False, classes=None):
     """q_sample + UNet + the objective's target + weighted MSE on the HIP engine.  Returns (loss[1], ctx).
     ``offset`` ([B, C] or None) / ``strength``: offset noise, added to ``noise`` inside the q_sample kernel.
     ``self_cond`` (self-conditioned network only): ``True`` = estimate pass first (``hip_loss_estimate``), a tensor = that
-    NCHW estimate."""
+    NCHW estimate.  ``classes``: device labels (``Unet.labels``) both passes of a class-conditional network read."""
     xt, target, img, noise, t, offset = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength)
     if gd.model.self_condition:
         if torch.is_tensor(self_cond):
             assert self_cond.shape == img.shape
             ops.nchw_to_nhwc(self_cond.detach().float().contiguous(), gd.model.sc_slice(xt))
         elif self_cond:
-            hip_loss_estimate(gd, xt, t)
-    return hip_loss_network(gd, xt, target, img, t, noise, offset, save)
+            hip_loss_estimate(gd, xt, t, classes)
+    return hip_loss_network(gd, xt, target, img, t, noise, offset, save, classes)
 
 
-def hip_loss_estimate(gd: "GaussianDiffusion", xt, t):
+def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None):
     """The estimate pass of a self-conditioned training step (:901-905): the network without saved activations on the input
     buffer whose self-conditioning slice is zero, then ONE launch that writes the unclipped x_start into that slice."""
     net = gd.model
     B, H, W, _ = xt.shape
-    out, _ = net.forward_nhwc(xt, t, False)
+    out, _ = net.forward_nhwc(xt, t, False, True, classes)
     ops.lib().lgm_selfcond_estimate(xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off, out.data_ptr(), ops.pitch(out),
                                     t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
                                     gd.sqrt_one_minus_alphas_cumprod.data_ptr(), gd.sqrt_recip_alphas_cumprod.data_ptr(),
@@ -1075,14 +1204,14 @@ def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, of
     return xt, target, img, noise, t, offset
 
 
-def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool):
+def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None):
     """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx)."""
     net = gd.model
     B, C, H, W = img.shape
     Cp = _r4(C)
     L = ops.lib()
     st = ops.stream()
-    out, tape = net.forward_nhwc(xt, t, save)
+    out, tape = net.forward_nhwc(xt, t, save, True, classes)
     per = ops.new((B,), img)
     loss = ops.new((1,), img)
     L.lgm_weighted_mse_fwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
@@ -1112,9 +1241,10 @@ class _PLossFn(torch.autograd.Function):
     """q_sample + UNet + the objective's target + weighted MSE, forward and hand-written backward."""
 
     @staticmethod
-    def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0, self_cond=False):
+    def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0, self_cond=False,
+                classes=None):
         loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]), offset, strength,
-                                           self_cond)
+                                           self_cond, classes)
         return loss.view(())
 
     @staticmethod
@@ -1123,7 +1253,7 @@ class _PLossFn(torch.autograd.Function):
         st = hip_loss_backward_phase1(ctx.stuff, gl)
         ctx.stuff[0].model.backward_phase2(st)
         ctx.stuff = None
-        return None, None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -1134,14 +1264,19 @@ class DDPM(LightningModule):
                  sampling_timesteps: Optional[int] = None, lr: float = 2e-5, betas: Tuple[float, float] = (0.9, 0.99),
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
-                 min_snr_gamma: float = 5, self_condition: bool = False):
+                 min_snr_gamma: float = 5, self_condition: bool = False, num_classes: Optional[int] = None,
+                 cond_drop_prob: float = 0.1, cond_scale: float = 1.0):
+        """``num_classes`` (extension): class-conditional training on the batches' labels with classifier-free guidance;
+        ``cond_drop_prob`` / ``cond_scale`` are read with it only."""
         super().__init__()
         self.save_hyperparameters()
-        model = Unet(dim=dim, channels=img_channels, self_condition=self_condition)
+        self.num_classes = num_classes
+        model = Unet(dim=dim, channels=img_channels, self_condition=self_condition, num_classes=num_classes)
+        cond = dict(cond_drop_prob=cond_drop_prob, cond_scale=cond_scale) if num_classes is not None else {}
         diffusion_model = GaussianDiffusion(model, img_size=img_size, timesteps=diffusion_timesteps,
                                             sampling_timesteps=sampling_timesteps, objective=objective,
                                             beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
-                                            min_snr_loss_weight=min_snr_loss_weight, min_snr_gamma=min_snr_gamma)
+                                            min_snr_loss_weight=min_snr_loss_weight, min_snr_gamma=min_snr_gamma, **cond)
         self.channels = img_channels
         self.img_size = img_size
         self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
@@ -1159,9 +1294,9 @@ class DDPM(LightningModule):
 
     def _common_step(self, batch, mode: str):
         assert mode in ["train", "val", "test"], f"Invalid mode: {mode}"
-        data, _ = batch
+        data, y = batch
         model = self.ema.model if self.training else self.ema.ema_model
-        loss = model(data)
+        loss = model(data, classes=y) if self.num_classes is not None else model(data)
         self.log(f"{mode}_loss", loss, prog_bar=True, logger=True, sync_dist=multi_rank())
         if self.sample_every and self.global_step % self.sample_every == 0 and _is_master():
             self._log_sample()
@@ -1170,7 +1305,11 @@ class DDPM(LightningModule):
     @torch.no_grad()
     def _log_sample(self):
         self.ema.ema_model.eval()
-        self.last_samples = self.ema.ema_model.sample(batch_size=64)
+        if self.num_classes is not None:             # every class in turn, at the configured guidance scale
+            classes = torch.arange(64, device=self.ema.ema_model.device) % self.num_classes
+            self.last_samples = self.ema.ema_model.sample(batch_size=64, classes=classes)
+        else:
+            self.last_samples = self.ema.ema_model.sample(batch_size=64)
         logger = getattr(self, "logger", None)
         if logger is not None and hasattr(logger, "experiment"):
             try:  # W&B is optional
