@@ -998,12 +998,12 @@ static int conv_xy_impl(const LgmConvGeom* g, const float* x, int64_t x_pitch, c
                               (hipStream_t)stream);
   if (use_3x3() && use_gstream() && wide_ok(y, y_pitch, res, res_pitch, bias) && g->KH == 1 && g->KW == 1 &&
       g->stride == 1 && g->pad == 0 && lgm_gemm_stream_supported((long)g->B * g->H * g->W, g->Nw, g->Cw, x_pitch, y_pitch, res ? res_pitch : 0))
-    return lgm_note_kernel(LGM_KNAME("gemm_stream_kernel")), lgm_gemm_stream_launch(x, x_pitch, w, bias, res, res_pitch, y, y_pitch,
-                                                                        (long)g->B * g->H * g->W, g->Nw, g->Cw, (hipStream_t)stream);
+    return lgm_gemm_stream_launch(x, x_pitch, w, bias, res, res_pitch, y, y_pitch, (long)g->B * g->H * g->W, g->Nw, g->Cw,
+                                  (hipStream_t)stream);
   if (use_3x3() && wide_ok(y, y_pitch, res, res_pitch, bias) && g->KH == 1 && g->KW == 1 && g->stride == 1 &&
       g->pad == 0 && lgm_gemm_rows_supported((long)g->B * g->H * g->W, g->Nw, g->Cw))
-    return lgm_note_kernel(LGM_KNAME("gemm_rows_kernel")), lgm_gemm_rows_launch(x, x_pitch, w, bias, res, res_pitch, y, y_pitch,
-                                                                    (long)g->B * g->H * g->W, g->Nw, g->Cw, (hipStream_t)stream);
+    return lgm_gemm_rows_launch(x, x_pitch, w, bias, res, res_pitch, y, y_pitch, (long)g->B * g->H * g->W, g->Nw, g->Cw,
+                                (hipStream_t)stream);
   IgemmArgs a{};
   a.a = x; a.w = w; a.bias = bias; a.res = res; a.out = y;
   a.a_pitch = x_pitch; a.res_pitch = res_pitch; a.out_pitch = y_pitch;
@@ -1376,6 +1376,7 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         attr = smem;
       }
+      lgm_note_kernel(LGM_KNAME("smalln_yx_lp_kernel<2, 2, 16>"));
       hipLaunchKernelGGL((smalln_yx_lp_kernel<2, 2, 16>), dim3(nbl, 4), dim3(256), smem, (hipStream_t)stream, q, lgc);
       LGM_LAUNCH_CHECK();
       return LGM_OK;
@@ -1383,6 +1384,7 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
     const long npq = q.npix / (g->stride * g->stride);
     const long want = (npq + 4 * (64 / lpp) - 1) / (4 * (64 / lpp));
     const unsigned nb = (unsigned)(want < 1024 ? want : 1024);
+    lgm_note_kernel(LGM_KNAME("smalln_yx_kernel<2, 2>"));
     hipLaunchKernelGGL((smalln_yx_kernel<2, 2>), dim3(nb, g->stride * g->stride), dim3(256), 0, (hipStream_t)stream, q);
     LGM_LAUNCH_CHECK();
     return LGM_OK;
@@ -1892,12 +1894,10 @@ static int conv_wgrad_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch
     if (int rc = lgm_wino_wgrad_launch(g, y, y_pitch, x, x_pitch, a.out, gbias ? 1 : 0, a.slab, a.splits, cpsw, totalw, s))
       return rc;
   } else if (fast3) {
-    lgm_note_kernel(LGM_KNAME("lgm3x3::wgrad3x3_kernel"));
     if (int rc = lgm_wgrad3x3_launch(g, y, y_pitch, x, x_pitch, a.out, a.bias_out, beta, a.slab, a.splits, tps3,
                                      total3, s))
       return rc;
   } else if (fast1) {
-    lgm_note_kernel(LGM_KNAME("wgrad1x1_kernel"));
     if (int rc = lgm_wgrad1x1_launch(g, y, y_pitch, x, x_pitch, a.out, a.bias_out, beta, a.slab, a.splits, per1, s))
       return rc;
   } else {

@@ -72,6 +72,7 @@ def test_label_emb_forward_kernel(dev, B, td):
         for what, y in _label_sets(g, B, K).items():
             temb, st = temb0.to(dev), torch.full((B, td), SENTINEL, device=dev)
             ops.label_emb_fwd(temb, st, embd.data_ptr(), y.to(dev), K)
+            assert ops.lib()._dll.lgm_last_kernel().decode() == "label_emb_fwd_kernel"
             z = temb0.double() + emb[y].double()
             s = z / (1 + (-z).exp())
             assert float(((temb.cpu().double() - z).abs() - U * z.abs()).max()) <= 0, (K, what)
@@ -106,6 +107,7 @@ def test_label_emb_weight_gradient_kernel_is_the_ascending_float32_sum(dev, B, t
                 assert absent.any()
                 out = old.to(dev)
                 ops.label_emb_wgrad(gt.to(dev), y.to(dev), out.data_ptr(), beta, K)
+                assert ops.lib()._dll.lgm_last_kernel().decode() == "label_emb_wgrad_kernel"
                 out = out.cpu()
                 assert torch.equal(out, want), (K, what, beta)
                 assert torch.equal(out[absent], old[absent] * beta), "rows no sample has: exactly beta x the old value"
@@ -126,6 +128,7 @@ def test_cfg_mix_kernel(dev, C):
     for s in (0.0, 1.0, 3.0):
         out = cond.to(dev)
         ops.cfg_mix(out, nd, s, C)
+        assert ops.lib()._dll.lgm_last_kernel().decode() == "cfg_mix_kernel"
         out2 = cond.to(dev)
         ops.cfg_mix(out2, nd, 123.0, C, scale_dev=torch.tensor([s], device=dev))   # the scale a captured step reads
         assert torch.equal(out, out2), "scale from the device buffer: the same bits"

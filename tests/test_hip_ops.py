@@ -58,7 +58,9 @@ def vec(v, dev):
 
 
 CONV_CASES = [
-    # B, H, W, Cin, Cout, k, stride, pad
+    # B, H, W, Cin, Cout, k, stride, pad.  The kernels named are what the direct entry points pick today (no Winograd weights
+    # registered; the weight gradient of a 3x3 layer the direct 3x3 kernels support runs on the Winograd kernels); which
+    # kernel runs is ASSERTED per kernel in tests/test_hip_kernel_ledger.py, not here
     (2, 16, 16, 64, 64, 3, 1, 1),
     (3, 8, 8, 192, 128, 3, 1, 1),
     (2, 32, 32, 3, 64, 7, 1, 3),      # init_conv (padded input channels)
@@ -67,19 +69,19 @@ CONV_CASES = [
     (2, 16, 16, 32, 64, 4, 2, 1),     # strided 4x4 (DCGAN D / VQ-VAE encoder)
     (5, 4, 4, 512, 1, 4, 1, 0),       # DCGAN critic head
     (1, 10, 6, 20, 36, 3, 1, 1),      # ragged sizes
-    (4, 16, 16, 128, 256, 3, 1, 1),   # N > 64: 128-wide tiles
-    (40, 32, 32, 64, 64, 3, 1, 1),    # enough rows for the 128x64 tile
-    (24, 16, 16, 128, 128, 3, 1, 1),  # 128x128 tile
-    (11, 4, 4, 256, 256, 3, 1, 1),    # 3x3 patch kernel: 8 images per tile, ragged batch
+    (4, 16, 16, 128, 256, 3, 1, 1),   # direct 3x3 kernel, four 64-column tiles
+    (40, 32, 32, 64, 64, 3, 1, 1),    # direct 3x3 kernel, 320 tiles of 4 x 32 pixels (F(4x4) weight gradient)
+    (24, 16, 16, 128, 128, 3, 1, 1),  # direct 3x3 kernel, M = 6144 (NOT the 128x128 implicit-GEMM tile)
+    (11, 4, 4, 256, 256, 3, 1, 1),    # 11 images are no whole groups of 8: 64x64 implicit GEMM and generic weight gradient
     (1, 64, 64, 64, 64, 3, 1, 1),     # 3x3 patch kernel: 64x64 images (two column tiles)
-    (5, 8, 8, 96, 64, 3, 1, 1),       # 3x3 patch kernel with 32-channel chunks (C % 64 != 0)
+    (5, 8, 8, 96, 64, 3, 1, 1),       # 5 images are no whole groups of 2: 64x64 implicit GEMM (C % 64 != 0)
     (3, 32, 32, 128, 64, 3, 1, 1),    # 3x3 patch kernel, two channel chunks
-    (13, 32, 32, 64, 384, 1, 1, 0),   # resident-tile 1x1 kernel (to_qkv shape), 128-row tiles, ragged M
-    (50, 16, 16, 384, 128, 1, 1, 0),  # resident-tile 1x1 kernel, 64-row tiles (K = 384)
-    (16, 32, 32, 64, 384, 1, 1, 0),   # streaming 1x1 weight gradient, 128x64 block of gw, three n-tiles
-    (20, 32, 32, 128, 64, 1, 1, 0),   # streaming 1x1 weight gradient, 64x128 block, ragged split
-    (64, 16, 16, 128, 128, 1, 1, 0),  # streaming 1x1 weight gradient, 128x128 block
-    (72, 16, 16, 192, 64, 1, 1, 0),   # streaming 1x1 weight gradient, 64x64 blocks, three k-tiles
+    (13, 32, 32, 64, 384, 1, 1, 0),   # resident-tile 1x1 kernel (to_qkv shape), 104 whole 128-row tiles
+    (50, 16, 16, 384, 128, 1, 1, 0),  # K = 384: 64x64 implicit GEMM forward; input gradient 128x64 tile / resident-tile kernel with w_t
+    (16, 32, 32, 64, 384, 1, 1, 0),   # streaming 1x1 forward (K = 64, 128-column slices) and weight gradient, 128x64 block of gw, three n-tiles
+    (20, 32, 32, 128, 64, 1, 1, 0),   # 64x64 implicit GEMM and generic weight gradient (too few rows for the streaming kernels)
+    (64, 16, 16, 128, 128, 1, 1, 0),  # resident-tile 1x1 kernel with 64-row tiles; generic weight gradient
+    (72, 16, 16, 192, 64, 1, 1, 0),   # streaming 1x1 weight gradient, 64x64 blocks, three k-tiles; 64x64 implicit GEMM forward
     (64, 32, 32, 128, 128, 1, 1, 0),  # resident-weight streaming 1x1 conv, K = 128 (forward and input gradient)
     (48, 32, 32, 192, 128, 1, 1, 0),  # resident-weight streaming 1x1 conv, K = 192
     (64, 32, 32, 256, 64, 1, 1, 0),   # resident-weight streaming 1x1 conv, K = 256 forward, K = 64 input gradient
@@ -87,13 +89,13 @@ CONV_CASES = [
     (64, 32, 32, 64, 64, 1, 1, 0),    # resident-weight streaming 1x1 conv, 64-column slice, K = 64
     # DCGAN critic / generator shapes: uniform-tap chunks (raw buffer loads), residue-class input gradient,
     # shift/mask weight-gradient gather, image-end kernels
-    (3, 64, 64, 3, 64, 4, 2, 1),      # image end: general decode forward, smalln input gradient with 16 lanes per pixel
-    (2, 64, 64, 3, 128, 4, 2, 1),     # image end of the generator: smalln input gradient with 32 lanes per pixel
+    (3, 64, 64, 3, 64, 4, 2, 1),      # image end: general decode forward, lane-pair smalln input gradient (Nw = 64)
+    (2, 64, 64, 3, 128, 4, 2, 1),     # image end of the generator: lane-pair smalln input gradient (Nw = 128)
     (2, 32, 32, 64, 128, 4, 2, 1),
     (5, 16, 16, 128, 256, 4, 2, 1),   # ragged batch
     (1, 8, 8, 256, 512, 4, 2, 1),     # 16 output pixels: one partial pixel chunk in the weight gradient, split-K forward
     (3, 12, 20, 32, 64, 4, 2, 1),     # maps that are not powers of two: uniform taps yes, shift/mask gather no
-    (2, 8, 8, 512, 1024, 4, 2, 1),    # 128-wide column tiles, long reduction
+    (2, 8, 8, 512, 1024, 4, 2, 1),    # 64x64 tiles in 16 column tiles, long reduction (K = 8192)
 ]
 
 
@@ -438,6 +440,7 @@ def test_rmsnorm_and_to_qkv_in_one_launch(dev, case):
     xd, gd, wd = nhwc(x, dev, extra=4), vec(gn, dev), w.contiguous().to(dev)
     r = ops.rms_qkv_fused(xd, gd.data_ptr(), wd.data_ptr(), N, any_size=True)
     assert r is not None
+    assert ops.lib()._dll.lgm_last_kernel().decode() == f"rms_qkv_fused_kernel<{C // 32}>"
     xn, qkv = r
     assert rel(nchw(xn), xn_ref) < RTOL
     assert rel(nchw(qkv), qkv_ref) < RTOL
@@ -475,6 +478,7 @@ def test_linear_attention_forward_with_fused_tail(dev, case):
     y = torch.full((B, H, W, C + 4), float("nan"), device=dev)[..., :C]
     ctx, kstat = ops.linattn_fwd_fused(qd, memd.data_ptr(), heads, d, M, wd.data_ptr(), bd.data_ptr(), gd.data_ptr(), xd,
                                        ao, o2, y)
+    assert ops.lib()._dll.lgm_last_kernel().decode() == f"linattn_out_fused_kernel<{C // 32}>"
     assert rel(nchw(ao), out_ref) < RTOL
     assert rel(nchw(o2), o2_ref) < RTOL
     assert rel(nchw(y), y_ref) < RTOL
@@ -515,6 +519,7 @@ def test_linear_attention_backward_with_fused_tail(dev, case, monkeypatch):
     dw, dm = ([], []) if deferred else (None, None)
     ops.linattn_bwd_fused(qd, memd.data_ptr(), god, ctx, kstat, xd, wd.data_ptr(), heads, d, M, gxn, gw.data_ptr(), 1.0, dw,
                           gm.data_ptr(), 1.0, dm)
+    assert ops.lib()._dll.lgm_last_kernel().decode() == "linattn_bwd_fused_kernel"
     if deferred:
         rows = dw + dm
         assert len(rows) == 2
@@ -823,6 +828,7 @@ def test_vqvae_residual_stack_forward_in_one_launch(dev, B, layers):
     w1d = [b.reshape(C, R).contiguous().to(dev) for b in w1]
     r = ops.resstack_fwd(xd, [t.data_ptr() for t in w3d], [t.data_ptr() for t in w1d], R)
     assert r is not None
+    assert ops.lib()._dll.lgm_last_kernel().decode() == "resstack_fwd_kernel"
     for l in range(layers):
         assert rel(nchw(r[0][l]), ys[l]) < 2e-5, l
         assert rel(nchw(r[1][l]), zs[l]) < 2e-5, l

@@ -125,6 +125,7 @@ def test_estimate_kernel(dev, tables, objective, C):
     td, tbd = t.to(dev), [tables[n].to(dev) for n in TABLES]
     ops.lib().lgm_selfcond_estimate(xin.data_ptr(), pitch, C, 0, vd.data_ptr(), _r4(C), td.data_ptr(),
                                     *[b.data_ptr() for b in tbd], objective, KB, C, KH * KW, 1000, ops.stream())
+    assert ops.lib()._dll.lgm_last_kernel().decode() == "selfcond_estimate_kernel"
     torch.cuda.synchronize()
     _, _, want, m = _predictions64(objective, x, v, t, tables, 0, 0)
     _within(_nchw(xin, 0, C), want, m, "x_start")
@@ -154,6 +155,7 @@ def test_qsample_slice_kernel(dev, tables, objective, with_offset, C):
     L.lgm_qsample_target_slice(imgd.data_ptr(), noised.data_ptr(), offd.data_ptr() if with_offset else None, strength,
                                td.data_ptr(), sad.data_ptr(), sbd.data_ptr(), 1, objective, xin.data_ptr(), pitch, C, 0,
                                tg.data_ptr(), Cp, KB, C, KH * KW, Cp, ops.stream())
+    assert L._dll.lgm_last_kernel().decode() == "qsample_slice_kernel"
     torch.cuda.synchronize()
     assert torch.equal(noised.cpu(), noise), "the kernel must not write the caller's noise"
     s32 = float(torch.tensor(strength, dtype=torch.float32))
@@ -203,6 +205,7 @@ def test_sample_step_slice_kernels(dev, tables, C):
             out = torch.full_like(xin, SENTINEL)
             L.lgm_sample_step_slice(xin.data_ptr(), out.data_ptr(), pitch, C, 0, vd.data_ptr(), _r4(C), nzd.data_ptr(), KB, C,
                                     HW, objective, A, Bv, clip, red, R, Rm1, C0, C1, C2, C3, ops.stream())
+            assert L._dll.lgm_last_kernel().decode() == "sample_step_slice_kernel"
             xi = xin.clone()
             L.lgm_sample_step_table_slice(xi.data_ptr(), pitch, C, 0, vd.data_ptr(), _r4(C), nzd.data_ptr(), KB, C, HW,
                                           table.data_ptr(), counter.data_ptr(), objective, clip, red, 0, ops.stream())

@@ -33,6 +33,7 @@ def test_batched_gemm(dev, M, N, K, batch, parity):
     from lgm_hip import ops
     ops.lib().lgm_weng_gemm(A.data_ptr(), Bm.data_ptr(), C.data_ptr(), M, N, K, K, K, N, batch, M * K, N * K, M * N,
                             ops.stream())
+    assert ops.lib()._dll.lgm_last_kernel().decode().startswith("lgmweng::weng_gemm_kernel<")
     ref = torch.einsum("bmk,bnk->bmn", A.double(), Bm.double())
     parity(f"batched NT GEMM {batch} x [{M} x {K}] [{N} x {K}]^T", rel(C, ref), 2e-6)
 

@@ -41,6 +41,7 @@ def wino(yx, g, a, u, bias, res, out):
     L.lgm_conv3x3_wino(yx, ctypes.byref(g), a.data_ptr(), ops.pitch(a), u.data_ptr(), None if bias is None else bias.data_ptr(),
                        None if res is None else res.data_ptr(), 0 if res is None else ops.pitch(res), out.data_ptr(),
                        ops.pitch(out), None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, ops.stream())
+    assert L._dll.lgm_last_kernel().decode().startswith("lgmwino::wino_conv_kernel<")       # the F(2x2) kernel is the one that ran
     return n
 
 
