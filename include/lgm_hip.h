@@ -385,8 +385,7 @@ int lgm_nchw_to_nhwc(const float* src, float* dst, int64_t dst_pitch, int B, int
 int lgm_nhwc_to_nchw(const float* src, int64_t src_pitch, float* dst, int B, int C, int HW,
                      void* stream);
 
-/* Diffusion training elementwise: GaussianDiffusion.forward/q_sample/predict_v
- * ddpm.py:945, 869-876, 684-688.  img, noise: NCHW dense; xt, target: NHWC pitch (pad zeroed). */
+/* lgm_qsample_target_slice with one slice (x_off 0, no sc slice, Cpad lanes), pred_v, no offset noise; kept for ABI 7 */
 int lgm_qsample_target(const float* img, const float* noise, const int64_t* t, const float* sqrt_ac,
                        const float* sqrt_1mac, int normalize, float* xt, float* target,
                        int64_t pitch, int B, int C, int HW, int Cpad, void* stream);
@@ -423,72 +422,74 @@ int lgm_time_mlp_bwd(const float* gst, const float* pe, const float* a1, const f
 int lgm_extract_axpby(const float* ta, const float* tb, const float* td, const int64_t* t, const float* x,
                       const float* y, float sb, int clip, float* out, int B, int64_t per_sample, int n_table,
                       void* stream);
-/* model_predictions ddpm.py:707-734, pred_v branch, in one pass over dense NCHW tensors with a per-sample t:
- *   x_start = maybe_clip(sqrt_ac[t] * x - sqrt_1mac[t] * v) ;  pred_noise = (sqrt_recip[t] * x - x_start) / sqrt_recipm1[t] */
+/* lgm_model_predictions_obj at objective 2 (pred_v); kept for ABI 7 */
 int lgm_model_predictions(const float* x, const float* v, const int64_t* t, const float* sqrt_ac,
                           const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1, int clip,
                           float* pred_noise, float* x_start, int B, int64_t per_sample, int n_table, void* stream);
 
-/* One reverse-diffusion update at a shared timestep (model_predictions ddpm.py:707-734 pred_v branch,
- * p_sample :748-757, ddim_sample loop body :805-829):
- *   x0 = clamp(A*x + Bv*v) ; eps = (R*x - x0)/Rm1 ; out = C0*x0 + C1*x + C2*eps + C3*noise
- * x, v, out, x0_out: dense NHWC with Cpad channels; noise: NCHW dense or NULL. */
+/* lgm_sample_step_slice with one slice of pitch Cpad (x, v, out, x0_out dense NHWC), pred_v, and the optional x0_out (the
+ * clipped x0, pad lanes zero); kept for ABI 7 */
 int lgm_sample_step(const float* x, const float* v, const float* noise, float* out, float* x0_out,
                     int B, int C, int HW, int Cpad, float A, float Bv, int clip, float R, float Rm1,
                     float C0, float C1, float C2, float C3, void* stream);
 
-/* The same update for a HIP-graph-replayed chain (p_sample_loop ddpm.py:759-780, ddim_sample :782-834 without the
- * per-step host round trip :775,829): scalars from row counter[0] of table[n_steps][8] = (A, Bv, R, Rm1, C0, C1, C2,
- * C3), x updated IN PLACE; lgm_sampler_time writes t[b] = ttable[counter[0]] for the UNet forward of the step;
- * advance != 0 appends counter[0] += 1 (the last node of a step). */
+/* A HIP-graph-replayed chain (p_sample_loop ddpm.py:759-780, ddim_sample :782-834 without the per-step host round trip
+ * :775,829): lgm_sampler_time writes t[b] = ttable[counter[0]] for the UNet forward of the step.
+ * lgm_sample_step_table: lgm_sample_step_table_slice with one slice of pitch Cpad, pred_v, optional x0_out; kept for ABI 7 */
 int lgm_sampler_time(const int64_t* ttable, const int32_t* counter, int64_t* t, int B, void* stream);
 int lgm_sample_step_table(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
                           int Cpad, const float* table, const int32_t* counter, int clip, int advance,
                           void* stream);
 
-/* The four diffusion entry points above for every objective GaussianDiffusion accepts (ddpm.py:562):
- * objective 0 = pred_noise, 1 = pred_x0, 2 = pred_v (same bits as the entry points above; the pred_v configuration keeps
- * calling those).  `out` / `v` is the raw network output.
- *
- * lgm_qsample_target_obj: lgm_qsample_target with the objective's target (ddpm.py:911-917: the noise, the normalised
- * x_start, or v) and offset noise (:889-891): offset [B*C] or NULL, n = noise + strength * offset[b*C+c], used for x_t AND
- * for the target. */
+/* lgm_qsample_target_slice with one slice (x_off 0, no sc slice, Cpad lanes; xt and target share `pitch`); kept for ABI 7 */
 int lgm_qsample_target_obj(const float* img, const float* noise, const float* offset, float strength,
                            const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
                            int objective, float* xt, float* target, int64_t pitch, int B, int C, int HW, int Cpad,
                            void* stream);
-/* model_predictions ddpm.py:707-734, all three branches:
+/* model_predictions ddpm.py:707-734 in one pass over dense NCHW tensors with a per-sample t; `out` is the raw network
+ * output, objective 0 = pred_noise, 1 = pred_x0, 2 = pred_v (ddpm.py:562):
  *   pred_noise: x_start = maybe_clip(sqrt_recip[t] * x - sqrt_recipm1[t] * out); pred_noise = out, or re-derived from the
  *               clipped x_start as below when clip AND rederive are set (:720-721)
  *   pred_x0   : x_start = maybe_clip(out);  pred_noise = (sqrt_recip[t] * x - x_start) / sqrt_recipm1[t]
- *   pred_v    : as lgm_model_predictions (rederive has no effect) */
+ *   pred_v    : x_start = maybe_clip(sqrt_ac[t] * x - sqrt_1mac[t] * out);  pred_noise as for pred_x0 (rederive has no
+ *               effect)
+ * Launches model_predictions_obj_kernel. */
 int lgm_model_predictions_obj(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
                               const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
                               int objective, int clip, int rederive, float* pred_noise, float* x_start, int B,
                               int64_t per_sample, int n_table, void* stream);
-/* lgm_sample_step / lgm_sample_step_table with (x0, eps) from the objective's branch of model_predictions; same scalars,
- * same table layout [n_steps][8].  p_sample passes clip only, ddim_sample clip and rederive. */
+/* lgm_sample_step_slice with one slice of pitch Cpad and the optional x0_out; kept for ABI 7 */
 int lgm_sample_step_obj(const float* x, const float* v, const float* noise, float* out, float* x0_out, int B,
                         int C, int HW, int Cpad, int objective, float A, float Bv, int clip, int rederive,
                         float R, float Rm1, float C0, float C1, float C2, float C3, void* stream);
+/* lgm_sample_step_table_slice with one slice of pitch Cpad and the optional x0_out; kept for ABI 7 */
 int lgm_sample_step_table_obj(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
                               int Cpad, const float* table, const int32_t* counter, int objective, int clip,
                               int rederive, int advance, void* stream);
 
-/* Self-conditioning (ddpm.py:428-435, 899-909).  A self-conditioned UNet reads ONE NHWC input buffer [B, HW, pitch] with
- * pitch = r4(2 C): lanes [sc_off, sc_off + C) = x_self_cond (sc_off = 0), lanes [x_off, x_off + C) = x (x_off = C) - the order
- * of cat((x_self_cond, x), dim=1) - and zeros in the remaining lanes.  These entry points produce the two slices in place of
- * a concat tensor; loads and stores are scalar, so the slices need no float4 alignment (C = 3: lanes 0 and 3 of 8).
- * sc_off < 0 means "no self-conditioning slice": with pitch = r4(C) and x_off = 0 the *_slice entry points give the bits of
- * the entry points above (objective 2: of the pred_v ones too).  `out` / `v` is the network output [B, HW, out_pitch].
+/* The diffusion elementwise ops on the network's input buffer.  A self-conditioned UNet (ddpm.py:428-435, 899-909) reads ONE
+ * NHWC input buffer [B, HW, pitch] with pitch = r4(2 C): lanes [sc_off, sc_off + C) = x_self_cond (sc_off = 0), lanes
+ * [x_off, x_off + C) = x (x_off = C) - the order of cat((x_self_cond, x), dim=1) - and zeros in the remaining lanes.  These
+ * entry points produce the two slices in place of a concat tensor; loads and stores are scalar, so the slices need no float4
+ * alignment (C = 3: lanes 0 and 3 of 8).  sc_off < 0 means "no self-conditioning slice": any other network, with
+ * pitch = r4(C) and x_off = 0.  `out` / `v` is the raw network output [B, HW, out_pitch]; objective as above.
  *
  * lgm_selfcond_estimate: xin[sc slice] = unclipped x_start of model_predictions (objective's branch) from xin[x slice] and
- *   `out`, per-sample t.  The x slice and the padding are not written.
- * lgm_qsample_target_slice: lgm_qsample_target_obj with x_t into the x slice, zeros into the self-conditioning slice and the
- *   padding; target [B, HW, target_pitch] with Cpad lanes written, as before (may be NULL).
- * lgm_sample_step_slice / lgm_sample_step_table_slice: lgm_sample_step_obj / lgm_sample_step_table_obj reading x from the x
- *   slice of xin, writing the next x into the x slice of xout (xout may be xin; the table form is in place), the x0 the
- *   reference hands to the next step (clipped when clip is set) into xout's self-conditioning slice, zeros into its padding. */
+ *   `out`, per-sample t.  The x slice and the padding are not written.  Launches selfcond_estimate_kernel.
+ * lgm_qsample_target_slice (GaussianDiffusion.forward / q_sample / predict_v ddpm.py:945, 869-876, 684-688; img, noise NCHW
+ *   dense): x0 = img*2-1 when normalize; n = noise + strength * offset[b*C+c] (offset noise :889-891, offset [B*C] or NULL),
+ *   used for x_t AND for the target; x_t = sqrt_ac[t]*x0 + sqrt_1mac[t]*n into the x slice, zeros into the self-conditioning
+ *   slice and the padding; the objective's target (:911-917: n, x0, or v = sqrt_ac[t]*n - sqrt_1mac[t]*x0) into target
+ *   [B, HW, target_pitch] with Cpad lanes written (may be NULL).  Launches qsample_slice_kernel.
+ * lgm_sample_step_slice: one reverse-diffusion update at a shared timestep (p_sample :748-757, ddim_sample loop body
+ *   :805-829), with (x0, eps) = model_predictions' branch from (A, -Bv, R, Rm1) = (sqrt_ac, sqrt_1mac, sqrt_recip,
+ *   sqrt_recipm1)[t] (p_sample passes clip only, ddim_sample clip and rederive):
+ *     out = C0*x0 + C1*x + C2*eps + C3*noise            (noise: NCHW dense or NULL)
+ *   x from the x slice of xin, the next x into the x slice of xout (xout may be xin), the x0 the reference hands to the next
+ *   step (clipped when clip is set) into xout's self-conditioning slice, zeros into its padding.
+ * lgm_sample_step_table_slice: the same IN PLACE with the scalars from row counter[0] of table[n_steps][8] = (A, Bv, R, Rm1,
+ *   C0, C1, C2, C3); advance != 0 appends counter[0] += 1 (the last node of a graph-replayed step).
+ *   Both launch sample_step_slice_kernel. */
 int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int sc_off, const float* out, int64_t out_pitch,
                           const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip,
                           const float* sqrt_recipm1, int objective, int B, int C, int HW, int n_table, void* stream);

@@ -353,36 +353,8 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------
-// Diffusion training elementwise (ddpm.py:869-876, 684-688, 945):
-//   x0 = img*2-1 (auto_normalize) ; x_t = sa[t]*x0 + sb[t]*noise ; v = sa[t]*noise - sb[t]*x0
-// img/noise NCHW dense [B,C,HW]; outputs NHWC with pitch (pad channels zeroed).
+// Diffusion training loss (ddpm.py:921-925, 945); q_sample and the objective's target are further down
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void qsample_kernel(const float* __restrict__ img, const float* __restrict__ noise,
-                                                      const int64_t* __restrict__ t, const float* __restrict__ sa,
-                                                      const float* __restrict__ sb, int normalize,
-                                                      float* __restrict__ xt, float* __restrict__ target, long pitch,
-                                                      int B, int C, int HW, int Cpad) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)B * HW * Cpad;
-  if (i >= total) return;
-  const int c = (int)(i % Cpad);
-  const long pix = i / Cpad;
-  const int b = (int)(pix / HW);
-  const int p = (int)(pix % HW);
-  float xv = 0.f, tv = 0.f;
-  if (c < C) {
-    const long s = ((long)b * C + c) * HW + p;
-    float x0 = img[s];
-    if (normalize) x0 = x0 * 2.f - 1.f;
-    const float n = noise[s];
-    const float a = sa[t[b]], bb = sb[t[b]];
-    xv = a * x0 + bb * n;
-    tv = a * n - bb * x0;
-  }
-  xt[pix * pitch + c] = xv;
-  if (target) target[pix * pitch + c] = tv;
-}
-
 // per-sample weighted MSE (ddpm.py:921-925): loss = mean_b( w[t_b] * mean_{chw} (out-target)^2 )
 // stage 1: one block per sample -> per-sample value; stage 2: one block -> scalar.  Also emits
 // gout = gscale * 2 * w[t_b] * (out - target) / (C*HW*B) when gout != null (gscale read from device).
@@ -462,46 +434,6 @@ __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ 
   gout[pix * pitch + c] = g;
 }
 
-
-// One reverse-diffusion update for a whole batch at a shared timestep (ddpm.py:707-757, 805-829):
-//   x0  = clamp(A*x + Bv*v, -1, 1)            (predict_start_from_v + clip)
-//   eps = (R*x - x0) / Rm1                    (predict_noise_from_start)
-//   out = C0*x0 + C1*x + C2*eps + C3*noise
-// x, v: NHWC pitch Cpad; noise: NCHW dense (or null); out: NHWC pitch Cpad; x0_out optional.
-// one update of one element; contraction off so that the by-value and the table-driven kernel round identically
-__device__ __forceinline__ void sample_update(float xv, float vv, float nz, float A, float Bv, int clip, float R,
-                                              float Rm1, float C0, float C1, float C2, float C3, float& o, float& x0) {
-#pragma clang fp contract(off)
-  x0 = A * xv + Bv * vv;
-  if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-  const float eps = (R * xv - x0) / Rm1;
-  o = C0 * x0 + C1 * xv + C2 * eps;
-  if (C3 != 0.f) o += C3 * nz;
-}
-
-__global__ __launch_bounds__(256) void sample_step_kernel(const float* __restrict__ x, const float* __restrict__ v,
-                                                          const float* __restrict__ noise, float* __restrict__ out,
-                                                          float* __restrict__ x0_out, int B, int C, int HW, int Cpad,
-                                                          float A, float Bv, int clip, float R, float Rm1, float C0,
-                                                          float C1, float C2, float C3) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)B * HW * Cpad;
-  if (i >= total) return;
-  const int c = (int)(i % Cpad);
-  const long pix = i / Cpad;
-  float o = 0.f, x0 = 0.f;
-  if (c < C) {
-    float nz = 0.f;
-    if (noise && C3 != 0.f) {
-      const int b = (int)(pix / HW), p = (int)(pix % HW);
-      nz = noise[((long)b * C + c) * HW + p];
-    }
-    sample_update(x[i], v[i], nz, A, Bv, clip, R, Rm1, C0, C1, C2, noise ? C3 : 0.f, o, x0);
-  }
-  out[i] = o;
-  if (x0_out) x0_out[i] = x0;
-}
-
 // GaussianDiffusion's `extract(table, t, shape) * tensor` algebra with a PER-SAMPLE timestep (ddpm.py:673-705, 869-876) on
 // dense NCHW tensors: one thread per element, the three table values of the sample are wave-uniform loads.  Contraction is
 // off: the reference rounds both products and the sum separately.  A timestep outside the table is clamped to it (the
@@ -527,67 +459,24 @@ __global__ __launch_bounds__(256) void extract_axpby_kernel(const float* __restr
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (long)gridDim.x * blockDim.x)
     out[base + i] = extract_axpby_one(a, bb, d, x[base + i], y ? y[base + i] : 0.f, clip);
 }
-__global__ __launch_bounds__(256) void model_predictions_kernel(const float* __restrict__ x, const float* __restrict__ v,
-                                                                const long* __restrict__ t, const float* __restrict__ sa,
-                                                                const float* __restrict__ s1, const float* __restrict__ r,
-                                                                const float* __restrict__ rm1, int clip,
-                                                                float* __restrict__ pn, float* __restrict__ xs, long per,
-                                                                int n_table) {
-#pragma clang fp contract(off)
-  const int b = blockIdx.y;
-  long ti = t[b];
-  ti = ti < 0 ? 0 : (ti >= n_table ? n_table - 1 : ti);
-  const float A = sa[ti], S = s1[ti], R = r[ti], Rm1 = rm1[ti];
-  const long base = (long)b * per;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (long)gridDim.x * blockDim.x) {
-    const float xv = x[base + i];
-    float x0 = A * xv - S * v[base + i];
-    if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-    xs[base + i] = x0;
-    pn[base + i] = (R * xv - x0) / Rm1;
-  }
-}
-
 // Graph-replayed sampling (lgm_hip/sampler.py): the per-step scalars come from a device table indexed by a
 // device-side step counter, so ONE captured graph serves every step of a chain.
-//   sampler_time_kernel : t[b] = ttable[counter]                              (before the UNet forward)
-//   sample_step_table   : sample_step with row `counter` of table[n][8] = (A, Bv, R, Rm1, C0, C1, C2, C3), in place
-//   sampler_advance     : counter += 1                                        (last node of the graph)
+//   sampler_time_kernel      : t[b] = ttable[counter]                         (before the UNet forward)
+//   sample_step_slice_kernel : row `counter` of table[n][8] = (A, Bv, R, Rm1, C0, C1, C2, C3), in place
+//   sampler_advance_kernel   : counter += 1                                   (last node of the graph)
 __global__ void sampler_time_kernel(const long* __restrict__ ttable, const int* __restrict__ counter,
                                     long* __restrict__ t, int B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B) t[i] = ttable[counter[0]];
 }
-__global__ __launch_bounds__(256) void sample_step_table_kernel(float* __restrict__ x, const float* __restrict__ v,
-                                                                const float* __restrict__ noise,
-                                                                float* __restrict__ x0_out, int B, int C, int HW,
-                                                                int Cpad, const float* __restrict__ table,
-                                                                const int* __restrict__ counter, int clip) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)B * HW * Cpad;
-  if (i >= total) return;
-  const float* row = table + 8 * counter[0];
-  const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], C0 = row[4], C1 = row[5], C2 = row[6], C3 = row[7];
-  const int c = (int)(i % Cpad);
-  const long pix = i / Cpad;
-  float o = 0.f, x0 = 0.f;
-  if (c < C) {
-    float nz = 0.f;
-    if (noise && C3 != 0.f) {
-      const int b = (int)(pix / HW), p = (int)(pix % HW);
-      nz = noise[((long)b * C + c) * HW + p];
-    }
-    sample_update(x[i], v[i], nz, A, Bv, clip, R, Rm1, C0, C1, C2, noise ? C3 : 0.f, o, x0);
-  }
-  x[i] = o;
-  if (x0_out) x0_out[i] = x0;
-}
 __global__ void sampler_advance_kernel(int* counter) { counter[0] += 1; }
 
 // ---------------------------------------------------------------------------------------
-// The same four kernels for every objective GaussianDiffusion accepts (ddpm.py:562): objective 0 = pred_noise (the network
-// predicts eps), 1 = pred_x0 (it predicts the image), 2 = pred_v.  The pred_v configuration keeps the kernels above; with
-// objective 2 these give the same bits (tests/test_hip_objectives.py).
+// Diffusion elementwise (ddpm.py:869-876, 684-688, 707-757, 805-829) for every objective GaussianDiffusion accepts
+// (ddpm.py:562): objective 0 = pred_noise (the network predicts eps), 1 = pred_x0 (it predicts the image), 2 = pred_v.
+//   q_sample + target : x0 = img*2-1 (auto_normalize) ; x_t = sa[t]*x0 + sb[t]*noise ; v = sa[t]*noise - sb[t]*x0
+//   reverse update    : (x0, eps) = model_predictions(x, network output) ; out = C0*x0 + C1*x + C2*eps + C3*noise
+// img / noise NCHW dense [B,C,HW]; the network's buffers NHWC with a pitch, pad lanes written as zero.
 // ---------------------------------------------------------------------------------------
 // offset noise (ddpm.py:889-891, `noise += strength * offset[b, c]`): product and sum rounded separately, like the two
 // ATen operations of the reference
@@ -596,46 +485,13 @@ __device__ __forceinline__ float offset_noise_one(float n, float strength, float
   const float d = strength * off;
   return n + d;
 }
-// x_t as the reference's q_sample rounds it (two products, one sum) and v with the one fused multiply-add qsample_kernel's
-// `a * n - bb * x0` compiles to, spelled out so that objective 2 gives that kernel's bits whatever the optimiser does here.
-// qsample_kernel has no contraction pragma, so that fusion is the compiler's choice: the bit-equality test of objective 2
-// (tests/test_hip_objectives.py) guards that choice; no product path depends on it, pred_v keeps calling qsample_kernel.
+// x_t as the reference's q_sample rounds it (two products, one sum) and v with one fused multiply-add, spelled out so that
+// the bits do not depend on what the optimiser does here
 __device__ __forceinline__ void qsample_one(float a, float bb, float x0, float n, float& xt, float& v) {
 #pragma clang fp contract(off)
   xt = a * x0 + bb * n;
   v = fmaf(a, n, -(bb * x0));
 }
-// qsample_kernel with the target of the objective (ddpm.py:911-917) and the optional offset noise; the offset noise goes
-// into x_t AND into the target, as in the reference (it is added before q_sample)
-__global__ __launch_bounds__(256) void qsample_obj_kernel(const float* __restrict__ img, const float* __restrict__ noise,
-                                                          const float* __restrict__ offset, float strength,
-                                                          const int64_t* __restrict__ t, const float* __restrict__ sa,
-                                                          const float* __restrict__ sb, int normalize, int objective,
-                                                          float* __restrict__ xt, float* __restrict__ target, long pitch,
-                                                          int B, int C, int HW, int Cpad) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)B * HW * Cpad;
-  if (i >= total) return;
-  const int c = (int)(i % Cpad);
-  const long pix = i / Cpad;
-  const int b = (int)(pix / HW);
-  const int p = (int)(pix % HW);
-  float xv = 0.f, tv = 0.f;
-  if (c < C) {
-    const long s = ((long)b * C + c) * HW + p;
-    float x0 = img[s];
-    if (normalize) x0 = x0 * 2.f - 1.f;
-    float n = noise[s];
-    if (offset) n = offset_noise_one(n, strength, offset[(long)b * C + c]);
-    const float a = sa[t[b]], bb = sb[t[b]];
-    float v;
-    qsample_one(a, bb, x0, n, xv, v);
-    tv = objective == 0 ? n : (objective == 1 ? x0 : v);
-  }
-  xt[pix * pitch + c] = xv;
-  if (target) target[pix * pitch + c] = tv;
-}
-
 // model_predictions ddpm.py:707-734, all three branches, from the network output `out` and the head (A, S, R, Rm1) =
 // (sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1)[t].  pred_noise keeps the RAW network output unless clip and rederive are
 // both set (:720-721).  Contraction off: the reference rounds every product and sum separately.  Written with selects on
@@ -669,8 +525,8 @@ __global__ __launch_bounds__(256) void model_predictions_obj_kernel(const float*
   }
 }
 
-// sample_update for the three objectives: the head (A, Bv, R, Rm1) of the coefficient row is the one the pred_v kernels
-// take (Bv = -sqrt_1mac[t]); pred_noise reads (R, Rm1), pred_x0 reads them for eps only
+// one reverse-diffusion update of one element: head (A, Bv, R, Rm1) of the coefficient row with Bv = -sqrt_1mac[t]; pred_v
+// reads all four, pred_noise reads (R, Rm1), pred_x0 reads them for eps only
 __device__ __forceinline__ void sample_update_obj(int objective, float xv, float ov, float nz, float A, float Bv, int clip,
                                                   int rederive, float R, float Rm1, float C0, float C1, float C2,
                                                   float C3, float& o, float& x0) {
@@ -680,62 +536,14 @@ __device__ __forceinline__ void sample_update_obj(int objective, float xv, float
   o = C0 * x0 + C1 * xv + C2 * eps;
   if (C3 != 0.f) o += C3 * nz;
 }
-__global__ __launch_bounds__(256) void sample_step_obj_kernel(const float* __restrict__ x, const float* __restrict__ v,
-                                                              const float* __restrict__ noise, float* __restrict__ out,
-                                                              float* __restrict__ x0_out, int B, int C, int HW, int Cpad,
-                                                              int objective, float A, float Bv, int clip, int rederive,
-                                                              float R, float Rm1, float C0, float C1, float C2, float C3) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)B * HW * Cpad;
-  if (i >= total) return;
-  const int c = (int)(i % Cpad);
-  const long pix = i / Cpad;
-  float o = 0.f, x0 = 0.f;
-  if (c < C) {
-    float nz = 0.f;
-    if (noise && C3 != 0.f) {
-      const int b = (int)(pix / HW), p = (int)(pix % HW);
-      nz = noise[((long)b * C + c) * HW + p];
-    }
-    sample_update_obj(objective, x[i], v[i], nz, A, Bv, clip, rederive, R, Rm1, C0, C1, C2, noise ? C3 : 0.f, o, x0);
-  }
-  out[i] = o;
-  if (x0_out) x0_out[i] = x0;
-}
-__global__ __launch_bounds__(256) void sample_step_table_obj_kernel(float* __restrict__ x, const float* __restrict__ v,
-                                                                    const float* __restrict__ noise,
-                                                                    float* __restrict__ x0_out, int B, int C, int HW,
-                                                                    int Cpad, const float* __restrict__ table,
-                                                                    const int* __restrict__ counter, int objective,
-                                                                    int clip, int rederive) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)B * HW * Cpad;
-  if (i >= total) return;
-  const float* row = table + 8 * counter[0];
-  const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], C0 = row[4], C1 = row[5], C2 = row[6], C3 = row[7];
-  const int c = (int)(i % Cpad);
-  const long pix = i / Cpad;
-  float o = 0.f, x0 = 0.f;
-  if (c < C) {
-    float nz = 0.f;
-    if (noise && C3 != 0.f) {
-      const int b = (int)(pix / HW), p = (int)(pix % HW);
-      nz = noise[((long)b * C + c) * HW + p];
-    }
-    sample_update_obj(objective, x[i], v[i], nz, A, Bv, clip, rederive, R, Rm1, C0, C1, C2, noise ? C3 : 0.f, o, x0);
-  }
-  x[i] = o;
-  if (x0_out) x0_out[i] = x0;
-}
-
 // ---------------------------------------------------------------------------------------
 // Self-conditioning (ddpm.py:428-435, 899-909): the UNet reads ONE NHWC input buffer [B, HW, pitch] whose lanes
 // [sc_off, sc_off + C) hold x_self_cond and [x_off, x_off + C) hold x (cat((x_self_cond, x), dim=1): sc_off = 0, x_off = C,
 // pitch = r4(2 C)); every other lane is padding and stays zero.  The kernels below are the producers of those two slices.
 // With C = 3 the slices start at lanes 0 and 3 of a pitch of 8: scalar loads and stores only, nothing assumes float4
 // alignment.  One thread per (pixel, lane); the lanes c < C do the arithmetic of channel c and write BOTH slices, the others
-// write the zeros of the padding they sit on (or nothing).  sc_off < 0: no self-conditioning slice (pitch = r4(C), x_off = 0:
-// the layout and the bits of the kernels above).
+// write the zeros of the padding they sit on (or nothing).  sc_off < 0: no self-conditioning slice (a network without
+// self-conditioning: pitch = r4(C), x_off = 0).
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ bool slice_pad_lane(int lane, int x_off, int sc_off, int C) {
   return !(lane >= x_off && lane < x_off + C) && !(sc_off >= 0 && lane >= sc_off && lane < sc_off + C);
@@ -759,8 +567,9 @@ __global__ __launch_bounds__(256) void selfcond_estimate_kernel(float* __restric
                   x0);
   xin[pix * pitch + sc_off + c] = x0;
 }
-// qsample_obj_kernel writing x_t into the x slice and zeros into the self-conditioning slice and the padding; the target
-// buffer (pitch tpitch, tCpad lanes written) as before
+// q_sample with the target of the objective (ddpm.py:911-917) and the optional offset noise, which goes into x_t AND into
+// the target as in the reference (it is added before q_sample).  x_t into the x slice, zeros into the self-conditioning
+// slice and the padding: `lanes` lanes of the pitch are written; the target buffer has pitch tpitch, tCpad lanes written
 __global__ __launch_bounds__(256) void qsample_slice_kernel(const float* __restrict__ img, const float* __restrict__ noise,
                                                             const float* __restrict__ offset, float strength,
                                                             const int64_t* __restrict__ t, const float* __restrict__ sa,
@@ -791,35 +600,37 @@ __global__ __launch_bounds__(256) void qsample_slice_kernel(const float* __restr
   }
   if (slice_pad_lane(c, x_off, sc_off, C)) xin[pix * pitch + c] = 0.f;
 }
-// sample_step_obj_kernel / sample_step_table_obj_kernel over the slices: x from the x slice of `xin`, the next x into the x
-// slice of `xout` (xout == xin: in place - a thread reads and writes its own lanes only), x0 as the reference hands it on
-// (clipped where it clips) into the self-conditioning slice of `xout`, zeros into xout's padding.  table == null: the scalars
-// by value in `row`.
+// The reverse update for a whole batch at a shared timestep: x from the x slice of `xin`, the next x into the x slice of
+// `xout` (xout == xin: in place - a thread reads and writes its own lanes only), x0 as the reference hands it on (clipped
+// where it clips) into the self-conditioning slice of `xout` and, when x0_out is given, into lanes [0, C) of that buffer
+// (its other lanes zero); zeros into xout's padding.  table == null: the scalars by value in `byval`.
 struct SampleRow { float v[8]; };
 __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin, float* xout, long pitch, int lanes, int x_off,
                                                                 int sc_off, const float* __restrict__ v, long v_pitch,
                                                                 const float* __restrict__ noise, int B, int C, int HW,
                                                                 SampleRow byval, const float* __restrict__ table,
                                                                 const int* __restrict__ counter, int objective, int clip,
-                                                                int rederive) {
+                                                                int rederive, float* __restrict__ x0_out, long x0_pitch) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)B * HW * lanes) return;
   const float* row = table ? table + 8 * counter[0] : byval.v;
   const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], C0 = row[4], C1 = row[5], C2 = row[6], C3 = row[7];
   const int c = (int)(i % lanes);
   const long pix = i / lanes;
+  float x0 = 0.f;
   if (c < C) {
     float nz = 0.f;
     if (noise && C3 != 0.f) {
       const int b = (int)(pix / HW), p = (int)(pix % HW);
       nz = noise[((long)b * C + c) * HW + p];
     }
-    float o, x0;
+    float o;
     sample_update_obj(objective, xin[pix * pitch + x_off + c], v[pix * v_pitch + c], nz, A, Bv, clip, rederive, R, Rm1, C0,
                       C1, C2, noise ? C3 : 0.f, o, x0);
     xout[pix * pitch + x_off + c] = o;
     if (sc_off >= 0) xout[pix * pitch + sc_off + c] = x0;
   }
+  if (x0_out) x0_out[pix * x0_pitch + c] = x0;
   if (slice_pad_lane(c, x_off, sc_off, C)) xout[pix * pitch + c] = 0.f;
 }
 
@@ -1098,19 +909,6 @@ extern "C" int lgm_extract_axpby(const float* ta, const float* tb, const float* 
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
-extern "C" int lgm_model_predictions(const float* x, const float* v, const int64_t* t, const float* sqrt_ac,
-                                     const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1, int clip,
-                                     float* pred_noise, float* x_start, int B, int64_t per_sample, int n_table,
-                                     void* stream) {
-  LGM_REQUIRE(x && v && t && sqrt_ac && sqrt_1mac && sqrt_recip && sqrt_recipm1 && pred_noise && x_start && B > 0 &&
-                  B <= 65535 && per_sample > 0 && n_table > 0,
-              "model_predictions: bad arguments");
-  const int gx = (int)(per_sample < 256L * 4096 ? lgm_cdiv(per_sample, 256) : 4096);
-  hipLaunchKernelGGL(model_predictions_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, v, (const long*)t,
-                     sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, clip, pred_noise, x_start, (long)per_sample, n_table);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
-}
 static bool tm_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static bool tm_dims_ok(int dim, int td) {
   // K / 4 lanes per weight row must be a power of two <= 64, or K a multiple of 256 up to 1024
@@ -1147,16 +945,6 @@ extern "C" int lgm_sampler_time(const int64_t* ttable, const int32_t* counter, i
   LGM_REQUIRE(ttable && counter && t && B > 0, "sampler_time: bad arguments");
   hipLaunchKernelGGL(sampler_time_kernel, dim3(lgm_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const long*)ttable, (const int*)counter, (long*)t, B);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
-}
-extern "C" int lgm_sample_step_table(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
-                                     int Cpad, const float* table, const int32_t* counter, int clip, int advance,
-                                     void* stream) {
-  LGM_REQUIRE(x && v && table && counter && B > 0 && C > 0 && HW > 0 && Cpad >= C, "sample_step_table: bad arguments");
-  hipLaunchKernelGGL(sample_step_table_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0,
-                     (hipStream_t)stream, x, v, noise, x0_out, B, C, HW, Cpad, table, (const int*)counter, clip);
-  if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1256,17 +1044,6 @@ extern "C" int lgm_nhwc_to_nchw(const float* src, int64_t src_pitch, float* dst,
   LGM_REQUIRE(src && dst && B > 0 && C > 0 && HW > 0 && src_pitch >= C, "nhwc_to_nchw: bad arguments");
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(lgm_cdiv((long)B * C * HW, 256)), dim3(256), 0, (hipStream_t)stream, src,
                      (long)src_pitch, dst, B, C, HW);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
-}
-
-extern "C" int lgm_qsample_target(const float* img, const float* noise, const int64_t* t, const float* sqrt_ac,
-                                  const float* sqrt_1mac, int normalize, float* xt, float* target, int64_t pitch,
-                                  int B, int C, int HW, int Cpad, void* stream) {
-  LGM_REQUIRE(img && noise && t && sqrt_ac && sqrt_1mac && xt && B > 0 && C > 0 && HW > 0 && Cpad >= C && pitch >= Cpad,
-              "qsample_target: bad arguments");
-  hipLaunchKernelGGL(qsample_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, img,
-                     noise, t, sqrt_ac, sqrt_1mac, normalize, xt, target, (long)pitch, B, C, HW, Cpad);
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1402,18 +1179,39 @@ extern "C" int lgm_weighted_mse_bwd(const float* out, const float* target, int64
   return LGM_OK;
 }
 
-extern "C" int lgm_sample_step(const float* x, const float* v, const float* noise, float* out, float* x0_out, int B,
-                               int C, int HW, int Cpad, float A, float Bv, int clip, float R, float Rm1, float C0,
-                               float C1, float C2, float C3, void* stream) {
-  LGM_REQUIRE(x && v && out && B > 0 && C > 0 && HW > 0 && Cpad >= C, "sample_step: bad arguments");
-  hipLaunchKernelGGL(sample_step_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     v, noise, out, x0_out, B, C, HW, Cpad, A, Bv, clip, R, Rm1, C0, C1, C2, C3);
-  LGM_LAUNCH_CHECK();
+// ---------------------------------------------------------------------------------------
+// Diffusion elementwise entry points: one launcher per op.  The *_slice forms take the network's input buffer as it is
+// (pitch, x slice, optional self-conditioning slice); the plain and *_obj forms are the same launch on a buffer of one
+// slice (x_off = 0, sc_off = -1, Cpad lanes), the plain ones at objective 2 (pred_v) without offset noise.
+// ---------------------------------------------------------------------------------------
+static bool objective_ok(int objective) { return objective >= 0 && objective <= 2; }
+// The two slices lie inside the pitch and do not overlap; sc_off < 0 = no self-conditioning slice.
+static bool slices_ok(int64_t pitch, int x_off, int sc_off, int C) {
+  if (C <= 0 || x_off < 0 || x_off + C > pitch) return false;
+  if (sc_off < 0) return true;
+  return sc_off + C <= pitch && (sc_off + C <= x_off || x_off + C <= sc_off);
+}
+
+static int qsample_slice_launch(const float* img, const float* noise, const float* offset, float strength, const int64_t* t,
+                                const float* sqrt_ac, const float* sqrt_1mac, int normalize, int objective, float* xin,
+                                int64_t pitch, int lanes, int x_off, int sc_off, float* target, int64_t target_pitch,
+                                int B, int C, int HW, int Cpad, void* stream) {
+  lgm_note_kernel(LGM_KNAME("qsample_slice_kernel"));
+  hipLaunchKernelGGL(qsample_slice_kernel, dim3(lgm_cdiv((long)B * HW * lanes, 256)), dim3(256), 0, (hipStream_t)stream, img,
+                     noise, offset, strength, t, sqrt_ac, sqrt_1mac, normalize, objective, xin, (long)pitch, lanes, x_off,
+                     sc_off, target, (long)target_pitch, Cpad, B, C, HW);
+  LGM_LAUNCH_CHECK_AS("qsample_target_slice");
   return LGM_OK;
 }
 
-// The entry points above for every objective (0 = pred_noise, 1 = pred_x0, 2 = pred_v); see the kernels' comments.
-static bool objective_ok(int objective) { return objective >= 0 && objective <= 2; }
+extern "C" int lgm_qsample_target(const float* img, const float* noise, const int64_t* t, const float* sqrt_ac,
+                                  const float* sqrt_1mac, int normalize, float* xt, float* target, int64_t pitch,
+                                  int B, int C, int HW, int Cpad, void* stream) {
+  LGM_REQUIRE(img && noise && t && sqrt_ac && sqrt_1mac && xt && B > 0 && C > 0 && HW > 0 && Cpad >= C && pitch >= Cpad,
+              "qsample_target: bad arguments");
+  return qsample_slice_launch(img, noise, nullptr, 0.f, t, sqrt_ac, sqrt_1mac, normalize, 2, xt, pitch, Cpad, 0, -1, target,
+                              pitch, B, C, HW, Cpad, stream);
+}
 
 extern "C" int lgm_qsample_target_obj(const float* img, const float* noise, const float* offset, float strength,
                                       const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
@@ -1422,11 +1220,42 @@ extern "C" int lgm_qsample_target_obj(const float* img, const float* noise, cons
   LGM_REQUIRE(img && noise && t && sqrt_ac && sqrt_1mac && xt && B > 0 && C > 0 && HW > 0 && Cpad >= C && pitch >= Cpad &&
                   objective_ok(objective),
               "qsample_target_obj: bad arguments");
-  hipLaunchKernelGGL(qsample_obj_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, img,
-                     noise, offset, strength, t, sqrt_ac, sqrt_1mac, normalize, objective, xt, target, (long)pitch, B, C, HW,
-                     Cpad);
-  LGM_LAUNCH_CHECK();
+  return qsample_slice_launch(img, noise, offset, strength, t, sqrt_ac, sqrt_1mac, normalize, objective, xt, pitch, Cpad, 0,
+                              -1, target, pitch, B, C, HW, Cpad, stream);
+}
+
+extern "C" int lgm_qsample_target_slice(const float* img, const float* noise, const float* offset, float strength,
+                                        const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
+                                        int objective, float* xin, int64_t pitch, int x_off, int sc_off, float* target,
+                                        int64_t target_pitch, int B, int C, int HW, int Cpad, void* stream) {
+  LGM_REQUIRE(img && noise && t && sqrt_ac && sqrt_1mac && xin && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) &&
+                  Cpad >= C && Cpad <= pitch && target_pitch >= Cpad && objective_ok(objective),
+              "qsample_target_slice: bad arguments");
+  return qsample_slice_launch(img, noise, offset, strength, t, sqrt_ac, sqrt_1mac, normalize, objective, xin, pitch,
+                              (int)pitch, x_off, sc_off, target, target_pitch, B, C, HW, Cpad, stream);
+}
+
+static int model_predictions_launch(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
+                                    const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                                    int objective, int clip, int rederive, float* pred_noise, float* x_start, int B,
+                                    int64_t per_sample, int n_table, void* stream) {
+  const int gx = (int)(per_sample < 256L * 4096 ? lgm_cdiv(per_sample, 256) : 4096);
+  hipLaunchKernelGGL(model_predictions_obj_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, out, (const long*)t,
+                     sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, objective, clip, rederive, pred_noise, x_start,
+                     (long)per_sample, n_table);
+  LGM_LAUNCH_CHECK_AS("model_predictions_obj");
   return LGM_OK;
+}
+
+extern "C" int lgm_model_predictions(const float* x, const float* v, const int64_t* t, const float* sqrt_ac,
+                                     const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1, int clip,
+                                     float* pred_noise, float* x_start, int B, int64_t per_sample, int n_table,
+                                     void* stream) {
+  LGM_REQUIRE(x && v && t && sqrt_ac && sqrt_1mac && sqrt_recip && sqrt_recipm1 && pred_noise && x_start && B > 0 &&
+                  B <= 65535 && per_sample > 0 && n_table > 0,
+              "model_predictions: bad arguments");
+  return model_predictions_launch(x, v, t, sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, 2, clip, 0, pred_noise, x_start, B,
+                                  per_sample, n_table, stream);
 }
 
 extern "C" int lgm_model_predictions_obj(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
@@ -1436,44 +1265,8 @@ extern "C" int lgm_model_predictions_obj(const float* x, const float* out, const
   LGM_REQUIRE(x && out && t && sqrt_ac && sqrt_1mac && sqrt_recip && sqrt_recipm1 && pred_noise && x_start && B > 0 &&
                   B <= 65535 && per_sample > 0 && n_table > 0 && objective_ok(objective),
               "model_predictions_obj: bad arguments");
-  const int gx = (int)(per_sample < 256L * 4096 ? lgm_cdiv(per_sample, 256) : 4096);
-  hipLaunchKernelGGL(model_predictions_obj_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, out, (const long*)t,
-                     sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, objective, clip, rederive, pred_noise, x_start,
-                     (long)per_sample, n_table);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
-}
-
-extern "C" int lgm_sample_step_obj(const float* x, const float* v, const float* noise, float* out, float* x0_out, int B,
-                                   int C, int HW, int Cpad, int objective, float A, float Bv, int clip, int rederive,
-                                   float R, float Rm1, float C0, float C1, float C2, float C3, void* stream) {
-  LGM_REQUIRE(x && v && out && B > 0 && C > 0 && HW > 0 && Cpad >= C && objective_ok(objective),
-              "sample_step_obj: bad arguments");
-  hipLaunchKernelGGL(sample_step_obj_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream,
-                     x, v, noise, out, x0_out, B, C, HW, Cpad, objective, A, Bv, clip, rederive, R, Rm1, C0, C1, C2, C3);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
-}
-
-extern "C" int lgm_sample_step_table_obj(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
-                                         int Cpad, const float* table, const int32_t* counter, int objective, int clip,
-                                         int rederive, int advance, void* stream) {
-  LGM_REQUIRE(x && v && table && counter && B > 0 && C > 0 && HW > 0 && Cpad >= C && objective_ok(objective),
-              "sample_step_table_obj: bad arguments");
-  hipLaunchKernelGGL(sample_step_table_obj_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0,
-                     (hipStream_t)stream, x, v, noise, x0_out, B, C, HW, Cpad, table, (const int*)counter, objective, clip,
-                     rederive);
-  if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
-}
-
-// The slice-aware entry points of a self-conditioned UNet's input buffer (see the kernels' comments).  The two slices lie
-// inside the pitch and do not overlap; sc_off < 0 = no self-conditioning slice.
-static bool slices_ok(int64_t pitch, int x_off, int sc_off, int C) {
-  if (C <= 0 || x_off < 0 || x_off + C > pitch) return false;
-  if (sc_off < 0) return true;
-  return sc_off + C <= pitch && (sc_off + C <= x_off || x_off + C <= sc_off);
+  return model_predictions_launch(x, out, t, sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, objective, clip, rederive,
+                                  pred_noise, x_start, B, per_sample, n_table, stream);
 }
 
 extern "C" int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int sc_off, const float* out, int64_t out_pitch,
@@ -1491,32 +1284,38 @@ extern "C" int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int s
   return LGM_OK;
 }
 
-extern "C" int lgm_qsample_target_slice(const float* img, const float* noise, const float* offset, float strength,
-                                        const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int normalize,
-                                        int objective, float* xin, int64_t pitch, int x_off, int sc_off, float* target,
-                                        int64_t target_pitch, int B, int C, int HW, int Cpad, void* stream) {
-  LGM_REQUIRE(img && noise && t && sqrt_ac && sqrt_1mac && xin && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) &&
-                  Cpad >= C && Cpad <= pitch && target_pitch >= Cpad && objective_ok(objective),
-              "qsample_target_slice: bad arguments");
-  lgm_note_kernel(LGM_KNAME("qsample_slice_kernel"));
-  hipLaunchKernelGGL(qsample_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, img,
-                     noise, offset, strength, t, sqrt_ac, sqrt_1mac, normalize, objective, xin, (long)pitch, (int)pitch,
-                     x_off, sc_off, target, (long)target_pitch, Cpad, B, C, HW);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
-}
-
+// x0_out (optional, pitch x0_pitch >= pitch): only the one-slice forms hand one in.  table != null: row `counter` of it, and
+// `advance` appends the counter's increment.
 static int sample_step_slice_launch(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
-                                    int64_t v_pitch, const float* noise, int B, int C, int HW, const SampleRow& row,
-                                    const float* table, const int32_t* counter, int objective, int clip, int rederive,
-                                    int advance, void* stream) {
+                                    int64_t v_pitch, const float* noise, float* x0_out, int64_t x0_pitch, int B, int C,
+                                    int HW, const SampleRow& row, const float* table, const int32_t* counter, int objective,
+                                    int clip, int rederive, int advance, void* stream) {
   lgm_note_kernel(LGM_KNAME("sample_step_slice_kernel"));
   hipLaunchKernelGGL(sample_step_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream,
                      xin, xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, B, C, HW, row, table,
-                     (const int*)counter, objective, clip, rederive);
+                     (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("sample_step_slice");
   return LGM_OK;
+}
+
+extern "C" int lgm_sample_step(const float* x, const float* v, const float* noise, float* out, float* x0_out, int B,
+                               int C, int HW, int Cpad, float A, float Bv, int clip, float R, float Rm1, float C0,
+                               float C1, float C2, float C3, void* stream) {
+  LGM_REQUIRE(x && v && out && B > 0 && C > 0 && HW > 0 && Cpad >= C, "sample_step: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, C0, C1, C2, C3}};
+  return sample_step_slice_launch(x, out, Cpad, 0, -1, v, Cpad, noise, x0_out, Cpad, B, C, HW, row, nullptr, nullptr, 2, clip,
+                                  0, 0, stream);
+}
+
+extern "C" int lgm_sample_step_obj(const float* x, const float* v, const float* noise, float* out, float* x0_out, int B,
+                                   int C, int HW, int Cpad, int objective, float A, float Bv, int clip, int rederive,
+                                   float R, float Rm1, float C0, float C1, float C2, float C3, void* stream) {
+  LGM_REQUIRE(x && v && out && B > 0 && C > 0 && HW > 0 && Cpad >= C && objective_ok(objective),
+              "sample_step_obj: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, C0, C1, C2, C3}};
+  return sample_step_slice_launch(x, out, Cpad, 0, -1, v, Cpad, noise, x0_out, Cpad, B, C, HW, row, nullptr, nullptr,
+                                  objective, clip, rederive, 0, stream);
 }
 
 extern "C" int lgm_sample_step_slice(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
@@ -1527,8 +1326,25 @@ extern "C" int lgm_sample_step_slice(const float* xin, float* xout, int64_t pitc
                   objective_ok(objective),
               "sample_step_slice: bad arguments");
   const SampleRow row = {{A, Bv, R, Rm1, C0, C1, C2, C3}};
-  return sample_step_slice_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, B, C, HW, row, nullptr, nullptr,
-                                  objective, clip, rederive, 0, stream);
+  return sample_step_slice_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, nullptr, 0, B, C, HW, row, nullptr,
+                                  nullptr, objective, clip, rederive, 0, stream);
+}
+
+extern "C" int lgm_sample_step_table(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
+                                     int Cpad, const float* table, const int32_t* counter, int clip, int advance,
+                                     void* stream) {
+  LGM_REQUIRE(x && v && table && counter && B > 0 && C > 0 && HW > 0 && Cpad >= C, "sample_step_table: bad arguments");
+  return sample_step_slice_launch(x, x, Cpad, 0, -1, v, Cpad, noise, x0_out, Cpad, B, C, HW, SampleRow{}, table, counter, 2,
+                                  clip, 0, advance, stream);
+}
+
+extern "C" int lgm_sample_step_table_obj(float* x, const float* v, const float* noise, float* x0_out, int B, int C, int HW,
+                                         int Cpad, const float* table, const int32_t* counter, int objective, int clip,
+                                         int rederive, int advance, void* stream) {
+  LGM_REQUIRE(x && v && table && counter && B > 0 && C > 0 && HW > 0 && Cpad >= C && objective_ok(objective),
+              "sample_step_table_obj: bad arguments");
+  return sample_step_slice_launch(x, x, Cpad, 0, -1, v, Cpad, noise, x0_out, Cpad, B, C, HW, SampleRow{}, table, counter,
+                                  objective, clip, rederive, advance, stream);
 }
 
 extern "C" int lgm_sample_step_table_slice(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
@@ -1538,8 +1354,8 @@ extern "C" int lgm_sample_step_table_slice(float* x, int64_t pitch, int x_off, i
   LGM_REQUIRE(x && v && table && counter && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) && v_pitch >= C &&
                   objective_ok(objective),
               "sample_step_table_slice: bad arguments");
-  return sample_step_slice_launch(x, x, pitch, x_off, sc_off, v, v_pitch, noise, B, C, HW, SampleRow{}, table, counter,
-                                  objective, clip, rederive, advance, stream);
+  return sample_step_slice_launch(x, x, pitch, x_off, sc_off, v, v_pitch, noise, nullptr, 0, B, C, HW, SampleRow{}, table,
+                                  counter, objective, clip, rederive, advance, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -9,18 +9,18 @@ Two ways to run a chain, bit-identical in their results (tests/test_hip_unet.py)
   * graph replay (default on the GPU when only the final image is wanted): ONE HIP graph per (network, shape)
     holds a whole step — t[b] <- device table[step counter], UNet forward, noise draw, in-place update with the
     step's scalars read from a device table, counter += 1 — and is replayed once per step: no Python between
-    the ~230 launches of a step, no host syncs, no per-step allocations (``lgm_sample_step_table``);
+    the ~230 launches of a step, no host syncs, no per-step allocations (``lgm_sample_step_table_slice``);
   * eager launches (``return_all_timesteps``, ``LGM_NO_SAMPLER_GRAPH=1``, or when capture fails): per-timestep
-    scalars from host copies of the schedule buffers (``lgm_sample_step``).
+    scalars from host copies of the schedule buffers (``lgm_sample_step_slice`` / ``lgm_sample_step_obj``).
 
-The pred_v configuration issues the launches above; pred_noise and pred_x0 take ``lgm_sample_step_obj`` /
-``lgm_sample_step_table_obj`` (same scalars and table, the objective's branch of model_predictions inside; the ancestral
-step clips x0 only, DDIM also re-derives the noise from the clipped x0, reference :720-721, 808-810).
+Every objective takes the same update kernel with the same scalars and table, the objective's branch of model_predictions
+inside; the ancestral step clips x0 only, DDIM also re-derives the noise from the clipped x0 (reference :720-721, 808-810).
 
-A self-conditioned network (reference :773-774, 807-810, 864-865) reads ONE input buffer with two slices (Unet.input_buffer):
-``lgm_sample_step_slice`` / ``lgm_sample_step_table_slice`` read x from its slice, write the next x there and the x_start the
-reference hands on (clipped, as p_sample and ddim_sample clip it) into the self-conditioning slice the next step reads.  A
-chain starts with that slice zero: the reference's ``x_start = None``.
+The update reads x from its slice of the network's input buffer (Unet.input_buffer) and writes the next x there.  A
+self-conditioned network (reference :773-774, 807-810, 864-865) has a second slice: the x_start the reference hands on
+(clipped, as p_sample and ddim_sample clip it) goes into that self-conditioning slice, which the next step reads.  A chain
+starts with that slice zero: the reference's ``x_start = None``.  For any other network the eager step writes x_start into a
+buffer of its own (``lgm_sample_step_obj``), for ``p_sample`` to return.
 
 A class-conditional network (``Unet(num_classes=K)``) reads one label per sample, fixed for the run.  With a guidance scale
 other than 1 a step is two forwards over the SAME input buffer - the labels, then the null label - and ``lgm_cfg_mix``
@@ -98,26 +98,22 @@ class _Chain:
                 self.tbuf[t] = tb
         return tb
 
-    def step(self, t: int, noise: Optional[torch.Tensor], clip: bool, C0, C1, C2, C3, rederive: bool = False):
-        hs = _host_schedule(self.gd)
+    def step(self, t: int, noise: Optional[torch.Tensor], coeffs, rederive: bool = False):
+        """One update with clipped x0; ``coeffs`` = (A, Bv, R, Rm1, C0, C1, C2, C3) of ``_p_sample_coeffs`` / ``_ddim_coeffs``"""
         B, C, H, W = self.shape
         v = self.net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
         nz = None if noise is None else noise.data_ptr()
-        A, Bv = _f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t])
-        R, Rm1 = _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t])
+        A, Bv, R, Rm1, C0, C1, C2, C3 = coeffs
         net = self.net
-        if net.self_condition:
+        if net.self_condition:                   # x_start into the self-conditioning slice the next step reads
             ops.lib().lgm_sample_step_slice(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
-                                            v.data_ptr(), ops.pitch(v), nz, B, C, H * W, _objective(self.gd), A, Bv,
-                                            1 if clip else 0, 1 if rederive else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
+                                            v.data_ptr(), ops.pitch(v), nz, B, C, H * W, _objective(self.gd), A, Bv, 1,
+                                            1 if rederive else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
             self.x0 = net.sc_slice(self.x_next)
-        elif self.gd.objective == "pred_v":
-            ops.lib().lgm_sample_step(self.x.data_ptr(), v.data_ptr(), nz, self.x_next.data_ptr(), self.x0.data_ptr(), B, C,
-                                      H * W, self.Cp, A, Bv, 1 if clip else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
-        else:
+        else:                                    # x_start into the buffer p_sample returns
             ops.lib().lgm_sample_step_obj(self.x.data_ptr(), v.data_ptr(), nz, self.x_next.data_ptr(), self.x0.data_ptr(),
-                                          B, C, H * W, self.Cp, _objective(self.gd), A, Bv, 1 if clip else 0,
-                                          1 if rederive else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
+                                          B, C, H * W, self.Cp, _objective(self.gd), A, Bv, 1, 1 if rederive else 0, R, Rm1,
+                                          C0, C1, C2, C3, ops.stream())
         self.x, self.x_next = self.x_next, self.x
 
     def image(self, unnormalize: bool) -> torch.Tensor:
@@ -139,6 +135,7 @@ def _p_sample_coeffs(gd, t: int):
 
 
 def _ddim_coeffs(gd, t: int, t_next: int, eta: float):
+    """the same 8 scalars of one DDIM step (loop body :805-829); t_next < 0: the last step returns x0"""
     hs = _host_schedule(gd)
     head = (_f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t]),
             _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t]))
@@ -166,7 +163,6 @@ class _GraphedChain:
     def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096, guided: bool = False):
         net = gd.model
         objective = _objective(gd)
-        is_v = gd.objective == "pred_v"
         self._net = weakref.ref(net)                 # the cache is keyed weakly on the network: no strong reference here
         B, C, H, W = shape
         dev = gd.betas.device
@@ -176,8 +172,6 @@ class _GraphedChain:
         self._bound = (weakref.ref(fp), fp.data.data_ptr(),
                        None if fp.data_uf is None else fp.data_uf.data_ptr(),
                        None if fp.data_t is None else fp.data_t.data_ptr())
-        Cp = _r4(C)
-        self_cond = net.self_condition
         self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)     # static input buffer (both slices when self-conditioned)
         self.t = torch.zeros(B, dtype=torch.long, device=dev)
         self.noise = torch.zeros(shape, device=dev) if with_noise else None     # injected noise goes here
@@ -198,18 +192,10 @@ class _GraphedChain:
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
-            if self_cond:                        # x and the x_start handed on: both slices of the static buffer, in place
-                L.lgm_sample_step_table_slice(self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(),
-                                              ops.pitch(v), None if nz is None else nz.data_ptr(), B, C, H * W,
-                                              self.table.data_ptr(), self.counter.data_ptr(), objective, 1,
-                                              1 if rederive else 0, 1, ops.stream())
-            elif is_v:
-                L.lgm_sample_step_table(self.x.data_ptr(), v.data_ptr(), None if nz is None else nz.data_ptr(), None, B, C,
-                                        H * W, Cp, self.table.data_ptr(), self.counter.data_ptr(), 1, 1, ops.stream())
-            else:
-                L.lgm_sample_step_table_obj(self.x.data_ptr(), v.data_ptr(), None if nz is None else nz.data_ptr(), None,
-                                            B, C, H * W, Cp, self.table.data_ptr(), self.counter.data_ptr(), objective, 1,
-                                            1 if rederive else 0, 1, ops.stream())
+            # x (and, self-conditioned, the x_start handed on): the slices of the static buffer, in place
+            L.lgm_sample_step_table_slice(self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v),
+                                          None if nz is None else nz.data_ptr(), B, C, H * W, self.table.data_ptr(),
+                                          self.counter.data_ptr(), objective, 1, 1 if rederive else 0, 1, ops.stream())
 
         net.refresh_derived_weights(False)
         rng_state = torch.cuda.get_rng_state(dev)
@@ -308,22 +294,13 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
 
 def p_sample_step(chain: _Chain, t: int, noise: Optional[torch.Tensor]):
     """One ancestral step (p_sample :748-757): clip x0, posterior mean + sigma * noise (t > 0)."""
-    hs = _host_schedule(chain.gd)
-    sigma = _f32(torch.as_tensor(0.5 * hs["posterior_log_variance_clipped"][t]).exp()) if t > 0 else 0.0
-    chain.step(t, noise if t > 0 else None, True, _f32(hs["posterior_mean_coef1"][t]),
-               _f32(hs["posterior_mean_coef2"][t]), 0.0, sigma)
+    chain.step(t, noise if t > 0 else None, _p_sample_coeffs(chain.gd, t))
 
 
 def ddim_step(chain: _Chain, t: int, t_next: int, noise: Optional[torch.Tensor], eta: float):
-    """One DDIM step (loop body :805-829)."""
-    hs = _host_schedule(chain.gd)
-    if t_next < 0:
-        chain.step(t, None, True, 1.0, 0.0, 0.0, 0.0, rederive=True)
-        return
-    a, an = hs["alphas_cumprod"][t], hs["alphas_cumprod"][t_next]
-    sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()
-    c = (1 - an - sigma ** 2).sqrt()
-    chain.step(t, noise if float(sigma) != 0.0 else None, True, _f32(an.sqrt()), 0.0, _f32(c), _f32(sigma), rederive=True)
+    """One DDIM step (loop body :805-829); no noise where sigma is zero (eta == 0, or the last step)."""
+    coeffs = _ddim_coeffs(chain.gd, t, t_next, eta)
+    chain.step(t, noise if coeffs[7] != 0.0 else None, coeffs, rederive=True)
 
 
 @torch.no_grad()

@@ -1066,21 +1066,13 @@ class GaussianDiffusion(nn.Module):
         B = x.shape[0]
         t = t.to(device=x.device, dtype=torch.long).contiguous()
         pred_noise, x_start = torch.empty_like(x), torch.empty_like(x)
-        if self.objective != "pred_v":
-            ops.lib().lgm_model_predictions_obj(x.data_ptr(), v.data_ptr(), t.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
-                                                self.sqrt_one_minus_alphas_cumprod.data_ptr(),
-                                                self.sqrt_recip_alphas_cumprod.data_ptr(),
-                                                self.sqrt_recipm1_alphas_cumprod.data_ptr(), OBJECTIVES[self.objective],
-                                                1 if clip_x_start else 0, 1 if rederive_pred_noise else 0,
-                                                pred_noise.data_ptr(), x_start.data_ptr(), B, x.numel() // B,
-                                                self.num_timesteps, ops.stream())
-            return ModelPrediction(pred_noise, x_start)
-        ops.lib().lgm_model_predictions(x.data_ptr(), v.data_ptr(), t.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
-                                        self.sqrt_one_minus_alphas_cumprod.data_ptr(),
-                                        self.sqrt_recip_alphas_cumprod.data_ptr(),
-                                        self.sqrt_recipm1_alphas_cumprod.data_ptr(), 1 if clip_x_start else 0,
-                                        pred_noise.data_ptr(), x_start.data_ptr(), B, x.numel() // B,
-                                        self.num_timesteps, ops.stream())
+        ops.lib().lgm_model_predictions_obj(x.data_ptr(), v.data_ptr(), t.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
+                                            self.sqrt_one_minus_alphas_cumprod.data_ptr(),
+                                            self.sqrt_recip_alphas_cumprod.data_ptr(),
+                                            self.sqrt_recipm1_alphas_cumprod.data_ptr(), OBJECTIVES[self.objective],
+                                            1 if clip_x_start else 0, 1 if rederive_pred_noise else 0,
+                                            pred_noise.data_ptr(), x_start.data_ptr(), B, x.numel() // B,
+                                            self.num_timesteps, ops.stream())
         return ModelPrediction(pred_noise, x_start)
 
     @torch.no_grad()
@@ -1172,7 +1164,8 @@ def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None):
 
 def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, offset=None, strength: float = 0.0):
     """x_t into the network's input buffer and the objective's target: one launch.  A self-conditioned network's buffer gets
-    x_t in its x slice and zeros in its self-conditioning slice."""
+    x_t in its x slice and zeros in its self-conditioning slice; any other network's buffer is the x slice alone
+    (``in_pitch = r4(C)``, ``x_off = 0``, ``sc_off = -1``)."""
     net = gd.model
     B, C, H, W = img.shape
     Cp = _r4(C)
@@ -1181,26 +1174,14 @@ def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, of
     t = t.contiguous()
     xt = net.input_buffer(B, H, W, img)
     target = ops.new((B, H, W, Cp), img)
-    L = ops.lib()
-    st = ops.stream()
     if offset is not None:
         offset = offset.detach().float().contiguous()
         assert offset.shape == (B, C), f"offset noise is one value per (sample, channel), got {tuple(offset.shape)}"
-    if net.self_condition:
-        L.lgm_qsample_target_slice(img.data_ptr(), noise.data_ptr(), None if offset is None else offset.data_ptr(),
-                                   float(strength), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
-                                   gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
-                                   OBJECTIVES[gd.objective], xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
-                                   target.data_ptr(), Cp, B, C, H * W, Cp, st)
-    elif gd.objective == "pred_v" and offset is None:
-        L.lgm_qsample_target(img.data_ptr(), noise.data_ptr(), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
-                             gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0, xt.data_ptr(),
-                             target.data_ptr(), Cp, B, C, H * W, Cp, st)
-    else:
-        L.lgm_qsample_target_obj(img.data_ptr(), noise.data_ptr(), None if offset is None else offset.data_ptr(),
-                                 float(strength), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
-                                 gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
-                                 OBJECTIVES[gd.objective], xt.data_ptr(), target.data_ptr(), Cp, B, C, H * W, Cp, st)
+    ops.lib().lgm_qsample_target_slice(img.data_ptr(), noise.data_ptr(), None if offset is None else offset.data_ptr(),
+                                       float(strength), t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
+                                       gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
+                                       OBJECTIVES[gd.objective], xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
+                                       target.data_ptr(), Cp, B, C, H * W, Cp, ops.stream())
     return xt, target, img, noise, t, offset
 
 

@@ -90,3 +90,97 @@ def test_new_entry_points_are_declared_and_exported():
     p = ctypes.addressof(one)
     with pytest.raises(_lib.LgmArgumentError, match="sample_step_obj"):
         L.lgm_sample_step_obj(p, p, None, p, None, 1, 1, 1, 4, 3, 0.0, 0.0, 1, 0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, None)
+
+
+class _Recorder:
+    """Stands in for the library: records (entry point, arguments) of every call and answers 0 (launched)."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith("lgm_"):
+            raise AttributeError(name)
+
+        def call(*args):
+            self.calls.append((name, args))
+            return 0
+        return call
+
+
+@pytest.fixture
+def recorder(monkeypatch):
+    from lgm_hip import ops
+    rec = _Recorder()
+    monkeypatch.setattr(ops, "lib", lambda: rec)
+    monkeypatch.setattr(ops, "stream", lambda: 0)
+    return rec
+
+
+def _diffusion(objective, self_condition):
+    from models.generative.diffusion.ddpm import GaussianDiffusion, Unet
+    return GaussianDiffusion(Unet(dim=16, channels=3, self_condition=self_condition), img_size=16, timesteps=1000,
+                             objective=objective)
+
+
+@pytest.mark.parametrize("self_condition", [False, True])
+@pytest.mark.parametrize("objective", ["pred_noise", "pred_x0", "pred_v"])
+def test_q_sample_is_one_slice_launch_for_every_network(recorder, objective, self_condition):
+    """hip_loss_qsample: one lgm_qsample_target_slice call whatever the objective, on the network's own buffer layout"""
+    from models.generative.diffusion.ddpm import OBJECTIVES, hip_loss_qsample
+    gd = _diffusion(objective, self_condition)
+    net = gd.model
+    assert (net.in_pitch, net.x_off, net.sc_off) == ((8, 3, 0) if self_condition else (4, 0, -1))
+    img, noise = torch.rand(2, 3, 16, 16), torch.randn(2, 3, 16, 16)
+    xt, target, *_ = hip_loss_qsample(gd, img, torch.tensor([3, 700]), noise, True)
+    assert [name for name, _ in recorder.calls] == ["lgm_qsample_target_slice"]
+    args = recorder.calls[0][1]
+    assert args[8] == OBJECTIVES[objective]
+    assert args[9] == xt.data_ptr() and args[10:13] == (net.in_pitch, net.x_off, net.sc_off)
+    assert args[13] == target.data_ptr() and args[14:19] == (4, 2, 3, 256, 4)
+    assert tuple(xt.shape) == (2, 16, 16, net.in_pitch) and tuple(target.shape) == (2, 16, 16, 4)
+
+
+@pytest.mark.parametrize("self_condition", [False, True])
+@pytest.mark.parametrize("objective", ["pred_noise", "pred_x0", "pred_v"])
+def test_eager_sampler_step_branches_on_where_x_start_goes(recorder, monkeypatch, objective, self_condition):
+    """_Chain.step: lgm_sample_step_slice for a self-conditioned network (x_start into its slice), lgm_sample_step_obj with
+    the x0 buffer otherwise - for every objective; the 8 scalars are the ones of the coefficient functions."""
+    from lgm_hip import sampler
+    from models.generative.diffusion.ddpm import OBJECTIVES
+    gd = _diffusion(objective, self_condition)
+    net = gd.model
+    monkeypatch.setattr(net, "prepare_hip", lambda device: None)
+    monkeypatch.setattr(net, "forward_guided", lambda x, t, classes=None, cond_scale=1.0, **kw: torch.zeros(
+        x.shape[:3] + (4,)))
+    shape = (2, 3, 16, 16)
+    for step, coeffs, rederive in (
+            (lambda ch, nz: sampler.p_sample_step(ch, 500, nz), sampler._p_sample_coeffs(gd, 500), 0),
+            (lambda ch, nz: sampler.ddim_step(ch, 999, 979, nz, 1.0), sampler._ddim_coeffs(gd, 999, 979, 1.0), 1)):
+        chain = sampler._Chain(gd, shape, torch.randn(shape))
+        x, x_next, x0, nz = chain.x, chain.x_next, chain.x0, torch.randn(shape)
+        recorder.calls.clear()
+        step(chain, nz)
+        (name, args), = recorder.calls
+        head, tail = (A, Bv), (R, Rm1, C0, C1, C2, C3) = coeffs[:2], coeffs[2:]
+        assert C3 != 0.0
+        if self_condition:
+            assert name == "lgm_sample_step_slice"
+            assert args[:5] == (x.data_ptr(), x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off)
+            assert args[6:11] == (4, nz.data_ptr(), 2, 3, 256)
+            assert args[11:] == (OBJECTIVES[objective], *head, 1, rederive, *tail, 0)
+            assert chain.x0.data_ptr() == net.sc_slice(x_next).data_ptr()
+        else:
+            assert name == "lgm_sample_step_obj"
+            assert args[2:5] == (nz.data_ptr(), x_next.data_ptr(), x0.data_ptr())
+            assert args[0] == x.data_ptr() and args[5:9] == (2, 3, 256, 4)
+            assert args[9:] == (OBJECTIVES[objective], *head, 1, rederive, *tail, 0)
+        assert chain.x is x_next and chain.x_next is x
+    # no noise where the step adds none: t == 0 of the ancestral chain, eta == 0 and the last pair of DDIM
+    for step in (lambda ch, nz: sampler.p_sample_step(ch, 0, nz), lambda ch, nz: sampler.ddim_step(ch, 999, 979, nz, 0.0),
+                 lambda ch, nz: sampler.ddim_step(ch, 19, -1, nz, 1.0)):
+        chain = sampler._Chain(gd, shape, torch.randn(shape))
+        recorder.calls.clear()
+        step(chain, torch.randn(shape))
+        (name, args), = recorder.calls
+        assert args[7 if self_condition else 2] is None

@@ -1,7 +1,7 @@
 """GPU: GaussianDiffusion on the pred_noise (eps) and pred_x0 objectives, with offset noise.
 
-  * the four ``lgm_*_obj`` kernels against float64 restatements, and objective 2 (pred_v) bit for bit against the entry
-    points the pred_v configuration keeps calling;
+  * the four ``lgm_*_obj`` entry points against float64 restatements, objective 2 (pred_v) bit for bit against the plain
+    entry points, and the kernel each of them launches;
   * training step, model_predictions and sampling against what the REFERENCE's GaussianDiffusion returned for both
     objectives (tests/golden/diffusion_objectives.npz, written by tools/make_golden_objectives.py), 1e-4 relative;
   * the timed paths (graph-replayed training step, graph-replayed sampler) bit for bit against eager launches;
@@ -70,6 +70,10 @@ def _within(got, want, bound, what):
     return float(((got - want).abs() / bound.double().clamp_min(1e-300)).max() / U)
 
 
+def _last(L):
+    return L._dll.lgm_last_kernel().decode()
+
+
 def _nhwc(x, C):
     """[B, H W, Cpad] device tensor -> (NCHW host view of the C real channels, the padded channels)"""
     x = x.cpu().reshape(KB, KH, KW, KCP)
@@ -96,6 +100,7 @@ def test_qsample_target_obj_kernel(dev, tables, objective, with_offset, C):
     L.lgm_qsample_target_obj(imgd.data_ptr(), noised.data_ptr(), offd.data_ptr() if with_offset else None, strength,
                              td.data_ptr(), sad.data_ptr(), sbd.data_ptr(), 1, objective, xt.data_ptr(), tg.data_ptr(),
                              KCP, KB, C, KH * KW, KCP, ops.stream())
+    assert _last(L) == "qsample_slice_kernel"
     torch.cuda.synchronize()
     assert torch.equal(noised.cpu(), noise), "the kernel must not write the caller's noise"
     # float64 restatement (reference ddpm.py:889-891, 869-876, 911-917) of the float32 inputs
@@ -117,10 +122,11 @@ def test_qsample_target_obj_kernel(dev, tables, objective, with_offset, C):
         assert torch.equal(got_tg, img * 2 - 1)
     if objective == 0 and not with_offset:
         assert torch.equal(got_tg, noise)
-    if objective == 2 and not with_offset:                     # the bits of the entry point pred_v keeps calling
+    if objective == 2 and not with_offset:                     # the bits of the plain entry point
         xt2, tg2 = torch.full_like(xt, 7.0), torch.full_like(tg, 7.0)
         L.lgm_qsample_target(imgd.data_ptr(), noised.data_ptr(), td.data_ptr(), sad.data_ptr(), sbd.data_ptr(), 1,
                              xt2.data_ptr(), tg2.data_ptr(), KCP, KB, C, KH * KW, KCP, ops.stream())
+        assert _last(L) == "qsample_slice_kernel"
         assert torch.equal(xt, xt2) and torch.equal(tg, tg2)
 
 
@@ -206,10 +212,12 @@ def test_sample_step_obj_kernels(dev, tables, C):
             o, x0 = torch.full_like(xd, 7.0), torch.full_like(xd, 7.0)
             L.lgm_sample_step_obj(xd.data_ptr(), vd.data_ptr(), nzd.data_ptr(), o.data_ptr(), x0.data_ptr(), KB, C, HW,
                                   KCP, objective, A, Bv, clip, red, R, Rm1, C0, C1, C2, C3, ops.stream())
+            assert _last(L) == "sample_step_slice_kernel"
             xi = xd.clone()
             x0i = torch.full_like(xd, 7.0)
             L.lgm_sample_step_table_obj(xi.data_ptr(), vd.data_ptr(), nzd.data_ptr(), x0i.data_ptr(), KB, C, HW, KCP,
                                         table.data_ptr(), counter.data_ptr(), objective, clip, red, 0, ops.stream())
+            assert _last(L) == "sample_step_slice_kernel"
             assert torch.equal(xi, o) and torch.equal(x0i, x0), (objective, clip, red)
             assert int(counter) == 1
             got_o, pad_o = _nhwc(o, C)
@@ -224,10 +232,12 @@ def test_sample_step_obj_kernels(dev, tables, C):
                 o2, x02 = torch.empty_like(xd), torch.empty_like(xd)
                 L.lgm_sample_step(xd.data_ptr(), vd.data_ptr(), nzd.data_ptr(), o2.data_ptr(), x02.data_ptr(), KB, C, HW,
                                   KCP, A, Bv, clip, R, Rm1, C0, C1, C2, C3, ops.stream())
+                assert _last(L) == "sample_step_slice_kernel"
                 assert torch.equal(o, o2) and torch.equal(x0, x02)
     xi = xd.clone()
     L.lgm_sample_step_table_obj(xi.data_ptr(), vd.data_ptr(), None, None, KB, C, HW, KCP, table.data_ptr(),
                                 counter.data_ptr(), 0, 1, 0, 1, ops.stream())
+    assert _last(L) == "sample_step_slice_kernel"
     assert int(counter) == 2                                   # advance != 0 appends counter += 1
 
 

@@ -3,7 +3,7 @@ every sampling loop).
 
   * the estimate kernel and the slice-aware q_sample / sample-step kernels against float64 restatements (the 8 u M rule of
     tests/test_hip_objectives.py, same shapes), what they must leave untouched, and - called without a self-conditioning
-    slice - bit for bit against the entry points a model that is not self-conditioned keeps calling;
+    slice - bit for bit against the plain and ``_obj`` entry points (adapters over the same kernels);
   * UNet output, training step (coin off / on), model_predictions and whole sampling chains against what the REFERENCE's
     ``Unet(self_condition=True)`` / ``GaussianDiffusion`` returned (tests/golden/diffusion_selfcond.npz, written by
     tools/make_golden_selfcond.py), 1e-4 relative; an unclipped x_start or a chain that misses 1e-4 is decided by the float64
