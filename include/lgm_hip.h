@@ -48,7 +48,7 @@ extern "C" {
                              * 7: lgm_gn_bwd_add, lgm_wgrad1x1_group*, lgm_wgrad_queue_*
                              * (entry points added since without a change to an existing one keep the number, as the
                              *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
-                             *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix - a library
+                             *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table - a library
                              *  that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -522,6 +522,24 @@ int lgm_label_emb_wgrad(const float* gtemb, const int64_t* y, float* gemb, float
                         int num_classes, void* stream);
 int lgm_cfg_mix(float* out_cond, int64_t cond_pitch, const float* out_null, int64_t null_pitch, float scale,
                 const float* scale_dev, int64_t rows, int C, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * DPM-Solver++(2M) sampling (Lu et al. 2022, data prediction; an extension of the reference).  Buffers as for
+ * lgm_sample_step_slice; `hist` [B, HW, r4(C)] NHWC is the one piece of solver state, a buffer of its own.
+ * lgm_dpm_step: one update at a shared timestep from the row (A, Bv, R, Rm1, Kx, K0, K1, Kn) of lgm_hip.sampler.dpm_coeffs:
+ *     x0  = the objective's model_predictions branch from (A, -Bv, R, Rm1), clipped to [-1, 1] when clip is set
+ *     out = Kx*x + K0*x0 [+ K1*hist when K1 != 0] [+ Kn*noise when noise != NULL and Kn != 0]    (no contraction, this order)
+ *   out into the x slice of xout (xout may be xin), x0 into hist (pad lanes zero) and into xout's self-conditioning slice
+ *   (sc_off >= 0), zeros into xout's padding.  hist is not read when K1 == 0 (the first step of a chain), the noise (NCHW
+ *   dense) not when Kn == 0.
+ * lgm_dpm_step_table: the same IN PLACE with row counter[0] of table[n_steps][8]; advance != 0 appends counter[0] += 1.
+ *   Both launch dpm_step_kernel. */
+int lgm_dpm_step(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
+                 const float* noise, float* hist, int B, int C, int HW, int objective, float A, float Bv, int clip,
+                 float R, float Rm1, float Kx, float K0, float K1, float Kn, void* stream);
+int lgm_dpm_step_table(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
+                       const float* noise, float* hist, int B, int C, int HW, const float* table,
+                       const int32_t* counter, int objective, int clip, int advance, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

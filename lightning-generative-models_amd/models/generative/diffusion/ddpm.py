@@ -874,11 +874,21 @@ class GaussianDiffusion(nn.Module):
     def __init__(self, model: Unet, *, img_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, cond_drop_prob=None,
-                 cond_scale=1.0):
+                 cond_scale=1.0, sampler="auto", dpm_order=2, dpm_stochastic=False):
         """``cond_drop_prob`` / ``cond_scale`` (extension, class-conditional ``model`` only): the probability with which
         ``forward`` replaces a training label by the null label, and the classifier-free-guidance scale ``sample`` uses.
-        ``cond_drop_prob=None`` is 0.1 on a class-conditional model and 0 on any other."""
+        ``cond_drop_prob=None`` is 0.1 on a class-conditional model and 0 on any other.
+        ``sampler`` (extension): ``"auto"`` = the reference's dispatch (DDIM when ``sampling_timesteps < timesteps``, else the
+        ancestral chain), ``"dpm++"`` = DPM-Solver++ in ``sampling_timesteps`` steps of order ``dpm_order`` (2 = the 2M
+        multistep, 1 = DDIM at eta 0), ``dpm_stochastic`` its SDE form."""
         super().__init__()
+        if sampler not in ("auto", "dpm++"):
+            raise ValueError(f"sampler must be 'auto' or 'dpm++', got {sampler!r}")
+        if dpm_order not in (1, 2):
+            raise ValueError(f"dpm_order must be 1 or 2, got {dpm_order!r}")
+        if sampler == "dpm++" and sampling_timesteps is None:
+            raise ValueError("sampler='dpm++' needs sampling_timesteps (the number of solver steps)")
+        self.sampler, self.dpm_order, self.dpm_stochastic = sampler, int(dpm_order), bool(dpm_stochastic)
         if objective not in OBJECTIVES:
             raise ValueError(f"objective must be one of {sorted(OBJECTIVES)}, got {objective!r}")
         self.num_classes = getattr(model, "num_classes", None)
@@ -936,6 +946,10 @@ class GaussianDiffusion(nn.Module):
         times = torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1)
         times = list(reversed(times.int().tolist()))
         return list(zip(times[:-1], times[1:]))
+
+    def dpm_time_pairs(self):
+        """the (t, t_next) grid of ``dpm_solver_sample``: the reference's DDIM grid, the last pair (t, -1) returning x0"""
+        return self.ddim_time_pairs()
 
     # -- training ---------------------------------------------------------------------------
     def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, classes=None, *, _offset_noise=None,
@@ -1108,10 +1122,18 @@ class GaussianDiffusion(nn.Module):
         return sampler.ddim_sample(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale)
 
     @torch.no_grad()
+    def dpm_solver_sample(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0):
+        """DPM-Solver++ on ``dpm_time_pairs()`` (order ``dpm_order``, ``dpm_stochastic``: the SDE form), one forward per step"""
+        from lgm_hip import sampler
+        return sampler.dpm_solver_sample(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale)
+
+    @torch.no_grad()
     def sample(self, batch_size=16, return_all_timesteps=False, classes=None, cond_scale=None):
         """``classes`` (class-conditional model): one label per image, ``None`` = the null label, in one forward per step;
         ``cond_scale=None`` takes the constructor's."""
         fn = self.ddim_sample if self.is_ddim_sampling else self.p_sample_loop
+        if self.sampler == "dpm++":
+            fn = self.dpm_solver_sample
         scale = self.cond_scale if cond_scale is None else cond_scale
         if classes is None:
             scale = 1.0                              # out_null + s * (out_null - out_null): the null forward alone
@@ -1246,9 +1268,11 @@ class DDPM(LightningModule):
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
                  min_snr_gamma: float = 5, self_condition: bool = False, num_classes: Optional[int] = None,
-                 cond_drop_prob: float = 0.1, cond_scale: float = 1.0):
+                 cond_drop_prob: float = 0.1, cond_scale: float = 1.0, sampler: str = "auto", dpm_order: int = 2,
+                 dpm_stochastic: bool = False):
         """``num_classes`` (extension): class-conditional training on the batches' labels with classifier-free guidance;
-        ``cond_drop_prob`` / ``cond_scale`` are read with it only."""
+        ``cond_drop_prob`` / ``cond_scale`` are read with it only.  ``sampler`` / ``dpm_order`` / ``dpm_stochastic``
+        (extension): ``"dpm++"`` samples with DPM-Solver++ in ``sampling_timesteps`` steps (GaussianDiffusion)."""
         super().__init__()
         self.save_hyperparameters()
         self.num_classes = num_classes
@@ -1257,7 +1281,8 @@ class DDPM(LightningModule):
         diffusion_model = GaussianDiffusion(model, img_size=img_size, timesteps=diffusion_timesteps,
                                             sampling_timesteps=sampling_timesteps, objective=objective,
                                             beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
-                                            min_snr_loss_weight=min_snr_loss_weight, min_snr_gamma=min_snr_gamma, **cond)
+                                            min_snr_loss_weight=min_snr_loss_weight, min_snr_gamma=min_snr_gamma,
+                                            sampler=sampler, dpm_order=dpm_order, dpm_stochastic=dpm_stochastic, **cond)
         self.channels = img_channels
         self.img_size = img_size
         self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
