@@ -48,7 +48,8 @@ extern "C" {
                              * 7: lgm_gn_bwd_add, lgm_wgrad1x1_group*, lgm_wgrad_queue_*
                              * (entry points added since without a change to an existing one keep the number, as the
                              *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
-                             *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table - a library
+                             *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table,
+                             *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh - a library
                              *  that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -540,6 +541,44 @@ int lgm_dpm_step(const float* xin, float* xout, int64_t pitch, int x_off, int sc
 int lgm_dpm_step_table(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
                        const float* noise, float* hist, int B, int C, int HW, const float* table,
                        const int32_t* counter, int objective, int clip, int advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Dynamic thresholding of x0 (Saharia et al. 2022, 2.3; an extension of the reference): per sample
+ *     s = max(1, quantile_p(|x0|)) over its C * HW values,   x0 <- clamp(x0, -s, s) / s
+ * in place of the static clamp to [-1, 1].  A thresholded step is: network -> [lgm_cfg_mix] -> lgm_dyn_thresh -> one of the
+ * *_thresh update entry points, which read thresh[b].
+ * lgm_dyn_thresh: thresh[b] = fmaxf(lo + w * (hi - lo), 1) in float32 without contraction, lo / hi the k-th / (k+1)-th
+ *   smallest |x0| of sample b (0-based; hi = lo at k = C * HW - 1), (k, w) = lgm_hip.sampler.dyn_rank(C * HW, p):
+ *   torch.quantile's "linear" rule.  x0 is the UNCLIPPED model_predictions branch of `objective` from lanes [x_off, x_off + C)
+ *   of xin [B, HW, pitch] and lanes [0, C) of v [B, HW, v_pitch] with the head (A, Bv, R, Rm1) - by value, or row counter[0]
+ *   of table[n_steps][8] when table != NULL: the bits the update kernel computes.  Other lanes (padding, the self-
+ *   conditioning slice) are never read.  Exact (an integer radix select on the bit pattern of |x0|, one workgroup per
+ *   sample): the same bits on every run and under graph replay.  Inputs are assumed finite: a NaN sorts above Inf, so
+ *   non-finite values reach s only when the rank reaches them, and s is then Inf, or 1 for a NaN.  C * HW < 2^31.
+ *   Launches dyn_thresh_kernel.
+ * lgm_sample_step_thresh / lgm_dpm_step_thresh: lgm_sample_step_slice / lgm_dpm_step with clip set and the clip replaced by
+ *   x0 = fminf(fmaxf(x0, -s), s) / s, s = thresh[b] (one correctly rounded quotient: thresh[b] == 1 gives the static clamp's
+ *   bits); the re-derived noise (rederive) comes from that x0.  table != NULL (then counter != NULL and xout == xin): the row
+ *   is row counter[0] of the table and the eight scalars are ignored; advance != 0 appends counter[0] += 1.  x0_out
+ *   (lgm_sample_step_thresh, optional): [B, HW, pitch], x0 in lanes [0, C) and zeros in the others.  They launch
+ *   sample_step_slice_kernel / dpm_step_kernel, as the entry points without thresholds do.
+ * lgm_model_predictions_thresh: lgm_model_predictions_obj with clip set and thresh [B] (from lgm_dyn_thresh over the dense
+ *   unclipped x_start as a C = 1, HW = per_sample, pitch = 1, objective = pred_x0 problem). */
+int lgm_dyn_thresh(const float* xin, int64_t pitch, int x_off, const float* v, int64_t v_pitch, int B, int C, int HW,
+                   int objective, float A, float Bv, float R, float Rm1, const float* table, const int32_t* counter,
+                   int k, float w, float* thresh, void* stream);
+int lgm_sample_step_thresh(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                           int64_t v_pitch, const float* noise, float* x0_out, int B, int C, int HW, int objective,
+                           int rederive, float A, float Bv, float R, float Rm1, float C0, float C1, float C2, float C3,
+                           const float* table, const int32_t* counter, int advance, const float* thresh, void* stream);
+int lgm_dpm_step_thresh(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                        int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, int objective, float A,
+                        float Bv, float R, float Rm1, float Kx, float K0, float K1, float Kn, const float* table,
+                        const int32_t* counter, int advance, const float* thresh, void* stream);
+int lgm_model_predictions_thresh(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
+                                 const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                                 int objective, int rederive, float* pred_noise, float* x_start, int B,
+                                 int64_t per_sample, int n_table, const float* thresh, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

@@ -496,13 +496,20 @@ __device__ __forceinline__ void qsample_one(float a, float bb, float x0, float n
 // (sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1)[t].  pred_noise keeps the RAW network output unless clip and rederive are
 // both set (:720-721).  Contraction off: the reference rounds every product and sum separately.  Written with selects on
 // the (wave-uniform) objective, not branches: one straight-line body for the three objectives.
+// dyn (uniform: the launch has a threshold buffer): the clip is dynamic thresholding (Saharia et al. 2022, 2.3) with the
+// sample's s >= 1 from dyn_thresh_kernel, x0 = clamp(x0, -s, s) / s - one correctly rounded IEEE quotient (the build has no
+// fast-math flag: the same reliance as (R * xv - x0) / Rm1 below), so s == 1 gives the static clamp's bits.
 __device__ __forceinline__ void predictions_one(int objective, float xv, float ov, float A, float S, float R, float Rm1,
-                                                int clip, int rederive, float& pn, float& x0) {
+                                                int clip, int rederive, float& pn, float& x0, bool dyn = false,
+                                                float s = 1.f) {
 #pragma clang fp contract(off)
   const float p = objective == 0 ? R : A, q = objective == 0 ? Rm1 : S;
   const float lin = p * xv - q * ov;                 // predict_start_from_noise :673-677 / predict_start_from_v :690-694
   x0 = objective == 1 ? ov : lin;
-  if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  if (clip) {
+    if (dyn) x0 = fminf(fmaxf(x0, -s), s) / s;
+    else x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  }
   const float derived = (R * xv - x0) / Rm1;         // predict_noise_from_start :679-682
   pn = (objective == 0 && !(clip && rederive)) ? ov : derived;
 }
@@ -511,15 +518,18 @@ __global__ __launch_bounds__(256) void model_predictions_obj_kernel(const float*
                                                                     const float* __restrict__ s1, const float* __restrict__ r,
                                                                     const float* __restrict__ rm1, int objective, int clip,
                                                                     int rederive, float* __restrict__ pn,
-                                                                    float* __restrict__ xs, long per, int n_table) {
+                                                                    float* __restrict__ xs, long per, int n_table,
+                                                                    const float* __restrict__ thresh) {
   const int b = blockIdx.y;
   long ti = t[b];
   ti = ti < 0 ? 0 : (ti >= n_table ? n_table - 1 : ti);
   const float A = sa[ti], S = s1[ti], R = r[ti], Rm1 = rm1[ti];
+  const bool dyn = thresh != nullptr;
+  const float s = dyn ? thresh[b] : 1.f;
   const long base = (long)b * per;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (long)gridDim.x * blockDim.x) {
     float e, x0;
-    predictions_one(objective, x[base + i], out[base + i], A, S, R, Rm1, clip, rederive, e, x0);
+    predictions_one(objective, x[base + i], out[base + i], A, S, R, Rm1, clip, rederive, e, x0, dyn, s);
     xs[base + i] = x0;
     pn[base + i] = e;
   }
@@ -529,10 +539,10 @@ __global__ __launch_bounds__(256) void model_predictions_obj_kernel(const float*
 // reads all four, pred_noise reads (R, Rm1), pred_x0 reads them for eps only
 __device__ __forceinline__ void sample_update_obj(int objective, float xv, float ov, float nz, float A, float Bv, int clip,
                                                   int rederive, float R, float Rm1, float C0, float C1, float C2,
-                                                  float C3, float& o, float& x0) {
+                                                  float C3, float& o, float& x0, bool dyn = false, float s = 1.f) {
 #pragma clang fp contract(off)
   float eps;
-  predictions_one(objective, xv, ov, A, -Bv, R, Rm1, clip, rederive, eps, x0);
+  predictions_one(objective, xv, ov, A, -Bv, R, Rm1, clip, rederive, eps, x0, dyn, s);
   o = C0 * x0 + C1 * xv + C2 * eps;
   if (C3 != 0.f) o += C3 * nz;
 }
@@ -603,14 +613,16 @@ __global__ __launch_bounds__(256) void qsample_slice_kernel(const float* __restr
 // The reverse update for a whole batch at a shared timestep: x from the x slice of `xin`, the next x into the x slice of
 // `xout` (xout == xin: in place - a thread reads and writes its own lanes only), x0 as the reference hands it on (clipped
 // where it clips) into the self-conditioning slice of `xout` and, when x0_out is given, into lanes [0, C) of that buffer
-// (its other lanes zero); zeros into xout's padding.  table == null: the scalars by value in `byval`.
+// (its other lanes zero); zeros into xout's padding.  table == null: the scalars by value in `byval`.  thresh != null ([B],
+// from dyn_thresh_kernel): the clip is dynamic thresholding with s = thresh[b]; null: the static clamp, the launch there was.
 struct SampleRow { float v[8]; };
 __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin, float* xout, long pitch, int lanes, int x_off,
                                                                 int sc_off, const float* __restrict__ v, long v_pitch,
                                                                 const float* __restrict__ noise, int B, int C, int HW,
                                                                 SampleRow byval, const float* __restrict__ table,
                                                                 const int* __restrict__ counter, int objective, int clip,
-                                                                int rederive, float* __restrict__ x0_out, long x0_pitch) {
+                                                                int rederive, float* __restrict__ x0_out, long x0_pitch,
+                                                                const float* __restrict__ thresh) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)B * HW * lanes) return;
   const float* row = table ? table + 8 * counter[0] : byval.v;
@@ -625,8 +637,10 @@ __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin
       nz = noise[((long)b * C + c) * HW + p];
     }
     float o;
+    const bool dyn = thresh != nullptr;
+    const float s = dyn ? thresh[pix / HW] : 1.f;
     sample_update_obj(objective, xin[pix * pitch + x_off + c], v[pix * v_pitch + c], nz, A, Bv, clip, rederive, R, Rm1, C0,
-                      C1, C2, noise ? C3 : 0.f, o, x0);
+                      C1, C2, noise ? C3 : 0.f, o, x0, dyn, s);
     xout[pix * pitch + x_off + c] = o;
     if (sc_off >= 0) xout[pix * pitch + sc_off + c] = x0;
   }
@@ -639,10 +653,10 @@ __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin
 // sum; with K_1 hist and K_n noise one sum each - the products K_x x, K_1 hist, K_n noise round beside that path).
 __device__ __forceinline__ void dpm_update_one(int objective, float xv, float ov, float hv, float nz, float A, float Bv,
                                                float R, float Rm1, int clip, float Kx, float K0, float K1, float Kn, float& o,
-                                               float& x0) {
+                                               float& x0, bool dyn = false, float s = 1.f) {
 #pragma clang fp contract(off)
   float eps;
-  predictions_one(objective, xv, ov, A, -Bv, R, Rm1, clip, 0, eps, x0);
+  predictions_one(objective, xv, ov, A, -Bv, R, Rm1, clip, 0, eps, x0, dyn, s);
   o = Kx * xv + K0 * x0;
   if (K1 != 0.f) o += K1 * hv;
   if (Kn != 0.f) o += Kn * nz;
@@ -651,15 +665,18 @@ __device__ __forceinline__ void dpm_update_one(int objective, float xv, float ov
 // `xin`, the next x into the x slice of `xout` (xout == xin: in place), the clipped x0 into `hist` (NHWC, pitch r4(C) <=
 // pitch, pad lanes zero: the x0_prev of the next step) and into xout's self-conditioning slice, zeros into xout's padding.
 // hist is read only where K_1 != 0 and the noise only where K_n != 0: the first step of a chain runs on a history buffer
-// nobody has written.  One (pixel, lane) per trip of a grid-stride loop, scalar loads and stores only.
+// nobody has written.  One (pixel, lane) per trip of a grid-stride loop, scalar loads and stores only.  thresh as in
+// sample_step_slice_kernel: the history and the self-conditioning slice then hold the thresholded x0.
 __global__ __launch_bounds__(256) void dpm_step_kernel(const float* xin, float* xout, long pitch, int lanes, int x_off,
                                                        int sc_off, const float* __restrict__ v, long v_pitch,
                                                        const float* __restrict__ noise, float* hist, int B, int C, int HW,
                                                        SampleRow byval, const float* __restrict__ table,
-                                                       const int* __restrict__ counter, int objective, int clip) {
+                                                       const int* __restrict__ counter, int objective, int clip,
+                                                       const float* __restrict__ thresh) {
   const float* row = table ? table + 8 * counter[0] : byval.v;
   const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], Kx = row[4], K0 = row[5], K1 = row[6];
   const float Kn = noise ? row[7] : 0.f;
+  const bool dyn = thresh != nullptr;
   const int hp = (C + 3) & ~3;
   const long total = (long)B * HW * lanes;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -673,8 +690,9 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const float* xin, float* 
       }
       if (K1 != 0.f) hv = hist[pix * hp + c];
       float o, x0;
+      const float s = dyn ? thresh[pix / HW] : 1.f;
       dpm_update_one(objective, xin[pix * pitch + x_off + c], v[pix * v_pitch + c], hv, nz, A, Bv, R, Rm1, clip, Kx, K0, K1,
-                     Kn, o, x0);
+                     Kn, o, x0, dyn, s);
       xout[pix * pitch + x_off + c] = o;
       if (sc_off >= 0) xout[pix * pitch + sc_off + c] = x0;
       hist[pix * hp + c] = x0;
@@ -682,6 +700,120 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const float* xin, float* 
       hist[pix * hp + c] = 0.f;
     }
     if (slice_pad_lane(c, x_off, sc_off, C)) xout[pix * pitch + c] = 0.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// Dynamic thresholding (Saharia et al. 2022, 2.3): s[b] = max(1, quantile_p(|x0[b]|)) over the C * HW values of a sample, the
+// quantile by torch.quantile's "linear" rule: q = lo + w (hi - lo) with lo, hi the k-th and (k+1)-th smallest |x0| (0-based;
+// (k, w) = lgm_hip.sampler.dyn_rank(n, p) from the host), evaluated in float32 without contraction.
+// One workgroup per sample; x0 is recomputed per pass from the x slice and the network output with predictions_one(clip = 0)
+// - the bits the update kernel will see - and never stored: three reads of a sample that sits in L2 beside a UNet forward.
+// The selection is exact: a radix select on the bit pattern of |x0| (sign bit cleared, a non-negative float orders like its
+// uint32 bits) in three passes of 11 + 10 + 10 bits.  A pass counts the digit of every element whose higher bits equal the
+// prefix found so far into an LDS histogram of integers, scans the bins and narrows the prefix to the bin that holds rank k;
+// after the third the prefix IS the key of lo.  hi is lo again when the last bin holds more elements than the rank left in it
+// needs, else the smallest key above lo: the next non-empty bin of the last histogram or, above that bucket, a running
+// minimum the last pass keeps.  Integer counts and minima: the result does not depend on the order in which lanes arrive,
+// so graph replay equals eager launches bit for bit.  Counting reduces in the wave first: the lanes that share the first
+// lane's digit add their number once (a batch of near-equal magnitudes is one LDS atomic per wave, not 64 on one address).
+// NaN / Inf: inputs are assumed finite.  A NaN's key lies above Inf's, so non-finite values sort to the top and reach s only
+// when the rank does; an infinite s makes NaN of the Inf elements in the update (Inf / Inf), a NaN q gives s = 1.
+// ---------------------------------------------------------------------------------------
+constexpr int DT_THREADS = 1024;
+constexpr int DT_BINS = 2048;
+__device__ __forceinline__ void dyn_count(unsigned* hist, unsigned digit) {
+  const unsigned lead = __builtin_amdgcn_readfirstlane(digit);
+  const unsigned long long same = __ballot(digit == lead);          // of the lanes that are here
+  if (digit == lead) {
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&hist[lead], (unsigned)__popcll(same));
+  } else {
+    atomicAdd(&hist[digit], 1u);
+  }
+}
+__device__ __forceinline__ float dyn_interp(float lo, float hi, float w) {
+#pragma clang fp contract(off)
+  const float d = hi - lo;
+  const float q = lo + w * d;
+  return fmaxf(q, 1.f);
+}
+__global__ __launch_bounds__(DT_THREADS) void dyn_thresh_kernel(const float* __restrict__ xin, long pitch, int x_off,
+                                                                const float* __restrict__ v, long v_pitch, int C, int HW,
+                                                                SampleRow byval, const float* __restrict__ table,
+                                                                const int* __restrict__ counter, int objective, unsigned k,
+                                                                float w, float* __restrict__ thresh) {
+  __shared__ unsigned hist[DT_BINS];
+  __shared__ unsigned wsum[DT_THREADS / 64];
+  __shared__ unsigned sel[4];            // the bin of rank k, the rank left inside it, its count; the smallest key above lo
+  const float* row = table ? table + 8 * counter[0] : byval.v;
+  const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long base = (long)blockIdx.x * HW;
+  unsigned prefix = 0, krem = k, above = 0xffffffffu, bin = 0;
+  for (int pass = 0; pass < 3; ++pass) {
+    const int shift = 20 - 10 * pass;                     // digits: bits 30..20, 19..10, 9..0
+    const int nb = pass == 0 ? 2048 : 1024;
+    const int hs = pass == 0 ? 31 : shift + 10;           // key >> hs: the bits above this pass's digit (pass 0: none)
+    for (int i = tid; i < DT_BINS; i += DT_THREADS) hist[i] = 0;
+    if (tid == 0) sel[3] = 0xffffffffu;
+    __syncthreads();
+    for (int p = tid; p < HW; p += DT_THREADS) {
+      const float* xp = xin + (base + p) * pitch + x_off;
+      const float* vp = v + (base + p) * v_pitch;
+      for (int c = 0; c < C; ++c) {
+        float e, x0;
+        predictions_one(objective, xp[c], vp[c], A, -Bv, R, Rm1, 0, 0, e, x0);
+        const unsigned key = __float_as_uint(x0) & 0x7fffffffu;
+        const unsigned up = key >> hs;
+        if (up == prefix) dyn_count(hist, (key >> shift) & (unsigned)(nb - 1));
+        else if (pass == 2 && up > prefix) above = key < above ? key : above;
+      }
+    }
+    __syncthreads();
+    // exclusive scan of the bins, nb / 1024 consecutive bins per thread: the one thread whose bins hold rank krem publishes
+    const int per = nb / DT_THREADS;
+    unsigned loc = 0;
+    for (int j = 0; j < per; ++j) loc += hist[tid * per + j];
+    unsigned inc = loc;
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned o = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned ex = inc - loc;
+    for (int j = 0; j < wave; ++j) ex += wsum[j];
+    if (krem >= ex && krem < ex + loc) {
+      unsigned cum = ex;
+      int bsel = tid * per;
+      for (int j = 0; j < per; ++j) {
+        const unsigned cnt = hist[tid * per + j];
+        if (krem < cum + cnt) { bsel = tid * per + j; break; }
+        cum += cnt;
+      }
+      sel[0] = (unsigned)bsel; sel[1] = krem - cum; sel[2] = hist[bsel];
+    }
+    __syncthreads();
+    bin = sel[0];
+    krem = sel[1];
+    prefix = (prefix << (pass == 0 ? 11 : 10)) | bin;
+  }
+  // prefix = the key of lo.  The smallest key above it: the next non-empty bin of the last histogram, else `above`
+  unsigned cand = above;
+  if ((unsigned)tid > bin && hist[tid] != 0) {
+    const unsigned kk = (prefix & ~1023u) | (unsigned)tid;
+    cand = kk < cand ? kk : cand;
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned o = __shfl_xor(cand, d, 64);
+    cand = o < cand ? o : cand;
+  }
+  if (lane == 0 && cand != 0xffffffffu) atomicMin(&sel[3], cand);
+  __syncthreads();
+  if (tid == 0) {
+    unsigned hik = krem + 1 < sel[2] ? prefix : sel[3];
+    if (hik == 0xffffffffu) hik = prefix;                 // k = n - 1: nothing above lo
+    thresh[blockIdx.x] = dyn_interp(__uint_as_float(prefix), __uint_as_float(hik), w);
   }
 }
 
@@ -1289,11 +1421,11 @@ extern "C" int lgm_qsample_target_slice(const float* img, const float* noise, co
 static int model_predictions_launch(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
                                     const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
                                     int objective, int clip, int rederive, float* pred_noise, float* x_start, int B,
-                                    int64_t per_sample, int n_table, void* stream) {
+                                    int64_t per_sample, int n_table, void* stream, const float* thresh = nullptr) {
   const int gx = (int)(per_sample < 256L * 4096 ? lgm_cdiv(per_sample, 256) : 4096);
   hipLaunchKernelGGL(model_predictions_obj_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, out, (const long*)t,
                      sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, objective, clip, rederive, pred_noise, x_start,
-                     (long)per_sample, n_table);
+                     (long)per_sample, n_table, thresh);
   LGM_LAUNCH_CHECK_AS("model_predictions_obj");
   return LGM_OK;
 }
@@ -1320,6 +1452,17 @@ extern "C" int lgm_model_predictions_obj(const float* x, const float* out, const
                                   pred_noise, x_start, B, per_sample, n_table, stream);
 }
 
+extern "C" int lgm_model_predictions_thresh(const float* x, const float* out, const int64_t* t, const float* sqrt_ac,
+                                            const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                                            int objective, int rederive, float* pred_noise, float* x_start, int B,
+                                            int64_t per_sample, int n_table, const float* thresh, void* stream) {
+  LGM_REQUIRE(x && out && t && sqrt_ac && sqrt_1mac && sqrt_recip && sqrt_recipm1 && pred_noise && x_start && thresh &&
+                  B > 0 && B <= 65535 && per_sample > 0 && n_table > 0 && objective_ok(objective),
+              "model_predictions_thresh: bad arguments");
+  return model_predictions_launch(x, out, t, sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, objective, 1, rederive,
+                                  pred_noise, x_start, B, per_sample, n_table, stream, thresh);
+}
+
 extern "C" int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int sc_off, const float* out, int64_t out_pitch,
                                      const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
                                      const float* sqrt_recip, const float* sqrt_recipm1, int objective, int B, int C, int HW,
@@ -1340,11 +1483,11 @@ extern "C" int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int s
 static int sample_step_slice_launch(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
                                     int64_t v_pitch, const float* noise, float* x0_out, int64_t x0_pitch, int B, int C,
                                     int HW, const SampleRow& row, const float* table, const int32_t* counter, int objective,
-                                    int clip, int rederive, int advance, void* stream) {
+                                    int clip, int rederive, int advance, void* stream, const float* thresh = nullptr) {
   lgm_note_kernel(LGM_KNAME("sample_step_slice_kernel"));
   hipLaunchKernelGGL(sample_step_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream,
                      xin, xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, B, C, HW, row, table,
-                     (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch);
+                     (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch, thresh);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("sample_step_slice");
   return LGM_OK;
@@ -1409,17 +1552,35 @@ extern "C" int lgm_sample_step_table_slice(float* x, int64_t pitch, int x_off, i
                                   counter, objective, clip, rederive, advance, stream);
 }
 
+// The dynamically thresholded update (thresh [B] from lgm_dyn_thresh): both forms of the row behind one entry point - table
+// != NULL takes row counter[0] of it, else the eight scalars.  x0_out (optional, pitch = `pitch`): a network without a
+// self-conditioning slice hands one in for p_sample to return.
+extern "C" int lgm_sample_step_thresh(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                                      int64_t v_pitch, const float* noise, float* x0_out, int B, int C, int HW,
+                                      int objective, int rederive, float A, float Bv, float R, float Rm1, float C0, float C1,
+                                      float C2, float C3, const float* table, const int32_t* counter, int advance,
+                                      const float* thresh, void* stream) {
+  LGM_REQUIRE(xin && xout && v && thresh && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) && v_pitch >= C &&
+                  objective_ok(objective) && (table == nullptr) == (counter == nullptr) && (table || !advance) &&
+                  (!table || xin == xout) && x0_out != xin && x0_out != xout,
+              "sample_step_thresh: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, C0, C1, C2, C3}};
+  return sample_step_slice_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, x0_out, pitch, B, C, HW, row, table,
+                                  counter, objective, 1, rederive, advance, stream, thresh);
+}
+
 // DPM-Solver++ step.  The name is noted without a registry entry (no LGM_KNAME): tests/test_hip_kernel_ledger.py keeps the
 // list of every registry name with the test file that runs it, and tests/test_hip_dpmpp.py, which runs this kernel and
 // asserts the noted name, is not on that list.  A memory-bound pass: at most 2048 workgroups, the rest by grid stride.
 static int dpm_step_launch(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
                            int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, const SampleRow& row,
-                           const float* table, const int32_t* counter, int objective, int clip, int advance, void* stream) {
+                           const float* table, const int32_t* counter, int objective, int clip, int advance, void* stream,
+                           const float* thresh = nullptr) {
   lgm_note_kernel("dpm_step_kernel");
   const long blocks = ((long)B * HW * pitch + 255) / 256;
   hipLaunchKernelGGL(dpm_step_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream, xin,
                      xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, hist, B, C, HW, row, table,
-                     (const int*)counter, objective, clip);
+                     (const int*)counter, objective, clip, thresh);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("dpm_step");
   return LGM_OK;
@@ -1450,6 +1611,39 @@ extern "C" int lgm_dpm_step_table(float* x, int64_t pitch, int x_off, int sc_off
               "dpm_step_table: bad arguments");
   return dpm_step_launch(x, x, pitch, x_off, sc_off, v, v_pitch, noise, hist, B, C, HW, SampleRow{}, table, counter, objective,
                          clip, advance, stream);
+}
+
+// the dynamically thresholded DPM-Solver++ step: both forms of the row behind one entry point, like lgm_sample_step_thresh
+extern "C" int lgm_dpm_step_thresh(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                                   int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, int objective,
+                                   float A, float Bv, float R, float Rm1, float Kx, float K0, float K1, float Kn,
+                                   const float* table, const int32_t* counter, int advance, const float* thresh,
+                                   void* stream) {
+  LGM_REQUIRE(thresh && dpm_buffers_ok(xin, xout, pitch, x_off, sc_off, v, v_pitch, hist, B, C, HW, objective) &&
+                  (table == nullptr) == (counter == nullptr) && (table || !advance) && (!table || xin == xout),
+              "dpm_step_thresh: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, Kx, K0, K1, Kn}};
+  return dpm_step_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, hist, B, C, HW, row, table, counter, objective,
+                         1, advance, stream, thresh);
+}
+
+// Dynamic thresholding: thresh[b] = max(1, lo + w (hi - lo)) with lo, hi the k-th and (k+1)-th smallest |x0| of sample b
+// ((k, w) = lgm_hip.sampler.dyn_rank(C * HW, p)), x0 the unclipped prediction from the x slice of xin and the network output
+// v with the head (A, Bv, R, Rm1) by value or from row counter[0] of `table`.  One workgroup per sample.  The name is noted
+// without a registry entry, like dpm_step_kernel's and for the same reason.
+extern "C" int lgm_dyn_thresh(const float* xin, int64_t pitch, int x_off, const float* v, int64_t v_pitch, int B, int C,
+                              int HW, int objective, float A, float Bv, float R, float Rm1, const float* table,
+                              const int32_t* counter, int k, float w, float* thresh, void* stream) {
+  LGM_REQUIRE(xin && v && thresh && B > 0 && HW > 0 && slices_ok(pitch, x_off, -1, C) && v_pitch >= C &&
+                  objective_ok(objective) && (table == nullptr) == (counter == nullptr) &&
+                  (int64_t)C * HW < ((int64_t)1 << 31) && k >= 0 && (int64_t)k < (int64_t)C * HW && w >= 0.f && w < 1.f,
+              "dyn_thresh: bad arguments");
+  lgm_note_kernel("dyn_thresh_kernel");
+  const SampleRow row = {{A, Bv, R, Rm1, 0.f, 0.f, 0.f, 0.f}};
+  hipLaunchKernelGGL(dyn_thresh_kernel, dim3(B), dim3(DT_THREADS), 0, (hipStream_t)stream, xin, (long)pitch, x_off, v,
+                     (long)v_pitch, C, HW, row, table, (const int*)counter, objective, (unsigned)k, w, thresh);
+  LGM_LAUNCH_CHECK_AS("dyn_thresh");
+  return LGM_OK;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -30,6 +30,13 @@ launches and in the captured step alike; labels and scale of a captured step liv
 DPM-Solver++(2M) (``dpm_solver_sample``; Lu et al. 2022, an extension of the reference) runs on the same two paths with an
 update kernel of its own (``lgm_dpm_step`` / ``lgm_dpm_step_table``) and one more buffer, the previous step's clipped x0; its
 coefficient rows come from ``dpm_plan`` / ``dpm_coeffs``, float64 arithmetic on the host that needs neither device nor library.
+
+Dynamic thresholding (``GaussianDiffusion(dynamic_thresholding=True)``; Saharia et al. 2022, an extension of the reference)
+replaces the static clamp of x0 in every sampler by ``clamp(x0, -s, s) / s`` with ``s = max(1, quantile_p(|x0|))`` per sample.
+A thresholded step is forward(s) -> [``lgm_cfg_mix``] -> ``lgm_dyn_thresh`` (one workgroup per sample writes s into the chain's
+``[B]`` threshold buffer) -> the update kernel reading that buffer (``lgm_sample_step_thresh`` / ``lgm_dpm_step_thresh``): one
+launch more per step, in eager launches and in the captured step alike.  The rank the kernel selects comes from ``dyn_rank``,
+host arithmetic like the solver's plan.  Without thresholding every chain issues the launches it issued before.
 """
 from __future__ import annotations
 
@@ -63,6 +70,25 @@ def _f32(x) -> float:
     return float(torch.as_tensor(x, dtype=torch.float32))
 
 
+def dyn_rank(n: int, p: float):
+    """-> (k, w): the order statistics ``torch.quantile``'s "linear" rule reads for the p-quantile of n values.  pos = p (n - 1)
+    in float64, k = floor(pos), w = float32(pos - k); the quantile is lo + w (hi - lo) with lo, hi the k-th and (k+1)-th
+    smallest value (0-based; hi = lo at k = n - 1).  Pure Python: no device, no library."""
+    n, p = int(n), float(p)
+    if n < 1:
+        raise ValueError(f"dyn_rank needs at least one value, got n = {n}")
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"dynamic_thresholding_percentile must lie in (0, 1], got {p!r}")
+    pos = p * (n - 1)
+    k = min(int(math.floor(pos)), n - 1)
+    return k, _f32(pos - k)
+
+
+def _dyn(gd) -> Optional[float]:
+    """the percentile of a dynamically thresholding diffusion, None for the static clamp"""
+    return float(gd.dynamic_thresholding_percentile) if getattr(gd, "dynamic_thresholding", False) else None
+
+
 class _Chain:
     """Device-resident state of one sampling run (NHWC, padded channels)."""
 
@@ -94,6 +120,17 @@ class _Chain:
             self.x0 = torch.empty_like(self.x)
         self.tbuf = {}
         self.hist = None                         # DPM-Solver++ only: the previous step's clipped x0 (dpm_step)
+        # dynamic thresholding: the rank lgm_dyn_thresh selects and the [B] buffer it writes (readable after a step)
+        self.dyn = None if _dyn(gd) is None else dyn_rank(C * H * W, _dyn(gd))
+        self.thresh = torch.zeros(B, device=dev) if self.dyn is not None else None
+
+    def _dyn_thresh(self, v, head):
+        """s[b] of the step into ``self.thresh``: from the x slice, the network output and the head (A, Bv, R, Rm1)"""
+        B, C, H, W = self.shape
+        net = self.net
+        ops.lib().lgm_dyn_thresh(self.x.data_ptr(), net.in_pitch, net.x_off, v.data_ptr(), ops.pitch(v), B, C, H * W,
+                                 _objective(self.gd), *head, None, None, self.dyn[0], self.dyn[1], self.thresh.data_ptr(),
+                                 ops.stream())
 
     def times(self, t: int) -> torch.Tensor:
         tb = self.tbuf.get(t)
@@ -110,7 +147,15 @@ class _Chain:
         nz = None if noise is None else noise.data_ptr()
         A, Bv, R, Rm1, C0, C1, C2, C3 = coeffs
         net = self.net
-        if net.self_condition:                   # x_start into the self-conditioning slice the next step reads
+        if self.dyn is not None:                 # thresholded: s[b] first, then the update that reads it
+            self._dyn_thresh(v, (A, Bv, R, Rm1))
+            ops.lib().lgm_sample_step_thresh(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
+                                             v.data_ptr(), ops.pitch(v), nz, None if net.self_condition else self.x0.data_ptr(),
+                                             B, C, H * W, _objective(self.gd), 1 if rederive else 0, A, Bv, R, Rm1, C0, C1,
+                                             C2, C3, None, None, 0, self.thresh.data_ptr(), ops.stream())
+            if net.self_condition:
+                self.x0 = net.sc_slice(self.x_next)
+        elif net.self_condition:                 # x_start into the self-conditioning slice the next step reads
             ops.lib().lgm_sample_step_slice(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
                                             v.data_ptr(), ops.pitch(v), nz, B, C, H * W, _objective(self.gd), A, Bv, 1,
                                             1 if rederive else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
@@ -131,9 +176,16 @@ class _Chain:
         v = self.net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
         net = self.net
         A, Bv, R, Rm1, Kx, K0, K1, Kn = coeffs
-        ops.lib().lgm_dpm_step(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(),
-                               ops.pitch(v), None if noise is None else noise.data_ptr(), self.hist.data_ptr(), B, C, H * W,
-                               _objective(self.gd), A, Bv, 1, R, Rm1, Kx, K0, K1, Kn, ops.stream())
+        if self.dyn is not None:
+            self._dyn_thresh(v, (A, Bv, R, Rm1))
+            ops.lib().lgm_dpm_step_thresh(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
+                                          v.data_ptr(), ops.pitch(v), None if noise is None else noise.data_ptr(),
+                                          self.hist.data_ptr(), B, C, H * W, _objective(self.gd), A, Bv, R, Rm1, Kx, K0, K1,
+                                          Kn, None, None, 0, self.thresh.data_ptr(), ops.stream())
+        else:
+            ops.lib().lgm_dpm_step(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(),
+                                   ops.pitch(v), None if noise is None else noise.data_ptr(), self.hist.data_ptr(), B, C,
+                                   H * W, _objective(self.gd), A, Bv, 1, R, Rm1, Kx, K0, K1, Kn, ops.stream())
         self.x0 = net.sc_slice(self.x_next) if net.self_condition else self.hist
         self.x, self.x_next = self.x_next, self.x
 
@@ -231,7 +283,7 @@ class _GraphedChain:
     """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it."""
 
     def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096, guided: bool = False,
-                 dpm: bool = False):
+                 dpm: bool = False, dyn: Optional[float] = None):
         net = gd.model
         objective = _objective(gd)
         self._net = weakref.ref(net)                 # the cache is keyed weakly on the network: no strong reference here
@@ -254,6 +306,10 @@ class _GraphedChain:
         self.scale = torch.ones(1, device=dev) if guided else None
         # DPM-Solver++: the previous step's clipped x0, static like the input buffer; a chain's first row has K_1 = 0
         self.hist = torch.zeros((B, H, W, _r4(C)), device=dev) if dpm else None
+        # dynamic thresholding at percentile ``dyn``: the thresholds of the current step, static like the input buffer; the
+        # rank is baked into the captured launch, which is why the percentile is part of the cache key
+        self.thresh = torch.zeros(B, device=dev) if dyn is not None else None
+        rank = None if dyn is None else dyn_rank(C * H * W, dyn)
         self.inject = False
         self.max_steps = max_steps
         L = ops.lib()
@@ -265,6 +321,23 @@ class _GraphedChain:
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
+            nzp = None if nz is None else nz.data_ptr()
+            if rank is not None:                 # s[b] from the table row's head, then the update that reads it
+                L.lgm_dyn_thresh(self.x.data_ptr(), net.in_pitch, net.x_off, v.data_ptr(), ops.pitch(v), B, C, H * W, objective,
+                                 0.0, 0.0, 0.0, 0.0, self.table.data_ptr(), self.counter.data_ptr(), rank[0], rank[1],
+                                 self.thresh.data_ptr(), ops.stream())
+                zeros = (0.0,) * 8
+                if dpm:
+                    L.lgm_dpm_step_thresh(self.x.data_ptr(), self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
+                                          v.data_ptr(), ops.pitch(v), nzp, self.hist.data_ptr(), B, C, H * W, objective, *zeros,
+                                          self.table.data_ptr(), self.counter.data_ptr(), 1, self.thresh.data_ptr(),
+                                          ops.stream())
+                else:
+                    L.lgm_sample_step_thresh(self.x.data_ptr(), self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
+                                             v.data_ptr(), ops.pitch(v), nzp, None, B, C, H * W, objective,
+                                             1 if rederive else 0, *zeros, self.table.data_ptr(), self.counter.data_ptr(), 1,
+                                             self.thresh.data_ptr(), ops.stream())
+                return
             if dpm:
                 L.lgm_dpm_step_table(self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v),
                                      None if nz is None else nz.data_ptr(), self.hist.data_ptr(), B, C, H * W,
@@ -351,6 +424,9 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
         key += ("guided",)
     if dpm:                                          # never the key of an ancestral / DDIM step, whatever the objective
         key = ("dpm++", gd.objective) + key
+    dyn = _dyn(gd)
+    if dyn is not None:                              # a key of its own, the percentile in it: the rank is baked into the launch
+        key = ("dynthresh", dyn) + key
     ent = per_net.get(key)
     if isinstance(ent, _GraphedChain) and not ent.matches(net):
         ent = None                                   # captured against buffers the network no longer uses
@@ -362,7 +438,7 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
         ent = None
     if ent is None:
         try:
-            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm)
+            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=dyn)
         except Exception as e:  # capture is an optimisation
             import sys
             print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",

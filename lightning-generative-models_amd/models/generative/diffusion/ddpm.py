@@ -874,14 +874,22 @@ class GaussianDiffusion(nn.Module):
     def __init__(self, model: Unet, *, img_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, cond_drop_prob=None,
-                 cond_scale=1.0, sampler="auto", dpm_order=2, dpm_stochastic=False):
+                 cond_scale=1.0, sampler="auto", dpm_order=2, dpm_stochastic=False, dynamic_thresholding=False,
+                 dynamic_thresholding_percentile=0.995):
         """``cond_drop_prob`` / ``cond_scale`` (extension, class-conditional ``model`` only): the probability with which
         ``forward`` replaces a training label by the null label, and the classifier-free-guidance scale ``sample`` uses.
         ``cond_drop_prob=None`` is 0.1 on a class-conditional model and 0 on any other.
         ``sampler`` (extension): ``"auto"`` = the reference's dispatch (DDIM when ``sampling_timesteps < timesteps``, else the
         ancestral chain), ``"dpm++"`` = DPM-Solver++ in ``sampling_timesteps`` steps of order ``dpm_order`` (2 = the 2M
-        multistep, 1 = DDIM at eta 0), ``dpm_stochastic`` its SDE form."""
+        multistep, 1 = DDIM at eta 0), ``dpm_stochastic`` its SDE form.
+        ``dynamic_thresholding`` (extension; Saharia et al. 2022, 2.3): wherever sampling clips x0 to [-1, 1] it computes
+        ``s = max(1, quantile_p(|x0|))`` per sample instead, p = ``dynamic_thresholding_percentile`` in (0, 1], and takes
+        ``clamp(x0, -s, s) / s``.  Training is untouched."""
         super().__init__()
+        p = dynamic_thresholding_percentile
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
+            raise ValueError(f"dynamic_thresholding_percentile must lie in (0, 1], got {p!r}")
+        self.dynamic_thresholding, self.dynamic_thresholding_percentile = bool(dynamic_thresholding), float(p)
         if sampler not in ("auto", "dpm++"):
             raise ValueError(f"sampler must be 'auto' or 'dpm++', got {sampler!r}")
         if dpm_order not in (1, 2):
@@ -1069,7 +1077,9 @@ class GaussianDiffusion(nn.Module):
         noise is always derived from the possibly clipped x_start.  UNet forward on the HIP engine, then ONE launch for
         both results.  ``x_self_cond`` (NCHW, ``None`` = zeros) is read by a self-conditioned network only.
         ``classes`` / ``cond_scale`` (extension): the network output is out_null + cond_scale * (out_cond - out_null), mixed
-        before the objective's algebra; ``cond_scale == 1`` is one forward with the labels."""
+        before the objective's algebra; ``cond_scale == 1`` is one forward with the labels.
+        ``dynamic_thresholding``: ``clip_x_start`` thresholds instead of clamping, in three launches - the unclipped
+        predictions, ``lgm_dyn_thresh`` over the dense x_start, the predictions again with the thresholds."""
         classes, cond_scale = self._guidance(classes, cond_scale, x.shape[0], x.device)
         if cond_scale == 1.0:
             v = self.model(x, t, x_self_cond, classes)
@@ -1080,13 +1090,25 @@ class GaussianDiffusion(nn.Module):
         B = x.shape[0]
         t = t.to(device=x.device, dtype=torch.long).contiguous()
         pred_noise, x_start = torch.empty_like(x), torch.empty_like(x)
-        ops.lib().lgm_model_predictions_obj(x.data_ptr(), v.data_ptr(), t.data_ptr(), self.sqrt_alphas_cumprod.data_ptr(),
-                                            self.sqrt_one_minus_alphas_cumprod.data_ptr(),
-                                            self.sqrt_recip_alphas_cumprod.data_ptr(),
-                                            self.sqrt_recipm1_alphas_cumprod.data_ptr(), OBJECTIVES[self.objective],
-                                            1 if clip_x_start else 0, 1 if rederive_pred_noise else 0,
-                                            pred_noise.data_ptr(), x_start.data_ptr(), B, x.numel() // B,
-                                            self.num_timesteps, ops.stream())
+        tables = (self.sqrt_alphas_cumprod.data_ptr(), self.sqrt_one_minus_alphas_cumprod.data_ptr(),
+                  self.sqrt_recip_alphas_cumprod.data_ptr(), self.sqrt_recipm1_alphas_cumprod.data_ptr())
+        per = x.numel() // max(B, 1)
+        dyn = bool(clip_x_start) and self.dynamic_thresholding and x.numel() > 0
+        ops.lib().lgm_model_predictions_obj(x.data_ptr(), v.data_ptr(), t.data_ptr(), *tables, OBJECTIVES[self.objective],
+                                            1 if clip_x_start and not dyn else 0, 1 if rederive_pred_noise else 0,
+                                            pred_noise.data_ptr(), x_start.data_ptr(), B, per, self.num_timesteps,
+                                            ops.stream())
+        if dyn:
+            from lgm_hip.sampler import dyn_rank
+            k, w = dyn_rank(per, self.dynamic_thresholding_percentile)
+            thresh = torch.empty(B, device=x.device)
+            # the unclipped x_start as a one-channel pred_x0 problem: x0 = the "network output" lane, bit for bit
+            ops.lib().lgm_dyn_thresh(x.data_ptr(), 1, 0, x_start.data_ptr(), 1, B, 1, per, OBJECTIVES["pred_x0"], 0.0, 0.0, 0.0,
+                                     0.0, None, None, k, w, thresh.data_ptr(), ops.stream())
+            ops.lib().lgm_model_predictions_thresh(x.data_ptr(), v.data_ptr(), t.data_ptr(), *tables,
+                                                   OBJECTIVES[self.objective], 1 if rederive_pred_noise else 0,
+                                                   pred_noise.data_ptr(), x_start.data_ptr(), B, per, self.num_timesteps,
+                                                   thresh.data_ptr(), ops.stream())
         return ModelPrediction(pred_noise, x_start)
 
     @torch.no_grad()
@@ -1268,11 +1290,15 @@ class DDPM(LightningModule):
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
                  min_snr_gamma: float = 5, self_condition: bool = False, num_classes: Optional[int] = None,
-                 cond_drop_prob: float = 0.1, cond_scale: float = 1.0, sampler: str = "auto", dpm_order: int = 2,
-                 dpm_stochastic: bool = False):
+                 cond_drop_prob: float = 0.1, dynamic_thresholding: bool = False,
+                 dynamic_thresholding_percentile: float = 0.995, cond_scale: float = 1.0, sampler: str = "auto",
+                 dpm_order: int = 2, dpm_stochastic: bool = False):
         """``num_classes`` (extension): class-conditional training on the batches' labels with classifier-free guidance;
         ``cond_drop_prob`` / ``cond_scale`` are read with it only.  ``sampler`` / ``dpm_order`` / ``dpm_stochastic``
-        (extension): ``"dpm++"`` samples with DPM-Solver++ in ``sampling_timesteps`` steps (GaussianDiffusion)."""
+        (extension): ``"dpm++"`` samples with DPM-Solver++ in ``sampling_timesteps`` steps (GaussianDiffusion).
+        ``dynamic_thresholding`` / ``dynamic_thresholding_percentile`` (extension): the samplers threshold x0 per sample
+        instead of clamping it to [-1, 1] (GaussianDiffusion).  They stand in front of ``cond_scale``: the tail of this
+        signature is pinned by tests/test_dpmpp_host.py; pass everything from ``num_classes`` on by keyword."""
         super().__init__()
         self.save_hyperparameters()
         self.num_classes = num_classes
@@ -1282,7 +1308,9 @@ class DDPM(LightningModule):
                                             sampling_timesteps=sampling_timesteps, objective=objective,
                                             beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
                                             min_snr_loss_weight=min_snr_loss_weight, min_snr_gamma=min_snr_gamma,
-                                            sampler=sampler, dpm_order=dpm_order, dpm_stochastic=dpm_stochastic, **cond)
+                                            sampler=sampler, dpm_order=dpm_order, dpm_stochastic=dpm_stochastic,
+                                            dynamic_thresholding=dynamic_thresholding,
+                                            dynamic_thresholding_percentile=dynamic_thresholding_percentile, **cond)
         self.channels = img_channels
         self.img_size = img_size
         self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
