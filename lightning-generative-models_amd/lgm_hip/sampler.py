@@ -1,47 +1,38 @@
-"""Reverse-diffusion sampling loops on the HIP engine.
+"""Reverse-diffusion sampling on the HIP engine: the ancestral chain, DDIM and DPM-Solver++(2M).
 
-Reference: GaussianDiffusion.p_sample_loop ddpm.py:759-780, ddim_sample :782-834,
-model_predictions :707-734, p_sample :748-757.  The reference copies the image to the host
-at EVERY step (``img.detach().cpu()`` :775,829); here the whole chain stays on the device:
-per step = one UNet forward (HIP engine, NHWC) + one fused update kernel.
+Reference: GaussianDiffusion.p_sample_loop ddpm.py:759-780, ddim_sample :782-834, model_predictions :707-734, p_sample
+:748-757; DPM-Solver++ (Lu et al. 2022) and dynamic thresholding (Saharia et al. 2022) are extensions.  The reference copies
+the image to the host at EVERY step (``img.detach().cpu()`` :775,829); here the whole chain stays on the device: per step one
+UNet forward (two and ``lgm_cfg_mix`` when guided) and one fused update kernel, one launch more when x0 is thresholded.
 
-Two ways to run a chain, bit-identical in their results (tests/test_hip_unet.py):
-  * graph replay (default on the GPU when only the final image is wanted): ONE HIP graph per (network, shape)
-    holds a whole step — t[b] <- device table[step counter], UNet forward, noise draw, in-place update with the
-    step's scalars read from a device table, counter += 1 — and is replayed once per step: no Python between
-    the ~230 launches of a step, no host syncs, no per-step allocations (``lgm_sample_step_table_slice``);
-  * eager launches (``return_all_timesteps``, ``LGM_NO_SAMPLER_GRAPH=1``, or when capture fails): per-timestep
-    scalars from host copies of the schedule buffers (``lgm_sample_step_slice`` / ``lgm_sample_step_obj``).
+Top down:
+  * Coefficients.  A step is a row of 8 float32 values: the head (A, Bv, R, Rm1) of ``_head``, with which the kernel turns the
+    network output into x0 and noise whatever the objective, then the update's four weights, the last one the noise's
+    (``_p_sample_coeffs``, ``_ddim_coeffs``, ``dpm_coeffs`` over ``dpm_plan``).  Host arithmetic: no device, no library.
+  * ``_Plan``: everything a sampler is, one builder per sampler.
+  * ``_launch_update``: the one place that picks an update entry point and lists its arguments, the row by value (eager
+    launches) or read on the device from a table row (the captured step).
+  * ``_Chain``, the device-resident state of a run and its eager step; ``_GraphedChain``, one captured step per ``_graph_key``:
+    t[b] <- time table[counter], forward, noise draw, in-place update from coefficient table[counter], counter += 1 - replayed
+    once per step with no Python between the ~230 launches, no host sync and no allocation.
+  * ``_run``: a chain of a plan.  Graph replay when only the final image is wanted, eager launches otherwise
+    (``return_all_timesteps``, ``LGM_NO_SAMPLER_GRAPH=1``, no device, capture failed); bit-identical (tests/test_hip_unet.py).
 
-Every objective takes the same update kernel with the same scalars and table, the objective's branch of model_predictions
-inside; the ancestral step clips x0 only, DDIM also re-derives the noise from the clipped x0 (reference :720-721, 808-810).
-
-The update reads x from its slice of the network's input buffer (Unet.input_buffer) and writes the next x there.  A
-self-conditioned network (reference :773-774, 807-810, 864-865) has a second slice: the x_start the reference hands on
-(clipped, as p_sample and ddim_sample clip it) goes into that self-conditioning slice, which the next step reads.  A chain
-starts with that slice zero: the reference's ``x_start = None``.  For any other network the eager step writes x_start into a
-buffer of its own (``lgm_sample_step_obj``), for ``p_sample`` to return.
-
-A class-conditional network (``Unet(num_classes=K)``) reads one label per sample, fixed for the run.  With a guidance scale
-other than 1 a step is two forwards over the SAME input buffer - the labels, then the null label - and ``lgm_cfg_mix``
-(out_null + scale * (out_cond - out_null), in place in the conditional output) in front of the update kernel, in the eager
-launches and in the captured step alike; labels and scale of a captured step live in static buffers.
-
-DPM-Solver++(2M) (``dpm_solver_sample``; Lu et al. 2022, an extension of the reference) runs on the same two paths with an
-update kernel of its own (``lgm_dpm_step`` / ``lgm_dpm_step_table``) and one more buffer, the previous step's clipped x0; its
-coefficient rows come from ``dpm_plan`` / ``dpm_coeffs``, float64 arithmetic on the host that needs neither device nor library.
-
-Dynamic thresholding (``GaussianDiffusion(dynamic_thresholding=True)``; Saharia et al. 2022, an extension of the reference)
-replaces the static clamp of x0 in every sampler by ``clamp(x0, -s, s) / s`` with ``s = max(1, quantile_p(|x0|))`` per sample.
-A thresholded step is forward(s) -> [``lgm_cfg_mix``] -> ``lgm_dyn_thresh`` (one workgroup per sample writes s into the chain's
-``[B]`` threshold buffer) -> the update kernel reading that buffer (``lgm_sample_step_thresh`` / ``lgm_dpm_step_thresh``): one
-launch more per step, in eager launches and in the captured step alike.  The rank the kernel selects comes from ``dyn_rank``,
-host arithmetic like the solver's plan.  Without thresholding every chain issues the launches it issued before.
+Buffers.  The update reads x from its slice of the network's input buffer (Unet.input_buffer) and writes the next x there.  A
+self-conditioned network (reference :773-774, 807-810, 864-865) has a second slice: the clipped x_start the reference hands on
+goes there for the next step to read; a chain starts with it zero, the reference's ``x_start = None``.  For any other network
+the eager ancestral / DDIM step writes x_start into a buffer of its own, for ``p_sample`` to return.  DPM-Solver++ keeps the
+previous step's clipped x0 in ``hist``.  A thresholded step first has one workgroup per sample write s = max(1,
+quantile_p(|x0|)) into ``thresh``; the update then takes clamp(x0, -s, s) / s in place of the static clamp.  A class-conditional
+network reads one label per sample, fixed for the run; labels and guidance scale of a captured step live in static buffers.
 """
 from __future__ import annotations
 
 import math
 import os
+import sys
+import weakref
+from dataclasses import dataclass
 from typing import List, Optional
 
 import torch
@@ -89,135 +80,29 @@ def _dyn(gd) -> Optional[float]:
     return float(gd.dynamic_thresholding_percentile) if getattr(gd, "dynamic_thresholding", False) else None
 
 
-class _Chain:
-    """Device-resident state of one sampling run (NHWC, padded channels)."""
-
-    def __init__(self, gd, shape, init_noise: Optional[torch.Tensor], x_self_cond: Optional[torch.Tensor] = None,
-                 classes=None, cond_scale: float = 1.0):
-        self.gd = gd
-        self.net = net = gd.model
-        B, C, H, W = shape
-        self.shape = shape
-        dev = gd.betas.device
-        self.net.prepare_hip(dev)
-        # the run's labels on the device (None: a network without classes) and its guidance scale
-        self.classes, self.cond_scale = gd._guidance(classes, cond_scale, B, dev)
-        self.Cp = _r4(C)
-        if init_noise is None:
-            init_noise = torch.randn(shape, device=dev)
-        if net.self_condition:
-            # both slices live in the input buffer; the update kernel writes the x_start of a step where the next step reads it
-            self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)
-            ops.nchw_to_nhwc(init_noise.float().contiguous(), net.x_slice(self.x, pad=True))
-            if x_self_cond is not None:
-                ops.nchw_to_nhwc(x_self_cond.float().contiguous(), net.sc_slice(self.x))
-            self.x_next = torch.zeros_like(self.x)
-            self.x0 = None                       # after a step: the self-conditioning slice of self.x
-        else:
-            self.x = torch.empty((B, H, W, self.Cp), device=dev)
-            ops.nchw_to_nhwc(init_noise.float().contiguous(), self.x)
-            self.x_next = torch.empty_like(self.x)
-            self.x0 = torch.empty_like(self.x)
-        self.tbuf = {}
-        self.hist = None                         # DPM-Solver++ only: the previous step's clipped x0 (dpm_step)
-        # dynamic thresholding: the rank lgm_dyn_thresh selects and the [B] buffer it writes (readable after a step)
-        self.dyn = None if _dyn(gd) is None else dyn_rank(C * H * W, _dyn(gd))
-        self.thresh = torch.zeros(B, device=dev) if self.dyn is not None else None
-
-    def _dyn_thresh(self, v, head):
-        """s[b] of the step into ``self.thresh``: from the x slice, the network output and the head (A, Bv, R, Rm1)"""
-        B, C, H, W = self.shape
-        net = self.net
-        ops.lib().lgm_dyn_thresh(self.x.data_ptr(), net.in_pitch, net.x_off, v.data_ptr(), ops.pitch(v), B, C, H * W,
-                                 _objective(self.gd), *head, None, None, self.dyn[0], self.dyn[1], self.thresh.data_ptr(),
-                                 ops.stream())
-
-    def times(self, t: int) -> torch.Tensor:
-        tb = self.tbuf.get(t)
-        if tb is None:
-            tb = torch.full((self.shape[0],), t, device=self.x.device, dtype=torch.long)
-            if len(self.tbuf) < 4096:
-                self.tbuf[t] = tb
-        return tb
-
-    def step(self, t: int, noise: Optional[torch.Tensor], coeffs, rederive: bool = False):
-        """One update with clipped x0; ``coeffs`` = (A, Bv, R, Rm1, C0, C1, C2, C3) of ``_p_sample_coeffs`` / ``_ddim_coeffs``"""
-        B, C, H, W = self.shape
-        v = self.net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
-        nz = None if noise is None else noise.data_ptr()
-        A, Bv, R, Rm1, C0, C1, C2, C3 = coeffs
-        net = self.net
-        if self.dyn is not None:                 # thresholded: s[b] first, then the update that reads it
-            self._dyn_thresh(v, (A, Bv, R, Rm1))
-            ops.lib().lgm_sample_step_thresh(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
-                                             v.data_ptr(), ops.pitch(v), nz, None if net.self_condition else self.x0.data_ptr(),
-                                             B, C, H * W, _objective(self.gd), 1 if rederive else 0, A, Bv, R, Rm1, C0, C1,
-                                             C2, C3, None, None, 0, self.thresh.data_ptr(), ops.stream())
-            if net.self_condition:
-                self.x0 = net.sc_slice(self.x_next)
-        elif net.self_condition:                 # x_start into the self-conditioning slice the next step reads
-            ops.lib().lgm_sample_step_slice(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
-                                            v.data_ptr(), ops.pitch(v), nz, B, C, H * W, _objective(self.gd), A, Bv, 1,
-                                            1 if rederive else 0, R, Rm1, C0, C1, C2, C3, ops.stream())
-            self.x0 = net.sc_slice(self.x_next)
-        else:                                    # x_start into the buffer p_sample returns
-            ops.lib().lgm_sample_step_obj(self.x.data_ptr(), v.data_ptr(), nz, self.x_next.data_ptr(), self.x0.data_ptr(),
-                                          B, C, H * W, self.Cp, _objective(self.gd), A, Bv, 1, 1 if rederive else 0, R, Rm1,
-                                          C0, C1, C2, C3, ops.stream())
-        self.x, self.x_next = self.x_next, self.x
-
-    def dpm_step(self, t: int, noise: Optional[torch.Tensor], coeffs):
-        """One DPM-Solver++ update; ``coeffs`` = one row (A, Bv, R, Rm1, K_x, K_0, K_1, K_n) of ``dpm_coeffs``.  The clipped
-        x0 goes into the history buffer (the solver's one piece of state, made by the first step of a chain) and, self-
-        conditioned, into the slice the next step reads."""
-        B, C, H, W = self.shape
-        if self.hist is None:
-            self.hist = torch.empty((B, H, W, self.Cp), device=self.x.device)
-        v = self.net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
-        net = self.net
-        A, Bv, R, Rm1, Kx, K0, K1, Kn = coeffs
-        if self.dyn is not None:
-            self._dyn_thresh(v, (A, Bv, R, Rm1))
-            ops.lib().lgm_dpm_step_thresh(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
-                                          v.data_ptr(), ops.pitch(v), None if noise is None else noise.data_ptr(),
-                                          self.hist.data_ptr(), B, C, H * W, _objective(self.gd), A, Bv, R, Rm1, Kx, K0, K1,
-                                          Kn, None, None, 0, self.thresh.data_ptr(), ops.stream())
-        else:
-            ops.lib().lgm_dpm_step(self.x.data_ptr(), self.x_next.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(),
-                                   ops.pitch(v), None if noise is None else noise.data_ptr(), self.hist.data_ptr(), B, C,
-                                   H * W, _objective(self.gd), A, Bv, 1, R, Rm1, Kx, K0, K1, Kn, ops.stream())
-        self.x0 = net.sc_slice(self.x_next) if net.self_condition else self.hist
-        self.x, self.x_next = self.x_next, self.x
-
-    def image(self, unnormalize: bool) -> torch.Tensor:
-        B, C, H, W = self.shape
-        out = torch.empty(self.shape, device=self.x.device)
-        ops.nhwc_to_nchw(self.net.x_slice(self.x), out)
-        if unnormalize:
-            out.mul_(0.5).add_(0.5)     # unnormalize_to_zero_to_one, once per sampling run
-        return out
+def _head(hs, t: int):
+    """(A, Bv, R, Rm1) at step t: x0 and noise from x and the network output, for every objective"""
+    return (_f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t]),
+            _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t]))
 
 
 def _p_sample_coeffs(gd, t: int):
-    """(A, Bv, R, Rm1, C0, C1, C2, C3) of one ancestral step — the scalars p_sample_step hands to the kernel"""
+    """(A, Bv, R, Rm1, C0, C1, C2, C3) of one ancestral step (p_sample :748-757): posterior mean + sigma * noise; sigma is
+    zero at t == 0 and nowhere else (the log variance is clipped at log 1e-20)"""
     hs = _host_schedule(gd)
     sigma = _f32(torch.as_tensor(0.5 * hs["posterior_log_variance_clipped"][t]).exp()) if t > 0 else 0.0
-    return (_f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t]),
-            _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t]),
-            _f32(hs["posterior_mean_coef1"][t]), _f32(hs["posterior_mean_coef2"][t]), 0.0, sigma)
+    return _head(hs, t) + (_f32(hs["posterior_mean_coef1"][t]), _f32(hs["posterior_mean_coef2"][t]), 0.0, sigma)
 
 
 def _ddim_coeffs(gd, t: int, t_next: int, eta: float):
     """the same 8 scalars of one DDIM step (loop body :805-829); t_next < 0: the last step returns x0"""
     hs = _host_schedule(gd)
-    head = (_f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t]),
-            _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t]))
     if t_next < 0:
-        return head + (1.0, 0.0, 0.0, 0.0)
+        return _head(hs, t) + (1.0, 0.0, 0.0, 0.0)
     a, an = hs["alphas_cumprod"][t], hs["alphas_cumprod"][t_next]
     sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()
     c = (1 - an - sigma ** 2).sqrt()
-    return head + (_f32(an.sqrt()), 0.0, _f32(c), _f32(sigma))
+    return _head(hs, t) + (_f32(an.sqrt()), 0.0, _f32(c), _f32(sigma))
 
 
 def dpm_plan(gd, pairs=None, order: int = 2, stochastic: bool = False):
@@ -263,18 +148,168 @@ def dpm_coeffs(gd, pairs=None, order: int = 2, stochastic: bool = False):
     kernel, then ``dpm_plan``'s row, every K computed in float64 and rounded once."""
     pairs = gd.ddim_time_pairs() if pairs is None else [(int(a), int(b)) for a, b in pairs]
     hs = _host_schedule(gd)
-    return [(_f32(hs["sqrt_alphas_cumprod"][t]), -_f32(hs["sqrt_one_minus_alphas_cumprod"][t]),
-             _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t]))
-            + tuple(_f32(k) for k in row)
-            for (t, _), row in zip(pairs, dpm_plan(gd, pairs, order, stochastic))]
+    return [_head(hs, t) + tuple(_f32(k) for k in row) for (t, _), row in zip(pairs, dpm_plan(gd, pairs, order, stochastic))]
 
 
-# net -> {(shape, with_noise): _GraphedChain}.  Weak on the network: a sampled model that goes away takes its graphs
+@dataclass(frozen=True)
+class _Plan:
+    """A sampler: ``times[i]`` and ``rows[i]`` (8 float32 values) of step i; ``draws[i]``: the eager loop draws noise for it (or
+    takes the caller's); ``with_noise``: the captured step has a noise operand; ``rederive`` / ``dpm``: see the module text."""
+    times: tuple
+    rows: tuple
+    draws: tuple
+    with_noise: bool
+    rederive: bool = False
+    dpm: bool = False
+
+
+def _plan_ancestral(gd, start: Optional[int] = None, steps: Optional[int] = None) -> _Plan:
+    """p_sample_loop :759-780 from step ``start`` - 1 (default T - 1) down to 0, or its first ``steps`` steps"""
+    ts = tuple(reversed(range(gd.num_timesteps if start is None else int(start))))[:steps]
+    return _Plan(ts, tuple(_p_sample_coeffs(gd, t) for t in ts), tuple(t > 0 for t in ts), True)
+
+
+def _plan_ddim(gd) -> _Plan:
+    eta, pairs = gd.ddim_sampling_eta, gd.ddim_time_pairs()
+    return _Plan(tuple(t for t, _ in pairs), tuple(_ddim_coeffs(gd, t, t_next, eta) for t, t_next in pairs),
+                 tuple(t_next >= 0 and eta != 0.0 for _, t_next in pairs), eta != 0.0, rederive=True)
+
+
+def _plan_dpm(gd) -> _Plan:
+    """``gd.dpm_order`` 1 or 2, ``gd.dpm_stochastic``: the SDE form, the only one that takes noise"""
+    stochastic, pairs = bool(gd.dpm_stochastic), gd.dpm_time_pairs()
+    return _Plan(tuple(t for t, _ in pairs), tuple(dpm_coeffs(gd, pairs, gd.dpm_order, stochastic)),
+                 tuple(t_next >= 0 and stochastic for _, t_next in pairs), stochastic, dpm=True)
+
+
+def _launch_thresh(net, shape, objective: int, x, v, head, rank, thresh, table=None, counter=None):
+    """s[b] of a step into ``thresh``: from the x slice of ``x``, the network output ``v`` and the head (A, Bv, R, Rm1) by
+    value, or from the row ``table[counter]`` (the by-value slots are then zero); ``rank`` = ``dyn_rank`` of a sample"""
+    B, C, H, W = shape
+    ops.lib().lgm_dyn_thresh(x.data_ptr(), net.in_pitch, net.x_off, v.data_ptr(), ops.pitch(v), B, C, H * W, objective, *head,
+                             ops._p(table), ops._p(counter), *rank, thresh.data_ptr(), ops.stream())
+
+
+def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, hist=None, thresh=None, rank=None, row=None,
+                   table=None, counter=None, rederive: bool = False, dpm: bool = False):
+    """The update of one step: ``x_next`` <- x slice of ``x``, network output ``v``, ``noise`` (None: none).  The row comes by
+    value (``row``, eager launches) or from ``table[counter]`` (the captured step, which also advances the counter and passes
+    zeros in the by-value slots).  ``rank`` (dynamic thresholding) puts ``_launch_thresh`` in front.  Every update clips x0.
+
+        solver            thresholded  row       self-conditioned  kernel entry
+        ancestral / DDIM  no           by value  yes               step_slice: x0 into the self-conditioning slice
+        ancestral / DDIM  no           by value  no                step_obj: x0 into ``x0``
+        ancestral / DDIM  no           table     either            step_table_slice, in place
+        ancestral / DDIM  yes          either    either            step_thresh (x0 into ``x0`` only by value, not self-cond.)
+        DPM               no           by value  either            dpm_step: x0 into ``hist`` (and the slice)
+        DPM               no           table     either            dpm_step_table
+        DPM               yes          either    either            dpm_step_thresh
+    """
+    B, C, H, W = shape
+    L, st, p = ops.lib(), ops.stream(), ops._p
+    tabled = table is not None
+    A, Bv, R, Rm1, W0, W1, W2, W3 = row if not tabled else (0.0,) * 8
+    red, tab = 1 if rederive else 0, (p(table), p(counter))
+    src = (net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v), p(noise))
+    if rank is not None:
+        _launch_thresh(net, shape, objective, x, v, (A, Bv, R, Rm1), rank, thresh, table, counter)
+        end = (A, Bv, R, Rm1, W0, W1, W2, W3, *tab, 1 if tabled else 0, thresh.data_ptr(), st)
+        if dpm:
+            L.lgm_dpm_step_thresh(x.data_ptr(), x_next.data_ptr(), *src, hist.data_ptr(), B, C, H * W, objective, *end)
+        else:
+            L.lgm_sample_step_thresh(x.data_ptr(), x_next.data_ptr(), *src, None if net.self_condition or tabled else p(x0),
+                                     B, C, H * W, objective, red, *end)
+    elif dpm and tabled:
+        L.lgm_dpm_step_table(x.data_ptr(), *src, hist.data_ptr(), B, C, H * W, *tab, objective, 1, 1, st)
+    elif dpm:
+        L.lgm_dpm_step(x.data_ptr(), x_next.data_ptr(), *src, hist.data_ptr(), B, C, H * W, objective, A, Bv, 1, R, Rm1, W0, W1,
+                       W2, W3, st)
+    elif tabled:
+        L.lgm_sample_step_table_slice(x.data_ptr(), *src, B, C, H * W, *tab, objective, 1, red, 1, st)
+    elif net.self_condition:
+        L.lgm_sample_step_slice(x.data_ptr(), x_next.data_ptr(), *src, B, C, H * W, objective, A, Bv, 1, red, R, Rm1, W0, W1,
+                                W2, W3, st)
+    else:
+        L.lgm_sample_step_obj(x.data_ptr(), v.data_ptr(), p(noise), x_next.data_ptr(), x0.data_ptr(), B, C, H * W, _r4(C),
+                              objective, A, Bv, 1, red, R, Rm1, W0, W1, W2, W3, st)
+
+
+class _Chain:
+    """Device-resident state of one sampling run (NHWC, padded channels) and its eager step."""
+
+    def __init__(self, gd, shape, init_noise: Optional[torch.Tensor], x_self_cond: Optional[torch.Tensor] = None,
+                 classes=None, cond_scale: float = 1.0):
+        self.gd = gd
+        self.net = net = gd.model
+        B, C, H, W = shape
+        self.shape = shape
+        dev = gd.betas.device
+        self.net.prepare_hip(dev)
+        # the run's labels on the device (None: a network without classes) and its guidance scale
+        self.classes, self.cond_scale = gd._guidance(classes, cond_scale, B, dev)
+        self.Cp = _r4(C)
+        if init_noise is None:
+            init_noise = torch.randn(shape, device=dev)
+        if net.self_condition:
+            # both slices live in the input buffer; the update kernel writes the x_start of a step where the next step reads it
+            self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)
+            ops.nchw_to_nhwc(init_noise.float().contiguous(), net.x_slice(self.x, pad=True))
+            if x_self_cond is not None:
+                ops.nchw_to_nhwc(x_self_cond.float().contiguous(), net.sc_slice(self.x))
+            self.x_next = torch.zeros_like(self.x)
+            self.x0 = None                       # after a step: the self-conditioning slice of self.x
+        else:
+            self.x = torch.empty((B, H, W, self.Cp), device=dev)
+            ops.nchw_to_nhwc(init_noise.float().contiguous(), self.x)
+            self.x_next = torch.empty_like(self.x)
+            self.x0 = torch.empty_like(self.x)
+        self.tbuf = {}
+        self.hist = None                         # DPM-Solver++ only: the previous step's clipped x0, made by the first step
+        # dynamic thresholding: the rank the threshold kernel selects and the [B] buffer it writes (readable after a step)
+        self.dyn = None if _dyn(gd) is None else dyn_rank(C * H * W, _dyn(gd))
+        self.thresh = torch.zeros(B, device=dev) if self.dyn is not None else None
+
+    def _dyn_thresh(self, v, head):
+        """s[b] of the step into ``self.thresh``: from the x slice, the network output and the head (A, Bv, R, Rm1)"""
+        _launch_thresh(self.net, self.shape, _objective(self.gd), self.x, v, head, self.dyn, self.thresh)
+
+    def times(self, t: int) -> torch.Tensor:
+        tb = self.tbuf.get(t)
+        if tb is None:
+            tb = torch.full((self.shape[0],), t, device=self.x.device, dtype=torch.long)
+            if len(self.tbuf) < 4096:
+                self.tbuf[t] = tb
+        return tb
+
+    def step(self, t: int, noise: Optional[torch.Tensor], row, rederive: bool = False, dpm: bool = False):
+        """One eager step at time t from a row of 8; no noise operand where the row weighs it with zero (t == 0 of the
+        ancestral chain, eta == 0, the ODE, a last step that returns x0).  Afterwards ``x`` is the new image and ``x0`` the
+        clipped x_start: the self-conditioning slice of ``x``, else ``hist`` (DPM-Solver++), else the buffer of its own."""
+        B, C, H, W = self.shape
+        net = self.net
+        if dpm and self.hist is None:
+            self.hist = torch.empty((B, H, W, self.Cp), device=self.x.device)
+        v = net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
+        _launch_update(net, self.shape, _objective(self.gd), v, noise if row[7] != 0.0 else None, x=self.x, x_next=self.x_next,
+                       x0=self.x0, hist=self.hist, thresh=self.thresh, rank=self.dyn, row=row, rederive=rederive, dpm=dpm)
+        if net.self_condition:
+            self.x0 = net.sc_slice(self.x_next)
+        elif dpm:
+            self.x0 = self.hist
+        self.x, self.x_next = self.x_next, self.x
+
+    def image(self, unnormalize: bool) -> torch.Tensor:
+        out = torch.empty(self.shape, device=self.x.device)
+        ops.nhwc_to_nchw(self.net.x_slice(self.x), out)
+        if unnormalize:
+            out.mul_(0.5).add_(0.5)     # unnormalize_to_zero_to_one, once per sampling run
+        return out
+
+
+# net -> {_graph_key(...): _GraphedChain}.  Weak on the network: a sampled model that goes away takes its graphs
 # (and their memory pool) with it.  Every entry remembers which flat parameter storage its launches were captured
 # against (see _GraphedChain.matches): a graph bakes buffer ADDRESSES in, so after prepare_hip() rebuilt the flat
 # storage (model.to(), replaced parameter storage) the entry is dropped and the step recaptured.
-import weakref
-
 _GRAPHS = weakref.WeakKeyDictionary()
 _CAPTURE_RETRY_AFTER = 8      # a failed capture is retried after this many eager chains, not cached for ever
 
@@ -301,7 +336,7 @@ class _GraphedChain:
         self.table = torch.zeros((max_steps, 8), device=dev)
         self.ttable = torch.zeros(max_steps, dtype=torch.long, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        # class-conditional network: the run's labels; guided step: its scale, read on the device by lgm_cfg_mix
+        # class-conditional network: the run's labels; guided step: its scale, read on the device by the mix
         self.classes = net.labels(None, B, dev).clone() if net.num_classes is not None else None
         self.scale = torch.ones(1, device=dev) if guided else None
         # DPM-Solver++: the previous step's clipped x0, static like the input buffer; a chain's first row has K_1 = 0
@@ -312,41 +347,16 @@ class _GraphedChain:
         rank = None if dyn is None else dyn_rank(C * H * W, dyn)
         self.inject = False
         self.max_steps = max_steps
-        L = ops.lib()
 
         def one_step():
-            st = ops.stream()
-            L.lgm_sampler_time(self.ttable.data_ptr(), self.counter.data_ptr(), self.t.data_ptr(), B, st)
+            ops.lib().lgm_sampler_time(self.ttable.data_ptr(), self.counter.data_ptr(), self.t.data_ptr(), B, ops.stream())
             v = net.forward_guided(self.x, self.t, self.classes, 1.0, refresh_weights=False, scale_dev=self.scale)
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
-            nzp = None if nz is None else nz.data_ptr()
-            if rank is not None:                 # s[b] from the table row's head, then the update that reads it
-                L.lgm_dyn_thresh(self.x.data_ptr(), net.in_pitch, net.x_off, v.data_ptr(), ops.pitch(v), B, C, H * W, objective,
-                                 0.0, 0.0, 0.0, 0.0, self.table.data_ptr(), self.counter.data_ptr(), rank[0], rank[1],
-                                 self.thresh.data_ptr(), ops.stream())
-                zeros = (0.0,) * 8
-                if dpm:
-                    L.lgm_dpm_step_thresh(self.x.data_ptr(), self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
-                                          v.data_ptr(), ops.pitch(v), nzp, self.hist.data_ptr(), B, C, H * W, objective, *zeros,
-                                          self.table.data_ptr(), self.counter.data_ptr(), 1, self.thresh.data_ptr(),
-                                          ops.stream())
-                else:
-                    L.lgm_sample_step_thresh(self.x.data_ptr(), self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
-                                             v.data_ptr(), ops.pitch(v), nzp, None, B, C, H * W, objective,
-                                             1 if rederive else 0, *zeros, self.table.data_ptr(), self.counter.data_ptr(), 1,
-                                             self.thresh.data_ptr(), ops.stream())
-                return
-            if dpm:
-                L.lgm_dpm_step_table(self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v),
-                                     None if nz is None else nz.data_ptr(), self.hist.data_ptr(), B, C, H * W,
-                                     self.table.data_ptr(), self.counter.data_ptr(), objective, 1, 1, ops.stream())
-                return
             # x (and, self-conditioned, the x_start handed on): the slices of the static buffer, in place
-            L.lgm_sample_step_table_slice(self.x.data_ptr(), net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v),
-                                          None if nz is None else nz.data_ptr(), B, C, H * W, self.table.data_ptr(),
-                                          self.counter.data_ptr(), objective, 1, 1 if rederive else 0, 1, ops.stream())
+            _launch_update(net, shape, objective, v, nz, x=self.x, x_next=self.x, hist=self.hist, thresh=self.thresh, rank=rank,
+                           table=self.table, counter=self.counter, rederive=rederive, dpm=dpm)
 
         net.refresh_derived_weights(False)
         rng_state = torch.cuda.get_rng_state(dev)
@@ -393,16 +403,28 @@ class _GraphedChain:
         self.table[:n].copy_(torch.tensor(coeffs, dtype=torch.float32), non_blocking=False)
         self.ttable[:n].copy_(torch.tensor(times, dtype=torch.long))
         self.counter.zero_()
+        inject = noises is not None and self.with_noise
         for i in range(n):
-            if noises is not None and self.with_noise and noises[i] is not None:
+            if inject and noises[i] is not None:
                 self.noise.copy_(noises[i])
-                self.graphs[True].replay()
-            elif noises is not None and self.with_noise:
+            elif inject:
                 self.noise.zero_()
-                self.graphs[True].replay()
-            else:
-                self.graphs[False].replay()
+            self.graphs[inject].replay()
         return self.x
+
+
+def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: bool):
+    """The cache key of a captured step under its network: everything baked into the launches that the network does not fix"""
+    key = (tuple(shape), bool(with_noise))
+    if gd.objective != "pred_v":                     # two diffusions of other objectives may share one network
+        key += (gd.objective, bool(rederive))
+    if guided:                                       # two forwards and the mix per step: a graph of its own
+        key += ("guided",)
+    if dpm:                                          # never the key of an ancestral / DDIM step, whatever the objective
+        key = ("dpm++", gd.objective) + key
+    if _dyn(gd) is not None:                         # the percentile in it: the rank is baked into the launch
+        key = ("dynthresh", _dyn(gd)) + key
+    return key
 
 
 def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bool = False, dpm: bool = False):
@@ -413,20 +435,8 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
         return None
     net = gd.model
     net.prepare_hip(gd.betas.device)                 # may rebuild the flat storage (model.to(), new parameter storage)
-    per_net = _GRAPHS.get(net)
-    if per_net is None:
-        per_net = {}
-        _GRAPHS[net] = per_net
-    key = (tuple(shape), bool(with_noise))
-    if gd.objective != "pred_v":                     # two diffusions of other objectives may share one network
-        key += (gd.objective, bool(rederive))
-    if guided:                                       # two forwards and the mix per step: a graph of its own
-        key += ("guided",)
-    if dpm:                                          # never the key of an ancestral / DDIM step, whatever the objective
-        key = ("dpm++", gd.objective) + key
-    dyn = _dyn(gd)
-    if dyn is not None:                              # a key of its own, the percentile in it: the rank is baked into the launch
-        key = ("dynthresh", dyn) + key
+    per_net = _GRAPHS.setdefault(net, {})
+    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm)
     ent = per_net.get(key)
     if isinstance(ent, _GraphedChain) and not ent.matches(net):
         ent = None                                   # captured against buffers the network no longer uses
@@ -438,9 +448,8 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
         ent = None
     if ent is None:
         try:
-            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=dyn)
+            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd))
         except Exception as e:  # capture is an optimisation
-            import sys
             print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",
                   file=sys.stderr, flush=True)
             per_net[key] = _CAPTURE_RETRY_AFTER
@@ -451,48 +460,38 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
 
 def p_sample_step(chain: _Chain, t: int, noise: Optional[torch.Tensor]):
     """One ancestral step (p_sample :748-757): clip x0, posterior mean + sigma * noise (t > 0)."""
-    chain.step(t, noise if t > 0 else None, _p_sample_coeffs(chain.gd, t))
+    chain.step(t, noise, _p_sample_coeffs(chain.gd, t))
 
 
 def ddim_step(chain: _Chain, t: int, t_next: int, noise: Optional[torch.Tensor], eta: float):
     """One DDIM step (loop body :805-829); no noise where sigma is zero (eta == 0, or the last step)."""
-    coeffs = _ddim_coeffs(chain.gd, t, t_next, eta)
-    chain.step(t, noise if coeffs[7] != 0.0 else None, coeffs, rederive=True)
+    chain.step(t, noise, _ddim_coeffs(chain.gd, t, t_next, eta), rederive=True)
 
 
-@torch.no_grad()
-def warm_chain(gd, shape, replays: int = 20) -> bool:
-    """Capture the ancestral chain's per-step graph for (network, shape) and run ``replays`` steps of it on noise
-    (benchmarks: warm-up without paying a whole 1000-step chain).  False when graph replay is unavailable."""
-    gc = _graph_chain(gd, shape, True)
-    if gc is None:
-        return False
-    ts = list(reversed(range(gd.num_timesteps)))[:replays]
-    chain = _Chain(gd, shape, None)
-    gc.run(chain.x, ts, [_p_sample_coeffs(gd, t) for t in ts], None, chain.classes)
-    return True
+def dpm_step(chain: _Chain, t: int, noise: Optional[torch.Tensor], coeffs):
+    """One DPM-Solver++ step from a row of ``dpm_coeffs``; no noise where K_n is zero (the ODE, or the last step)."""
+    chain.step(t, noise, coeffs, dpm=True)
 
 
-@torch.no_grad()
-def p_sample_loop(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-                  start: Optional[int] = None, unnormalize: Optional[bool] = None, classes=None, cond_scale: float = 1.0):
-    """``start``: walk the chain from step start - 1 down to 0 (GaussianDiffusion.interpolate :861-865) instead of from
-    T - 1; ``unnormalize``: default = the model's auto_normalize (p_sample_loop :779), False for interpolate."""
+def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
+         classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None):
+    """One chain of ``plan`` from ``init_noise`` (default: drawn) -> the image, or every image of the chain stacked along
+    dim 1.  ``noises``: one NCHW tensor (or None) per step in place of the draws; ``unnormalize``: default = the model's
+    auto_normalize (p_sample_loop :779).  No graph for a chain without steps."""
     chain = _Chain(gd, shape, init_noise, None, classes, cond_scale)
-    dev = chain.x.device
-    ts = list(reversed(range(gd.num_timesteps if start is None else int(start))))
     unn = gd.auto_normalize if unnormalize is None else bool(unnormalize)
-    gc = None if return_all_timesteps or not ts else _graph_chain(gd, shape, True, guided=chain.cond_scale != 1.0)
+    gc = None
+    if plan.times and not return_all_timesteps:
+        gc = _graph_chain(gd, shape, plan.with_noise, rederive=plan.rederive, guided=chain.cond_scale != 1.0, dpm=plan.dpm)
     if gc is not None:
-        x = gc.run(chain.x, ts, [_p_sample_coeffs(gd, t) for t in ts], noises, chain.classes, chain.cond_scale)
-        chain.x = x
+        chain.x = gc.run(chain.x, plan.times, plan.rows, noises if plan.with_noise else None, chain.classes, chain.cond_scale)
         return chain.image(unn)
     frames = [chain.image(False)] if return_all_timesteps else None
-    for i, t in enumerate(ts):
+    for i, (t, row, draws) in enumerate(zip(plan.times, plan.rows, plan.draws)):
         nz = None
-        if t > 0:
-            nz = noises[i] if noises is not None else torch.randn(shape, device=dev)
-        p_sample_step(chain, t, nz)
+        if draws:
+            nz = noises[i] if noises is not None else torch.randn(shape, device=chain.x.device)
+        chain.step(t, nz, row, plan.rederive, plan.dpm)
         if return_all_timesteps:
             frames.append(chain.image(False))
     if return_all_timesteps:
@@ -502,63 +501,32 @@ def p_sample_loop(gd, shape, return_all_timesteps=False, init_noise=None, noises
 
 
 @torch.no_grad()
+def warm_chain(gd, shape, replays: int = 20) -> bool:
+    """Capture the ancestral chain's per-step graph for (network, shape) and run ``replays`` steps of it on noise
+    (benchmarks: warm-up without paying a whole 1000-step chain).  False when graph replay is unavailable."""
+    if _graph_chain(gd, shape, True) is None:
+        return False
+    _run(gd, shape, _plan_ancestral(gd, steps=replays))
+    return True
+
+
+@torch.no_grad()
+def p_sample_loop(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
+                  start: Optional[int] = None, unnormalize: Optional[bool] = None, classes=None, cond_scale: float = 1.0):
+    """``start``: walk the chain from step start - 1 down to 0 (GaussianDiffusion.interpolate :861-865) instead of from
+    T - 1; ``unnormalize``: False for interpolate."""
+    return _run(gd, shape, _plan_ancestral(gd, start), return_all_timesteps, init_noise, noises, classes, cond_scale, unnormalize)
+
+
+@torch.no_grad()
 def ddim_sample(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
                 classes=None, cond_scale: float = 1.0):
-    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale)
-    dev = chain.x.device
-    eta = gd.ddim_sampling_eta
-    pairs = gd.ddim_time_pairs()
-    gc = None if return_all_timesteps else _graph_chain(gd, shape, eta != 0.0, rederive=True,
-                                                        guided=chain.cond_scale != 1.0)
-    if gc is not None:
-        x = gc.run(chain.x, [a for a, _ in pairs], [_ddim_coeffs(gd, a, b, eta) for a, b in pairs],
-                   noises if eta != 0.0 else None, chain.classes, chain.cond_scale)
-        chain.x = x
-        return chain.image(gd.auto_normalize)
-    frames = [chain.image(False)] if return_all_timesteps else None
-    for i, (t, t_next) in enumerate(pairs):
-        nz = None
-        if t_next >= 0 and eta != 0.0:
-            nz = noises[i] if noises is not None else torch.randn(shape, device=dev)
-        ddim_step(chain, t, t_next, nz, eta)
-        if return_all_timesteps:
-            frames.append(chain.image(False))
-    if return_all_timesteps:
-        ret = torch.stack(frames, dim=1)
-        return (ret + 1) * 0.5 if gd.auto_normalize else ret
-    return chain.image(gd.auto_normalize)
-
-
-def dpm_step(chain: _Chain, t: int, noise: Optional[torch.Tensor], coeffs):
-    """One DPM-Solver++ step from a row of ``dpm_coeffs``; no noise where K_n is zero (the ODE, or the last step)."""
-    chain.dpm_step(t, noise if coeffs[7] != 0.0 else None, coeffs)
+    return _run(gd, shape, _plan_ddim(gd), return_all_timesteps, init_noise, noises, classes, cond_scale)
 
 
 @torch.no_grad()
 def dpm_solver_sample(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
                       classes=None, cond_scale: float = 1.0):
-    """DPM-Solver++(2M) (``gd.dpm_order`` 1 or 2; ``gd.dpm_stochastic``: the SDE form) on ``gd.dpm_time_pairs()``: one network
-    forward (two when guided) and one update kernel per step, graph-replayed like ``ddim_sample``.  ``noises``: one NCHW
-    tensor per pair with t_next >= 0, read by the SDE form only."""
-    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale)
-    dev = chain.x.device
-    stochastic = bool(gd.dpm_stochastic)
-    pairs = gd.dpm_time_pairs()
-    coeffs = dpm_coeffs(gd, pairs, gd.dpm_order, stochastic)
-    gc = None if return_all_timesteps else _graph_chain(gd, shape, stochastic, guided=chain.cond_scale != 1.0, dpm=True)
-    if gc is not None:
-        x = gc.run(chain.x, [a for a, _ in pairs], coeffs, noises if stochastic else None, chain.classes, chain.cond_scale)
-        chain.x = x
-        return chain.image(gd.auto_normalize)
-    frames = [chain.image(False)] if return_all_timesteps else None
-    for i, ((t, t_next), row) in enumerate(zip(pairs, coeffs)):
-        nz = None
-        if t_next >= 0 and stochastic:
-            nz = noises[i] if noises is not None else torch.randn(shape, device=dev)
-        dpm_step(chain, t, nz, row)
-        if return_all_timesteps:
-            frames.append(chain.image(False))
-    if return_all_timesteps:
-        ret = torch.stack(frames, dim=1)
-        return (ret + 1) * 0.5 if gd.auto_normalize else ret
-    return chain.image(gd.auto_normalize)
+    """DPM-Solver++(2M) on ``gd.dpm_time_pairs()``, graph-replayed like ``ddim_sample``.  ``noises``: one NCHW tensor per pair
+    with t_next >= 0, read by the SDE form only."""
+    return _run(gd, shape, _plan_dpm(gd), return_all_timesteps, init_noise, noises, classes, cond_scale)
