@@ -1,18 +1,22 @@
 """HIP-graph replay of the training steps.
 
 At small per-GPU batches (strong scaling: 128 / N images per GPU) the ~400 kernel launches of a DDPM step are
-host-bound when issued from Python.  The step is therefore captured ONCE and replayed:
+host-bound when issued from Python.  The step is therefore captured ONCE and replayed (GraphedDDPMStep).  The UNet's
+backward pass runs in four phases, each of which makes one exchange bucket of the flat gradient buffer final
+(``Unet.BACKWARD_PHASES`` / ``bucket_ranges()``); a LAYOUT says which phases share a graph:
 
-    one rank : ONE graph - t ~ randint, noise ~ randn, q_sample, UNet forward, loss, the whole backward -
-               then fused Adam (1 eager kernel) and EMA (every 10th step); a diffusion with offset noise also
-               draws its [B, C] offsets inside the graph
-    N ranks  : FOUR graphs, cut where an exchange bucket of the flat gradient buffer becomes final
-               (GraphedDDPMStep), with the asynchronous all-reduce of each bucket issued between the replays
+    one rank : ((0, 1, 2, 3),)            ONE graph - t ~ randint, noise ~ randn (a diffusion with offset noise also
+                                          draws its [B, C] offsets, a class-conditional one its label drop), q_sample,
+                                          UNet forward, loss, the whole backward - then fused Adam (1 eager kernel) and
+                                          EMA (every 10th step);  ``LGM_ONE_GRAPH=0``: ((0, 1), (2, 3))
+    N ranks  : ((0,), (1,), (2,), (3,))   FOUR graphs, cut where a bucket becomes final, with the asynchronous
+                                          all-reduce of each bucket issued between the replays
 
 Collectives are never captured, the optimiser's step count lives on the host, and the RNG is torch's graph-safe
 Philox generator.  The arithmetic is identical to the eager path (same kernels, same order) - tested bit for bit.
-ModuleFastStep (VQ-VAE: one graph) and WGANFastStep (critic graph / generator graph) follow the same rules: warm-up and
-capture leave the training state untouched (_TrainingState), also when capture fails.
+ModuleFastStep (VQ-VAE: one graph) and WGANFastStep (critic graph / generator graph) follow the same rules and keep
+what they captured in a ``_Captured``: warm-up and capture leave the training state untouched (_TrainingState), also
+when capture fails.  Every step class falls back to eager launches when capture is not possible (``_eager_fallback``).
 """
 from __future__ import annotations
 
@@ -66,21 +70,25 @@ class _TrainingState:
         torch.cuda.set_rng_state(self.rng, self.device)
 
 
-def _capture(fn, warmup: int, pool=None):
-    """Eager warm-up of ``fn`` on a side stream (sizes workspaces, sets kernel attributes), then its capture into a
-    HIP graph.  Returns (graph, fn's return value inside the capture, BatchNorm modules whose train-mode forward
-    ran inside it — a replay does not pass through Python, so the step object advances their host-side batch
-    counters itself).  thread_local: only THIS thread is held to the capture rules — the RCCL watchdog thread of a
-    multi-GPU job keeps polling its events while the step is being captured."""
-    from . import bn
+def _warm_up(fn, n: int):
+    """``n`` eager runs of ``fn`` on a side stream (they size workspaces and set kernel attributes), joined before return."""
     cur = torch.cuda.current_stream()
     side = torch.cuda.Stream()
     side.wait_stream(cur)
     with torch.cuda.stream(side):
-        for _ in range(warmup):
+        for _ in range(n):
             fn()
     cur.wait_stream(side)
     torch.cuda.synchronize()
+
+
+def _capture(fn, warmup: int, pool=None):
+    """Eager warm-up of ``fn``, then its capture into a HIP graph.  Returns (graph, fn's return value inside the capture,
+    BatchNorm modules whose train-mode forward ran inside it — a replay does not pass through Python, so the step
+    object advances their host-side batch counters itself).  thread_local: only THIS thread is held to the capture
+    rules — the RCCL watchdog thread of a multi-GPU job keeps polling its events while the step is being captured."""
+    from . import bn
+    _warm_up(fn, warmup)
     g = torch.cuda.CUDAGraph()
     bn.CAPTURE_TRACE = []
     try:
@@ -95,23 +103,64 @@ def _capture(fn, warmup: int, pool=None):
     return g, out, trace
 
 
+def _eager_fallback(step, e: Exception):
+    """Capture is an optimisation: when it is not possible the step object goes on with eager launches."""
+    import sys
+    print(f"[lgm_hip] HIP-graph capture unavailable ({type(e).__name__}: {e}); eager launches", file=sys.stderr, flush=True)
+    step.use_graph = False
+
+
+class _Captured:
+    """One captured function of a training step: its graph, the static inputs a batch is copied into, what the function
+    returned inside the capture (tensors in the graph's memory: every replay refreshes them in place) and the BatchNorm
+    modules whose forward ran inside."""
+
+    def __init__(self, graph, static, out, bn_trace):
+        self.graph, self.static, self.out, self.bn_trace = graph, static, out, bn_trace
+
+    @classmethod
+    def of(cls, fn, batch, modules, device):
+        """Capture ``fn(static copy of batch)``.  Whatever warm-up and capture did to the training state is undone, on
+        success and when capture raises."""
+        static = tuple(b.clone() if torch.is_tensor(b) else b for b in batch)
+        state = _TrainingState(modules, device)
+        try:
+            g, out, trace = _capture(lambda: fn(static), 2)
+        finally:
+            state.restore()
+        return cls(g, static, out, trace)
+
+    def matches(self, batch) -> bool:
+        return all((not torch.is_tensor(b)) or b.shape == s.shape for b, s in zip(batch, self.static))
+
+    def replay(self, batch):
+        for b, s in zip(batch, self.static):
+            if torch.is_tensor(b):
+                s.copy_(b)
+        self.graph.replay()
+        for b in self.bn_trace:                      # BatchNorm forwards inside the graph: host-side batch counters
+            b._nbt_pending += 1
+        return self.out
+
+
+LAYOUT_ONE, LAYOUT_TWO, LAYOUT_BUCKETS = ((0, 1, 2, 3),), ((0, 1), (2, 3)), ((0,), (1,), (2,), (3,))
+
+
 class GraphedDDPMStep:
-    """``inject=True`` (parity tests): ``t`` / ``noise`` (and ``offset``, the [B, C] offset noise of a diffusion with
-    ``offset_noise_strength > 0``) are static INPUT buffers the caller fills before each step instead of being drawn
-    inside graph 1.  Either way ``self.t`` / ``self.noise`` / ``self.offset`` hold the values the last replay used.
+    """The DDPM step as graphs.  ``self.layout`` holds, per graph, the backward phases (= exchange buckets) it runs:
 
-    One rank: ONE graph for the whole forward + backward (``LGM_ONE_GRAPH=0``: two, forward + backward phase 1 | phase 2 -
-    no measurable difference), one Adam launch.  With a gradient exchange
-    (``sync``) the backward is cut at every bucket boundary - four graphs - so that each bucket's all-reduce is issued
-    the moment its slice is final and runs beside everything that follows it:
+        phase 0  backward of final block + up path          -> bucket 0 [ups], [final]
+        phase 1  backward of the middle blocks              -> bucket 1 [mid]
+        phase 2  backward of the down path + init conv      -> bucket 2 [init, downs]
+        phase 3  backward of the time MLP / FiLM projections -> bucket 3 [FiLM, time]
 
-        g1a  t, noise, q_sample, UNet forward, loss, backward of final block + up path   -> bucket 0 [ups], [final]
-        g1b  backward of the middle blocks                                               -> bucket 1 [mid]
-        g2a  backward of the down path + init conv                                       -> bucket 2 [init, downs]
-        g2b  backward of the time MLP / FiLM projections                                 -> bucket 3 [FiLM, time]
+    The first graph opens with t, noise, q_sample, UNet forward, loss and the loss gradient.  One rank: ``LAYOUT_ONE``,
+    one Adam launch (``LGM_ONE_GRAPH=0``: ``LAYOUT_TWO`` - no measurable difference).  With a gradient exchange (``sync``):
+    ``LAYOUT_BUCKETS``, so that each bucket's all-reduce is issued the moment its slice is final and runs beside
+    everything that follows it; ``self.ranges[i]`` are the flat-buffer slices final after graph i.
 
     ``LGM_STEP_PIPELINE=1`` (opt-in, measured SLOWER on one GPU: 11.69 vs 11.44 ms at B = 128, 4.77 vs 4.65 ms at
-    B = 16): four graphs on every rank count, and behind each of them on a SIDE stream the bucket's weight-sized passes -
+    B = 16): ``LAYOUT_BUCKETS`` on every rank count, and behind each graph on a SIDE stream the bucket's weight-sized passes -
     batched slab reduction, all-reduce, ITS slice of the Adam update (a bucket's weights are not read again by the
     backward once its gradients are final).  Bit-identical to the default (tested), but the streaming kernels' workgroups
     delay the one-workgroup-per-CU convolutions more than the overlap returns, and two more graph boundaries plus five
@@ -122,163 +171,118 @@ class GraphedDDPMStep:
     behind the launch that draws t / noise and writes x_t (``pre``), the estimate pass - the network without saved
     activations + the kernel that writes x_start into the self-conditioning slice of the input buffer - is a graph of its own
     (``est``) replayed on the steps whose coin says so, and the saved forward pass opens the next graph.  ``pre`` zeroes the
-    self-conditioning slice on every step.  A model without self-conditioning captures exactly the graphs listed above.
+    self-conditioning slice on every step.  A model without self-conditioning captures exactly the graphs of its layout.
 
     Class-conditional model: ``y`` is a second static input buffer (the batch's labels, copied beside ``x`` before replay).
     The label drop of classifier-free guidance - rand(B) < cond_drop_prob - is drawn inside the graph behind t, noise and
-    offset, the order ``GaussianDiffusion.forward`` draws in; ``self.classes`` holds the labels the last replay used (with
-    ``inject`` it is the input buffer of already-dropped labels).  A model without classes draws nothing more."""
+    offset, the order ``GaussianDiffusion.forward`` draws in.  A model without classes draws nothing more.
 
-    def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, inject: bool = False,
-                 y: Optional[torch.Tensor] = None):
-        from models.generative.diffusion.ddpm import (hip_loss_backward_phase1a, hip_loss_estimate, hip_loss_forward,
-                                                      hip_loss_network, hip_loss_qsample)
+    ``self.t`` / ``self.noise`` / ``self.offset`` (the [B, C] offset noise of a diffusion with ``offset_noise_strength > 0``)
+    / ``self.classes`` hold what the last replay drew."""
+
+    def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None):
+        from models.generative.diffusion.ddpm import (hip_loss_backward_begin, hip_loss_estimate, hip_loss_network,
+                                                      hip_loss_qsample)
         self.model, self.opt, self.sync = model, opt, sync
-        self.gd = model.ema.online_model
-        self.net = self.gd.model
+        self.gd = gd = model.ema.online_model
+        self.net = net = gd.model
         self.x = x                                   # static input buffer (copy new batches into it)
         self.one = torch.ones(1, device=x.device)
-        self.net.grad_sync = None                    # collectives are issued by step(), never captured
-        fp = self.net._flat
-        net = self.net
-        self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device) if inject else None
-        self.noise = torch.zeros_like(x) if inject else None
-        strength = float(self.gd.offset_noise_strength)
-        self.offset = torch.zeros(x.shape[:2], device=x.device) if inject and strength > 0.0 else None
-        self.y = self.classes = None
-        if net.num_classes is not None:
-            self.y = net.labels(y, x.shape[0], x.device).clone()
-            self.classes = self.y.clone() if inject else None
+        net.grad_sync = None                         # collectives are issued by step(), never captured
+        fp = net._flat
+        self.t = self.noise = self.offset = self.classes = None
+        strength = float(gd.offset_noise_strength)
+        self.y = net.labels(y, x.shape[0], x.device).clone() if net.num_classes is not None else None
         # (the pipelined variant applies a bucket's Adam slice right behind ITS all-reduce: only with the overlapped exchange)
         self.pipeline = _STEP_PIPELINE and (sync is None or getattr(sync, "overlap", True))
-        split = sync is not None or self.pipeline
-
-        self_cond = bool(self.net.self_condition)
+        self.layout = (LAYOUT_BUCKETS if sync is not None or self.pipeline else LAYOUT_ONE if _ONE_GRAPH else LAYOUT_TWO)
+        self_cond = bool(net.self_condition)
         self.pre = self.est = None                   # self-conditioned model only: see the class comment
 
-        def draws():
-            gd = self.gd
-            if inject:
-                return self.t, self.noise, self.offset
-            # the draws of GaussianDiffusion.forward / p_losses, in their order
-            t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
-            noise = torch.randn_like(self.x)
-            offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
-            self.t, self.noise, self.offset = t, noise, offset
+        def qsample():
+            # the draws of GaussianDiffusion.forward / p_losses, in their order, and the q_sample launch
+            self.t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
+            self.noise = torch.randn_like(self.x)
+            self.offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
             if self.y is not None:
                 self.classes = gd.drop_labels(self.y)
-            return t, noise, offset
+            return hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength)
 
-        def part0():                                 # self-conditioned: the draws and the q_sample launch
-            t, noise, offset = draws()
-            return hip_loss_qsample(self.gd, self.x, t, noise, self.gd.auto_normalize, offset, strength)
+        def estimate(q):
+            hip_loss_estimate(gd, q[0], q[4], self.classes)
 
-        def part1a(q=None):
-            gd = self.gd
-            if self_cond:
-                xt, target, img, noise, t, offset = q
-                loss, ctx = hip_loss_network(gd, xt, target, img, t, noise, offset, True, self.classes)
-            else:
-                t, noise, offset = draws()
-                loss, ctx = hip_loss_forward(gd, self.x, t, noise, gd.auto_normalize, True, offset, strength,
-                                             classes=self.classes)
+        def begin(q):                                # the saved forward, the loss, its gradient: the backward is open
+            xt, target, img, noise, t, offset = q
+            loss, ctx = hip_loss_network(gd, xt, target, img, t, noise, offset, True, self.classes)
             fp.zero_grad()
-            return loss, hip_loss_backward_phase1a(ctx, self.one)
+            return loss, hip_loss_backward_begin(ctx, self.one)
 
         def whole():
-            q = None
+            q = qsample()
             if self_cond:
-                q = part0()
-                hip_loss_estimate(self.gd, q[0], q[4], self.classes)
-            _, st = part1a(q)
-            net.backward_phase2(net.backward_phase1b(st))
+                estimate(q)
+            net.backward_run(begin(q)[1])
 
         # warm-up and capture must not perturb the random stream: a run that captures at batch 0 and a run that
         # resumes from a checkpoint (and captures later) draw the same (t, noise) for the same seed
         rng_state = torch.cuda.get_rng_state(x.device)
         try:
-            # (the eager warm-up runs the WHOLE step: the pieces share workspaces and kernel attributes)
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):            # eager warm-up (sizes workspaces, sets kernel attributes)
-                for _ in range(warmup):
-                    whole()
-            cur.wait_stream(side)
-            torch.cuda.synchronize()
+            _warm_up(whole, warmup)                  # (the WHOLE step: the pieces share workspaces and kernel attributes)
             if self.pipeline:
                 net._flush_collect = {}              # the phases hand their reduction rows over instead of launching
             try:
-                q, pool0 = None, None
+                q, pool = None, None
                 if self_cond:
-                    self.pre, q, _ = _capture(part0, 0)
-                    pool0 = self.pre.pool()
-                    self.est, _, _ = _capture(lambda: hip_loss_estimate(self.gd, q[0], q[4], self.classes), 0, pool0)
+                    self.pre, q, _ = _capture(qsample, 0)
+                    pool = self.pre.pool()
+                    self.est, _, _ = _capture(lambda: estimate(q), 0, pool)
                     self._q = q                      # keeps the input buffer and the target alive
-                if split:
-                    g1a, (self.loss, st), _ = _capture(lambda: part1a(q), 0, pool0)
-                    pool = g1a.pool()
-                    g1b, st, _ = _capture(lambda: net.backward_phase1b(st), 0, pool)
-                    g2a, st, _ = _capture(lambda: net.backward_phase2a(st), 0, pool)
-                    g2b, _, _ = _capture(lambda: net.backward_phase2b(st), 0, pool)
-                    self.graphs = [g1a, g1b, g2a, g2b]
-                elif _ONE_GRAPH:
-                    def everything():                # one rank: nothing has to happen between the phases
-                        loss, st1 = part1a(q)
-                        st2 = net.backward_phase1b(st1)
-                        net.backward_phase2(st2)
-                        return loss, st2
-                    g1, (self.loss, st), _ = _capture(everything, 0, pool0)
-                    self.graphs = [g1]
-                else:
-                    def part1():
-                        loss, st1 = part1a(q)
-                        return loss, net.backward_phase1b(st1)
-                    g1, (self.loss, st), _ = _capture(part1, 0, pool0)
-                    g2, _, _ = _capture(lambda: net.backward_phase2(st), 0, g1.pool())
-                    self.graphs = [g1, g2]
+                self.graphs = []
+                for phases in self.layout:
+                    def part():
+                        if phases[0] == 0:
+                            self.loss, self._st = begin(q if self_cond else qsample())
+                        net.backward_run(self._st, phases[0], phases[-1])
+                    g, _, _ = _capture(part, 0, pool)
+                    pool = g.pool() if pool is None else pool        # every later graph: the first one's pool
+                    self.graphs.append(g)
                 rows = net._flush_collect if self.pipeline else {}
             finally:
                 net._flush_collect = None
-            self.ranges = net.bucket_ranges()
+            buckets = net.bucket_ranges()
+            self.ranges = [[r for k in phases for r in buckets[k]] for phases in self.layout]
             if self.pipeline:
                 self.reducers = [ops.make_reducer(rows.get(k), x.device) for k in range(4)]
                 self.side = torch.cuda.Stream()
                 self.events = [torch.cuda.Event() for _ in range(4)]
-            self._st = st                            # keeps the captured buffers alive
         finally:
             torch.cuda.set_rng_state(rng_state, x.device)
 
-    def _replay_pre(self, self_cond: bool):
-        """Self-conditioned model: draws + q_sample, then the estimate pass when this step's host coin says so."""
-        if self.pre is not None:
+    def step(self, batch_idx: int = 0, self_cond: bool = False):
+        """``self_cond``: this step's coin (read by a self-conditioned model only)."""
+        if self.pre is not None:                     # draws + q_sample, then the estimate pass when the coin says so
             self.pre.replay()
             if self_cond:
                 self.est.replay()
-
-    def step(self, batch_idx: int = 0, self_cond: bool = False):
-        """``self_cond``: this step's coin (read by a self-conditioned model only)."""
-        self._replay_pre(self_cond)
-        if self.pipeline:
-            return self._step_pipelined(batch_idx)
         sync = self.sync
-        if sync is None:
-            for g in self.graphs:
-                g.replay()
+        if self.pipeline:
+            self._replay_pipelined()
         else:
-            for k, g in enumerate(self.graphs):
+            for g, ranges in zip(self.graphs, self.ranges):
                 g.replay()
-                for lo, hi in self.ranges[k]:
-                    sync.ready(lo, hi)               # asynchronous, on RCCL's stream, behind the replay just enqueued
-            sync.finish()
-        self.opt.step()
+                if sync is not None:
+                    for lo, hi in ranges:
+                        sync.ready(lo, hi)           # asynchronous, on RCCL's stream, behind the replay just enqueued
+            if sync is not None:
+                sync.finish()
+            self.opt.step()
         self.opt.zero_grad()                         # host flag only: the next backward overwrites
         self.model.on_train_batch_end(None, None, batch_idx)
         return self.loss
 
-    def _step_pipelined(self, batch_idx: int):
-        net, sync = self.net, self.sync
-        fp = net._flat
+    def _replay_pipelined(self):
+        sync = self.sync
+        fp = self.net._flat
         main, side = torch.cuda.current_stream(), self.side
         inner = getattr(self.opt, "_opt", self.opt)
         group, st = inner.begin_step(fp)
@@ -300,9 +304,6 @@ class GraphedDDPMStep:
             sync.finish()
         if hasattr(self.opt, "count_step"):
             self.opt.count_step()                    # MiniTrainer's proxy: one optimizer step
-        self.opt.zero_grad()                         # host flag only: the next backward overwrites
-        self.model.on_train_batch_end(None, None, batch_idx)
-        return self.loss
 
 
 class DDPMFastStep:
@@ -324,7 +325,7 @@ class DDPMFastStep:
         self.use_graph = use_graph
         self.graphed: Optional[GraphedDDPMStep] = None
         self.mode = "eager"
-        # self-conditioned model: the coin of reference :902, drawn on the host once per step (tests inject a sequence here)
+        # self-conditioned model: the coin of reference :902, drawn on the host once per step (tests put a sequence here)
         self.coin = lambda: random.random() < 0.5
 
     def _capture(self, x, y=None):
@@ -335,11 +336,8 @@ class DDPMFastStep:
                          f"hipGraph replay ({n} graph{'s' if n > 1 else ''}/step)")
             if self.graphed.est is not None:
                 self.mode = self.mode[:-1] + ", + the estimate graph on self-conditioned steps)"
-        except Exception as e:  # capture is an optimisation: fall back to eager launches
-            import sys
-            print(f"[lgm_hip] HIP-graph capture unavailable ({type(e).__name__}: {e}); eager launches",
-                  file=sys.stderr, flush=True)
-            self.use_graph = False
+        except Exception as e:
+            _eager_fallback(self, e)
             self.graphed = None
 
     def step(self, batch, batch_idx: int = 0):
@@ -393,11 +391,8 @@ class ModuleFastStep:
         if world > 1:
             inner.grad_scale = 1.0 / world
         self.use_graph = use_graph and not (collective_inside and world > 1)
-        self.graph = None
-        self.static = None
-        self.loss = None
-        self._captured_logs = {}
-        self._bn_trace = []
+        self.captured: Optional[_Captured] = None    # its ``out``: (loss, what training_step logged inside the capture)
+        self.static = None                           # the captured step's input tensors
         self._one = None
         self.mode = "eager"
 
@@ -421,44 +416,27 @@ class ModuleFastStep:
 
     def _capture(self, batch):
         m = self.model
-        dev = self.flat.grad.device
-        state = None
-        try:
-            static = tuple(b.clone() if torch.is_tensor(b) else b for b in batch)
-            state = _TrainingState([m], dev)
+
+        def fn(static):
+            # what training_step logs during capture lives in the graph's memory: every replay refreshes those
+            # tensors in place, so they are what the module reports after each replayed step
             if hasattr(m, "logged"):
                 m.logged.clear()
-            g, loss, trace = _capture(lambda: self._fwd_bwd(static, 0), 2)
-            # what training_step logged during capture lives in the graph's memory: every replay refreshes those
-            # tensors in place, so they are what the module reports after each replayed step
-            self._captured_logs = dict(getattr(m, "logged", {}))
-            self.graph, self.static, self.loss, self._bn_trace = g, static, loss, trace
+            return self._fwd_bwd(static, 0), dict(getattr(m, "logged", {}))
+        try:
+            self.captured = _Captured.of(fn, batch, [m], self.flat.grad.device)
+            self.static = self.captured.static
             self.mode = "hipGraph replay (1 graph/step)"
-        except Exception as e:  # capture is an optimisation: fall back to eager launches
-            import sys
-            print(f"[lgm_hip] HIP-graph capture unavailable ({type(e).__name__}: {e}); eager launches",
-                  file=sys.stderr, flush=True)
-            self.use_graph = False
-            self.graph = None
-        finally:
-            if state is not None:                    # on BOTH paths: undo what warm-up / capture did to the training state
-                state.restore()
+        except Exception as e:
+            _eager_fallback(self, e)
 
     def step(self, batch, batch_idx: int = 0):
-        if self.use_graph and self.graph is None:
+        if self.use_graph and self.captured is None:
             self._capture(batch)
-        g = self.graph
-        same = g is not None and all((not torch.is_tensor(b)) or b.shape == s.shape for b, s in zip(batch, self.static))
-        if same:
-            for b, s in zip(batch, self.static):
-                if torch.is_tensor(b):
-                    s.copy_(b)
-            g.replay()
-            loss = self.loss
-            for b in self._bn_trace:                 # BatchNorm forwards inside the graph: host-side batch counters
-                b._nbt_pending += 1
+        if self.captured is not None and self.captured.matches(batch):
+            loss, logs = self.captured.replay(batch)
             if hasattr(self.model, "logged"):
-                self.model.logged.update(self._captured_logs)
+                self.model.logged.update(logs)
         else:
             loss = self._fwd_bwd(batch, batch_idx)
         self._finish(batch, batch_idx)
@@ -487,7 +465,7 @@ class WGANFastStep:
         self.sync = ({"d": FlatGradSync(model.D._flat, beside_backward=False),
                       "g": FlatGradSync(model.G._flat, beside_backward=False)} if world > 1 else None)
         self.use_graph = use_graph
-        self.graphs = {}          # "d" / "g" -> (graph, static x, captured logs, BatchNorm trace)
+        self.graphs = {}          # "d" / "g" -> _Captured; its ``out``: the update's logs
         self.mode = "eager"
 
     # the two updates, without exchange / optimizer step (what a graph holds)
@@ -508,24 +486,12 @@ class WGANFastStep:
         return ld
 
     def _capture(self, key, x):
-        m = self.model
-        state = None
+        fn = self._critic if key == "d" else self._generator
         try:
-            static = x.clone()
-            fn = self._critic if key == "d" else self._generator
-            state = _TrainingState([m], x.device)
-            g, logs, trace = _capture(lambda: fn(static), 2)
-            self.graphs[key] = (g, static, dict(logs), trace)
+            self.graphs[key] = _Captured.of(lambda static: dict(fn(static[0])), (x,), [self.model], x.device)
             self.mode = "hipGraph replay (critic graph / generator graph)"
-        except Exception as e:  # capture is an optimisation: fall back to eager launches
-            import sys
-            print(f"[lgm_hip] HIP-graph capture unavailable ({type(e).__name__}: {e}); eager launches",
-                  file=sys.stderr, flush=True)
-            self.use_graph = False
-            self.graphs.pop(key, None)
-        finally:
-            if state is not None:
-                state.restore()
+        except Exception as e:
+            _eager_fallback(self, e)
 
     def step(self, batch, batch_idx: int = 0):
         m = self.model
@@ -535,12 +501,8 @@ class WGANFastStep:
         if self.use_graph and key not in self.graphs and m.training:
             self._capture(key, x)
         ent = self.graphs.get(key)
-        if ent is not None and ent[1].shape == x.shape:
-            g, static, logs, trace = ent
-            static.copy_(x)
-            g.replay()
-            for b in trace:
-                b._nbt_pending += 1
+        if ent is not None and ent.matches((x,)):
+            logs = ent.replay((x,))
         else:
             logs = self._critic(x) if critic else self._generator(x)
         if self.sync is not None:

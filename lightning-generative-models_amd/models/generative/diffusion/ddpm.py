@@ -626,8 +626,7 @@ class Unet(nn.Module):
 
     def backward_nhwc(self, tape_all, gout):
         """Hand-written backward pass: parameter gradients into the flat gradient buffer."""
-        st = self.backward_phase1(tape_all, gout)
-        self.backward_phase2(st)
+        self.backward_run(self.backward_begin(tape_all, gout))
 
     def _flush(self, gc: GradCtx, bucket: int):
         """End of an exchange bucket (0: ups + final, 1: mid, 2: init + downs, 3: FiLM + time): the deferred slab / row
@@ -645,30 +644,40 @@ class Unet(nn.Module):
                 gc.deferred.clear()
 
     def bucket_ranges(self):
-        """Flat-buffer slices of the four exchange buckets, in backward completion order."""
+        """Flat-buffer slices of the four exchange buckets, in backward completion order: bucket k is final when phase k
+        of the backward pass (``BACKWARD_PHASES``) ends.  [ups] + [final] are 18.6 M of the 35.7 M parameters at dim 64,
+        [mid] 10.2 M: their exchange overlaps everything that follows."""
         t = self._flat.total
         return [[(self._ups_start, self._mid_start), (self._final_start, t)], [(self._mid_start, self._final_start)],
                 [(self._head_end, self._ups_start)], [(0, self._head_end)]]
 
-    def backward_phase1(self, tape_all, gout):
-        """final conv -> final block -> up path -> middle.  After it the gradient slice
-        [_ups_start, total) of the flat buffer is final (first exchange buckets)."""
-        return self.backward_phase1b(self.backward_phase1a(tape_all, gout))
+    def _bucket_done(self, gc: GradCtx, bucket: int):
+        """The last statement of phase ``bucket``: its reductions, then its slices go to the gradient exchange."""
+        self._flush(gc, bucket)
+        sync = getattr(self, "grad_sync", None)
+        if sync is not None:
+            for lo, hi in self.bucket_ranges()[bucket]:
+                sync.ready(lo, hi)
+        if bucket == 3:                  # the whole gradient buffer is final
+            self._flat.bind_grad_views()
 
-    def backward_phase1a(self, tape_all, gout):
-        """final conv -> final block -> up path.  After it the slices [_ups_start, _mid_start) and
-        [_final_start, total) of the flat gradient buffer are final: 18.6 M of the 35.7 M parameters, whose exchange
-        overlaps everything that follows."""
-        time_saved, tape, sm1, sm2, sm3, ups_tape, sf, fin, x_in, cat_shapes = tape_all
-        fp = self._flat
-        gc = GradCtx(fp, defer=True)     # weight-gradient slabs: one batched reduce per exchange bucket
+    def backward_begin(self, tape_all, gout):
+        """The state the phases work on; no phase has run."""
+        return _Backward(self, tape_all, gout)
+
+    def backward_run(self, st: "_Backward", first: int = 0, last: int = 3):
+        """Phases ``first`` .. ``last`` of the backward pass ``backward_begin`` opened."""
+        for phase in self.BACKWARD_PHASES[first:last + 1]:
+            phase(self, st)
+
+    def _backward_up(self, st: "_Backward"):
+        """final conv -> final block -> up path"""
+        gc, gsl, k, x_in = st.gc, st.gsl, st.k, st.x_in
+        ups_tape, sf, fin, cat_shapes, gout, *held = st.head
+        st.head = None
         B, S = x_in.shape[0], x_in.shape[1]
         dim = self.dim
         n = len(self.in_out)
-        rbs = self.resblocks()
-        gss_all = ops.new((B, self._ss_total), x_in)
-        gsl = [gss_all[:, o:o + 2 * rb.dim_out] for o, rb in zip(self._ss_offsets, rbs)]
-        k = len(rbs) - 1
         gfin = self.final_conv.bwd(gc, fin, gout)
         gcatF = ops.new((B, S, S, 2 * dim), x_in)
         self.final_res_block.bwd(gc, sf, gfin, gsl[k], gcatF, False); k -= 1
@@ -697,18 +706,13 @@ class Unet(nn.Module):
             b1.bwd(gc, s1, _chan(gcat2, 0, co), gsl[k], gcat1, False); k -= 1
             gcats[s] = (gcat1, gcat2)
             g_next = _chan(gcat1, 0, co)
-        self._flush(gc, 0)
-        sync = getattr(self, "grad_sync", None)
-        if sync is not None:
-            sync.ready(self._ups_start, self._mid_start)
-            sync.ready(self._final_start, fp.total)
-        return dict(gc=gc, tape=tape, time_saved=time_saved, gss_all=gss_all, gsl=gsl, k=k, gcats=gcats,
-                    gcatF=gcatF, g_next=g_next, x_in=x_in, mid=(sm1, sm2, sm3))
+        st.k, st.gcats, st.gcatF, st.g = k, gcats, gcatF, g_next
+        self._bucket_done(gc, 0)
 
-    def backward_phase1b(self, st):
-        """middle blocks.  After it [_mid_start, _final_start) is final (10.2 M parameters)."""
-        gc, gsl, k, g_next, x_in = (st[key] for key in ("gc", "gsl", "k", "g_next", "x_in"))
-        sm1, sm2, sm3 = st["mid"]
+    def _backward_mid(self, st: "_Backward"):
+        """middle blocks"""
+        gc, gsl, k, g_next, x_in = st.gc, st.gsl, st.k, st.g, st.x_in
+        sm1, sm2, sm3 = st.mid
         gm2 = ops.new(sm3[0].shape, x_in)
         self.mid_block2.bwd(gc, sm3, g_next, gsl[k], gm2, False); k -= 1
         gm1 = ops.new(gm2.shape, x_in)
@@ -717,25 +721,14 @@ class Unet(nn.Module):
         gcur = ops.new(gm1.shape, x_in)
         self.mid_block1.bwd(gc, sm1, gm1, gsl[k], gcur, False); k -= 1
         del gm1
-        self._flush(gc, 1)
-        sync = getattr(self, "grad_sync", None)
-        if sync is not None:
-            sync.ready(self._mid_start, self._final_start)
-        st = dict(st)
-        st.update(k=k, gcur=gcur)
-        return st
+        st.k, st.g = k, gcur
+        self._bucket_done(gc, 1)
 
-    def backward_phase2(self, st):
-        """down path -> init conv -> time embedding / FiLM projections."""
-        self.backward_phase2b(self.backward_phase2a(st))
-
-    def backward_phase2a(self, st):
-        """down path -> init conv.  After it [_head_end, _ups_start) is final."""
-        gc, tape, gsl, k, gcats, gcatF, gcur, x_in = (st[key] for key in
-                                                      ("gc", "tape", "gsl", "k", "gcats", "gcatF", "gcur", "x_in"))
+    def _backward_down(self, st: "_Backward"):
+        """down path -> init conv"""
+        gc, tape, gsl, k, gcats, gcatF, gcur, x_in = st.gc, st.tape, st.gsl, st.k, st.gcats, st.gcatF, st.g, st.x_in
         dim = self.dim
         n = len(self.in_out)
-        sync = getattr(self, "grad_sync", None)
         for s in range(n - 1, -1, -1):
             b1, b2, attn, down = self.downs[s]
             ci, co = self.in_out[s]
@@ -761,20 +754,14 @@ class Unet(nn.Module):
                 gcur = gprev
         assert k == -1
         self.init_conv.bwd(gc, x_in, gcur, need_gx=False)
-        self._flush(gc, 2)
-        if sync is not None:
-            sync.ready(self._head_end, self._ups_start)
-        return st
+        self._bucket_done(gc, 2)
 
-    def backward_phase2b(self, st):
-        """time embedding / FiLM projections.  After it [0, _head_end) is final."""
-        gc = st["gc"]
-        sync = getattr(self, "grad_sync", None)
-        self._time_bwd(gc, st["time_saved"], st["gss_all"])
-        self._flush(gc, 3)
-        if sync is not None:
-            sync.ready(0, self._head_end)
-        self._flat.bind_grad_views()
+    def _backward_time(self, st: "_Backward"):
+        """time embedding / FiLM projections"""
+        self._time_bwd(st.gc, st.time_saved, st.gss_all)
+        self._bucket_done(st.gc, 3)
+
+    BACKWARD_PHASES = (_backward_up, _backward_mid, _backward_down, _backward_time)
 
     def forward(self, x: torch.Tensor, time: torch.Tensor, x_self_cond=None, classes=None) -> torch.Tensor:
         """NCHW in / NCHW out, like the reference Unet.forward (:428-471); ``x_self_cond`` is a constant (no gradient
@@ -820,6 +807,24 @@ class Unet(nn.Module):
         y = ops.new((B, self.out_dim, H, W), x)
         ops.nhwc_to_nchw(out, y)
         return y, tape, out
+
+
+class _Backward:
+    """What the phases of ``Unet``'s backward pass hand to each other: the gradient context, the saved activations the
+    later phases read, the gradients of the FiLM projections (``gss_all``, ``gsl`` its per-block views), the running
+    resblock index ``k``, the gradient concat buffers (``gcats``, ``gcatF``), the current gradient ``g`` and the
+    network input.  ``head``: what the first phase alone reads, and what else is to live until it returns."""
+
+    def __init__(self, net: Unet, tape_all, gout):
+        time_saved, tape, sm1, sm2, sm3, ups_tape, sf, fin, x_in, cat_shapes = tape_all
+        rbs = net.resblocks()
+        self.gc = GradCtx(net._flat, defer=True)     # weight-gradient slabs: one batched reduce per exchange bucket
+        self.time_saved, self.tape, self.mid, self.x_in = time_saved, tape, (sm1, sm2, sm3), x_in
+        self.head = (ups_tape, sf, fin, cat_shapes, gout)
+        self.gss_all = ops.new((x_in.shape[0], net._ss_total), x_in)
+        self.gsl = [self.gss_all[:, o:o + 2 * rb.dim_out] for o, rb in zip(net._ss_offsets, rbs)]
+        self.k = len(rbs) - 1
+        self.gcats = self.gcatF = self.g = None
 
 
 class _UnetFn(torch.autograd.Function):
@@ -1244,13 +1249,8 @@ def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset,
     return loss, (gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
 
 
-def hip_loss_backward_phase1(ctx, gl):
-    """Loss gradient + first half of the UNet backward.  ``gl``: device scalar [1] = dL/dloss."""
-    return ctx[0].model.backward_phase1b(hip_loss_backward_phase1a(ctx, gl))
-
-
-def hip_loss_backward_phase1a(ctx, gl):
-    """Loss gradient + backward of the final block and the up path (see Unet.backward_phase1a)."""
+def hip_loss_backward_begin(ctx, gl):
+    """Loss gradient (``gl``: device scalar [1] = dL/dloss) and the opened UNet backward (``Unet.backward_run``)."""
     gd, tape, out, target, t, (B, C, H, W) = ctx[:6]
     if tape is None:
         raise RuntimeError("p_losses forward ran without saving activations")
@@ -1259,7 +1259,9 @@ def hip_loss_backward_phase1a(ctx, gl):
     ops.lib().lgm_weighted_mse_bwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(),
                                    gd.loss_weight.data_ptr(), gl.data_ptr(), B, C, H * W, Cp,
                                    gout.data_ptr(), ops.stream())
-    return gd.model.backward_phase1a(tape, gout)
+    st = gd.model.backward_begin(tape, gout)
+    st.head += (out, target)             # let go of with the phase that reads ``gout``, also when ``ctx`` is gone by then
+    return st
 
 
 class _PLossFn(torch.autograd.Function):
@@ -1275,8 +1277,7 @@ class _PLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         gl = gloss.detach().float().reshape(1).contiguous()
-        st = hip_loss_backward_phase1(ctx.stuff, gl)
-        ctx.stuff[0].model.backward_phase2(st)
+        ctx.stuff[0].model.backward_run(hip_loss_backward_begin(ctx.stuff, gl))
         ctx.stuff = None
         return None, None, None, None, None, None, None, None, None, None
 

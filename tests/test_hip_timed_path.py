@@ -1,4 +1,4 @@
-"""GPU: parity of the path bench.py TIMES (``GraphedDDPMStep``: two HIP graphs per step) and of the BASELINE
+"""GPU: parity of the path bench.py TIMES (``GraphedDDPMStep``: one HIP graph per step) and of the BASELINE
 sizes themselves (B=128 DDPM against the CPU oracle, N=4096 x K=512 VQ with a non-collapsed codebook), plus
 the 2-rank data-parallel DDPM step (gloo ranks sharing the one GPU of the box)."""
 import json
