@@ -49,7 +49,8 @@ extern "C" {
                              * (entry points added since without a change to an existing one keep the number, as the
                              *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
                              *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table,
-                             *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh - a library
+                             *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh,
+                             *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint - a library
                              *  that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -579,6 +580,37 @@ int lgm_model_predictions_thresh(const float* x, const float* out, const int64_t
                                  const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
                                  int objective, int rederive, float* pred_noise, float* x_start, int B,
                                  int64_t per_sample, int n_table, const float* thresh, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Inpainting (RePaint, Lugmayr et al. 2022, Algorithm 1; an extension of the reference): a step of lgm_sample_step_thresh /
+ * lgm_dpm_step_thresh to level s (thresh may be NULL here: the static clamp; clip is always set), followed in the same
+ * kernel, per element, by
+ *     known_s = Ma*known + Mn*eps_k                                   the given image at level s
+ *     y       = m*known_s + (1 - m)*x_s                               m = 1: keep the known pixel
+ *     out     = (Jx, Jn) == (1, 0) ? y : Jx*y + Jn*eps_j              the jump back up to level u
+ * every product and sum rounded separately in this order (no contraction): m == 1 gives known_s and m == 0 gives x_s bit
+ * for bit.  (Ma, Mn, Jx, Jn) is a row of lgm_hip.sampler's inpainting plan: Ma = sqrt(acp[s]), Mn = sqrt(1 - acp[s]) ((1, 0)
+ * on the step that lands on the clean image), Jx = sqrt(acp[u] / acp[s]), Jn = sqrt(1 - acp[u] / acp[s]).
+ *   known  [B, HW, r4(C)] NHWC, pad lanes never read;   mask [B, HW] in [0, 1], shared by the channels;
+ *   eps_k, eps_j  [B, C, HW] NCHW dense like `noise`; eps_k is read only where Mn != 0, eps_j only where Jn != 0, and either
+ *   may be NULL where its weight is passed by value as zero.
+ * table != NULL (then counter and itable != NULL and xout == xin): the rows are row counter[0] of table[n_steps][8] and of
+ * itable[n_steps][4], the twelve scalars are ignored and both draws must be given; advance != 0 appends counter[0] += 1.
+ * The x0 that goes into the self-conditioning slice, into hist and into x0_out is the step's clipped prediction, not blended.
+ * known == NULL (then mask, eps_k, eps_j and itable NULL too): the update alone.  A mask without known is an error.
+ * They launch sample_step_slice_kernel / dpm_step_kernel, as every other update entry point does. */
+int lgm_sample_step_inpaint(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                            int64_t v_pitch, const float* noise, float* x0_out, int B, int C, int HW, int objective,
+                            int rederive, float A, float Bv, float R, float Rm1, float C0, float C1, float C2, float C3,
+                            const float* table, const int32_t* counter, int advance, const float* thresh,
+                            const float* known, const float* mask, const float* eps_k, const float* eps_j, float Ma,
+                            float Mn, float Jx, float Jn, const float* itable, void* stream);
+int lgm_dpm_step_inpaint(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                         int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, int objective, float A,
+                         float Bv, float R, float Rm1, float Kx, float K0, float K1, float Kn, const float* table,
+                         const int32_t* counter, int advance, const float* thresh, const float* known, const float* mask,
+                         const float* eps_k, const float* eps_j, float Ma, float Mn, float Jx, float Jn,
+                         const float* itable, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

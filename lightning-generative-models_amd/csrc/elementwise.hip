@@ -616,13 +616,47 @@ __global__ __launch_bounds__(256) void qsample_slice_kernel(const float* __restr
 // (its other lanes zero); zeros into xout's padding.  table == null: the scalars by value in `byval`.  thresh != null ([B],
 // from dyn_thresh_kernel): the clip is dynamic thresholding with s = thresh[b]; null: the static clamp, the launch there was.
 struct SampleRow { float v[8]; };
+// Inpainting (RePaint, Lugmayr et al. 2022, Algorithm 1; lgm_hip/sampler.py inpaint_walk): the operands of the tail both
+// update kernels run after their own body when `known` is non-null.  known NHWC [B, HW, r4(C)] (pad lanes never read), mask
+// [B, HW] (1 = keep the known pixel, shared by the channels), eps_k / eps_j NCHW dense like the step's noise; the row (M_a,
+// M_n, J_x, J_n) by value in `row`, or row counter[0] of table[n][4] (the counter the 8-wide table is read with).
+struct InpaintOps {
+  const float* known;
+  const float* mask;
+  const float* eps_k;
+  const float* eps_j;
+  const float* table;
+  float row[4];
+};
+// known_s = the given image at the level the step lands on, blended with the step's x_s where the mask says so, then the jump
+// back up (one affine Gaussian step however many levels) unless the row says (1, 0).  Contraction off, this order: m == 1
+// gives known_s and m == 0 gives x_s, bit for bit.
+__device__ __forceinline__ float inpaint_tail_one(float xs, float kv, float m, float ek, float ej, float Ma, float Mn,
+                                                  float Jx, float Jn) {
+#pragma clang fp contract(off)
+  const float known_s = Ma * kv + Mn * ek;
+  const float y = m * known_s + (1.f - m) * xs;
+  return (Jx == 1.f && Jn == 0.f) ? y : Jx * y + Jn * ej;
+}
+// the tail for element (pix, c) of sample b: loads what its row weighs with something other than zero
+__device__ __forceinline__ float inpaint_tail(const InpaintOps& ip, const int* __restrict__ counter, float xs, long pix, int c,
+                                              int C, int HW) {
+  const long r = ip.table ? 4L * counter[0] : 0;
+  const float Ma = ip.table ? ip.table[r + 0] : ip.row[0], Mn = ip.table ? ip.table[r + 1] : ip.row[1];
+  const float Jx = ip.table ? ip.table[r + 2] : ip.row[2], Jn = ip.table ? ip.table[r + 3] : ip.row[3];
+  const long b = pix / HW, p = pix % HW;
+  const long dense = (b * C + c) * HW + p;
+  const float ek = Mn != 0.f ? ip.eps_k[dense] : 0.f;
+  const float ej = Jn != 0.f ? ip.eps_j[dense] : 0.f;
+  return inpaint_tail_one(xs, ip.known[pix * ((C + 3) & ~3) + c], ip.mask[pix], ek, ej, Ma, Mn, Jx, Jn);
+}
 __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin, float* xout, long pitch, int lanes, int x_off,
                                                                 int sc_off, const float* __restrict__ v, long v_pitch,
                                                                 const float* __restrict__ noise, int B, int C, int HW,
                                                                 SampleRow byval, const float* __restrict__ table,
                                                                 const int* __restrict__ counter, int objective, int clip,
                                                                 int rederive, float* __restrict__ x0_out, long x0_pitch,
-                                                                const float* __restrict__ thresh) {
+                                                                const float* __restrict__ thresh, InpaintOps ip) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)B * HW * lanes) return;
   const float* row = table ? table + 8 * counter[0] : byval.v;
@@ -641,6 +675,7 @@ __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin
     const float s = dyn ? thresh[pix / HW] : 1.f;
     sample_update_obj(objective, xin[pix * pitch + x_off + c], v[pix * v_pitch + c], nz, A, Bv, clip, rederive, R, Rm1, C0,
                       C1, C2, noise ? C3 : 0.f, o, x0, dyn, s);
+    if (ip.known) o = inpaint_tail(ip, counter, o, pix, c, C, HW);
     xout[pix * pitch + x_off + c] = o;
     if (sc_off >= 0) xout[pix * pitch + sc_off + c] = x0;
   }
@@ -672,7 +707,7 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const float* xin, float* 
                                                        const float* __restrict__ noise, float* hist, int B, int C, int HW,
                                                        SampleRow byval, const float* __restrict__ table,
                                                        const int* __restrict__ counter, int objective, int clip,
-                                                       const float* __restrict__ thresh) {
+                                                       const float* __restrict__ thresh, InpaintOps ip) {
   const float* row = table ? table + 8 * counter[0] : byval.v;
   const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], Kx = row[4], K0 = row[5], K1 = row[6];
   const float Kn = noise ? row[7] : 0.f;
@@ -693,6 +728,7 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const float* xin, float* 
       const float s = dyn ? thresh[pix / HW] : 1.f;
       dpm_update_one(objective, xin[pix * pitch + x_off + c], v[pix * v_pitch + c], hv, nz, A, Bv, R, Rm1, clip, Kx, K0, K1,
                      Kn, o, x0, dyn, s);
+      if (ip.known) o = inpaint_tail(ip, counter, o, pix, c, C, HW);
       xout[pix * pitch + x_off + c] = o;
       if (sc_off >= 0) xout[pix * pitch + sc_off + c] = x0;
       hist[pix * hp + c] = x0;
@@ -1483,11 +1519,12 @@ extern "C" int lgm_selfcond_estimate(float* xin, int64_t pitch, int x_off, int s
 static int sample_step_slice_launch(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
                                     int64_t v_pitch, const float* noise, float* x0_out, int64_t x0_pitch, int B, int C,
                                     int HW, const SampleRow& row, const float* table, const int32_t* counter, int objective,
-                                    int clip, int rederive, int advance, void* stream, const float* thresh = nullptr) {
+                                    int clip, int rederive, int advance, void* stream, const float* thresh = nullptr,
+                                    const InpaintOps& ip = InpaintOps{}) {
   lgm_note_kernel(LGM_KNAME("sample_step_slice_kernel"));
   hipLaunchKernelGGL(sample_step_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream,
                      xin, xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, B, C, HW, row, table,
-                     (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch, thresh);
+                     (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch, thresh, ip);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("sample_step_slice");
   return LGM_OK;
@@ -1575,12 +1612,12 @@ extern "C" int lgm_sample_step_thresh(const float* xin, float* xout, int64_t pit
 static int dpm_step_launch(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
                            int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, const SampleRow& row,
                            const float* table, const int32_t* counter, int objective, int clip, int advance, void* stream,
-                           const float* thresh = nullptr) {
+                           const float* thresh = nullptr, const InpaintOps& ip = InpaintOps{}) {
   lgm_note_kernel("dpm_step_kernel");
   const long blocks = ((long)B * HW * pitch + 255) / 256;
   hipLaunchKernelGGL(dpm_step_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream, xin,
                      xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, hist, B, C, HW, row, table,
-                     (const int*)counter, objective, clip, thresh);
+                     (const int*)counter, objective, clip, thresh, ip);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("dpm_step");
   return LGM_OK;
@@ -1625,6 +1662,55 @@ extern "C" int lgm_dpm_step_thresh(const float* xin, float* xout, int64_t pitch,
   const SampleRow row = {{A, Bv, R, Rm1, Kx, K0, K1, Kn}};
   return dpm_step_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, hist, B, C, HW, row, table, counter, objective,
                          1, advance, stream, thresh);
+}
+
+// Inpainting: the update with the tail of inpaint_tail_one behind it, in the same launch.  One entry point per kernel for both
+// forms of the rows (table != NULL: row counter[0] of table[n][8] and of itable[n][4], the scalars ignored) and with or
+// without thresholds (thresh NULL: the static clamp).  known / mask / eps_k / eps_j as InpaintOps describes them; eps_k may
+// be NULL only where M_n is zero by value, eps_j only where J_n is - a table step needs both.  known == NULL (then no mask, no
+// draws, no itable): the update alone, the body the other entry points run.
+static bool inpaint_ops_ok(const float* known, const float* mask, const float* eps_k, const float* eps_j, float Mn, float Jn,
+                           const float* table, const float* itable, const void* xin, const void* xout) {
+  if (!known) return !mask && !eps_k && !eps_j && !itable;
+  if (!mask || known == xin || known == xout || mask == xin || mask == xout) return false;
+  if ((table == nullptr) != (itable == nullptr)) return false;
+  if (itable) return eps_k && eps_j;
+  return (eps_k || Mn == 0.f) && (eps_j || Jn == 0.f);
+}
+
+extern "C" int lgm_sample_step_inpaint(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                                       int64_t v_pitch, const float* noise, float* x0_out, int B, int C, int HW,
+                                       int objective, int rederive, float A, float Bv, float R, float Rm1, float C0,
+                                       float C1, float C2, float C3, const float* table, const int32_t* counter,
+                                       int advance, const float* thresh, const float* known, const float* mask,
+                                       const float* eps_k, const float* eps_j, float Ma, float Mn, float Jx, float Jn,
+                                       const float* itable, void* stream) {
+  LGM_REQUIRE(xin && xout && v && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) && v_pitch >= C &&
+                  objective_ok(objective) && (table == nullptr) == (counter == nullptr) && (table || !advance) &&
+                  (!table || xin == xout) && x0_out != xin && x0_out != xout &&
+                  inpaint_ops_ok(known, mask, eps_k, eps_j, Mn, Jn, table, itable, xin, xout),
+              "sample_step_inpaint: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, C0, C1, C2, C3}};
+  const InpaintOps ip = {known, mask, eps_k, eps_j, itable, {Ma, Mn, Jx, Jn}};
+  return sample_step_slice_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, x0_out, pitch, B, C, HW, row, table,
+                                  counter, objective, 1, rederive, advance, stream, thresh, ip);
+}
+
+extern "C" int lgm_dpm_step_inpaint(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                                    int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, int objective,
+                                    float A, float Bv, float R, float Rm1, float Kx, float K0, float K1, float Kn,
+                                    const float* table, const int32_t* counter, int advance, const float* thresh,
+                                    const float* known, const float* mask, const float* eps_k, const float* eps_j, float Ma,
+                                    float Mn, float Jx, float Jn, const float* itable, void* stream) {
+  LGM_REQUIRE(dpm_buffers_ok(xin, xout, pitch, x_off, sc_off, v, v_pitch, hist, B, C, HW, objective) &&
+                  (table == nullptr) == (counter == nullptr) && (table || !advance) && (!table || xin == xout) &&
+                  known != hist && mask != hist &&
+                  inpaint_ops_ok(known, mask, eps_k, eps_j, Mn, Jn, table, itable, xin, xout),
+              "dpm_step_inpaint: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, Kx, K0, K1, Kn}};
+  const InpaintOps ip = {known, mask, eps_k, eps_j, itable, {Ma, Mn, Jx, Jn}};
+  return dpm_step_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, hist, B, C, HW, row, table, counter, objective,
+                         1, advance, stream, thresh, ip);
 }
 
 // Dynamic thresholding: thresh[b] = max(1, lo + w (hi - lo)) with lo, hi the k-th and (k+1)-th smallest |x0| of sample b

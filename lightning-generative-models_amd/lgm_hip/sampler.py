@@ -15,6 +15,11 @@ Top down:
   * ``_Chain``, the device-resident state of a run and its eager step; ``_GraphedChain``, one captured step per ``_graph_key``:
     t[b] <- time table[counter], forward, noise draw, in-place update from coefficient table[counter], counter += 1 - replayed
     once per step with no Python between the ~230 launches, no host sync and no allocation.
+  * Inpainting (RePaint, Lugmayr et al. 2022, Algorithm 1; an extension): ``inpaint_walk`` / ``inpaint_steps`` / ``inpaint_plan``
+    turn (jump_length, resamples) into a longer chain of any of the three samplers with a second row of 4 float32 values per
+    step (M_a, M_n, J_x, J_n); the update launch then also blends the known image, noised to the level the step lands on, into
+    the known region and, after a step that is followed by a jump, re-noises the result up to the jump's level
+    (``_plan_inpaint``, ``inpaint``).  A chain without a known image takes the path, key, buffers and launches it took.
   * ``_run``: a chain of a plan.  Graph replay when only the final image is wanted, eager launches otherwise
     (``return_all_timesteps``, ``LGM_NO_SAMPLER_GRAPH=1``, no device, capture failed); bit-identical (tests/test_hip_unet.py).
 
@@ -25,6 +30,9 @@ the eager ancestral / DDIM step writes x_start into a buffer of its own, for ``p
 previous step's clipped x0 in ``hist``.  A thresholded step first has one workgroup per sample write s = max(1,
 quantile_p(|x0|)) into ``thresh``; the update then takes clamp(x0, -s, s) / s in place of the static clamp.  A class-conditional
 network reads one label per sample, fixed for the run; labels and guidance scale of a captured step live in static buffers.
+An inpainting chain holds the known image (NHWC, pitch r4(C)) and its mask ([B, HW]); its captured step has them, the two
+draws of the tail (eps_k, eps_j) and a second table [max_steps, 4] as static buffers, and draws in the fixed order noise,
+eps_k, eps_j, which the eager loop follows.  A chain longer than the tables is replayed in table-sized segments.
 """
 from __future__ import annotations
 
@@ -154,13 +162,18 @@ def dpm_coeffs(gd, pairs=None, order: int = 2, stochastic: bool = False):
 @dataclass(frozen=True)
 class _Plan:
     """A sampler: ``times[i]`` and ``rows[i]`` (8 float32 values) of step i; ``draws[i]``: the eager loop draws noise for it (or
-    takes the caller's); ``with_noise``: the captured step has a noise operand; ``rederive`` / ``dpm``: see the module text."""
+    takes the caller's); ``with_noise``: the captured step has a noise operand; ``rederive`` / ``dpm``: see the module text.
+    An inpainting plan (``_plan_inpaint``) also has ``irows[i]``, the 4 float32 values (M_a, M_n, J_x, J_n) of step i, and
+    ``kdraws[i]`` / ``jdraws[i]``: the eager loop draws eps_k / eps_j for it (M_n / J_n is not zero)."""
     times: tuple
     rows: tuple
     draws: tuple
     with_noise: bool
     rederive: bool = False
     dpm: bool = False
+    irows: Optional[tuple] = None
+    kdraws: tuple = ()
+    jdraws: tuple = ()
 
 
 def _plan_ancestral(gd, start: Optional[int] = None, steps: Optional[int] = None) -> _Plan:
@@ -182,6 +195,123 @@ def _plan_dpm(gd) -> _Plan:
                  tuple(t_next >= 0 and stochastic for _, t_next in pairs), stochastic, dpm=True)
 
 
+def inpaint_walk(n: int, jump_length: int, resamples: int) -> List[int]:
+    """The levels an inpainting chain visits (RePaint, Lugmayr et al. 2022: ``get_schedule_jump``).  Level n - 1 is the
+    sampler's first time, level 0 its last, -1 the clean image.  ``jumps[l] = resamples - 1`` for l in range(0, n -
+    jump_length, jump_length); the walk goes down one level at a time, and on arriving at a level with jumps left it uses
+    one and goes up ``jump_length`` levels; after level 0 comes -1.  Pure Python: no device, no library."""
+    n, jump_length, resamples = int(n), int(jump_length), int(resamples)
+    if n < 1:
+        raise ValueError(f"inpaint_walk needs at least one level, got n = {n}")
+    if jump_length < 1:
+        raise ValueError(f"jump_length must be at least 1, got {jump_length}")
+    if resamples < 1:
+        raise ValueError(f"resamples must be at least 1, got {resamples}")
+    if resamples > 1 and jump_length > n:
+        raise ValueError(f"jump_length {jump_length} exceeds the sampler's {n} levels")
+    jumps = {l: resamples - 1 for l in range(0, n - jump_length, jump_length)}
+    levels, l = [], n
+    while l >= 1:
+        l -= 1
+        levels.append(l)
+        if jumps.get(l, 0) > 0:
+            jumps[l] -= 1
+            for _ in range(jump_length):
+                l += 1
+                levels.append(l)
+    levels.append(-1)
+    return levels
+
+
+def inpaint_steps(levels):
+    """-> [(l, s, u)], one per forward of the walk ``levels``: the network runs at level l, the update lands on s = l - 1 and
+    the jump folded into the step goes up to u (u == s: none).  A down move followed by up moves is ONE step; an up move never
+    stands alone."""
+    steps, i = [], 0
+    while i + 1 < len(levels):
+        l, s = levels[i], levels[i + 1]
+        if s != l - 1:
+            raise ValueError(f"the walk goes up from level {l} without a step down before it")
+        j = i + 1
+        while j + 1 < len(levels) and levels[j + 1] == levels[j] + 1:
+            j += 1
+        steps.append((l, s, levels[j]))
+        i = j
+    return steps
+
+
+def inpaint_plan(acp, grid, steps):
+    """One float64 row (M_a, M_n, J_x, J_n) per step (l, s, u) of ``inpaint_steps``: the given image at level s is M_a known +
+    M_n eps_k with M_a = sqrt(acp_s), M_n = sqrt(1 - acp_s), (1, 0) at s = -1; the jump from s up to u is one Gaussian, x_u =
+    J_x x_s + J_n eps_j with J_x = sqrt(acp_u / acp_s), J_n = sqrt(1 - acp_u / acp_s), (1, 0) without a jump.  ``grid[l]``: the
+    time of level l; ``acp``: alphas_cumprod by time.  Pure Python on float64: no device, no library."""
+    rows = []
+    for l, s, u in steps:
+        a_s = float(acp[grid[s]]) if s >= 0 else 1.0
+        ma, mn = (math.sqrt(a_s), math.sqrt(1.0 - a_s)) if s >= 0 else (1.0, 0.0)
+        jx, jn = 1.0, 0.0
+        if u != s:
+            ratio = float(acp[grid[u]]) / a_s
+            jx, jn = math.sqrt(ratio), math.sqrt(1.0 - ratio)
+        rows.append((ma, mn, jx, jn))
+    return rows
+
+
+def inpaint_grid(gd, kind: str) -> List[int]:
+    """``grid[l]``, the time of level l: the ancestral chain's 0 .. T - 1, else the first times of the sampler's pairs"""
+    if kind == "ancestral":
+        return list(range(gd.num_timesteps))
+    pairs = gd.dpm_time_pairs() if kind == "dpm" else gd.ddim_time_pairs()
+    return [int(t) for t, _ in reversed(pairs)]
+
+
+def _sampler_kind(gd) -> str:
+    """which of the three samplers ``GaussianDiffusion.sample`` dispatches to"""
+    return "dpm" if gd.sampler == "dpm++" else "ddim" if gd.is_ddim_sampling else "ancestral"
+
+
+def _plan_inpaint(gd, jump_length: int = 1, resamples: int = 1, kind: Optional[str] = None) -> _Plan:
+    """The sampler ``kind`` (default: the one ``sample`` dispatches to) along ``inpaint_walk`` over its grid: the sampler's own
+    row for every step down - for DPM-Solver++ every monotone run of the walk is a chain of its own to ``dpm_plan``, so the
+    step after a jump is first-order and no history is read across one - and the 4-wide rows of ``inpaint_plan``.
+    ``resamples == 1``: the sampler's own plan with rows (M_a, M_n, 1, 0) beside it."""
+    kind = _sampler_kind(gd) if kind is None else kind
+    if kind not in ("ancestral", "ddim", "dpm"):
+        raise ValueError(f"unknown sampler kind {kind!r}")
+    grid = inpaint_grid(gd, kind)
+    steps = inpaint_steps(inpaint_walk(len(grid), jump_length, resamples))
+    time = lambda l: grid[l] if l >= 0 else -1  # noqa: E731
+    times = tuple(time(l) for l, _, _ in steps)
+    if kind == "ancestral":
+        rows = [_p_sample_coeffs(gd, t) for t in times]
+        draws, with_noise = tuple(t > 0 for t in times), True
+    elif kind == "ddim":
+        eta = gd.ddim_sampling_eta
+        rows = [_ddim_coeffs(gd, time(l), time(s), eta) for l, s, _ in steps]
+        draws, with_noise = tuple(s >= 0 and eta != 0.0 for _, s, _ in steps), eta != 0.0
+    else:
+        stochastic = bool(gd.dpm_stochastic)
+        rows, run = [], []
+        for l, s, u in steps:
+            run.append((time(l), time(s)))
+            if u != s or s < 0:
+                rows += dpm_coeffs(gd, run, gd.dpm_order, stochastic)
+                run = []
+        assert not run
+        draws, with_noise = tuple(s >= 0 and stochastic for _, s, _ in steps), stochastic
+    acp = [float(v) for v in gd.alphas_cumprod.detach().double().cpu().tolist()]
+    irows = tuple(tuple(_f32(c) for c in row) for row in inpaint_plan(acp, grid, steps))
+    return _Plan(times, tuple(rows), draws, with_noise, rederive=kind == "ddim", dpm=kind == "dpm", irows=irows,
+                 kdraws=tuple(r[1] != 0.0 for r in irows), jdraws=tuple(r[3] != 0.0 for r in irows))
+
+
+def _segments(n: int, max_steps: int):
+    """[(lo, hi)]: the steps of a chain of n in table-sized pieces, in order; a chain is never truncated to its tables"""
+    if max_steps < 1:
+        raise ValueError(f"max_steps must be at least 1, got {max_steps}")
+    return [(lo, min(lo + max_steps, n)) for lo in range(0, n, max_steps)]
+
+
 def _launch_thresh(net, shape, objective: int, x, v, head, rank, thresh, table=None, counter=None):
     """s[b] of a step into ``thresh``: from the x slice of ``x``, the network output ``v`` and the head (A, Bv, R, Rm1) by
     value, or from the row ``table[counter]`` (the by-value slots are then zero); ``rank`` = ``dyn_rank`` of a sample"""
@@ -191,7 +321,7 @@ def _launch_thresh(net, shape, objective: int, x, v, head, rank, thresh, table=N
 
 
 def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, hist=None, thresh=None, rank=None, row=None,
-                   table=None, counter=None, rederive: bool = False, dpm: bool = False):
+                   table=None, counter=None, rederive: bool = False, dpm: bool = False, inpaint=None):
     """The update of one step: ``x_next`` <- x slice of ``x``, network output ``v``, ``noise`` (None: none).  The row comes by
     value (``row``, eager launches) or from ``table[counter]`` (the captured step, which also advances the counter and passes
     zeros in the by-value slots).  ``rank`` (dynamic thresholding) puts ``_launch_thresh`` in front.  Every update clips x0.
@@ -204,6 +334,10 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
         DPM               no           by value  either            dpm_step: x0 into ``hist`` (and the slice)
         DPM               no           table     either            dpm_step_table
         DPM               yes          either    either            dpm_step_thresh
+
+    ``inpaint`` = (known, mask, eps_k, eps_j, irow, itable): the inpainting tail in the same launch, its row of 4 by value
+    (``irow``) or from ``itable[counter]``; whatever the other columns say the entry is then step_inpaint / dpm_step_inpaint,
+    which take the thresholds (or none) and both forms of the rows.
     """
     B, C, H, W = shape
     L, st, p = ops.lib(), ops.stream(), ops._p
@@ -211,7 +345,18 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
     A, Bv, R, Rm1, W0, W1, W2, W3 = row if not tabled else (0.0,) * 8
     red, tab = 1 if rederive else 0, (p(table), p(counter))
     src = (net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v), p(noise))
-    if rank is not None:
+    if inpaint is not None:
+        known, mask, eps_k, eps_j, irow, itable = inpaint
+        if rank is not None:
+            _launch_thresh(net, shape, objective, x, v, (A, Bv, R, Rm1), rank, thresh, table, counter)
+        end = (A, Bv, R, Rm1, W0, W1, W2, W3, *tab, 1 if tabled else 0, p(thresh if rank is not None else None),
+               known.data_ptr(), mask.data_ptr(), p(eps_k), p(eps_j), *(irow if not tabled else (0.0,) * 4), p(itable), st)
+        if dpm:
+            L.lgm_dpm_step_inpaint(x.data_ptr(), x_next.data_ptr(), *src, hist.data_ptr(), B, C, H * W, objective, *end)
+        else:
+            L.lgm_sample_step_inpaint(x.data_ptr(), x_next.data_ptr(), *src, None if net.self_condition or tabled else p(x0),
+                                      B, C, H * W, objective, red, *end)
+    elif rank is not None:
         _launch_thresh(net, shape, objective, x, v, (A, Bv, R, Rm1), rank, thresh, table, counter)
         end = (A, Bv, R, Rm1, W0, W1, W2, W3, *tab, 1 if tabled else 0, thresh.data_ptr(), st)
         if dpm:
@@ -238,7 +383,8 @@ class _Chain:
     """Device-resident state of one sampling run (NHWC, padded channels) and its eager step."""
 
     def __init__(self, gd, shape, init_noise: Optional[torch.Tensor], x_self_cond: Optional[torch.Tensor] = None,
-                 classes=None, cond_scale: float = 1.0):
+                 classes=None, cond_scale: float = 1.0, known: Optional[torch.Tensor] = None,
+                 mask: Optional[torch.Tensor] = None):
         self.gd = gd
         self.net = net = gd.model
         B, C, H, W = shape
@@ -268,6 +414,12 @@ class _Chain:
         # dynamic thresholding: the rank the threshold kernel selects and the [B] buffer it writes (readable after a step)
         self.dyn = None if _dyn(gd) is None else dyn_rank(C * H * W, _dyn(gd))
         self.thresh = torch.zeros(B, device=dev) if self.dyn is not None else None
+        # inpainting: the given image (normalised, NCHW -> NHWC with pitch r4(C)) and its mask [B, HW], 1 = keep
+        self.known = self.mask = None
+        if known is not None:
+            self.known = torch.zeros((B, H, W, self.Cp), device=dev)
+            ops.nchw_to_nhwc(known.to(dev).float().contiguous(), self.known)
+            self.mask = mask.to(dev).float().reshape(B, H * W).contiguous()
 
     def _dyn_thresh(self, v, head):
         """s[b] of the step into ``self.thresh``: from the x slice, the network output and the head (A, Bv, R, Rm1)"""
@@ -281,17 +433,23 @@ class _Chain:
                 self.tbuf[t] = tb
         return tb
 
-    def step(self, t: int, noise: Optional[torch.Tensor], row, rederive: bool = False, dpm: bool = False):
+    def step(self, t: int, noise: Optional[torch.Tensor], row, rederive: bool = False, dpm: bool = False, irow=None,
+             eps_k: Optional[torch.Tensor] = None, eps_j: Optional[torch.Tensor] = None):
         """One eager step at time t from a row of 8; no noise operand where the row weighs it with zero (t == 0 of the
         ancestral chain, eta == 0, the ODE, a last step that returns x0).  Afterwards ``x`` is the new image and ``x0`` the
-        clipped x_start: the self-conditioning slice of ``x``, else ``hist`` (DPM-Solver++), else the buffer of its own."""
+        clipped x_start: the self-conditioning slice of ``x``, else ``hist`` (DPM-Solver++), else the buffer of its own.
+        ``irow`` (an inpainting chain): the step's (M_a, M_n, J_x, J_n); ``eps_k`` / ``eps_j`` go in where M_n / J_n is not zero."""
         B, C, H, W = self.shape
         net = self.net
         if dpm and self.hist is None:
             self.hist = torch.empty((B, H, W, self.Cp), device=self.x.device)
         v = net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
+        inpaint = None
+        if irow is not None:
+            inpaint = (self.known, self.mask, eps_k if irow[1] != 0.0 else None, eps_j if irow[3] != 0.0 else None, irow, None)
         _launch_update(net, self.shape, _objective(self.gd), v, noise if row[7] != 0.0 else None, x=self.x, x_next=self.x_next,
-                       x0=self.x0, hist=self.hist, thresh=self.thresh, rank=self.dyn, row=row, rederive=rederive, dpm=dpm)
+                       x0=self.x0, hist=self.hist, thresh=self.thresh, rank=self.dyn, row=row, rederive=rederive, dpm=dpm,
+                       inpaint=inpaint)
         if net.self_condition:
             self.x0 = net.sc_slice(self.x_next)
         elif dpm:
@@ -318,13 +476,13 @@ class _GraphedChain:
     """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it."""
 
     def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096, guided: bool = False,
-                 dpm: bool = False, dyn: Optional[float] = None):
+                 dpm: bool = False, dyn: Optional[float] = None, inpaint: bool = False):
         net = gd.model
         objective = _objective(gd)
         self._net = weakref.ref(net)                 # the cache is keyed weakly on the network: no strong reference here
         B, C, H, W = shape
         dev = gd.betas.device
-        self.shape, self.with_noise = shape, with_noise
+        self.shape, self.with_noise, self.inpaint = shape, with_noise, inpaint
         fp = net._flat
         # identity of everything whose address the captured launches carry: the flat object and its buffers
         self._bound = (weakref.ref(fp), fp.data.data_ptr(),
@@ -345,6 +503,13 @@ class _GraphedChain:
         # rank is baked into the captured launch, which is why the percentile is part of the cache key
         self.thresh = torch.zeros(B, device=dev) if dyn is not None else None
         rank = None if dyn is None else dyn_rank(C * H * W, dyn)
+        # inpainting: the given image and its mask, the two draws of the tail and the 4-wide table, static like the rest; the
+        # tail reads a draw only where the step's row weighs it
+        self.known = torch.zeros((B, H, W, _r4(C)), device=dev) if inpaint else None
+        self.mask = torch.zeros((B, H * W), device=dev) if inpaint else None
+        self.eps_k = torch.zeros(shape, device=dev) if inpaint else None
+        self.eps_j = torch.zeros(shape, device=dev) if inpaint else None
+        self.itable = torch.zeros((max_steps, 4), device=dev) if inpaint else None
         self.inject = False
         self.max_steps = max_steps
 
@@ -354,9 +519,14 @@ class _GraphedChain:
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
+            tail = None
+            if inpaint:                              # the draws in a fixed order: noise, eps_k, eps_j
+                ek = self.eps_k if self.inject else torch.randn(shape, device=dev)
+                ej = self.eps_j if self.inject else torch.randn(shape, device=dev)
+                tail = (self.known, self.mask, ek, ej, None, self.itable)
             # x (and, self-conditioned, the x_start handed on): the slices of the static buffer, in place
             _launch_update(net, shape, objective, v, nz, x=self.x, x_next=self.x, hist=self.hist, thresh=self.thresh, rank=rank,
-                           table=self.table, counter=self.counter, rederive=rederive, dpm=dpm)
+                           table=self.table, counter=self.counter, rederive=rederive, dpm=dpm, inpaint=tail)
 
         net.refresh_derived_weights(False)
         rng_state = torch.cuda.get_rng_state(dev)
@@ -369,7 +539,7 @@ class _GraphedChain:
         cur.wait_stream(side)
         torch.cuda.synchronize()
         self.graphs = {}
-        for inject in ((False, True) if with_noise else (False,)):
+        for inject in ((False, True) if with_noise or inpaint else (False,)):
             self.inject = inject
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
@@ -385,35 +555,51 @@ class _GraphedChain:
                 and (None if fp.data_uf is None else fp.data_uf.data_ptr()) == uf
                 and (None if fp.data_t is None else fp.data_t.data_ptr()) == dt)
 
-    def run(self, x0_nhwc, times, coeffs, noises, classes=None, cond_scale: float = 1.0):
+    def run(self, x0_nhwc, times, coeffs, noises, classes=None, cond_scale: float = 1.0, inpaint=None):
         """times[i], coeffs[i] (8 floats) per step; noises: None (draw on device) or a list with one NCHW tensor or
         None per step; classes: the run's device labels (class-conditional network).  Returns the final NHWC image (a view
-        of the static buffer)."""
+        of the static buffer).  ``inpaint`` (a step captured for inpainting) = (known NHWC, mask [B, HW], rows of 4); an entry
+        of ``noises`` is then a triple (noise, eps_k, eps_j) or None.  A chain longer than the tables is replayed in table-
+        sized segments: refill the tables, zero the counter."""
         n = len(times)
         if self.classes is not None:
             self.classes.copy_(classes)
         if self.scale is not None:
             self.scale.fill_(float(cond_scale))
-        assert n <= self.max_steps
+        assert (inpaint is not None) == self.inpaint
+        if self.inpaint:
+            known, mask, irows = inpaint
+            self.known.copy_(known)
+            self.mask.copy_(mask)
         self._net().refresh_derived_weights(False)   # the weights may have moved since the last chain (EMA updates)
         self.x.copy_(x0_nhwc)
         net = self._net()
         if net.self_condition:
             net.sc_slice(self.x).zero_()             # a chain starts without an estimate (the reference's x_start = None)
-        self.table[:n].copy_(torch.tensor(coeffs, dtype=torch.float32), non_blocking=False)
-        self.ttable[:n].copy_(torch.tensor(times, dtype=torch.long))
-        self.counter.zero_()
-        inject = noises is not None and self.with_noise
-        for i in range(n):
-            if inject and noises[i] is not None:
-                self.noise.copy_(noises[i])
-            elif inject:
-                self.noise.zero_()
-            self.graphs[inject].replay()
+        inject = noises is not None and (self.with_noise or self.inpaint)
+
+        def put(buf, value):
+            if buf is not None and value is not None:
+                buf.copy_(value)
+            elif buf is not None:
+                buf.zero_()
+        for lo, hi in _segments(n, self.max_steps):
+            self.table[:hi - lo].copy_(torch.tensor(coeffs[lo:hi], dtype=torch.float32), non_blocking=False)
+            self.ttable[:hi - lo].copy_(torch.tensor(times[lo:hi], dtype=torch.long))
+            if self.inpaint:
+                self.itable[:hi - lo].copy_(torch.tensor(irows[lo:hi], dtype=torch.float32))
+            self.counter.zero_()
+            for i in range(lo, hi):
+                if inject and self.inpaint:
+                    nz, ek, ej = noises[i] if noises[i] is not None else (None, None, None)
+                    put(self.noise, nz), put(self.eps_k, ek), put(self.eps_j, ej)
+                elif inject:
+                    put(self.noise, noises[i])
+                self.graphs[inject].replay()
         return self.x
 
 
-def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: bool):
+def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: bool, inpaint: bool = False):
     """The cache key of a captured step under its network: everything baked into the launches that the network does not fix"""
     key = (tuple(shape), bool(with_noise))
     if gd.objective != "pred_v":                     # two diffusions of other objectives may share one network
@@ -424,19 +610,23 @@ def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: b
         key = ("dpm++", gd.objective) + key
     if _dyn(gd) is not None:                         # the percentile in it: the rank is baked into the launch
         key = ("dynthresh", _dyn(gd)) + key
+    if inpaint:                                      # the tail's operands and the 4-wide table in the launch
+        key = ("inpaint",) + key
     return key
 
 
-def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bool = False, dpm: bool = False):
+def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bool = False, dpm: bool = False,
+                 inpaint: bool = False):
     """-> a _GraphedChain for (network, shape, objective), or None (graph replay disabled / capture failed: eager launches).
     ``rederive``: the DDIM chain's re-derived noise, part of the captured launch for pred_noise / pred_x0.
-    ``dpm``: the DPM-Solver++ step (its own update kernel and history buffer): a graph of its own."""
+    ``dpm``: the DPM-Solver++ step (its own update kernel and history buffer): a graph of its own.
+    ``inpaint``: the step with the inpainting tail (its operands are static buffers of the graph): a graph of its own."""
     if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or gd.betas.device.type != "cuda":
         return None
     net = gd.model
     net.prepare_hip(gd.betas.device)                 # may rebuild the flat storage (model.to(), new parameter storage)
     per_net = _GRAPHS.setdefault(net, {})
-    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm)
+    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint)
     ent = per_net.get(key)
     if isinstance(ent, _GraphedChain) and not ent.matches(net):
         ent = None                                   # captured against buffers the network no longer uses
@@ -448,7 +638,7 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
         ent = None
     if ent is None:
         try:
-            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd))
+            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd), inpaint=inpaint)
         except Exception as e:  # capture is an optimisation
             print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",
                   file=sys.stderr, flush=True)
@@ -474,24 +664,48 @@ def dpm_step(chain: _Chain, t: int, noise: Optional[torch.Tensor], coeffs):
 
 
 def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-         classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None):
+         classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None, known=None, mask=None):
     """One chain of ``plan`` from ``init_noise`` (default: drawn) -> the image, or every image of the chain stacked along
     dim 1.  ``noises``: one NCHW tensor (or None) per step in place of the draws; ``unnormalize``: default = the model's
-    auto_normalize (p_sample_loop :779).  No graph for a chain without steps."""
-    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale)
+    auto_normalize (p_sample_loop :779).  No graph for a chain without steps.  An inpainting plan takes ``known`` (NCHW,
+    normalised) and ``mask`` ([B, HW] or [B, 1, H, W], 1 = keep); an entry of ``noises`` is then a triple (noise, eps_k,
+    eps_j) with a tensor wherever the plan's draw flag of the step is set; the draws are taken in that order."""
+    tail = plan.irows is not None
+    if tail and (known is None or mask is None):
+        raise ValueError("an inpainting plan needs the known image and its mask")
+    if tail and noises is not None:
+        for i, trip in enumerate(noises):
+            flags = (plan.draws[i], plan.kdraws[i], plan.jdraws[i])
+            if any(f and (trip is None or trip[k] is None) for k, f in enumerate(flags)):
+                raise ValueError(f"step {i} of the inpainting chain draws {flags}, the injected triple lacks one of them")
+    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale, **(dict(known=known, mask=mask) if tail else {}))
     unn = gd.auto_normalize if unnormalize is None else bool(unnormalize)
     gc = None
     if plan.times and not return_all_timesteps:
-        gc = _graph_chain(gd, shape, plan.with_noise, rederive=plan.rederive, guided=chain.cond_scale != 1.0, dpm=plan.dpm)
+        gc = _graph_chain(gd, shape, plan.with_noise, rederive=plan.rederive, guided=chain.cond_scale != 1.0, dpm=plan.dpm,
+                          inpaint=tail)
+    if gc is not None and tail:
+        chain.x = gc.run(chain.x, plan.times, plan.rows, noises, chain.classes, chain.cond_scale,
+                         inpaint=(chain.known, chain.mask, plan.irows))
+        return chain.image(unn)
     if gc is not None:
         chain.x = gc.run(chain.x, plan.times, plan.rows, noises if plan.with_noise else None, chain.classes, chain.cond_scale)
         return chain.image(unn)
     frames = [chain.image(False)] if return_all_timesteps else None
+    draw = lambda: torch.randn(shape, device=chain.x.device)  # noqa: E731
     for i, (t, row, draws) in enumerate(zip(plan.times, plan.rows, plan.draws)):
-        nz = None
-        if draws:
-            nz = noises[i] if noises is not None else torch.randn(shape, device=chain.x.device)
-        chain.step(t, nz, row, plan.rederive, plan.dpm)
+        if tail:                                     # the draws in the captured step's order: noise, eps_k, eps_j
+            flags = (draws, plan.kdraws[i], plan.jdraws[i])
+            if noises is None:
+                nz, ek, ej = (draw() if f else None for f in flags)
+            else:
+                nz, ek, ej = (g if f else None for g, f in zip(noises[i] or (None,) * 3, flags))
+            chain.step(t, nz, row, plan.rederive, plan.dpm, plan.irows[i], ek, ej)
+        else:
+            nz = None
+            if draws:
+                nz = noises[i] if noises is not None else draw()
+            chain.step(t, nz, row, plan.rederive, plan.dpm)
         if return_all_timesteps:
             frames.append(chain.image(False))
     if return_all_timesteps:
@@ -530,3 +744,15 @@ def dpm_solver_sample(gd, shape, return_all_timesteps=False, init_noise=None, no
     """DPM-Solver++(2M) on ``gd.dpm_time_pairs()``, graph-replayed like ``ddim_sample``.  ``noises``: one NCHW tensor per pair
     with t_next >= 0, read by the SDE form only."""
     return _run(gd, shape, _plan_dpm(gd), return_all_timesteps, init_noise, noises, classes, cond_scale)
+
+
+@torch.no_grad()
+def inpaint(gd, known, mask, jump_length: int = 1, resamples: int = 1, return_all_timesteps=False, init_noise=None,
+            noises=None, classes=None, cond_scale: float = 1.0, kind: Optional[str] = None, unnormalize: Optional[bool] = None):
+    """Inpainting (RePaint, Lugmayr et al. 2022, Algorithm 1) with the sampler ``kind`` (default: the one ``sample`` dispatches
+    to): a chain from noise in which every step replaces the known region (``mask`` 1) by ``known`` (NCHW, normalised) noised
+    to the level the step lands on, walked along ``inpaint_walk(n, jump_length, resamples)``.  Per step one forward and the
+    ONE update launch of the plain chain; graph-replayed like it.  ``noises``: per step a triple (noise, eps_k, eps_j)."""
+    shape = tuple(known.shape)
+    return _run(gd, shape, _plan_inpaint(gd, jump_length, resamples, kind), return_all_timesteps, init_noise, noises, classes,
+                cond_scale, unnormalize, known=known, mask=mask)

@@ -1169,6 +1169,29 @@ class GaussianDiffusion(nn.Module):
                   classes=classes, cond_scale=scale)
 
     @torch.no_grad()
+    def inpaint(self, known, mask, jump_length=1, resamples=1, classes=None, cond_scale=None, return_all_timesteps=False):
+        """Inpainting (extension; RePaint, Lugmayr et al. 2022, Algorithm 1): keep ``known`` ([B, C, H, W] in the data range,
+        normalised as ``forward`` normalises) where ``mask`` ([B, 1, H, W] or [B, H, W], values in [0, 1]) is 1 and generate
+        the rest.  The sampler is the one ``sample`` dispatches to; every step replaces the known region by the image noised
+        to the step's level, and with ``resamples`` > 1 the chain is walked back up ``jump_length`` levels at a time
+        (``lgm_hip.sampler.inpaint_walk``).  ``classes`` / ``cond_scale`` as in ``sample``."""
+        from lgm_hip import sampler
+        if known.dim() != 4 or tuple(known.shape[1:]) != (self.channels, self.img_size, self.img_size):
+            raise ValueError(f"known must be [B, {self.channels}, {self.img_size}, {self.img_size}], got {tuple(known.shape)}")
+        b, _, h, w = known.shape
+        if tuple(mask.shape) not in ((b, 1, h, w), (b, h, w)):
+            raise ValueError(f"mask must be [{b}, 1, {h}, {w}] or [{b}, {h}, {w}], got {tuple(mask.shape)}")
+        mask = mask.to(device=self.device, dtype=torch.float32).reshape(b, h * w)
+        if mask.numel() and not bool(((mask >= 0) & (mask <= 1)).all()):
+            raise ValueError("mask values must lie in [0, 1]")
+        scale = self.cond_scale if cond_scale is None else cond_scale
+        if classes is None:
+            scale = 1.0
+        classes, scale = self._guidance(classes, scale, b, self.device)
+        return sampler.inpaint(self, self.normalize(known.to(self.device).float()), mask, jump_length, resamples,
+                               return_all_timesteps, classes=classes, cond_scale=scale)
+
+    @torch.no_grad()
     def interpolate(self, x1, x2, t=None, lam=0.5, classes=None, cond_scale=1.0):
         """reference :847-867: noise both images to step t, blend, walk the ancestral chain back to 0 (no unnormalise)."""
         from lgm_hip import sampler
@@ -1352,6 +1375,12 @@ class DDPM(LightningModule):
                 logger.experiment.log({"Random Generation": [wandb.Image(self.last_samples)]}, step=self.global_step)
             except Exception:  # noqa
                 pass
+
+    @torch.no_grad()
+    def inpaint(self, known, mask, **kw):
+        """``GaussianDiffusion.inpaint`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model.inpaint(known, mask, **kw)
 
     def training_step(self, batch):
         return self._common_step(batch, "train")
