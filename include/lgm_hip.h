@@ -50,7 +50,7 @@ extern "C" {
                              *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
                              *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table,
                              *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh,
-                             *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint - a library
+                             *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint, lgm_vlb_term, lgm_vlb_term_table - a library
                              *  that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -611,6 +611,35 @@ int lgm_dpm_step_inpaint(const float* xin, float* xout, int64_t pitch, int x_off
                          const int32_t* counter, int advance, const float* thresh, const float* known, const float* mask,
                          const float* eps_k, const float* eps_j, float Ma, float Mn, float Jx, float Jn,
                          const float* itable, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Variational-bound likelihood in bits per dimension (Ho et al. 2020, eq. 5; Nichol & Dhariwal 2021, calc_bpd_loop; an
+ * extension of the reference).  One evaluated timestep is: lgm_qsample_target_slice -> network -> one of the two entry points
+ * below, which reduce over a sample's C * HW elements, one workgroup per sample, into out[n_rows][3][B] (float32):
+ *     out[r][0][b]  the term of the bound in bits per dimension (below)
+ *     out[r][1][b]  mean (x0_pred - x0)^2          out[r][2][b]  mean (eps_pred - noise)^2
+ * img [B, C, HW] NCHW dense (x0 = img * 2 - 1 when normalize), noise NCHW dense (the draw q_sample used), x_t in lanes [x_off,
+ * x_off + C) of xin [B, HW, pitch], the network output in lanes [0, C) of v [B, HW, v_pitch]; no other lane is read.  (x0_pred,
+ * eps_pred) is model_predictions' branch of `objective` from the head (A, S, R, Rm1) = (sqrt_ac, sqrt_1mac, sqrt_recip,
+ * sqrt_recipm1)[t], x0_pred clamped to [-1, 1] when clip is set and the noise then re-derived from it.  By kind:
+ *   0  KL(q(x_{t-1} | x_t, x0) || p(x_{t-1} | x_t)), t >= 1:  (KC + KW * mean(d^2)) / ln 2, d = P1 * (x0_pred - x0) - the difference of
+ *      the two posterior means, which share P2 * x_t; KC = 0.5 (-1 + lv_p - lv_q + exp(lv_q - lv_p)), KW = 0.5 exp(-lv_p)
+ *   1  decoder, t = 0:  -mean(log p) / ln 2, log p the discretised Gaussian log-likelihood of x0 on the 8-bit grid under mean
+ *      P1 * x0_pred + P2 * x_t and standard deviation 1 / inv_std with the tanh approximation of the normal CDF, probabilities
+ *      floored at 1e-12, evaluated in a cancellation-free form (csrc/elementwise.hip vlb_decoder_logp)
+ *   2  prior KL(q(x_T | x0) || N(0, I)):  (KC + KW * mean(x0^2)) / ln 2 with KC = 0.5 (-1 - log(1 - acp) + (1 - acp)), KW = 0.5 acp
+ *      from the host; reads img only (noise, xin, v may be NULL), out[r][1] and out[r][2] come out 0
+ * No contraction; the sums in a fixed order, no atomics: the same bits on every run and under graph replay.
+ * lgm_vlb_term: the row by value, output row out_row.  lgm_vlb_term_table: the row is table[stride * counter[0] ...] = (A, S, R,
+ *   Rm1, P1, P2, kind, KC, KW, inv_std, ., .) (stride >= 12; lgm_hip.likelihood.vlb_plan), the output row counter[0]; a counter
+ *   outside [0, n_rows) writes nothing; advance != 0 appends counter[0] += 1.  Both launch vlb_term_kernel. */
+int lgm_vlb_term(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch, int x_off,
+                 const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip, float A, float S, float R,
+                 float Rm1, float P1, float P2, int kind, float KC, float KW, float inv_std, float* out, int n_rows,
+                 int out_row, void* stream);
+int lgm_vlb_term_table(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch, int x_off,
+                       const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip, const float* table,
+                       int stride, const int32_t* counter, float* out, int n_rows, int advance, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

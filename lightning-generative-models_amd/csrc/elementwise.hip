@@ -854,6 +854,108 @@ __global__ __launch_bounds__(DT_THREADS) void dyn_thresh_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------------------------------
+// Variational-bound terms in bits per dimension (Ho et al. 2020, eq. 5; Nichol & Dhariwal 2021, calc_bpd_loop; an extension
+// of the reference; lgm_hip/likelihood.py vlb_plan): per sample b and evaluated timestep (row r)
+//     out[r][0][b]  the term of the bound   out[r][1][b] = mean (x0_pred - x0)^2   out[r][2][b] = mean (eps_pred - noise)^2
+// from the image x0 (NCHW, normalised here when `normalize`), the noise q_sample drew (NCHW), x_t in the x slice of the network's
+// input buffer and the network output, with (x0_pred, eps_pred) = predictions_one(rederive = 1).  The row of VLB_ROW floats
+//     (A, S, R, Rm1, P1, P2, kind, KC, KW, inv_std, ., .)        P1, P2 = posterior_mean_coef1/2[t]
+//   kind 0, KL (t >= 1):  (KC + KW mean(d^2)) / ln 2,  d = P1 (x0_pred - x0).  Both posterior means share P2 x_t, so the
+//           difference of the means IS P1 (x0_pred - x0); at large t, P1 is 1e-2 ... 1e-4 and two O(1) means formed in float32
+//           and subtracted would keep three to four digits less.
+//   kind 1, decoder (t = 0):  -mean(log p) / ln 2,  log p = vlb_decoder_logp below.
+//   kind 2, prior:  (KC + KW mean(x0^2)) / ln 2 with the host's KC = 0.5 (-1 - log(1 - acp) + (1 - acp)), KW = 0.5 acp: the
+//           sum in KC cancels to ~acp^2 / 2 and is formed in float64 on the host.  Reads img only; [1] and [2] come out 0.
+// One workgroup per sample; a lane owns pixels and loops over the channels (the NCHW reads coalesce over pixels); three sums
+// through lgm_block_sum in its fixed order - no atomics, no second stage: eager launches and graph replays give the same
+// bits.  kind is launch-uniform.  A row index outside [0, n_rows) writes nothing.
+// ---------------------------------------------------------------------------------------
+constexpr int VLB_ROW = 12;
+constexpr int VLB_THREADS = 256;
+struct VlbRow { float v[VLB_ROW]; };
+__device__ __forceinline__ float vlb_softplus(float x) { return x > 0.f ? x + log1pf(expf(-x)) : log1pf(expf(x)); }
+// log(1 - exp(-y)) for y > 0 without cancellation at either end
+__device__ __forceinline__ float vlb_log1mexp(float y) { return y > 0.69314718f ? log1pf(-expf(-y)) : logf(-expm1f(-y)); }
+// Discretised Gaussian log-likelihood (Nichol & Dhariwal 2021, discretized_gaussian_log_likelihood) of x on the 8-bit grid
+// of [-1, 1] under N(mean, 1 / inv_std^2) with the tanh approximation of the normal CDF, Phi(z) = (1 + tanh(k (z + 0.044715
+// z^3))) / 2 = sigmoid(2 u(z)), k = sqrt(2 / pi): log Phi(z+) for x < -0.999, log(1 - Phi(z-)) for x > 0.999, else log(Phi(z+) -
+// Phi(z-)), z+- = inv_std (x - mean +- 1/255), every probability floored at 1e-12.  1 - tanh(u) has no float32 bits left from
+// |z| ~ 4.6 while the floor only takes over at |z| ~ 6.1, so the same function is evaluated without cancellation: with a =
+// 2 u(z+), b = 2 u(z-), h = (a - b) / 2 > 0 and m = (a + b) / 2
+//     sigmoid(a) - sigmoid(b) = sinh(h) / (cosh(m) + cosh(h)),   log sigmoid(a) = -softplus(-a),   log(1 - sigmoid(b)) = -softplus(b)
+// h and m come from the polynomial identities in (z_c, delta) = (inv_std (x - mean), inv_std / 255), not from a difference of
+// two values of u, and the logarithm of the quotient is taken with max(|m|, h) factored out, so no exponential overflows.
+__device__ __forceinline__ float vlb_decoder_logp(float x, float mean, float inv_std) {
+#pragma clang fp contract(off)
+  const float K = 0.7978845608f, C3 = 0.044715f, FLOOR = -27.6310211f;     // sqrt(2 / pi); log 1e-12
+  const float zc = inv_std * (x - mean), dl = inv_std * (1.f / 255.f);
+  float lp;
+  if (x < -0.999f || x > 0.999f) {
+    const float z = x < 0.f ? zc + dl : zc - dl;
+    const float a = 2.f * (K * (z + C3 * (z * z * z)));
+    lp = -vlb_softplus(x < 0.f ? -a : a);
+  } else {
+    const float h = K * (2.f * dl + C3 * (6.f * (zc * zc) * dl + 2.f * (dl * dl * dl)));
+    const float m = fabsf(K * (2.f * zc + C3 * (2.f * (zc * zc * zc) + 6.f * zc * (dl * dl))));
+    // log sinh h = h + log(1 - e^{-2h}) - ln 2;  log(cosh m + cosh h) = M + log(1 + rest) - ln 2,  M = max(m, h)
+    const float rest = h >= m ? expf(m - h) + expf(-m - h) + expf(-2.f * h) : expf(h - m) + expf(-h - m) + expf(-2.f * m);
+    lp = (h >= m ? 0.f : h - m) + vlb_log1mexp(2.f * h) - log1pf(rest);
+  }
+  return fmaxf(lp, FLOOR);
+}
+__global__ __launch_bounds__(VLB_THREADS) void vlb_term_kernel(const float* __restrict__ img, const float* __restrict__ noise,
+                                                               int normalize, const float* __restrict__ xin, long pitch,
+                                                               int x_off, const float* __restrict__ v, long v_pitch, int B,
+                                                               int C, int HW, VlbRow byval, const float* __restrict__ table,
+                                                               int stride, const int* __restrict__ counter, int out_row,
+                                                               int objective, int clip, float* __restrict__ out, int n_rows) {
+#pragma clang fp contract(off)
+  __shared__ float sh[16];
+  const int r = table ? counter[0] : out_row;
+  if (r < 0 || r >= n_rows) return;
+  const float* row = table ? table + (long)stride * r : byval.v;
+  const float A = row[0], S = row[1], R = row[2], Rm1 = row[3], P1 = row[4], P2 = row[5];
+  const int kind = (int)row[6];
+  const float KC = row[7], KW = row[8], inv_std = row[9];
+  const int b = blockIdx.x;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  for (int p = threadIdx.x; p < HW; p += VLB_THREADS) {
+    const long pix = (long)b * HW + p;
+    for (int c = 0; c < C; ++c) {
+      const long dense = ((long)b * C + c) * HW + p;
+      float x0 = img[dense];
+      if (normalize) x0 = x0 * 2.f - 1.f;
+      if (kind == 2) {
+        s0 += x0 * x0;
+        continue;
+      }
+      const float xv = xin[pix * pitch + x_off + c];
+      float e, x0p;
+      predictions_one(objective, xv, v[pix * v_pitch + c], A, S, R, Rm1, clip, 1, e, x0p);
+      const float d0 = x0p - x0, de = e - noise[dense];
+      s1 += d0 * d0;
+      s2 += de * de;
+      if (kind == 0) {
+        const float d = P1 * d0;
+        s0 += d * d;
+      } else {
+        s0 += vlb_decoder_logp(x0, P1 * x0p + P2 * xv, inv_std);
+      }
+    }
+  }
+  s0 = lgm_block_sum(s0, sh);
+  s1 = lgm_block_sum(s1, sh);
+  s2 = lgm_block_sum(s2, sh);
+  if (threadIdx.x == 0) {
+    const float n = (float)C * (float)HW, LN2 = 0.69314718f;
+    float* o = out + (long)r * 3 * B + b;
+    o[0] = (kind == 1 ? -(s0 / n) : KC + KW * (s0 / n)) / LN2;
+    o[B] = s1 / n;
+    o[2 * B] = s2 / n;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // The UNet's time embedding in ONE launch (reference ddpm.py:119-132 SinusoidalPosEmb, :328-333 time_mlp = Linear ->
 // GELU -> Linear, and the SiLU in front of every ResnetBlock.mlp's Linear :181-183).  It was six launches of 4 - 7 us that
 // no batch size shrinks (posemb, GEMM, GELU, split-K GEMM, reducer, SiLU): ~32 us of every training step and of every
@@ -1730,6 +1832,52 @@ extern "C" int lgm_dyn_thresh(const float* xin, int64_t pitch, int x_off, const 
                      (long)v_pitch, C, HW, row, table, (const int*)counter, objective, (unsigned)k, w, thresh);
   LGM_LAUNCH_CHECK_AS("dyn_thresh");
   return LGM_OK;
+}
+
+// Variational-bound terms (vlb_term_kernel): the row by value with an explicit output row, or row counter[0] of a table with
+// `stride` floats per row, written to output row counter[0].  The name is noted without a registry entry, like
+// dpm_step_kernel's and for the same reason.  A prior row (kind 2) reads img only.
+static bool vlb_operands_ok(const float* img, const float* noise, const float* xin, int64_t pitch, int x_off, const float* v,
+                            int64_t v_pitch, int B, int C, int HW, int objective, const float* out, int n_rows, bool prior) {
+  if (!img || !out || out == img || B <= 0 || C <= 0 || HW <= 0 || n_rows <= 0 || !objective_ok(objective)) return false;
+  if ((int64_t)n_rows * 3 * B >= ((int64_t)1 << 31)) return false;
+  if (prior) return true;
+  return noise && xin && v && out != noise && out != xin && out != v && slices_ok(pitch, x_off, -1, C) && v_pitch >= C;
+}
+static int vlb_term_launch(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch, int x_off,
+                           const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip, const VlbRow& row,
+                           const float* table, int stride, const int32_t* counter, int out_row, float* out, int n_rows,
+                           int advance, void* stream) {
+  lgm_note_kernel("vlb_term_kernel");
+  hipLaunchKernelGGL(vlb_term_kernel, dim3(B), dim3(VLB_THREADS), 0, (hipStream_t)stream, img, noise, normalize, xin,
+                     (long)pitch, x_off, v, (long)v_pitch, B, C, HW, row, table, stride, (const int*)counter, out_row,
+                     objective, clip ? 1 : 0, out, n_rows);
+  if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
+  LGM_LAUNCH_CHECK_AS("vlb_term");
+  return LGM_OK;
+}
+
+extern "C" int lgm_vlb_term(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch, int x_off,
+                            const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip, float A, float S,
+                            float R, float Rm1, float P1, float P2, int kind, float KC, float KW, float inv_std, float* out,
+                            int n_rows, int out_row, void* stream) {
+  LGM_REQUIRE(kind >= 0 && kind <= 2 && out_row >= 0 && out_row < n_rows &&
+                  vlb_operands_ok(img, noise, xin, pitch, x_off, v, v_pitch, B, C, HW, objective, out, n_rows, kind == 2),
+              "vlb_term: bad arguments");
+  const VlbRow row = {{A, S, R, Rm1, P1, P2, (float)kind, KC, KW, inv_std, 0.f, 0.f}};
+  return vlb_term_launch(img, noise, normalize, xin, pitch, x_off, v, v_pitch, B, C, HW, objective, clip, row, nullptr, 0,
+                         nullptr, out_row, out, n_rows, 0, stream);
+}
+
+extern "C" int lgm_vlb_term_table(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch,
+                                  int x_off, const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip,
+                                  const float* table, int stride, const int32_t* counter, float* out, int n_rows, int advance,
+                                  void* stream) {
+  LGM_REQUIRE(table && counter && stride >= VLB_ROW && out != table && (const void*)out != (const void*)counter &&
+                  vlb_operands_ok(img, noise, xin, pitch, x_off, v, v_pitch, B, C, HW, objective, out, n_rows, false),
+              "vlb_term_table: bad arguments");
+  return vlb_term_launch(img, noise, normalize, xin, pitch, x_off, v, v_pitch, B, C, HW, objective, clip, VlbRow{}, table,
+                         stride, counter, 0, out, n_rows, advance, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1,0 +1,295 @@
+"""The variational bound of a trained diffusion in bits per dimension, on the HIP engine.
+
+Ho et al. 2020 (eq. 5, the table's NLL column) and Nichol & Dhariwal 2021 (``calc_bpd_loop``); an extension of the reference,
+which has no likelihood evaluation.  For held-out images x0 the bound is
+    L = L_prior + sum_{t >= 1} KL(q(x_{t-1} | x_t, x0) || p(x_{t-1} | x_t)) - log p(x0 | x_1)
+every term a mean over a sample's elements, divided by ln 2.  Per evaluated timestep t: x_t = q_sample(x0, t, noise), ONE
+network forward, and one reducing launch (``vlb_term_kernel``) that writes the term, mean (x0_pred - x0)^2 and mean (eps_pred -
+noise)^2 of every sample.  T forwards: a hot path of the shape of sampling, replayed as a captured graph like it.
+
+Top down:
+  * ``vlb_plan``: one row of ``VLB_ROW`` float32 scalars per evaluated timestep and a last row for the prior, every scalar
+    computed in float64 and rounded once.  Host arithmetic on ``math`` only: no device, no library.
+  * ``_eager_terms``: the loop in eager launches; ``_GraphedVLB``: one captured step per ``_vlb_key`` - t[b] <- time
+    table[counter], the noise draw, q_sample into the static input buffer, forward, the reducer from row table[counter] into
+    output row counter, counter += 1 - replayed once per timestep with no Python between the launches, no host sync and no
+    allocation.  It lives in ``sampler._GRAPHS`` beside the sampling steps of its network under a key no sampler can have.
+  * ``vlb_terms``: the public function behind ``GaussianDiffusion.vlb_terms``; the prior row is one more eager launch, and the
+    host reads the [n + 1, 3, B] result once, the only synchronisation.
+
+The model's variance is fixed (the reference's network has no variance head), by Nichol & Dhariwal's two conventions:
+``fixed_small`` = the posterior variance beta~_t, ``fixed_large`` = beta_t, both with t = 0 taking log beta~_1 - not the
+reference's ``posterior_log_variance_clipped[0]`` = log 1e-20, under which the decoder would be a step function.
+"""
+from __future__ import annotations
+
+import math
+import os
+import struct
+import sys
+import weakref
+from collections import namedtuple
+from typing import List, Optional
+
+import torch
+
+from . import ops, sampler
+from .flat import _r4
+
+VLB_ROW = 12                                   # floats per row; the kernel reads the first ten
+KL, DECODER, PRIOR = 0, 1, 2                   # row[6]
+VARIANCES = ("fixed_small", "fixed_large")
+VLBTerms = namedtuple("VLBTerms", "total_bpd prior_bpd vb xstart_mse mse timesteps")
+
+
+def _f32(x: float) -> float:
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+def _tables64(gd):
+    """(betas, alphas_cumprod, posterior_log_variance_clipped) as lists of Python floats: the diffusion's own tables (built in
+    float64, kept in float32 - the values its samplers use), widened"""
+    return tuple([float(v) for v in getattr(gd, n).detach().double().cpu().tolist()]
+                 for n in ("betas", "alphas_cumprod", "posterior_log_variance_clipped"))
+
+
+def vlb_plan(gd, timesteps=None, variance: str = "fixed_small"):
+    """-> n + 1 rows of ``VLB_ROW`` float32 values: one per timestep of ``timesteps`` (default T - 1 ... 0; else distinct ints
+    in [0, T), evaluated in the order given), then the prior's.  A row is
+        (A, S, R, Rm1, P1, P2, kind, KC, KW, inv_std, lv_p, lv_q)
+    (A, S, R, Rm1) the head ``predictions_one`` reads (the diffusion's own float32 tables at t), P1 / P2 =
+    ``posterior_mean_coef1/2[t]``, kind ``KL`` (t >= 1), ``DECODER`` (t = 0) or ``PRIOR``.  With lv_q =
+    ``posterior_log_variance_clipped[t]`` (log max(beta~_t, 1e-20), the reference's clipping) and the model's log-variance
+    lv_p (``fixed_small``: log beta~_t, ``fixed_large``: log beta_t, both log beta~_1 at t = 0):
+        KL       KC = 0.5 (-1 + lv_p - lv_q + exp(lv_q - lv_p)), KW = 0.5 exp(-lv_p): the KL per element in nats is KC + KW d^2,
+                 d the difference of the posterior means.  ``fixed_small``: KC == 0.0 exactly.
+        DECODER  inv_std = exp(-0.5 lv_p)
+        PRIOR    slots 10 / 11 hold acp_{T-1} and log(1 - acp_{T-1}); KC = 0.5 (-1 - log(1 - acp) + (1 - acp)) and KW = 0.5 acp,
+                 so that the KL per element is KC + KW x0^2 (the sum in KC cancels to about acp^2 / 2: float64 here, not float32
+                 on the device).
+    Everything in float64 from the diffusion's tables, rounded once.  Pure Python: no device, no library."""
+    if variance not in VARIANCES:
+        raise ValueError(f"variance must be one of {VARIANCES}, got {variance!r}")
+    T = int(gd.num_timesteps)
+    ts = list(reversed(range(T))) if timesteps is None else [int(t) for t in timesteps]
+    if any(not 0 <= t < T for t in ts):
+        raise ValueError(f"timesteps must lie in [0, {T}), got {[t for t in ts if not 0 <= t < T]}")
+    if len(set(ts)) != len(ts):
+        raise ValueError("timesteps must be distinct")
+    betas, acp, lv_q = _tables64(gd)
+    first = lv_q[1] if T > 1 else math.log(betas[0])
+    lv_p = [first] + ([lv_q[t] for t in range(1, T)] if variance == "fixed_small" else [math.log(b) for b in betas[1:]])
+    hs = sampler._host_schedule(gd)
+    rows = []
+    for t in ts:
+        A, Bv, R, Rm1 = sampler._head(hs, t)
+        head = (A, -Bv, R, Rm1, float(hs["posterior_mean_coef1"][t]), float(hs["posterior_mean_coef2"][t]))
+        if t == 0:
+            rows.append(head + (float(DECODER), 0.0, 0.0, _f32(math.exp(-0.5 * lv_p[0])), _f32(lv_p[0]), _f32(lv_q[0])))
+        else:
+            d = lv_q[t] - lv_p[t]
+            kc = 0.5 * (math.expm1(d) - d)                     # -1 - d + e^d without the cancellation at small d
+            rows.append(head + (float(KL), _f32(kc), _f32(0.5 * math.exp(-lv_p[t])), 0.0, _f32(lv_p[t]), _f32(lv_q[t])))
+    a, l1m = acp[-1], math.log1p(-acp[-1])
+    rows.append((0.0,) * 6 + (float(PRIOR), _f32(0.5 * (-1.0 - l1m + (1.0 - a))), _f32(0.5 * a), 0.0, _f32(a), _f32(l1m)))
+    return rows
+
+
+def _byval(row):
+    """a row as ``lgm_vlb_term`` takes it: ten scalars, the kind an int"""
+    return (*row[:6], int(row[6]), *row[7:10])
+
+
+def _qsample(gd, img, nz, t, sa, sb, xin):
+    """x_t into the x slice of the input buffer (zeros into a self-conditioning slice and the padding); no target wanted"""
+    net = gd.model
+    B, C, H, W = img.shape
+    ops.lib().lgm_qsample_target_slice(img.data_ptr(), nz.data_ptr(), None, 0.0, t.data_ptr(), sa.data_ptr(), sb.data_ptr(),
+                                       1 if gd.auto_normalize else 0, sampler._objective(gd), xin.data_ptr(), net.in_pitch,
+                                       net.x_off, net.sc_off, None, _r4(C), B, C, H * W, _r4(C), ops.stream())
+
+
+def _launch_term(gd, img, nz, xin, v, clip: bool, out, *, row=None, at: int = 0, table=None, counter=None):
+    """The reducer of one timestep: the row by value into output row ``at``, or row ``table[counter]`` into output row
+    ``counter`` (the captured step, which also advances the counter).  A prior row takes ``nz = xin = v = None``."""
+    net = gd.model
+    B, C, H, W = img.shape
+    src = (img.data_ptr(), ops._p(nz), 1 if gd.auto_normalize else 0, ops._p(xin), net.in_pitch, net.x_off, ops._p(v),
+           _r4(C) if v is None else ops.pitch(v), B, C, H * W, sampler._objective(gd), 1 if clip else 0)
+    if table is not None:
+        ops.lib().lgm_vlb_term_table(*src, table.data_ptr(), VLB_ROW, counter.data_ptr(), out.data_ptr(), out.shape[0], 1,
+                                     ops.stream())
+    else:
+        ops.lib().lgm_vlb_term(*src, *_byval(row), out.data_ptr(), out.shape[0], at, ops.stream())
+
+
+def _eager_terms(gd, img, times, rows, noises, classes, clip: bool):
+    """the n timesteps in eager launches -> [n, 3, B] on the device"""
+    net = gd.model
+    B, C, H, W = img.shape
+    dev = img.device
+    out = torch.zeros((len(times), 3, B), device=dev)
+    xin = torch.zeros((B, H, W, net.in_pitch), device=dev)
+    for i, (t, row) in enumerate(zip(times, rows)):
+        tb = torch.full((B,), t, device=dev, dtype=torch.long)
+        nz = noises[i] if noises is not None else torch.randn(img.shape, device=dev)
+        _qsample(gd, img, nz, tb, gd.sqrt_alphas_cumprod, gd.sqrt_one_minus_alphas_cumprod, xin)
+        v = net.forward_guided(xin, tb, classes, 1.0)
+        _launch_term(gd, img, nz, xin, v, clip, out, row=row, at=i)
+    return out
+
+
+class _GraphedVLB:
+    """One captured evaluation step for a (network, batch shape, objective, clip); replayed once per timestep.  Static
+    buffers: the image, the noise, the network's input buffer, the schedule's two q_sample tables, the time and row tables,
+    the counter and the [max_steps, 3, B] output.  Capture, warm-up, RNG-state restore and ``matches`` as ``_GraphedChain``."""
+
+    matches = sampler._GraphedChain.matches
+
+    def __init__(self, gd, shape, clip: bool, max_steps: int = 4096):
+        net = gd.model
+        self._net = weakref.ref(net)
+        B, C, H, W = shape
+        dev = gd.betas.device
+        self.shape, self.max_steps = shape, max_steps
+        fp = net._flat
+        self._bound = (weakref.ref(fp), fp.data.data_ptr(),
+                       None if fp.data_uf is None else fp.data_uf.data_ptr(),
+                       None if fp.data_t is None else fp.data_t.data_ptr())
+        self.img = torch.zeros(shape, device=dev)
+        self.noise = torch.zeros(shape, device=dev)                   # injected noise goes here
+        self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)
+        self.t = torch.zeros(B, dtype=torch.long, device=dev)
+        self.sa = torch.zeros(gd.num_timesteps, device=dev)           # a diffusion's tables are copied in per run: two
+        self.sb = torch.zeros(gd.num_timesteps, device=dev)           # diffusions of one length may share the step
+        self.table = torch.zeros((max_steps, VLB_ROW), device=dev)
+        self.ttable = torch.zeros(max_steps, dtype=torch.long, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.out = torch.zeros((max_steps, 3, B), device=dev)
+        self.classes = net.labels(None, B, dev).clone() if net.num_classes is not None else None
+        self.inject = False
+
+        def one_step():
+            ops.lib().lgm_sampler_time(self.ttable.data_ptr(), self.counter.data_ptr(), self.t.data_ptr(), B, ops.stream())
+            nz = self.noise if self.inject else torch.randn(shape, device=dev)
+            _qsample(gd, self.img, nz, self.t, self.sa, self.sb, self.x)
+            v = net.forward_guided(self.x, self.t, self.classes, 1.0, refresh_weights=False)
+            _launch_term(gd, self.img, nz, self.x, v, clip, self.out, table=self.table, counter=self.counter)
+
+        net.refresh_derived_weights(False)
+        rng_state = torch.cuda.get_rng_state(dev)
+        cur = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):            # eager warm-up (sizes workspaces, sets kernel attributes)
+            for _ in range(2):
+                one_step()
+        cur.wait_stream(side)
+        torch.cuda.synchronize()
+        self.graphs = {}
+        for inject in (False, True):
+            self.inject = inject
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                one_step()
+            self.graphs[inject] = g
+        torch.cuda.set_rng_state(rng_state, dev)     # capture leaves the random stream where it was
+
+    def run(self, gd, img, times, rows, noises, classes=None):
+        """times[i], rows[i] (``VLB_ROW`` floats) per timestep; noises: None (draw on the device) or one NCHW tensor per
+        timestep.  -> [n, 3, B] on the device.  More timesteps than table rows are replayed in table-sized segments."""
+        n = len(times)
+        if self.classes is not None:
+            self.classes.copy_(classes)
+        self._net().refresh_derived_weights(False)   # the weights may have moved since the last evaluation (EMA updates)
+        self.img.copy_(img)
+        self.sa.copy_(gd.sqrt_alphas_cumprod)
+        self.sb.copy_(gd.sqrt_one_minus_alphas_cumprod)
+        res = torch.empty((n, 3, self.shape[0]), device=img.device)
+        inject = noises is not None
+        for lo, hi in sampler._segments(n, self.max_steps):
+            self.table[:hi - lo].copy_(torch.tensor(rows[lo:hi], dtype=torch.float32))
+            self.ttable[:hi - lo].copy_(torch.tensor(times[lo:hi], dtype=torch.long))
+            self.counter.zero_()
+            for i in range(lo, hi):
+                if inject:
+                    self.noise.copy_(noises[i])
+                self.graphs[inject].replay()
+            res[lo:hi].copy_(self.out[:hi - lo])
+        return res
+
+
+def _vlb_key(gd, shape, clip: bool):
+    """The cache key of a captured evaluation step under its network.  It starts with "vlb": a sampler's key (``_graph_key``)
+    starts with a shape tuple, "dpm++", "dynthresh" or "inpaint".  The variance choice lives in the table, not here."""
+    return ("vlb", gd.objective, bool(clip), tuple(shape), bool(gd.auto_normalize), int(gd.num_timesteps))
+
+
+def _graph_vlb(gd, shape, clip: bool) -> Optional[_GraphedVLB]:
+    """-> the network's ``_GraphedVLB`` for the key, or None (graph replay disabled, no device, capture failed: eager launches);
+    invalidation and the retry after a failed capture as ``sampler._graph_chain``"""
+    if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or gd.betas.device.type != "cuda":
+        return None
+    net = gd.model
+    net.prepare_hip(gd.betas.device)
+    per_net = sampler._GRAPHS.setdefault(net, {})
+    key = _vlb_key(gd, shape, clip)
+    ent = per_net.get(key)
+    if isinstance(ent, _GraphedVLB) and not ent.matches(net):
+        ent = None
+        per_net.pop(key, None)
+    if isinstance(ent, int):
+        if ent > 0:
+            per_net[key] = ent - 1
+            return None
+        ent = None
+    if ent is None:
+        try:
+            ent = _GraphedVLB(gd, tuple(shape), clip)
+        except Exception as e:  # capture is an optimisation
+            print(f"[lgm_hip] likelihood graph capture unavailable ({type(e).__name__}: {e}); eager launches",
+                  file=sys.stderr, flush=True)
+            per_net[key] = sampler._CAPTURE_RETRY_AFTER
+            return None
+        per_net[key] = ent
+    return ent
+
+
+@torch.no_grad()
+def vlb_terms(gd, img, *, timesteps=None, noise: Optional[List[torch.Tensor]] = None, clip_denoised: bool = True,
+              variance: str = "fixed_small", classes=None) -> VLBTerms:
+    """See ``GaussianDiffusion.vlb_terms``.  The result's tensors are float64 on the host: the device's float32 values, read
+    once, and ``total_bpd`` their sum over the rows in row order."""
+    net = gd.model
+    if img.dim() != 4 or tuple(img.shape[1:]) != (gd.channels, gd.img_size, gd.img_size):
+        raise ValueError(f"img must be [B, {gd.channels}, {gd.img_size}, {gd.img_size}], got {tuple(img.shape)}")
+    rows = vlb_plan(gd, timesteps, variance)
+    times = list(reversed(range(gd.num_timesteps))) if timesteps is None else [int(t) for t in timesteps]
+    shape = tuple(img.shape)
+    dev = gd.betas.device
+    if noise is not None:
+        noise = list(noise)
+        if len(noise) != len(times) or any(tuple(z.shape) != shape for z in noise):
+            raise ValueError(f"noise must be {len(times)} tensors of shape {shape}, one per evaluated timestep")
+        noise = [z.to(dev).float().contiguous() for z in noise]
+    net.prepare_hip(dev)
+    classes = net.labels(classes, shape[0], dev)
+    img = img.to(dev).float().contiguous()
+    clip = bool(clip_denoised)
+    n = len(times)
+    gv = _graph_vlb(gd, shape, clip) if n else None
+    if gv is not None:
+        terms = gv.run(gd, img, times, rows[:n], noise, classes)
+    else:
+        terms = _eager_terms(gd, img, times, rows[:n], noise, classes, clip)
+    prior = torch.zeros((1, 3, shape[0]), device=dev)
+    _launch_term(gd, img, None, None, None, clip, prior, row=rows[n], at=0)
+    host = torch.cat([terms, prior]).double().cpu()            # the one read: [n + 1, 3, B]
+    vb, prior_bpd = host[:n, 0], host[n, 0]
+    total = None
+    if n == gd.num_timesteps:
+        total = torch.zeros_like(prior_bpd)
+        for i in range(n):                                     # float64, in row order, the prior last
+            total += vb[i]
+        total += prior_bpd
+    return VLBTerms(total, prior_bpd, vb, host[:n, 1], host[:n, 2], tuple(times))

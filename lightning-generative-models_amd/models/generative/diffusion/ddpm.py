@@ -1192,6 +1192,32 @@ class GaussianDiffusion(nn.Module):
                                return_all_timesteps, classes=classes, cond_scale=scale)
 
     @torch.no_grad()
+    def vlb_terms(self, img, *, timesteps=None, noise=None, clip_denoised=True, variance="fixed_small", classes=None):
+        """The variational bound of ``img`` in bits per dimension (extension; Ho et al. 2020 eq. 5, Nichol & Dhariwal 2021
+        ``calc_bpd_loop``) -> ``VLBTerms(total_bpd, prior_bpd, vb, xstart_mse, mse, timesteps)``: per evaluated timestep and
+        sample the term of the bound (``vb``: the KL of the two posteriors for t >= 1, the discretised-Gaussian decoder NLL at
+        t = 0), mean (x0_pred - x0)^2 and mean (eps_pred - noise)^2, each [n, B]; ``prior_bpd`` [B]; ``total_bpd = vb.sum(0) +
+        prior_bpd`` [B] when all T timesteps were evaluated, else None.  float64 on the host.
+        ``img``: [B, C, H, W] in the data range, normalised as ``forward`` normalises.  ``timesteps``: None = T - 1 ... 0, else
+        distinct ints in [0, T) in the order to evaluate.  ``noise``: one NCHW draw per evaluated timestep (parity tests).
+        ``variance``: ``"fixed_small"`` (beta~_t) or ``"fixed_large"`` (beta_t), see ``lgm_hip.likelihood``.
+        One forward per timestep, graph-replayed like sampling.  A self-conditioned network is evaluated with a zero
+        self-conditioning input at every timestep: that is a Markov model of its own and therefore a valid bound (of that
+        model, not of the sampler that feeds x_start forward).  A class-conditional network: ``classes=None`` is the null
+        label, labels give the conditional bound; there is no guidance here - a guided output is not a probabilistic model."""
+        from lgm_hip import likelihood
+        return likelihood.vlb_terms(self, img, timesteps=timesteps, noise=noise, clip_denoised=clip_denoised,
+                                    variance=variance, classes=classes)
+
+    @torch.no_grad()
+    def nll_bpd(self, img, **kw):
+        """``vlb_terms(img, **kw).total_bpd``: the bound over all T timesteps, [B] bits per dimension"""
+        ts = kw.get("timesteps")
+        if ts is not None and len({int(t) for t in ts}) != self.num_timesteps:
+            raise ValueError("nll_bpd evaluates every timestep; use vlb_terms for a subset")
+        return self.vlb_terms(img, **kw).total_bpd
+
+    @torch.no_grad()
     def interpolate(self, x1, x2, t=None, lam=0.5, classes=None, cond_scale=1.0):
         """reference :847-867: noise both images to step t, blend, walk the ancestral chain back to 0 (no unnormalise)."""
         from lgm_hip import sampler
@@ -1339,6 +1365,8 @@ class DDPM(LightningModule):
         self.img_size = img_size
         self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
         self.sample_every = 1000          # reference: every 1000 steps on rank 0 (:1025)
+        self.bpd_every = 0                # > 0: validation_step also logs val_bpd on every bpd_every-th batch (extension)
+        self._val_batches = 0
         self.last_samples = None
 
     def prepare_hip(self, device):
@@ -1382,6 +1410,12 @@ class DDPM(LightningModule):
         self.ema.ema_model.eval()
         return self.ema.ema_model.inpaint(known, mask, **kw)
 
+    @torch.no_grad()
+    def bits_per_dim(self, img, classes=None, **kw):
+        """``GaussianDiffusion.nll_bpd`` of the diffusion ``_log_sample`` samples from (the EMA weights): [B] bits per dimension"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model.nll_bpd(img, classes=classes, **kw)
+
     def training_step(self, batch):
         return self._common_step(batch, "train")
 
@@ -1389,7 +1423,14 @@ class DDPM(LightningModule):
         self.ema.update()
 
     def validation_step(self, batch):
-        return self._common_step(batch, "val")
+        loss = self._common_step(batch, "val")
+        if self.bpd_every > 0:
+            if self._val_batches % self.bpd_every == 0:
+                data, y = batch
+                bpd = self.bits_per_dim(data, classes=y if self.num_classes is not None else None)
+                self.log("val_bpd", bpd.mean().float(), prog_bar=True, logger=True, sync_dist=multi_rank())
+            self._val_batches += 1
+        return loss
 
     def configure_optimizers(self):
         return FusedAdam(self.ema.model.parameters(), lr=self.hparams.lr, betas=self.hparams.betas)
