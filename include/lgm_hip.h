@@ -39,13 +39,14 @@
 extern "C" {
 #endif
 
-#define LGM_ABI_VERSION 7   /* 2: lgm_posemb takes a frequency table, BatchNorm entry points, *_planes / *_partial;
+#define LGM_ABI_VERSION 8   /* 2: lgm_posemb takes a frequency table, BatchNorm entry points, *_planes / *_partial;
                              * 3: lgm_conv3x3_wino4*, lgm_gn_fwd_stats, lgm_conv3x3_wino_wgradn* + LgmWgradItem, a negative
                              *    dst offset in lgm_wino_weights table rows means "skip that copy", lgm_kernel_name*;
                              * 4: LgmPostOp carries the BatchNorm-backward sums (bn_*), lgm_bn_reduce3_coef_tiles;
                              * 5: lgm_set_cu_margin / lgm_cu_margin;
                              * 6: lgm_extract_axpby, lgm_model_predictions (GaussianDiffusion's per-sample-time algebra), lgm_time_mlp_*, lgm_weng_*;
-                             * 7: lgm_gn_bwd_add, lgm_wgrad1x1_group*, lgm_wgrad_queue_*
+                             * 7: lgm_gn_bwd_add, lgm_wgrad1x1_group*, lgm_wgrad_queue_*;
+                             * 8: lgm_adam_step / lgm_rmsprop_step take their betas / alpha as doubles
                              * (entry points added since without a change to an existing one keep the number, as the
                              *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
                              *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table,
@@ -1000,17 +1001,20 @@ int lgm_conv3x3_wino4_wgrad(const LgmConvGeom* g, const float* y, int64_t y_pitc
  * Optimiser kernels on flat storage.
  * torch.optim.Adam (coupled L2; decoupled=1 gives AdamW) — ddpm.py:1053-1059, vqvae.py:207-214,
  * wgan.py:183-195.  step: 1-based count (host value, or read from step_dev when non-NULL).
+ * b1, b2 are the caller's doubles: torch forms 1 - beta and 1 - beta^step in doubles, and so do these (a float32 0.999
+ * puts 1 - b2 off by 1.3e-5).  Host step and step_dev give the same bits.
  * ------------------------------------------------------------------------------------- */
-int lgm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
-                  float b2, float eps, float weight_decay, float step, const float* step_dev,
+int lgm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1,
+                  double b2, float eps, float weight_decay, float step, const float* step_dev,
                   float grad_scale, int decoupled, void* stream);
 /* torch.optim.RMSprop with its defaults (momentum 0, not centred) - the critic / generator optimiser
  * of the weight-clipping WGAN (wgan.py:171-181): sq = alpha*sq + (1-alpha)*g^2; p -= lr*g/(sqrt(sq)+eps) */
-int lgm_rmsprop_step(float* p, const float* g, float* sq, int64_t n, float lr, float alpha, float eps,
+int lgm_rmsprop_step(float* p, const float* g, float* sq, int64_t n, float lr, double alpha, float eps,
                      float weight_decay, float grad_scale, void* stream);
 /* WGAN weight clipping, param.data.clamp_(-c, c) over the critic's flat parameter buffer (wgan.py:158-168) */
 int lgm_clamp(float* x, int64_t n, float lo, float hi, void* stream);
-/* ema_pytorch.EMA.update (ddpm.py:1047-1048): shadow += (online - shadow) * w   (w = 1 copies) */
+/* ema_pytorch.EMA.update (ddpm.py:1047-1048): shadow += (online - shadow) * w; w = 1 copies online bit for bit, w = 0
+ * leaves the shadow's bits */
 int lgm_ema_lerp(float* shadow, const float* online, int64_t n, float w, void* stream);
 int lgm_add_scalar(float* x, float a, void* stream);
 int lgm_fill(float* x, int64_t n, float val, void* stream);

@@ -93,6 +93,34 @@ __global__ __launch_bounds__(256) void colsum_stage(const float* __restrict__ a,
   }
 }
 
+// second stage of a split colsum: out[c] = beta*out[c] + sum_k planes[k][c], in the ORDER of the batched reducer that sums the
+// same planes for lgm_colsum_deferred (wgrad_reduce_batch_kernel: four lanes, plane k on lane k % 4 in chain (k % 16) / 4,
+// chains and lanes joined pairwise) - the direct and the deferred form give the same bits
+__global__ __launch_bounds__(256) void colsum_planes_kernel(const float* __restrict__ planes, long cols, int splits,
+                                                            float* __restrict__ out, float beta) {
+  __shared__ float sh[4][64];
+  const int col = threadIdx.x & 63, lane = threadIdx.x >> 6;
+  const long c = (long)blockIdx.x * 64 + col;
+  float s = 0.f;
+  if (c < cols) {
+    float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
+    for (int k = lane; k < splits; k += 16) {
+      t0 += planes[(long)k * cols + c];
+      if (k + 4 < splits) t1 += planes[(long)(k + 4) * cols + c];
+      if (k + 8 < splits) t2 += planes[(long)(k + 8) * cols + c];
+      if (k + 12 < splits) t3 += planes[(long)(k + 12) * cols + c];
+    }
+    s = (t0 + t1) + (t2 + t3);
+  }
+  sh[lane][col] = s;
+  __syncthreads();
+  if (lane == 0 && c < cols) {
+    float t = (sh[0][col] + sh[1][col]) + (sh[2][col] + sh[3][col]);
+    if (beta != 0.f) t += out[c] * beta;
+    out[c] = t;
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t lgm_colsum_workspace(int64_t rows, int64_t cols) {
@@ -114,8 +142,8 @@ extern "C" int lgm_colsum(const float* a, int64_t pitch, int64_t rows, int64_t c
   } else {
     hipLaunchKernelGGL(colsum_stage, dim3(lgm_cdiv(cols, cl), ns), dim3(256), 0, s, a, (long)pitch, (long)rows,
                        (long)cols, rpb, (float*)workspace, (long)cols, 0.f, lg);
-    hipLaunchKernelGGL(colsum_stage, dim3(lgm_cdiv(cols, cl), 1), dim3(256), 0, s, (const float*)workspace,
-                       (long)cols, (long)ns, (long)cols, (long)ns, out, 0L, beta, lg);
+    hipLaunchKernelGGL(colsum_planes_kernel, dim3(lgm_cdiv(cols, 64)), dim3(256), 0, s, (const float*)workspace, (long)cols, ns,
+                       out, beta);
   }
   LGM_LAUNCH_CHECK();
   return LGM_OK;

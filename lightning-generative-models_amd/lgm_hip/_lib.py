@@ -20,7 +20,7 @@ class ConvGeom(ctypes.Structure):
 
 
 _CTYPES = {
-    "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+    "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
     "void": None,
 }
 

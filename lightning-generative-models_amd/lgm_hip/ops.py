@@ -1357,6 +1357,7 @@ def nhwc_to_nchw(src, dst):
 
 
 def adam_step(p, g, m, v, n, lr, b1, b2, eps, wd, step, step_dev=None, grad_scale=1.0, decoupled=False):
+    """b1, b2 cross the ABI as doubles: 1 - beta and 1 - beta ** step are formed from them in doubles, as torch does."""
     lib().lgm_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, b1, b2, eps, wd,
                         float(step), _p(step_dev), grad_scale, 1 if decoupled else 0, stream())
 
@@ -1382,6 +1383,7 @@ def clamp_(x, lo, hi):
 
 
 def ema_lerp(shadow, online, w):
+    """shadow += (online - shadow) * w; w == 1 copies online bit for bit, w == 0 leaves the shadow alone."""
     lib().lgm_ema_lerp(shadow.data_ptr(), online.data_ptr(), shadow.numel(), w, stream())
 
 

@@ -211,7 +211,7 @@ class EMA(nn.Module):
         fo = _first_flat(self.online_model)
         fs = _first_flat(self.ema_model)
         if fo is not None and fs is not None and fo.total == fs.total:
-            ops.ema_lerp(fs.data, fo.data, w)          # one kernel over the flat storage
+            ops.ema_lerp(fs.data, fo.data, w)          # one kernel over the flat storage (w == 1: an exact copy)
             done = {id(s.param) for s in fs.slots}
         else:
             done = set()

@@ -176,7 +176,7 @@ def test_new_entry_points_are_declared_and_exported():
         assert hasattr(dll, name), f"{name} is not exported by the library"
     assert len(protos["lgm_vlb_term"][1]) == 27 and len(protos["lgm_vlb_term_table"][1]) == 20
     L = _lib.lib()
-    assert L.lgm_abi_version() == _lib.ABI_VERSION == 7
+    assert L.lgm_abi_version() == _lib.ABI_VERSION == 8
     syms = subprocess.run(["nm", "-C", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     assert "vlb_term_kernel(" in syms, "the library holds no vlb_term_kernel"
     names = [L.lgm_kernel_name(i) for i in range(L.lgm_kernel_name_count())]

@@ -45,7 +45,7 @@ def test_new_entry_points_are_declared_exported_and_named():
         assert name in protos, f"{name} is not declared in include/lgm_hip.h"
         assert hasattr(dll, name), f"{name} is not exported by the library"
     L = _lib.lib()
-    assert L.lgm_abi_version() == _lib.ABI_VERSION == 7
+    assert L.lgm_abi_version() == _lib.ABI_VERSION == 8
     L._dll.lgm_kernel_name.restype = ctypes.c_char_p
     noted = {L._dll.lgm_kernel_name(i).decode() for i in range(L._dll.lgm_kernel_name_count())}
     for k in NEW_KERNELS:                                      # tests/test_cabi.py checks every noted name against the symbols

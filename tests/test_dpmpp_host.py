@@ -153,7 +153,7 @@ def test_new_entry_points_are_declared_and_exported():
         assert hasattr(dll, name), f"{name} is not exported by the library"
     assert len(protos["lgm_dpm_step"][1]) == 23 and len(protos["lgm_dpm_step_table"][1]) == 17
     L = _lib.lib()
-    assert L.lgm_abi_version() == _lib.ABI_VERSION == 7
+    assert L.lgm_abi_version() == _lib.ABI_VERSION == 8
     import subprocess
     syms = subprocess.run(["nm", "-C", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     assert "dpm_step_kernel(" in syms, "the library holds no dpm_step_kernel"

@@ -98,7 +98,7 @@ def test_new_entry_points_are_declared_exported_and_check_their_arguments():
         assert hasattr(dll, name), f"{name} is not exported by the library"
         assert len(protos[name][1]) == nargs, name
     L = _lib.lib()
-    assert L.lgm_abi_version() == _lib.ABI_VERSION == 7
+    assert L.lgm_abi_version() == _lib.ABI_VERSION == 8
     # the kernels: the library's registry where the ledger test admits a name (it lists every registry name and the file
     # that asserts it, so sample_step_slice_kernel is there and a new name cannot be), the symbol table for all four
     L._dll.lgm_kernel_name.restype = ctypes.c_char_p

@@ -263,7 +263,7 @@ def test_entry_points_are_declared_exported_and_check_their_arguments():
     assert protos["lgm_sample_step_inpaint"][1][-14:] == [vp, vp, i32, vp, vp, vp, vp, vp, fl, fl, fl, fl, vp, vp]
     assert protos["lgm_dpm_step_inpaint"][1][-14:] == [vp, vp, i32, vp, vp, vp, vp, vp, fl, fl, fl, fl, vp, vp]
     L = _lib.lib()
-    assert L.lgm_abi_version() == _lib.ABI_VERSION == 7
+    assert L.lgm_abi_version() == _lib.ABI_VERSION == 8
     syms = subprocess.run(["nm", "-C", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     for kernel in ("sample_step_slice_kernel(", "dpm_step_kernel("):     # the two kernels there were, and no third
         assert kernel in syms
