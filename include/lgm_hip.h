@@ -51,7 +51,8 @@ extern "C" {
                              *  lgm_*_obj ones did: lgm_selfcond_estimate, lgm_qsample_target_slice, lgm_sample_step_slice,
                              *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table,
                              *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh,
-                             *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint, lgm_vlb_term, lgm_vlb_term_table - a library
+                             *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint, lgm_vlb_term, lgm_vlb_term_table,
+                             *  lgm_grad_sqnorm_*, lgm_grad_clip_scale, lgm_adam_step_scaled, lgm_grad_accumulate - a library
                              *  that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -1018,6 +1019,31 @@ int lgm_clamp(float* x, int64_t n, float lo, float hi, void* stream);
 int lgm_ema_lerp(float* shadow, const float* online, int64_t n, float w, void* stream);
 int lgm_add_scalar(float* x, float a, void* stream);
 int lgm_fill(float* x, int64_t n, float val, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The gradient tail: global-norm clipping (torch.nn.utils.clip_grad_norm_, norm type 2, error_if_nonfinite=False) and
+ * gradient accumulation, between "the flat gradient is final" and the Adam launch.  No host read anywhere.
+ *
+ * lgm_grad_sqnorm_partial: sum of g^2 as per-workgroup partial sums in double (products and sums formed in double from the
+ * first add: at most n * 2^-53 relative).  Workgroup b covers the contiguous span [b * span, (b + 1) * span) and writes ONE
+ * double to partials[b]; lgm_grad_sqnorm_span(n) and lgm_grad_sqnorm_partials(n) = ceil(n / span) are host-only queries that
+ * depend on n alone (not on lgm_cu_margin()).  No atomics: two runs give equal bits.  g 16-byte aligned.
+ * lgm_grad_clip_scale: ONE workgroup sums `count` partials (those of several flat buffers laid end to end) in a fixed tree
+ * and forms, in double, norm = |grad_scale| sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)) (NaN propagates, an infinite
+ * norm gives 0), out2[0] = (float)(grad_scale * coef), out2[1] = (float)norm.
+ * lgm_adam_step_scaled: lgm_adam_step with the gradient scale read from scale_dev[0] (= out2) in place of grad_scale; the
+ * same kernel, the same bits for the same scale.  Weight decay is applied after the scale.
+ * lgm_grad_accumulate: dst = overwrite ? src : dst + src over a flat 16-byte aligned slice (one float add per element).
+ * ------------------------------------------------------------------------------------- */
+int64_t lgm_grad_sqnorm_span(int64_t n);
+int64_t lgm_grad_sqnorm_partials(int64_t n);
+int lgm_grad_sqnorm_partial(const float* g, int64_t n, double* partials, void* stream);
+int lgm_grad_clip_scale(const double* partials, int64_t count, float grad_scale, float max_norm,
+                        float* out2, void* stream);
+int lgm_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1,
+                         double b2, float eps, float weight_decay, float step, const float* step_dev,
+                         const float* scale_dev, int decoupled, void* stream);
+int lgm_grad_accumulate(float* dst, const float* src, int64_t n, int overwrite, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,8 +16,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float b2, float omb1, float omb2, double log_b1, double log_b2,
                                                    float eps, float wd, float step_host,
                                                    const float* __restrict__ step_dev, float grad_scale,
-                                                   int decoupled) {
-  __shared__ float sc[2];
+                                                   int decoupled, const float* __restrict__ scale_dev) {
+  // scale_dev (lgm_adam_step_scaled): the clipped gradient scale grad_clip_scale_kernel left on the device takes
+  // grad_scale's place; thread 0 reads it beside the bias corrections, the streaming path carries nothing new.
+  __shared__ float sc[3];
   const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const bool whole = i + 3 < n;
   f32x4 pv, gv, mv, vv;
@@ -33,10 +35,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     const double bc2 = -expm1(step * log_b2);
     sc[0] = (float)((double)lr / bc1);
     sc[1] = (float)(1.0 / sqrt(bc2));
+    if (scale_dev) sc[2] = scale_dev[0];
   }
   __syncthreads();
   const float step_size = sc[0];
   const float inv_sqrt_bc2 = sc[1];
+  if (scale_dev) grad_scale = sc[2];
   if (i >= n) return;
   if (whole) {
     gv *= grad_scale;
@@ -95,9 +99,9 @@ __global__ __launch_bounds__(256) void fill_kernel(float* __restrict__ x, long n
 
 }  // namespace
 
-extern "C" int lgm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1, double b2,
-                             float eps, float weight_decay, float step, const float* step_dev, float grad_scale,
-                             int decoupled, void* stream) {
+static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1, double b2, float eps,
+                       float weight_decay, float step, const float* step_dev, float grad_scale, int decoupled,
+                       const float* scale_dev, void* stream) {
   LGM_REQUIRE(p && g && m && v && n > 0, "adam_step: bad arguments");
   LGM_REQUIRE(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0, "adam_step: betas must lie in [0, 1)");
   LGM_REQUIRE(lgm_aligned16(p) && lgm_aligned16(g) && lgm_aligned16(m) && lgm_aligned16(v),
@@ -106,7 +110,143 @@ extern "C" int lgm_adam_step(float* p, const float* g, float* m, float* v, int64
   const long nthreads = (n + 3) / 4;
   hipLaunchKernelGGL(adam_kernel, dim3(lgm_cdiv(nthreads, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
                      lr, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), log(b1), log(b2), eps, weight_decay, step, step_dev,
-                     grad_scale, decoupled);
+                     grad_scale, decoupled, scale_dev);
+  LGM_LAUNCH_CHECK_AS("lgm_adam_step");
+  return LGM_OK;
+}
+
+extern "C" int lgm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1, double b2,
+                             float eps, float weight_decay, float step, const float* step_dev, float grad_scale,
+                             int decoupled, void* stream) {
+  return adam_launch(p, g, m, v, n, lr, b1, b2, eps, weight_decay, step, step_dev, grad_scale, decoupled, nullptr, stream);
+}
+
+// The same kernel with the gradient scale read from the device (scale_dev[0], written by lgm_grad_clip_scale): the clipped
+// step needs no host read.  Weight decay is applied after the scale, as torch clips before the optimizer adds wd * p.
+extern "C" int lgm_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1, double b2,
+                                    float eps, float weight_decay, float step, const float* step_dev,
+                                    const float* scale_dev, int decoupled, void* stream) {
+  LGM_REQUIRE(scale_dev, "adam_step_scaled: scale_dev is null");
+  return adam_launch(p, g, m, v, n, lr, b1, b2, eps, weight_decay, step, step_dev, 1.f, decoupled, scale_dev, stream);
+}
+
+// ---- gradient tail: global-norm clipping and accumulation ---------------------------------------------------------------------
+// Sum g^2 over a flat buffer as per-workgroup partial sums in double: workgroup b covers the fixed span
+// [b * SQNORM_SPAN, (b + 1) * SQNORM_SPAN) and writes ONE double.  The span is a constant, so the partial count depends on n
+// alone (not on lgm_cu_budget(): a rank with a CU margin and a single GPU give equal bits).  A float x float product is exact in
+// double and every add is a double add from the first one, so the only error is the summation's: at most n * 2^-53 relative on a
+// sum of non-negative terms, in whatever order.  The order is fixed all the same (lane-sequential, shuffle tree, the four waves
+// in order; no atomics), so two runs give equal bits.  One 4 B/element read; four double FMAs per 16-B load.
+constexpr long SQNORM_SPAN = 8192;              // floats per workgroup: 8 loads of 16 B per lane
+constexpr int SQNORM_ITERS = SQNORM_SPAN / (256 * 4);
+
+namespace {
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// block-wide double sum of 256 threads in a fixed order; the result is valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__device__ __forceinline__ double sq4(double acc, const f32x4 g) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) acc = fma((double)g[k], (double)g[k], acc);
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, long n, double* __restrict__ partials) {
+  __shared__ double sh[4];
+  const long base = (long)blockIdx.x * SQNORM_SPAN + (long)threadIdx.x * 4;
+  double acc = 0.0;
+  if ((long)(blockIdx.x + 1) * SQNORM_SPAN <= n) {          // a whole span: every load in flight before the first add
+    f32x4 gv[SQNORM_ITERS];
+#pragma unroll
+    for (int j = 0; j < SQNORM_ITERS; ++j) gv[j] = *reinterpret_cast<const f32x4*>(g + base + (long)j * 1024);
+#pragma unroll
+    for (int j = 0; j < SQNORM_ITERS; ++j) acc = sq4(acc, gv[j]);
+  } else {
+    for (int j = 0; j < SQNORM_ITERS; ++j) {
+      const long i = base + (long)j * 1024;
+      if (i + 3 < n)
+        acc = sq4(acc, *reinterpret_cast<const f32x4*>(g + i));
+      else
+        for (long k = i; k < n; ++k) acc = fma((double)g[k], (double)g[k], acc);
+    }
+  }
+  acc = block_sum_f64(acc, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+// ONE workgroup: the partials (of several flat buffers laid end to end) in a fixed tree, then torch's clip_grad_norm_
+// (norm type 2, error_if_nonfinite=False) on the gradient the optimizer would see, grad_scale * g, in double:
+//   norm = |grad_scale| sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)), out2 = (grad_scale * coef, norm).
+// The min propagates NaN as torch's clamp does (fminf(1, NaN) is 1); an infinite norm gives coefficient 0.
+__global__ __launch_bounds__(256) void grad_clip_scale_kernel(const double* __restrict__ partials, long count, float grad_scale,
+                                                              float max_norm, float* __restrict__ out2) {
+  __shared__ double sh[4];
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < count; i += 256) acc += partials[i];
+  acc = block_sum_f64(acc, sh);
+  if (threadIdx.x == 0) {
+    const double norm = fabs((double)grad_scale) * sqrt(acc);
+    const double r = (double)max_norm / (norm + 1e-6);
+    const double coef = r > 1.0 ? 1.0 : r;                  // NaN > 1 is false: NaN stays
+    out2[0] = (float)((double)grad_scale * coef);
+    out2[1] = (float)norm;
+  }
+}
+
+// dst = overwrite ? src : dst + src: one float add per element (nothing to contract), the bits of torch's dst + src
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, long n,
+                                                              int overwrite) {
+  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (i + 3 < n) {
+    f32x4 s = *reinterpret_cast<const f32x4*>(src + i);
+    if (!overwrite) s += *reinterpret_cast<const f32x4*>(dst + i);
+    *reinterpret_cast<f32x4*>(dst + i) = s;
+  } else {
+    for (long j = i; j < n; ++j) dst[j] = overwrite ? src[j] : dst[j] + src[j];
+  }
+}
+}  // namespace
+
+extern "C" int64_t lgm_grad_sqnorm_span(int64_t n) { return n > 0 ? SQNORM_SPAN : -1; }
+
+extern "C" int64_t lgm_grad_sqnorm_partials(int64_t n) { return n > 0 ? (n + SQNORM_SPAN - 1) / SQNORM_SPAN : -1; }
+
+extern "C" int lgm_grad_sqnorm_partial(const float* g, int64_t n, double* partials, void* stream) {
+  LGM_REQUIRE(g && partials && n > 0 && lgm_aligned16(g) && (((uintptr_t)partials) & 7u) == 0,
+              "grad_sqnorm_partial: bad arguments");
+  LGM_REQUIRE(lgm_grad_sqnorm_partials(n) <= 0x7fffffffL, "grad_sqnorm_partial: buffer too large");
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)lgm_grad_sqnorm_partials(n)), dim3(256), 0, (hipStream_t)stream, g,
+                     (long)n, partials);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+extern "C" int lgm_grad_clip_scale(const double* partials, int64_t count, float grad_scale, float max_norm, float* out2,
+                                   void* stream) {
+  LGM_REQUIRE(partials && out2 && count > 0 && (((uintptr_t)partials) & 7u) == 0, "grad_clip_scale: bad arguments");
+  LGM_REQUIRE(max_norm >= 0.f, "grad_clip_scale: max_norm must not be negative");
+  hipLaunchKernelGGL(grad_clip_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long)count, grad_scale,
+                     max_norm, out2);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+extern "C" int lgm_grad_accumulate(float* dst, const float* src, int64_t n, int overwrite, void* stream) {
+  LGM_REQUIRE(dst && src && n > 0 && lgm_aligned16(dst) && lgm_aligned16(src), "grad_accumulate: bad arguments");
+  const long nthreads = (n + 3) / 4;
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3(lgm_cdiv(nthreads, 256)), dim3(256), 0, (hipStream_t)stream, dst, src,
+                     (long)n, overwrite);
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }

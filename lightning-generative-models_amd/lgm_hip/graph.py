@@ -17,6 +17,8 @@ Philox generator.  The arithmetic is identical to the eager path (same kernels, 
 ModuleFastStep (VQ-VAE: one graph) and WGANFastStep (critic graph / generator graph) follow the same rules and keep
 what they captured in a ``_Captured``: warm-up and capture leave the training state untouched (_TrainingState), also
 when capture fails.  Every step class falls back to eager launches when capture is not possible (``_eager_fallback``).
+``accumulate > 1`` (DDPMFastStep, ModuleFastStep) leaves the captured graphs as they are: the micro-gradients are summed in one
+extra flat buffer behind the replays and the exchange, the norm and Adam run once per K micro-steps (``_GradAccumulation``).
 """
 from __future__ import annotations
 
@@ -143,6 +145,63 @@ class _Captured:
         return self.out
 
 
+class _GradAccumulation:
+    """``accumulate_grad_batches = K > 1`` over one flat gradient buffer.  The backward passes (captured or eager) go on
+    overwriting ``flat.grad``; this object owns the ONE extra buffer ``acc`` and counts micro-steps.  Micro-step k of K:
+
+        k = 1 < K   ``stash``: acc = grad           no exchange, no optimizer step
+        1 < k < K   ``stash``: acc += grad          no exchange, no optimizer step
+        k = K       ``fold``:  grad += acc          (slice by slice, in front of that slice's exchange), then the tail
+                                                    of a plain step: exchange, norm, Adam - all of them read ``flat.grad``
+
+    so the stepped gradient is the sequential float32 sum ((g1 + g2) + ...) + gK, and ``scale()`` = base / K is the
+    mean over micro-batches that Lightning's ``loss / K`` gives, folded into Adam like 1 / world."""
+
+    def __init__(self, flat, K: int):
+        self.flat, self.K, self.k = flat, int(K), 0      # k: micro-gradients held in ``acc``
+        self.acc = torch.empty_like(flat.grad)
+
+    @property
+    def stepping(self) -> bool:
+        """the micro-step now running is the Kth: its tail ends in the optimizer step"""
+        return self.k == self.K - 1
+
+    def scale(self, base: float) -> float:
+        return base / self.K
+
+    def stash(self):
+        ops.grad_accumulate(self.acc, self.flat.grad, overwrite=self.k == 0)
+        self.k += 1
+
+    def fold(self, lo: int, hi: int):
+        if self.k:
+            ops.grad_accumulate(self.flat.grad[lo:hi], self.acc[lo:hi])
+
+    def unstash(self):
+        """``flush``: the pending sum becomes the gradient (no micro-gradient of this step exists)"""
+        ops.grad_accumulate(self.flat.grad, self.acc, overwrite=True)
+        self.k = 0                                       # nothing left to fold
+
+    def stepped(self):
+        self.k = 0
+
+
+def _accumulated_step(opt, sync, accum: _GradAccumulation):
+    """The end of the Kth micro-step and of ``flush``.  Without an exchange nothing has read the gradient yet: ONE add
+    over the whole buffer.  Then the optimizer step at 1 / (K world) and a new sum."""
+    if sync is None:
+        accum.fold(0, accum.flat.total)
+    else:
+        sync.finish()
+    getattr(opt, "_opt", opt).grad_scale = accum.scale(sync.grad_scale if sync is not None else 1.0)
+    opt.step()
+    accum.stepped()
+
+
+def _clipping(opt) -> bool:
+    return bool(getattr(getattr(opt, "_opt", opt), "clipping", False))
+
+
 LAYOUT_ONE, LAYOUT_TWO, LAYOUT_BUCKETS = ((0, 1, 2, 3),), ((0, 1), (2, 3)), ((0,), (1,), (2,), (3,))
 
 
@@ -180,10 +239,11 @@ class GraphedDDPMStep:
     ``self.t`` / ``self.noise`` / ``self.offset`` (the [B, C] offset noise of a diffusion with ``offset_noise_strength > 0``)
     / ``self.classes`` hold what the last replay drew."""
 
-    def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None):
+    def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None,
+                 accum: Optional[_GradAccumulation] = None):
         from models.generative.diffusion.ddpm import (hip_loss_backward_begin, hip_loss_estimate, hip_loss_network,
                                                       hip_loss_qsample)
-        self.model, self.opt, self.sync = model, opt, sync
+        self.model, self.opt, self.sync, self.accum = model, opt, sync, accum
         self.gd = gd = model.ema.online_model
         self.net = net = gd.model
         self.x = x                                   # static input buffer (copy new batches into it)
@@ -194,7 +254,9 @@ class GraphedDDPMStep:
         strength = float(gd.offset_noise_strength)
         self.y = net.labels(y, x.shape[0], x.device).clone() if net.num_classes is not None else None
         # (the pipelined variant applies a bucket's Adam slice right behind ITS all-reduce: only with the overlapped exchange)
-        self.pipeline = _STEP_PIPELINE and (sync is None or getattr(sync, "overlap", True))
+        # (and a slice cannot be updated before the whole gradient norm exists, or before the last micro-batch)
+        self.pipeline = (_STEP_PIPELINE and (sync is None or getattr(sync, "overlap", True))
+                         and accum is None and not _clipping(opt))
         self.layout = (LAYOUT_BUCKETS if sync is not None or self.pipeline else LAYOUT_ONE if _ONE_GRAPH else LAYOUT_TWO)
         self_cond = bool(net.self_condition)
         self.pre = self.est = None                   # self-conditioned model only: see the class comment
@@ -267,6 +329,8 @@ class GraphedDDPMStep:
         sync = self.sync
         if self.pipeline:
             self._replay_pipelined()
+        elif self.accum is not None:
+            self._replay_accumulating()
         else:
             for g, ranges in zip(self.graphs, self.ranges):
                 g.replay()
@@ -279,6 +343,24 @@ class GraphedDDPMStep:
         self.opt.zero_grad()                         # host flag only: the next backward overwrites
         self.model.on_train_batch_end(None, None, batch_idx)
         return self.loss
+
+    def _replay_accumulating(self):
+        """Micro-steps 1 ... K-1: the replays and one accumulate launch.  Micro-step K: ``grad += acc`` per graph over
+        that graph's slices, right behind its replay and in front of their ``sync.ready``, so the all-reduces still run
+        beside the later graphs; then the tail of a plain step."""
+        sync, accum = self.sync, self.accum
+        if not accum.stepping:
+            for g in self.graphs:
+                g.replay()
+            accum.stash()
+            return
+        for g, ranges in zip(self.graphs, self.ranges):
+            g.replay()
+            if sync is not None:
+                for lo, hi in ranges:
+                    accum.fold(lo, hi)
+                    sync.ready(lo, hi)
+        _accumulated_step(self.opt, sync, accum)
 
     def _replay_pipelined(self):
         sync = self.sync
@@ -314,7 +396,7 @@ class DDPMFastStep:
     Logging (``train_loss``) and the reference's periodic in-training sampling (ddpm.py:1017-1027) stay
     outside the graphs."""
 
-    def __init__(self, model, opt, world: int, use_graph: bool = True):
+    def __init__(self, model, opt, world: int, use_graph: bool = True, accumulate: int = 1):
         from .lightning import FlatGradSync
         self.model, self.opt = model, opt
         self.net = model.ema.online_model.model
@@ -322,6 +404,8 @@ class DDPMFastStep:
         inner = getattr(opt, "_opt", opt)            # MiniTrainer wraps optimizers in a step-counting proxy
         if self.sync is not None:
             inner.grad_scale = self.sync.grad_scale  # 1/N folded into Adam (no divide pass)
+        # accumulate_grad_batches: one extra flat buffer and a micro-step count; 1: no buffer, no launch more than before
+        self.accum = _GradAccumulation(self.net._flat, accumulate) if int(accumulate) > 1 else None
         self.use_graph = use_graph
         self.graphed: Optional[GraphedDDPMStep] = None
         self.mode = "eager"
@@ -330,9 +414,9 @@ class DDPMFastStep:
 
     def _capture(self, x, y=None):
         try:
-            self.graphed = GraphedDDPMStep(self.model, self.opt, x.clone(), self.sync, y=y)
+            self.graphed = GraphedDDPMStep(self.model, self.opt, x.clone(), self.sync, y=y, accum=self.accum)
             n = len(self.graphed.graphs) + (1 if self.graphed.pre is not None else 0)
-            self.mode = ("hipGraph replay (4 graphs/step, weight passes on a side stream)" if _STEP_PIPELINE else
+            self.mode = ("hipGraph replay (4 graphs/step, weight passes on a side stream)" if self.graphed.pipeline else
                          f"hipGraph replay ({n} graph{'s' if n > 1 else ''}/step)")
             if self.graphed.est is not None:
                 self.mode = self.mode[:-1] + ", + the estimate graph on self-conditioned steps)"
@@ -356,21 +440,48 @@ class DDPMFastStep:
                 self.graphed.y.copy_(y)
             loss = self.graphed.step(batch_idx, self_cond)
         else:
-            self.net.grad_sync = self.sync           # backward phases hand finished buckets to the exchange
+            accum = self.accum
+            # backward phases hand finished buckets to the exchange (an accumulating step exchanges behind its backward:
+            # a bucket is final only once the pending sum is added)
+            self.net.grad_sync = self.sync if accum is None else None
             gd = m.ema.online_model
             kw = dict(_self_cond=self_cond) if self.net.self_condition else {}
             if y is not None:
                 kw["classes"] = y
             loss = gd(x, **kw)
             loss.backward()
-            if self.sync is not None:
-                self.sync.finish()
-            self.opt.step()
+            if accum is None:
+                if self.sync is not None:
+                    self.sync.finish()
+                self.opt.step()
+            elif accum.stepping:
+                self._exchange_accumulated()
+                _accumulated_step(self.opt, self.sync, accum)
+            else:
+                accum.stash()
             self.opt.zero_grad()
             m.on_train_batch_end(None, batch, batch_idx)
             self.net.grad_sync = None
         m.log("train_loss", loss, prog_bar=True, logger=True, sync_dist=multi_rank())
         return loss
+
+    def _exchange_accumulated(self):
+        """eager launches / ``flush``: every bucket's pending sum added and handed to the exchange, in bucket order"""
+        if self.sync is not None:
+            for ranges in self.net.bucket_ranges():
+                for lo, hi in ranges:
+                    self.accum.fold(lo, hi)
+                    self.sync.ready(lo, hi)
+
+    def flush(self):
+        """Step on whatever is pending, at the same 1 / K scale (Lightning steps on the last batch of an epoch)."""
+        accum = self.accum
+        if accum is None or accum.k == 0:
+            return
+        accum.unstash()
+        self._exchange_accumulated()
+        _accumulated_step(self.opt, self.sync, accum)
+        self.opt.zero_grad()
 
 
 class ModuleFastStep:
@@ -384,12 +495,14 @@ class ModuleFastStep:
     when capture is not possible, a collective sits inside ``training_step`` (``collective_inside``) or a batch has
     another shape."""
 
-    def __init__(self, model, opt, world: int = 1, use_graph: bool = True, collective_inside: bool = False):
+    def __init__(self, model, opt, world: int = 1, use_graph: bool = True, collective_inside: bool = False,
+                 accumulate: int = 1):
         self.model, self.opt, self.world = model, opt, world
         self.flat = model._flat
         inner = getattr(opt, "_opt", opt)
         if world > 1:
             inner.grad_scale = 1.0 / world
+        self.accum = _GradAccumulation(self.flat, accumulate) if int(accumulate) > 1 else None
         self.use_graph = use_graph and not (collective_inside and world > 1)
         self.captured: Optional[_Captured] = None    # its ``out``: (loss, what training_step logged inside the capture)
         self.static = None                           # the captured step's input tensors
@@ -406,13 +519,33 @@ class ModuleFastStep:
         loss.backward(one)
         return loss
 
-    def _finish(self, batch, batch_idx):
+    def _optimizer_step(self):
+        accum = self.accum
+        if accum is not None:
+            accum.fold(0, self.flat.total)
+            getattr(self.opt, "_opt", self.opt).grad_scale = accum.scale(1.0 / self.world)
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(self.flat.grad)
         self.opt.step()
+        if accum is not None:
+            accum.stepped()
+
+    def _finish(self, batch, batch_idx):
+        if self.accum is None or self.accum.stepping:
+            self._optimizer_step()
+        else:
+            self.accum.stash()
         self.opt.zero_grad()
         self.model.on_train_batch_end(None, batch, batch_idx)
+
+    def flush(self):
+        """Step on whatever is pending, at the same 1 / K scale (Lightning steps on the last batch of an epoch)."""
+        if self.accum is None or self.accum.k == 0:
+            return
+        self.accum.unstash()
+        self._optimizer_step()
+        self.opt.zero_grad()
 
     def _capture(self, batch):
         m = self.model

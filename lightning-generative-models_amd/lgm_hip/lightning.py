@@ -500,9 +500,19 @@ class MiniTrainer:
 
     def __init__(self, max_steps=-1, max_epochs=-1, accumulate_grad_batches=1, device=None,
                  default_root_dir=None, log_every=50, check_val_every_n_epoch=1, ckpt_every_n_steps=1000,
-                 limit_val_batches=None, fast_path=True, **_ignored):
+                 limit_val_batches=None, fast_path=True, gradient_clip_val=None, gradient_clip_algorithm="norm",
+                 **_ignored):
+        """``gradient_clip_val`` (None or 0: off): the global L2 norm of the accumulated, averaged gradient is clipped
+        before every optimizer step, as ``torch.nn.utils.clip_grad_norm_`` does.  ``gradient_clip_algorithm="value"`` is
+        not built and is refused."""
         self.max_steps, self.max_epochs = max_steps, max_epochs
         self.accumulate = max(1, int(accumulate_grad_batches))
+        if gradient_clip_algorithm not in (None, "norm"):
+            raise ValueError(f"gradient_clip_algorithm={gradient_clip_algorithm!r}: only 'norm' is built")
+        self.clip = float(gradient_clip_val) if gradient_clip_val else None
+        if self.clip is not None and not self.clip > 0:
+            raise ValueError(f"gradient_clip_val={gradient_clip_val!r} must be positive (None or 0: off)")
+        self._clipped_norm = None                    # clip_grad_norm_'s result for an optimizer that does not clip itself
         self.device = device
         self.root = default_root_dir
         self.log_every = log_every
@@ -528,6 +538,29 @@ class MiniTrainer:
             if getattr(p, "_lgm_flat", None) is None and p.grad is not None:
                 dist.all_reduce(p.grad)
                 p.grad.div_(self.world)
+
+    def _clip_before_step(self, opt):
+        """An optimizer without ``max_grad_norm`` (the CPU plumbing models): torch's own clipping over its parameters.
+        The fused optimizers clip inside ``step()``."""
+        if self.clip is not None and not hasattr(opt, "max_grad_norm"):
+            params = [p for g in opt.param_groups for p in g["params"] if p.grad is not None]
+            self._clipped_norm = torch.nn.utils.clip_grad_norm_(params, self.clip)
+
+    def _step(self, model, opt):
+        """the slow path's optimizer step: exchange, clip, step"""
+        self.allreduce_grads(model)
+        self._clip_before_step(opt)
+        opt.step()
+        opt.zero_grad()
+
+    def _log_grad_norm(self, model):
+        """``grad_norm`` joins the logged scalars when they are read (a device scalar: no host read per step)"""
+        if self.clip is None or not model._optimizers:
+            return
+        norm = getattr(model._optimizers[0], "last_grad_norm", None)
+        norm = self._clipped_norm if norm is None else norm
+        if norm is not None:
+            model.log("grad_norm", norm)
 
     # -- checkpoints (reference: ModelCheckpoint(dirpath, save_last=True, monitor="val_loss")) ------
     def _save_last(self, model, epoch):
@@ -596,6 +629,14 @@ class MiniTrainer:
             for o, osd in zip(opts, ckpt.get("optimizer_states", [])):
                 o.load_state_dict(osd)
         model._optimizers = [_CountingOptimizer(o, model) for o in opts]
+        if not model.automatic_optimization and (self.accumulate > 1 or self.clip is not None):
+            # Lightning refuses both for manual optimisation: the module steps its own optimizers
+            raise ValueError("accumulate_grad_batches > 1 and gradient_clip_val are not supported with manual "
+                             f"optimisation ({type(model).__name__} steps its optimizers itself)")
+        if self.clip is not None:
+            for o in opts:
+                if hasattr(o, "max_grad_norm"):
+                    o.max_grad_norm = self.clip      # the fused optimizers clip on the device, inside step()
         if self.world > 1 and opts and all(hasattr(o, "grad_scale") for o in opts):
             # SUM all-reduce + 1/world folded into the fused optimizer kernels: no divide pass over the gradients
             for o in opts:
@@ -608,10 +649,12 @@ class MiniTrainer:
             val_dataloader = datamodule.val_dataloader()
         model.train()
         fast = None
-        if (self.fast_path and self.accumulate == 1 and device.type == "cuda" and hasattr(model, "make_fast_step")):
+        if self.fast_path and device.type == "cuda" and hasattr(model, "make_fast_step"):
             # automatic optimisation: one optimizer; manual optimisation (GANs): the module's optimizer list
-            fast = model.make_fast_step(model._optimizers[0] if model.automatic_optimization else model._optimizers,
-                                        self.world)
+            if model.automatic_optimization:
+                fast = model.make_fast_step(model._optimizers[0], self.world, accumulate=self.accumulate)
+            else:
+                fast = model.make_fast_step(model._optimizers, self.world)
         self.fast = fast
         epoch = int(ckpt.get("epoch", 0)) if ckpt is not None else 0
         done = False
@@ -636,15 +679,14 @@ class MiniTrainer:
                         loss.backward()
                         pending += 1
                         if pending == self.accumulate:
-                            self.allreduce_grads(model)
-                            opt.step()
-                            opt.zero_grad()
+                            self._step(model, opt)
                             pending = 0
                         model.on_train_batch_end(None, batch, batch_idx)
                     else:
                         model.training_step(batch, batch_idx) if takes_idx else model.training_step(batch)
                         model.on_train_batch_end(None, batch, batch_idx)
                     if self.log_every and model.global_step % self.log_every == 0:
+                        self._log_grad_norm(model)
                         msg = model.synced_logs()            # collective (sync_dist scalars): every rank takes part
                         if self.rank == 0:
                             print(f"[step {model.global_step}] {msg} ({time.time() - t0:.1f}s)", flush=True)
@@ -655,9 +697,9 @@ class MiniTrainer:
                         done = stopped_mid_epoch = True
                         break
                 if pending:                          # Lightning steps on the last batch of an epoch
-                    self.allreduce_grads(model)
-                    model._optimizers[0].step()
-                    model._optimizers[0].zero_grad()
+                    self._step(model, model._optimizers[0])
+                if fast is not None and hasattr(fast, "flush"):
+                    fast.flush()                     # the same for the micro-batches the step object holds
                 if not stopped_mid_epoch:            # an epoch cut short by max_steps is not a completed epoch:
                     epoch += 1                       # a resume from its checkpoint runs that epoch again
                 if 0 < self.max_epochs <= epoch:

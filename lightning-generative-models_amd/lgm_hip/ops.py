@@ -1362,6 +1362,40 @@ def adam_step(p, g, m, v, n, lr, b1, b2, eps, wd, step, step_dev=None, grad_scal
                         float(step), _p(step_dev), grad_scale, 1 if decoupled else 0, stream())
 
 
+def adam_step_scaled(p, g, m, v, n, lr, b1, b2, eps, wd, step, step_dev, scale_dev, decoupled=False):
+    """adam_step with the gradient scale read from the device: ``scale_dev[0]`` as grad_clip_scale left it"""
+    lib().lgm_adam_step_scaled(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, b1, b2, eps, wd,
+                               float(step), _p(step_dev), scale_dev.data_ptr(), 1 if decoupled else 0, stream())
+
+
+def grad_sqnorm_partials(n: int) -> int:
+    """doubles lgm_grad_sqnorm_partial writes for a flat buffer of n floats (host-only, a function of n alone)"""
+    return int(lib().lgm_grad_sqnorm_partials(n))
+
+
+def grad_sqnorm_span(n: int) -> int:
+    return int(lib().lgm_grad_sqnorm_span(n))
+
+
+def grad_sqnorm_partial(g, partials):
+    """partials[b] = sum of g^2 over workgroup b's span, in double; ``partials``: float64, grad_sqnorm_partials(n) long"""
+    assert g.dtype == torch.float32 and partials.dtype == torch.float64 and g.is_contiguous() and partials.is_contiguous()
+    assert partials.numel() >= grad_sqnorm_partials(g.numel())
+    lib().lgm_grad_sqnorm_partial(g.data_ptr(), g.numel(), partials.data_ptr(), stream())
+
+
+def grad_clip_scale(partials, grad_scale, max_norm, out2):
+    """out2 = (grad_scale * min(1, max_norm / (norm + 1e-6)), norm), norm = |grad_scale| sqrt(sum(partials))"""
+    assert partials.dtype == torch.float64 and out2.dtype == torch.float32 and out2.numel() >= 2
+    lib().lgm_grad_clip_scale(partials.data_ptr(), partials.numel(), grad_scale, max_norm, out2.data_ptr(), stream())
+
+
+def grad_accumulate(dst, src, overwrite=False):
+    """dst = src (overwrite) or dst += src over flat float32 slices: the bits of torch's dst + src"""
+    assert dst.numel() == src.numel() and dst.dtype == src.dtype == torch.float32
+    lib().lgm_grad_accumulate(dst.data_ptr(), src.data_ptr(), dst.numel(), 1 if overwrite else 0, stream())
+
+
 def image_transform(src_u8: torch.Tensor, size: int, flip: Optional[torch.Tensor] = None, out=None):
     """u8 [B,H,W,C] decoded images -> fp32 NCHW [B,C,size,size] in [-1,1] (reference DataModule transforms)."""
     assert src_u8.dtype == torch.uint8 and src_u8.dim() == 4 and src_u8.is_contiguous()

@@ -10,7 +10,7 @@ buffer.  EMA: ema_pytorch.EMA surface used by ddpm.py:998,1014,1033,1048 (``.mod
 from __future__ import annotations
 
 import copy
-from typing import Iterable, List
+from typing import Iterable, List, Optional
 
 import torch
 from torch import nn
@@ -20,12 +20,22 @@ from .flat import FlatParams
 
 
 class FusedAdam(torch.optim.Optimizer):
+    """``grad_scale`` and ``max_grad_norm`` are attributes, not param-group entries: ``state_dict()`` keeps torch's layout.
+
+    ``max_grad_norm`` (None: off) clips the global L2 norm of the gradient the optimizer sees (``grad_scale * grad``, over
+    every flat buffer of every group) as ``torch.nn.utils.clip_grad_norm_`` does, without a host read: one partial-sum
+    pass per flat buffer into one workspace, one launch that forms the clipped scale on the device, then the Adam kernel
+    reading that scale.  ``last_grad_norm`` is the device scalar of the norm before clipping."""
+
     def __init__(self, params: Iterable[nn.Parameter], lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0, decoupled=False):
+                 weight_decay=0.0, decoupled=False, max_grad_norm: Optional[float] = None):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, decoupled=decoupled)
         super().__init__(params, defaults)
         self._flat_state = {}   # id(FlatParams) -> dict(m, v, step, flat)
         self.grad_scale = 1.0   # e.g. 1/world_size after a SUM all-reduce (folded into the kernel)
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm: Optional[torch.Tensor] = None
+        self._clip_ws = None    # (partials float64, out2 float32 = (clipped scale, norm)): allocated at the first clipped step
 
     def _flats(self, group) -> List[FlatParams]:
         seen, out = set(), []
@@ -39,19 +49,55 @@ class FusedAdam(torch.optim.Optimizer):
                 out.append(fp)
         return out
 
+    def _state(self, fp: FlatParams):
+        st = self._flat_state.get(id(fp))
+        if st is None:
+            st = dict(m=torch.zeros_like(fp.data), v=torch.zeros_like(fp.data), step=0, flat=fp)
+            self._flat_state[id(fp)] = st
+        return st
+
+    @property
+    def clipping(self) -> bool:
+        return self.max_grad_norm is not None and self.max_grad_norm > 0
+
+    def _clip_scale(self):
+        """The partial pass over every flat buffer of every group and the one launch that turns the partials into
+        (grad_scale * coef, norm) on the device -> the two-float tensor the Adam launches read."""
+        flats, seen = [], set()
+        for group in self.param_groups:
+            for fp in self._flats(group):
+                if id(fp) not in seen:
+                    seen.add(id(fp))
+                    flats.append(fp)
+        counts = [ops.grad_sqnorm_partials(fp.total) for fp in flats]
+        if self._clip_ws is None or self._clip_ws[0].numel() != sum(counts) or self._clip_ws[0].device != flats[0].grad.device:
+            dev = flats[0].grad.device
+            self._clip_ws = (torch.empty(sum(counts), dtype=torch.float64, device=dev),
+                             torch.empty(2, dtype=torch.float32, device=dev))
+            self.last_grad_norm = self._clip_ws[1][1]
+        partials, out2 = self._clip_ws
+        off = 0
+        for fp, c in zip(flats, counts):
+            ops.grad_sqnorm_partial(fp.grad, partials[off:off + c])
+            off += c
+        ops.grad_clip_scale(partials, self.grad_scale, float(self.max_grad_norm), out2)
+        return out2
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        scale_dev = self._clip_scale() if self.clipping else None
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for fp in self._flats(group):
-                st = self._flat_state.get(id(fp))
-                if st is None:
-                    st = dict(m=torch.zeros_like(fp.data), v=torch.zeros_like(fp.data), step=0, flat=fp)
-                    self._flat_state[id(fp)] = st
+                st = self._state(fp)
                 st["step"] += 1
-                ops.adam_step(fp.data, fp.grad, st["m"], st["v"], fp.total, group["lr"], b1, b2, group["eps"],
-                              group["weight_decay"], st["step"], None, self.grad_scale, group["decoupled"])
+                if scale_dev is None:
+                    ops.adam_step(fp.data, fp.grad, st["m"], st["v"], fp.total, group["lr"], b1, b2, group["eps"],
+                                  group["weight_decay"], st["step"], None, self.grad_scale, group["decoupled"])
+                else:
+                    ops.adam_step_scaled(fp.data, fp.grad, st["m"], st["v"], fp.total, group["lr"], b1, b2, group["eps"],
+                                         group["weight_decay"], st["step"], None, scale_dev, group["decoupled"])
         return loss
 
     # ---- one step issued slice by slice (lgm_hip.graph: a bucket's slice as soon as ITS gradients are final) --------
@@ -59,10 +105,7 @@ class FusedAdam(torch.optim.Optimizer):
         """Advance the step count of ``fp``'s state once; returns (group, state) for ``step_slice``."""
         for group in self.param_groups:
             if any(f is fp for f in self._flats(group)):
-                st = self._flat_state.get(id(fp))
-                if st is None:
-                    st = dict(m=torch.zeros_like(fp.data), v=torch.zeros_like(fp.data), step=0, flat=fp)
-                    self._flat_state[id(fp)] = st
+                st = self._state(fp)
                 st["step"] += 1
                 return group, st
         raise RuntimeError("begin_step: this optimizer does not own the flat buffer")
@@ -70,6 +113,8 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step_slice(self, fp: FlatParams, group, st, lo: int, hi: int):
         """The Adam update of elements [lo, hi) (multiples of 4) - same kernel, same arithmetic as step()."""
+        if self.clipping:
+            raise RuntimeError("step_slice: with max_grad_norm set no slice can be updated before the whole norm exists")
         assert lo % 4 == 0 and hi % 4 == 0 and 0 <= lo < hi <= fp.total
         b1, b2 = group["betas"]
         ops.adam_step(fp.data[lo:hi], fp.grad[lo:hi], st["m"][lo:hi], st["v"][lo:hi], hi - lo, group["lr"], b1, b2,
@@ -145,6 +190,18 @@ class FusedRMSprop(FusedAdam):
                                                           momentum=0, centered=False))
         self._flat_state = {}
         self.grad_scale = 1.0
+        self.last_grad_norm = None
+        self._clip_ws = None
+
+    @property
+    def max_grad_norm(self):
+        """not built for RMSprop: its only user is a manual-optimisation module"""
+        return None
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            raise ValueError("FusedRMSprop does not clip gradients (max_grad_norm)")
 
     @torch.no_grad()
     def step(self, closure=None):

@@ -1,7 +1,8 @@
 """Training entry point with the reference's CLI (train.py:31-66):
 
     python train.py --config_path configs/diffusion/ddpm.json [--max_steps N] [--max_epochs N]
-                    [--accumulate_grad_batches K] [--ckpt_path last.ckpt] [--strategy ddp|auto]
+                    [--accumulate_grad_batches K] [--gradient_clip_val C] [--gradient_clip_algorithm norm]
+                    [--ckpt_path last.ckpt] [--strategy ddp|auto]
 
 One process per GPU.  Like the reference (``--strategy`` defaults to DDP when the node shows more than one
 GPU, and Lightning starts the ranks), a plain ``python train.py ...`` on a multi-GPU node becomes the parent of one rank
@@ -14,6 +15,10 @@ installed: the HIP engine's flat gradient buffers, overlapped bucketed all-reduc
 are driven by it (for DDPM: the same DDPMFastStep bench.py times).  It keeps the reference trainer's
 observable behaviour: ``last.ckpt`` (+ the best-``val_loss`` checkpoint) in the experiment directory,
 validation at the end of every epoch, ``--max_steps`` / ``--max_epochs`` / ``--accumulate_grad_batches``.
+``--accumulate_grad_batches K`` stays on the graph-replayed step (K micro-batches summed in one extra flat buffer, one
+exchange and one optimizer step per K); ``--gradient_clip_val C`` clips the global L2 norm of that accumulated, averaged
+gradient on the device before Adam (``--gradient_clip_algorithm value`` is not built and is refused; manual-optimisation
+modules - the GANs - refuse both flags, as Lightning does).
 """
 import argparse
 import os
@@ -61,6 +66,8 @@ def setup_arguments(argv=None, print_args=True, save_args=True):
     p.add_argument("--max_steps", type=int, default=-1)
     p.add_argument("--strategy", type=str, default="auto")
     p.add_argument("--accumulate_grad_batches", type=int, default=1)
+    p.add_argument("--gradient_clip_val", type=float, default=None)
+    p.add_argument("--gradient_clip_algorithm", type=str, default="norm")
     p.add_argument("--precision", type=str, default=None)
     p.add_argument("--ckpt_path", type=str, default=None)
     p.add_argument("--project", type=str, default="Lightning generative models")
@@ -138,6 +145,7 @@ def main(argv=None):
         device = torch.device("cpu")
     trainer = MiniTrainer(max_epochs=args.max_epochs, max_steps=args.max_steps, default_root_dir=args.experiment_dir,
                           accumulate_grad_batches=args.accumulate_grad_batches, device=device,
+                          gradient_clip_val=args.gradient_clip_val, gradient_clip_algorithm=args.gradient_clip_algorithm,
                           check_val_every_n_epoch=args.check_val_every_n_epoch)   # reference train.py: Trainer(...)
     trainer.fit(model, datamodule=datamodule, ckpt_path=args.ckpt_path)
     if world > 1:
