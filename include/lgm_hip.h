@@ -52,8 +52,9 @@ extern "C" {
                              *  lgm_sample_step_table_slice, lgm_label_emb_fwd, lgm_label_emb_wgrad, lgm_cfg_mix, lgm_dpm_step, lgm_dpm_step_table,
                              *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh,
                              *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint, lgm_vlb_term, lgm_vlb_term_table,
-                             *  lgm_grad_sqnorm_*, lgm_grad_clip_scale, lgm_adam_step_scaled, lgm_grad_accumulate - a library
-                             *  that lacks a declared symbol fails to load) */
+                             *  lgm_grad_sqnorm_*, lgm_grad_clip_scale, lgm_adam_step_scaled, lgm_grad_accumulate, lgm_hybrid_loss_fwd,
+                             *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned
+                             *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
 #define LGM_ERR_UNSUPPORTED (-2)
@@ -642,6 +643,54 @@ int lgm_vlb_term(const float* img, const float* noise, int normalize, const floa
 int lgm_vlb_term_table(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch, int x_off,
                        const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip, const float* table,
                        int stride, const int32_t* counter, float* out, int n_rows, int advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Learned variance (Nichol & Dhariwal 2021; the reference's Unet(learned_variance=True), which its diffusion never trains):
+ * the network output v [B, HW, v_pitch] carries 2 C lanes, [0, C) the objective's prediction and [C, 2 C) the interpolation
+ * coefficient.  The model's log-variance of an element is lv = f * log_beta + (1 - f) * log_tilde with f = (v + 1) / 2 (f outside
+ * [0, 1] is legal), log_beta = log beta_t and log_tilde = posterior_log_variance_clipped[t], log beta~_1 at t = 0.  One device
+ * function (csrc/elementwise.hip learned_term) gives the bound's term of an element in nats and its derivative in lv:
+ *   t >= 1  KL = 0.5 (-1 + lv - lv_q + exp(lv_q - lv) + d^2 exp(-lv)), d = P1 (x0_pred - x0), lv_q = log_tilde
+ *   t = 0   -log p of lgm_vlb_term's decoder with standard deviation exp(0.5 lv); the derivative in the same cancellation-free
+ *           form, 0 where the probability is floored at 1e-12
+ * lgm_hybrid_loss_fwd / _bwd (training): L = mean_b(lw[t_b] mse_b) + vb_weight mean_b(vb_b); mse_b = mean over lanes [0, C) of
+ *   (out - target)^2 as lgm_weighted_mse_fwd forms it, vb_b = mean(term) / ln 2 at t_b with the model mean P1 x0_pred + P2 x_t
+ *   detached and built from the UNCLIPPED x0_pred.  out [B, HW, pitch >= 2 C], target [B, HW, target_pitch >= C], img NCHW dense
+ *   (x0 = img * 2 - 1 when normalize), x_t in lanes [x_off, x_off + C) of xin [B, HW, x_pitch]; the four head tables and
+ *   loss_weight (NULL => 1) as lgm_model_predictions_obj takes them; tab [n_table][8] = (log beta_t, log_tilde, lv_q, P1, P2, 0,
+ *   0, 0) (GaussianDiffusion.learned_table).  fwd: one workgroup per sample, fixed-order sums, no atomics; per [2][B] =
+ *   (lw mse_b, vb_b); loss [1] (optional) by a one-workgroup second stage.  bwd: elementwise over the pitch; gout lanes [0, C)
+ *   exactly what lgm_weighted_mse_bwd writes, lanes [C, 2 C) = gloss * vb_weight / (B * C * HW * ln 2) * dterm/dlv * 0.5 * (log_beta
+ *   - log_tilde), every other lane 0.  They launch hybrid_loss_fwd_kernel (+ hybrid_mean_kernel) / hybrid_loss_bwd_kernel.
+ * lgm_sample_step_learned / lgm_sample_step_table_learned (ancestral sampling): lgm_sample_step_slice / _table_slice with clip
+ *   set and the row (A, Bv, R, Rm1, P1, P2, log_beta, log_tilde): x_{t-1} = P1 x0 + P2 x_t + exp(0.5 lv) noise, lv per element;
+ *   log_tilde = -inf marks the step without noise (t = 0).  x0_out (optional, pitch = `pitch`) as lgm_sample_step_thresh.  The
+ *   same launch of sample_step_slice_kernel as every other update.
+ * lgm_vlb_term_learned (likelihood): lgm_vlb_term / lgm_vlb_term_table behind one entry point (table != NULL: row counter[0],
+ *   else the scalars) for kind 3 (KL) and 4 (decoder) of a learned-variance network; table rows carry log_beta / log_tilde in
+ *   slots 10 / 11.  v_pitch >= 2 C.  lgm_vlb_term_table given such a row for an output without the head writes nothing. */
+int lgm_hybrid_loss_fwd(const float* out, int64_t pitch, const float* target, int64_t target_pitch, const float* img,
+                        int normalize, const float* xin, int64_t x_pitch, int x_off, const int64_t* t,
+                        const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                        const float* loss_weight, const float* tab, int n_table, int objective, float vb_weight, int B,
+                        int C, int HW, float* per, float* loss, void* stream);
+int lgm_hybrid_loss_bwd(const float* out, int64_t pitch, const float* target, int64_t target_pitch, const float* img,
+                        int normalize, const float* xin, int64_t x_pitch, int x_off, const int64_t* t,
+                        const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                        const float* loss_weight, const float* tab, int n_table, int objective, float vb_weight,
+                        const float* gloss, int B, int C, int HW, float* gout, void* stream);
+int lgm_sample_step_learned(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                            int64_t v_pitch, const float* noise, float* x0_out, int B, int C, int HW, int objective,
+                            float A, float Bv, float R, float Rm1, float P1, float P2, float log_beta, float log_tilde,
+                            void* stream);
+int lgm_sample_step_table_learned(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
+                                  const float* noise, int B, int C, int HW, const float* table, const int32_t* counter,
+                                  int objective, int advance, void* stream);
+int lgm_vlb_term_learned(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch, int x_off,
+                         const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip, float A, float S,
+                         float R, float Rm1, float P1, float P2, int kind, float log_beta, float log_tilde,
+                         const float* table, int stride, const int32_t* counter, float* out, int n_rows, int out_row,
+                         int advance, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

@@ -888,7 +888,8 @@ extern "C" int64_t lgm_conv_workspace(const LgmConvGeom* g, int yx) {
 }
 
 namespace {
-// 1x1 convolution between 64 channels and <= 4 (the UNet's final_conv 64 -> 3, reference ddpm.py:422, and its input gradient).
+// 1x1 convolution between 64 channels and <= 4 or <= 8 (the UNet's final_conv 64 -> 3, reference ddpm.py:422, 64 -> 6 with the
+// learned variance :418, and its input gradient).
 // As a GEMM it has N = 4 and idles 15/16 of a 64-wide MFMA tile (igemm_kernel<0, 128, 64>: 25 us for 33.5 MB at B = 128); it
 // is a streaming dot product: the 16 lanes of a DPP row own one pixel (lane = four channels, one 16-byte load), the four
 // weight rows sit in registers, the row sums are four rotate-and-add steps on the DPP path (no LDS, no shuffle through the
@@ -905,15 +906,22 @@ __device__ __forceinline__ float lgm_row16_sum(float v) {
   return v;
 }
 
+// NW = 4 or 8 outputs (the final_conv of a learned-variance network, 64 -> 2 C = 6): NW weight rows in registers, NW / 4 stores
+// of 16 bytes per pixel; the NW = 4 instantiation is the kernel there was, instruction for instruction.
+template <int NW>
 __global__ __launch_bounds__(256) void narrow1x1_fwd_kernel(const float* __restrict__ x, long x_pitch,
                                                             const float* __restrict__ w, const float* __restrict__ bias,
                                                             float* __restrict__ y, long y_pitch, long P) {
   const int cl = threadIdx.x & 15, slot = threadIdx.x >> 4;          // 16 pixels per block and trip
-  f32x4 wr[4];
+  f32x4 wr[NW];
 #pragma unroll
-  for (int n = 0; n < 4; ++n) wr[n] = *reinterpret_cast<const f32x4*>(w + n * 64 + cl * 4);
-  f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-  if (bias) bv = *reinterpret_cast<const f32x4*>(bias);
+  for (int n = 0; n < NW; ++n) wr[n] = *reinterpret_cast<const f32x4*>(w + n * 64 + cl * 4);
+  f32x4 bv[NW / 4];
+#pragma unroll
+  for (int q = 0; q < NW / 4; ++q) {
+    bv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (bias) bv[q] = *reinterpret_cast<const f32x4*>(bias + 4 * q);
+  }
   const long stride = (long)gridDim.x * 64;                          // four trips' pixels in flight per thread
   for (long p0 = (long)blockIdx.x * 64 + slot; p0 < P; p0 += stride) {
     f32x4 xv[4];
@@ -925,46 +933,55 @@ __global__ __launch_bounds__(256) void narrow1x1_fwd_kernel(const float* __restr
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long pix = p0 + 16 * u;
-      f32x4 o;
 #pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const f32x4 t = xv[u] * wr[n];
-        o[n] = lgm_row16_sum((t[0] + t[1]) + (t[2] + t[3]));
+      for (int q = 0; q < NW / 4; ++q) {
+        f32x4 o;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+          const f32x4 t = xv[u] * wr[4 * q + n];
+          o[n] = lgm_row16_sum((t[0] + t[1]) + (t[2] + t[3]));
+        }
+        if (cl == 0 && pix < P) *reinterpret_cast<f32x4*>(y + pix * y_pitch + 4 * q) = o + bv[q];
       }
-      if (cl == 0 && pix < P) *reinterpret_cast<f32x4*>(y + pix * y_pitch) = o + bv;
     }
   }
 }
 
+template <int NW>
 __global__ __launch_bounds__(256) void narrow1x1_dgrad_kernel(const float* __restrict__ gy, long gy_pitch,
                                                               const float* __restrict__ w, float* __restrict__ gx,
                                                               long gx_pitch, long P) {
   const int cl = threadIdx.x & 15, slot = threadIdx.x >> 4;
-  f32x4 wr[4];
+  f32x4 wr[NW];
 #pragma unroll
-  for (int n = 0; n < 4; ++n) wr[n] = *reinterpret_cast<const f32x4*>(w + n * 64 + cl * 4);
+  for (int n = 0; n < NW; ++n) wr[n] = *reinterpret_cast<const f32x4*>(w + n * 64 + cl * 4);
   const long stride = (long)gridDim.x * 64;
   for (long p0 = (long)blockIdx.x * 64 + slot; p0 < P; p0 += stride) {
-    f32x4 g[4];
+    f32x4 g[4][NW / 4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long pix = p0 + 16 * u;
-      g[u] = pix < P ? *reinterpret_cast<const f32x4*>(gy + pix * gy_pitch) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < NW / 4; ++q)
+        g[u][q] = pix < P ? *reinterpret_cast<const f32x4*>(gy + pix * gy_pitch + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long pix = p0 + 16 * u;
-      if (pix < P)
-        *reinterpret_cast<f32x4*>(gx + pix * gx_pitch + cl * 4) =
-            (wr[0] * g[u][0] + wr[1] * g[u][1]) + (wr[2] * g[u][2] + wr[3] * g[u][3]);
+      f32x4 acc = (wr[0] * g[u][0][0] + wr[1] * g[u][0][1]) + (wr[2] * g[u][0][2] + wr[3] * g[u][0][3]);
+#pragma unroll
+      for (int q = 1; q < NW / 4; ++q)       // the next four rows as a group of their own, then one sum per group
+        acc = acc + ((wr[4 * q] * g[u][q][0] + wr[4 * q + 1] * g[u][q][1]) +
+                     (wr[4 * q + 2] * g[u][q][2] + wr[4 * q + 3] * g[u][q][3]));
+      if (pix < P) *reinterpret_cast<f32x4*>(gx + pix * gx_pitch + cl * 4) = acc;
     }
   }
 }
 
-// the layers these two kernels take: 1x1 / stride 1 / unpadded, 64 channels on the wide side, 4 (padded) on the narrow one
+// the layers these two kernels take: 1x1 / stride 1 / unpadded, 64 channels on the wide side, 4 or 8 (padded) on the narrow one
 bool narrow1x1_geom(const LgmConvGeom* g) {
   static const bool off = lgm_env_set("LGM_NO_NARROW1X1");        // A/B switch
-  return !off && g->KH == 1 && g->KW == 1 && g->stride == 1 && g->pad == 0 && g->Nw == 4 && g->Cw == 64;
+  return !off && g->KH == 1 && g->KW == 1 && g->stride == 1 && g->pad == 0 && (g->Nw == 4 || g->Nw == 8) && g->Cw == 64;
 }
 unsigned narrow1x1_blocks(long P) {
   const long want = (P + 63) / 64;
@@ -986,8 +1003,12 @@ static int conv_xy_impl(const LgmConvGeom* g, const float* x, int64_t x_pitch, c
   if (use_3x3() && narrow1x1_geom(g) && !res && !stats && !t_post.post && wide_ok(y, y_pitch, nullptr, 0, bias)) {
     const long P = (long)g->B * g->H * g->W;
     lgm_note_kernel(LGM_KNAME("narrow1x1_fwd_kernel"));
-    hipLaunchKernelGGL(narrow1x1_fwd_kernel, dim3(narrow1x1_blocks(P)), dim3(256), 0, (hipStream_t)stream, x, (long)x_pitch, w,
-                       bias, y, (long)y_pitch, P);
+    if (g->Nw == 8)
+      hipLaunchKernelGGL(narrow1x1_fwd_kernel<8>, dim3(narrow1x1_blocks(P)), dim3(256), 0, (hipStream_t)stream, x,
+                         (long)x_pitch, w, bias, y, (long)y_pitch, P);
+    else
+      hipLaunchKernelGGL(narrow1x1_fwd_kernel<4>, dim3(narrow1x1_blocks(P)), dim3(256), 0, (hipStream_t)stream, x,
+                         (long)x_pitch, w, bias, y, (long)y_pitch, P);
     LGM_LAUNCH_CHECK();
     return LGM_OK;
   }
@@ -1335,8 +1356,12 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
   if (use_3x3() && narrow1x1_geom(g) && !res && !bias && !stats && !t_post.post && wide_ok(x, x_pitch, nullptr, 0, nullptr)) {
     const long P = (long)g->B * g->H * g->W;
     lgm_note_kernel(LGM_KNAME("narrow1x1_dgrad_kernel"));
-    hipLaunchKernelGGL(narrow1x1_dgrad_kernel, dim3(narrow1x1_blocks(P)), dim3(256), 0, (hipStream_t)stream, y, (long)y_pitch, w,
-                       x, (long)x_pitch, P);
+    if (g->Nw == 8)
+      hipLaunchKernelGGL(narrow1x1_dgrad_kernel<8>, dim3(narrow1x1_blocks(P)), dim3(256), 0, (hipStream_t)stream, y,
+                         (long)y_pitch, w, x, (long)x_pitch, P);
+    else
+      hipLaunchKernelGGL(narrow1x1_dgrad_kernel<4>, dim3(narrow1x1_blocks(P)), dim3(256), 0, (hipStream_t)stream, y,
+                         (long)y_pitch, w, x, (long)x_pitch, P);
     LGM_LAUNCH_CHECK();
     return LGM_OK;
   }

@@ -644,6 +644,12 @@ __global__ __launch_bounds__(256) void qsample_slice_kernel(const float* __restr
 // (its other lanes zero); zeros into xout's padding.  table == null: the scalars by value in `byval`.  thresh != null ([B],
 // from dyn_thresh_kernel): the clip is dynamic thresholding with s = thresh[b]; null: the static clamp, the launch there was.
 struct SampleRow { float v[8]; };
+__device__ __forceinline__ float learned_logvar(float v, float log_beta, float log_tilde);
+// x_{t-1} = mean + exp(0.5 lv) noise of the learned-variance ancestral step, product and sum rounded separately
+__device__ __forceinline__ float learned_step_noise(float mean, float nz, float vv, float log_beta, float log_tilde) {
+#pragma clang fp contract(off)
+  return mean + expf(0.5f * learned_logvar(vv, log_beta, log_tilde)) * nz;
+}
 // Inpainting (RePaint, Lugmayr et al. 2022, Algorithm 1; lgm_hip/sampler.py inpaint_walk): the operands of the tail both
 // update kernels run after their own body when `known` is non-null.  known NHWC [B, HW, r4(C)] (pad lanes never read), mask
 // [B, HW] (1 = keep the known pixel, shared by the channels), eps_k / eps_j NCHW dense like the step's noise; the row (M_a,
@@ -684,11 +690,16 @@ __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin
                                                                 SampleRow byval, const float* __restrict__ table,
                                                                 const int* __restrict__ counter, int objective, int clip,
                                                                 int rederive, float* __restrict__ x0_out, long x0_pitch,
-                                                                const float* __restrict__ thresh, InpaintOps ip) {
+                                                                const float* __restrict__ thresh, InpaintOps ip,
+                                                                int learned) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)B * HW * lanes) return;
   const float* row = table ? table + 8 * counter[0] : byval.v;
-  const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], C0 = row[4], C1 = row[5], C2 = row[6], C3 = row[7];
+  const float A = row[0], Bv = row[1], R = row[2], Rm1 = row[3], C0 = row[4], C1 = row[5];
+  // learned (uniform; ancestral step of a learned-variance network): slots 6 / 7 are (log beta_t, log beta~_t), the noise is
+  // weighed per element with exp(0.5 lv), lv from lanes [C, 2 C) of v; log beta~_t = -inf marks the step without noise (t = 0)
+  const float LB = row[6], LT = row[7];
+  const float C2 = learned ? 0.f : row[6], C3 = learned ? (LT == -INFINITY ? 0.f : 1.f) : row[7];
   const int c = (int)(i % lanes);
   const long pix = i / lanes;
   float x0 = 0.f;
@@ -702,7 +713,8 @@ __global__ __launch_bounds__(256) void sample_step_slice_kernel(const float* xin
     const bool dyn = thresh != nullptr;
     const float s = dyn ? thresh[pix / HW] : 1.f;
     sample_update_obj(objective, xin[pix * pitch + x_off + c], v[pix * v_pitch + c], nz, A, Bv, clip, rederive, R, Rm1, C0,
-                      C1, C2, noise ? C3 : 0.f, o, x0, dyn, s);
+                      C1, C2, noise && !learned ? C3 : 0.f, o, x0, dyn, s);
+    if (learned && noise && C3 != 0.f) o = learned_step_noise(o, nz, v[pix * v_pitch + C + c], LB, LT);
     if (ip.known) o = inpaint_tail(ip, counter, o, pix, c, C, HW);
     xout[pix * pitch + x_off + c] = o;
     if (sc_off >= 0) xout[pix * pitch + sc_off + c] = x0;
@@ -892,6 +904,8 @@ __global__ __launch_bounds__(DT_THREADS) void dyn_thresh_kernel(const float* __r
 //           difference of the means IS P1 (x0_pred - x0); at large t, P1 is 1e-2 ... 1e-4 and two O(1) means formed in float32
 //           and subtracted would keep three to four digits less.
 //   kind 1, decoder (t = 0):  -mean(log p) / ln 2,  log p = vlb_decoder_logp below.
+//   kind 3 / 4, KL / decoder of a learned-variance network: mean(learned_term) / ln 2 with the element's own log-variance from
+//           lanes [C, 2 C) of the network output and slots 10 / 11 = (log beta_t, log beta~_t); these kinds read 12 slots.
 //   kind 2, prior:  (KC + KW mean(x0^2)) / ln 2 with the host's KC = 0.5 (-1 - log(1 - acp) + (1 - acp)), KW = 0.5 acp: the
 //           sum in KC cancels to ~acp^2 / 2 and is formed in float64 on the host.  Reads img only; [1] and [2] come out 0.
 // One workgroup per sample; a lane owns pixels and loops over the channels (the NCHW reads coalesce over pixels); three sums
@@ -931,12 +945,184 @@ __device__ __forceinline__ float vlb_decoder_logp(float x, float mean, float inv
   }
   return fmaxf(lp, FLOOR);
 }
+// ---------------------------------------------------------------------------------------
+// Learned variance (Nichol & Dhariwal 2021, 3.1): the network's lanes [C, 2 C) hold v, and the model's log-variance of an
+// element is lv = f log beta_t + (1 - f) log beta~_t with f = (v + 1) / 2 (f outside [0, 1] is legal; log beta~_1 at t = 0,
+// lgm_hip/likelihood.py's convention).  learned_logvar is that interpolation, learned_term the bound's term of ONE element in
+// nats with the model mean P1 x0_pred + P2 x_t and, when dlv is given, its derivative with respect to lv - the one function
+// behind the training loss (hybrid_loss_*_kernel) and the likelihood (vlb_term_kernel, kinds 3 and 4).
+//   KL (t >= 1):  0.5 (-1 + lv - lv_q + exp(lv_q - lv) + d^2 exp(-lv)),  d = P1 (x0_pred - x0)
+//                 d/dlv = 0.5 (1 - exp(lv_q - lv) - d^2 exp(-lv))
+//   decoder (t = 0):  -vlb_decoder_logp(x0, mean, s),  s = exp(-0.5 lv).  z+-, and with them a, h, m of vlb_decoder_logp, are
+//                 proportional to s up to the cubic term, so s d/ds of them is the same polynomial with the cubic term tripled
+//                 (az, hs, ms below) and d(-log p)/dlv = 0.5 s dlog p/ds.  In the same cancellation-free form:
+//                 end bins     s dlog p/ds = sigmoid(-a) az  (x < -0.999),  -sigmoid(a) az  (x > 0.999)
+//                 interior     dlog p/dh = coth h - sinh h / (cosh m + cosh h) = (cosh h cosh m + 1) / (sinh h (cosh m + cosh h)),
+//                              dlog p/d|m| = -sinh |m| / (cosh m + cosh h), both with e^{max(|m|, h)} factored out
+//                 A floored probability has gradient 0, as clamp(min = 1e-12) gives.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float learned_logvar(float v, float log_beta, float log_tilde) {
+#pragma clang fp contract(off)
+  const float f = 0.5f * (v + 1.f);
+  return f * log_beta + (1.f - f) * log_tilde;
+}
+__device__ __forceinline__ float learned_term(bool decoder, float x0, float x0p, float xv, float P1, float P2, float lv,
+                                              float lv_q, float* dlv) {
+#pragma clang fp contract(off)
+  if (!decoder) {
+    const float d = P1 * (x0p - x0);
+    const float r = expf(lv_q - lv), q = (d * d) * expf(-lv);
+    if (dlv) *dlv = 0.5f * ((1.f - r) - q);
+    return 0.5f * (((-1.f + (lv - lv_q)) + r) + q);
+  }
+  const float K = 0.7978845608f, C3 = 0.044715f, FLOOR = -27.6310211f;
+  const float inv_std = expf(-0.5f * lv);
+  const float mean = P1 * x0p + P2 * xv;
+  const float lp = vlb_decoder_logp(x0, mean, inv_std);
+  if (dlv) {
+    const float zc = inv_std * (x0 - mean), dl = inv_std * (1.f / 255.f);
+    float g;                                   // s dlog p / ds
+    if (x0 < -0.999f || x0 > 0.999f) {
+      const float z = x0 < 0.f ? zc + dl : zc - dl;
+      const float a = 2.f * (K * (z + C3 * (z * z * z)));
+      const float az = 2.f * (K * (z + 3.f * C3 * (z * z * z)));
+      g = x0 < 0.f ? az / (1.f + expf(a)) : -(az / (1.f + expf(-a)));
+    } else {
+      const float h = K * (2.f * dl + C3 * (6.f * (zc * zc) * dl + 2.f * (dl * dl * dl)));
+      const float m = fabsf(K * (2.f * zc + C3 * (2.f * (zc * zc * zc) + 6.f * zc * (dl * dl))));
+      const float hs = K * (2.f * dl + 3.f * C3 * (6.f * (zc * zc) * dl + 2.f * (dl * dl * dl)));
+      const float ms = fabsf(K * (2.f * zc + 3.f * C3 * (2.f * (zc * zc * zc) + 6.f * zc * (dl * dl))));
+      const float E = expf(-2.f * h), F = expf(-2.f * m);
+      const float omE = -expm1f(-2.f * h), omF = -expm1f(-2.f * m);
+      float num, den, sm;
+      if (m >= h) {
+        const float e = expf(h - m);
+        den = (1.f + F) + e * (1.f + E);
+        num = (1.f + E) * (1.f + F) + 4.f * expf(-h - m);
+        sm = omF;
+      } else {
+        const float e = expf(m - h);
+        den = e * (1.f + F) + (1.f + E);
+        num = e * ((1.f + E) * (1.f + F)) + 4.f * E;
+        sm = e * omF;
+      }
+      g = (num / (omE * den)) * hs - (sm / den) * ms;
+    }
+    *dlv = lp > FLOOR ? 0.5f * g : 0.f;
+  }
+  return -lp;
+}
+// ---------------------------------------------------------------------------------------
+// Hybrid loss of a learned-variance network (Nichol & Dhariwal 2021, eq. 16; lgm_hybrid_loss_fwd / _bwd):
+//     L = mean_b(lw[t_b] mse_b) + vb_weight mean_b(vb_b)
+// mse_b over lanes [0, C) as mse_sample_kernel forms it, vb_b the bound's term at t_b in bits per dimension (learned_term; the
+// mean is detached and built from the UNCLIPPED x0 prediction).  tab [T][8] = (log beta_t, log beta~_t, lv_q, P1, P2, 0, 0, 0).
+// Forward: one workgroup per sample, two sums through lgm_block_sum in its fixed order, per[b] = lw mse_b, per[B + b] = vb_b;
+// a one-workgroup second stage writes the scalar.  Backward: elementwise over the output's pitch; lanes [0, C) as
+// mse_bwd_kernel writes them, lanes [C, 2 C) the gradient through lv alone, every other lane zero.
+// ---------------------------------------------------------------------------------------
+struct HybridTables {
+  const float* sa;
+  const float* s1;
+  const float* r;
+  const float* rm1;
+  const float* lw;
+  const float* tab;
+  int n_table;
+};
+__device__ __forceinline__ float hybrid_element(const HybridTables& T, long ti, int objective, float x0, float xv, float ov,
+                                                float vv, float* dlv) {
+  const float* row = T.tab + 8 * ti;
+  float e, x0p;
+  predictions_one(objective, xv, ov, T.sa[ti], T.s1[ti], T.r[ti], T.rm1[ti], 0, 0, e, x0p);
+  const float lv = learned_logvar(vv, row[0], row[1]);
+  return learned_term(ti == 0, x0, x0p, xv, row[3], row[4], lv, row[2], dlv);
+}
+__global__ __launch_bounds__(256) void hybrid_loss_fwd_kernel(const float* __restrict__ out, long pitch,
+                                                              const float* __restrict__ target, long t_pitch,
+                                                              const float* __restrict__ img, int normalize,
+                                                              const float* __restrict__ xin, long x_pitch, int x_off,
+                                                              const long* __restrict__ t, HybridTables T, int objective,
+                                                              int C, int HW, float* __restrict__ per, int B) {
+#pragma clang fp contract(off)
+  __shared__ float sh[16];
+  const int b = blockIdx.x;
+  long ti = t[b];
+  ti = ti < 0 ? 0 : (ti >= T.n_table ? T.n_table - 1 : ti);
+  float s = 0.f, sv = 0.f;
+  for (int p = threadIdx.x; p < HW; p += 256) {
+    const long pix = (long)b * HW + p;
+    for (int c = 0; c < C; ++c) {
+      const float ov = out[pix * pitch + c];
+      const float d = ov - target[pix * t_pitch + c];
+      s += d * d;
+      float x0 = img[((long)b * C + c) * HW + p];
+      if (normalize) x0 = x0 * 2.f - 1.f;
+      sv += hybrid_element(T, ti, objective, x0, xin[pix * x_pitch + x_off + c], ov, out[pix * pitch + C + c], nullptr);
+    }
+  }
+  s = lgm_block_sum(s, sh);
+  sv = lgm_block_sum(sv, sh);
+  if (threadIdx.x == 0) {
+    const float n = (float)C * (float)HW;
+    per[b] = s / n * (T.lw ? T.lw[ti] : 1.f);
+    per[B + b] = sv / n / 0.69314718f;
+  }
+}
+__global__ void hybrid_mean_kernel(const float* __restrict__ per, int B, float vb_weight, float* __restrict__ loss) {
+#pragma clang fp contract(off)
+  __shared__ float sh[16];
+  float s = 0.f, sv = 0.f;
+  for (int i = threadIdx.x; i < B; i += blockDim.x) {
+    s += per[i];
+    sv += per[B + i];
+  }
+  s = lgm_block_sum(s, sh);
+  sv = lgm_block_sum(sv, sh);
+  if (threadIdx.x == 0) loss[0] = s / (float)B + vb_weight * (sv / (float)B);
+}
+__global__ __launch_bounds__(256) void hybrid_loss_bwd_kernel(const float* __restrict__ out, long pitch,
+                                                              const float* __restrict__ target, long t_pitch,
+                                                              const float* __restrict__ img, int normalize,
+                                                              const float* __restrict__ xin, long x_pitch, int x_off,
+                                                              const long* __restrict__ t, HybridTables T, int objective,
+                                                              const float* __restrict__ gloss, float vb_weight, int B,
+                                                              int C, int HW, float* __restrict__ gout) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)B * HW * pitch;
+  if (i >= total) return;
+  const int c = (int)(i % pitch);
+  const long pix = i / pitch;
+  const int b = (int)(pix / HW);
+  float g = 0.f;
+  if (c < 2 * C) {
+    long ti = t[b];
+    ti = ti < 0 ? 0 : (ti >= T.n_table ? T.n_table - 1 : ti);
+    if (c < C) {
+      const float w = T.lw ? T.lw[ti] : 1.f;
+      const float scale = gloss[0] * 2.f * w / ((float)C * (float)HW * (float)B);
+      g = scale * (out[pix * pitch + c] - target[pix * t_pitch + c]);
+    } else {
+#pragma clang fp contract(off)
+      const int cc = c - C, p = (int)(pix % HW);
+      float x0 = img[((long)b * C + cc) * HW + p];
+      if (normalize) x0 = x0 * 2.f - 1.f;
+      float dlv;
+      hybrid_element(T, ti, objective, x0, xin[pix * x_pitch + x_off + cc], out[pix * pitch + cc], out[pix * pitch + c], &dlv);
+      const float* row = T.tab + 8 * ti;
+      const float scale = gloss[0] * vb_weight / ((float)B * ((float)C * (float)HW) * 0.69314718f);
+      g = scale * dlv * (0.5f * (row[0] - row[1]));
+    }
+  }
+  gout[pix * pitch + c] = g;
+}
 __global__ __launch_bounds__(VLB_THREADS) void vlb_term_kernel(const float* __restrict__ img, const float* __restrict__ noise,
                                                                int normalize, const float* __restrict__ xin, long pitch,
                                                                int x_off, const float* __restrict__ v, long v_pitch, int B,
                                                                int C, int HW, VlbRow byval, const float* __restrict__ table,
                                                                int stride, const int* __restrict__ counter, int out_row,
-                                                               int objective, int clip, float* __restrict__ out, int n_rows) {
+                                                               int objective, int clip, float* __restrict__ out, int n_rows,
+                                                               int v_lanes) {
 #pragma clang fp contract(off)
   __shared__ float sh[16];
   const int r = table ? counter[0] : out_row;
@@ -945,6 +1131,9 @@ __global__ __launch_bounds__(VLB_THREADS) void vlb_term_kernel(const float* __re
   const float A = row[0], S = row[1], R = row[2], Rm1 = row[3], P1 = row[4], P2 = row[5];
   const int kind = (int)row[6];
   const float KC = row[7], KW = row[8], inv_std = row[9];
+  if (kind < 0 || kind > 4 || (kind >= 3 && v_lanes < 2 * C)) return;     // a learned row on an output without the head
+  const bool learned = kind == 3 || kind == 4;          // slots 10 / 11: log beta_t, log beta~_t; lanes [C, 2 C) of v: the head
+  const float LB = learned ? row[10] : 0.f, LT = learned ? row[11] : 0.f;
   const int b = blockIdx.x;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   for (int p = threadIdx.x; p < HW; p += VLB_THREADS) {
@@ -963,7 +1152,9 @@ __global__ __launch_bounds__(VLB_THREADS) void vlb_term_kernel(const float* __re
       const float d0 = x0p - x0, de = e - noise[dense];
       s1 += d0 * d0;
       s2 += de * de;
-      if (kind == 0) {
+      if (learned) {
+        s0 += learned_term(kind == 4, x0, x0p, xv, P1, P2, learned_logvar(v[pix * v_pitch + C + c], LB, LT), LT, nullptr);
+      } else if (kind == 0) {
         const float d = P1 * d0;
         s0 += d * d;
       } else {
@@ -977,7 +1168,7 @@ __global__ __launch_bounds__(VLB_THREADS) void vlb_term_kernel(const float* __re
   if (threadIdx.x == 0) {
     const float n = (float)C * (float)HW, LN2 = 0.69314718f;
     float* o = out + (long)r * 3 * B + b;
-    o[0] = (kind == 1 ? -(s0 / n) : KC + KW * (s0 / n)) / LN2;
+    o[0] = (learned ? s0 / n : kind == 1 ? -(s0 / n) : KC + KW * (s0 / n)) / LN2;
     o[B] = s1 / n;
     o[2 * B] = s2 / n;
   }
@@ -1541,6 +1732,57 @@ static bool slices_ok(int64_t pitch, int x_off, int sc_off, int C) {
   return sc_off + C <= pitch && (sc_off + C <= x_off || x_off + C <= sc_off);
 }
 
+// Hybrid loss of a learned-variance network (hybrid_loss_*_kernel): out [B, HW, pitch] with 2 C lanes, target [B, HW,
+// target_pitch], img NCHW (normalised here when `normalize`), x_t in the x slice of xin, tab [T][8] (ddpm.py learned_table),
+// per [2][B] = (lw mse_b, vb_b), loss [1] (optional) = mean_b(per[0]) + vb_weight mean_b(per[1]).
+static bool hybrid_ok(const float* out, int64_t pitch, const float* target, int64_t target_pitch, const float* img,
+                      const float* xin, int64_t x_pitch, int x_off, const int64_t* t, const float* const* tables,
+                      const float* tab, int B, int C, int HW, int objective, int n_table) {
+  if (!out || !target || !img || !xin || !t || !tab || B <= 0 || C <= 0 || HW <= 0 || n_table <= 0) return false;
+  for (int i = 0; i < 4; ++i)
+    if (!tables[i]) return false;
+  return pitch >= 2 * (int64_t)C && target_pitch >= C && slices_ok(x_pitch, x_off, -1, C) && objective_ok(objective) &&
+         (int64_t)B * HW * pitch < ((int64_t)1 << 40);
+}
+extern "C" int lgm_hybrid_loss_fwd(const float* out, int64_t pitch, const float* target, int64_t target_pitch,
+                                   const float* img, int normalize, const float* xin, int64_t x_pitch, int x_off,
+                                   const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip,
+                                   const float* sqrt_recipm1, const float* loss_weight, const float* tab, int n_table,
+                                   int objective, float vb_weight, int B, int C, int HW, float* per, float* loss,
+                                   void* stream) {
+  const float* tables[4] = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1};
+  LGM_REQUIRE(per && hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, tables, tab, B, C, HW, objective,
+                               n_table),
+              "hybrid_loss_fwd: bad arguments");
+  const HybridTables T = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, loss_weight, tab, n_table};
+  hipStream_t s = (hipStream_t)stream;
+  lgm_note_kernel("hybrid_loss_fwd_kernel");
+  hipLaunchKernelGGL(hybrid_loss_fwd_kernel, dim3(B), dim3(256), 0, s, out, (long)pitch, target, (long)target_pitch, img,
+                     normalize, xin, (long)x_pitch, x_off, (const long*)t, T, objective, C, HW, per, B);
+  if (loss) hipLaunchKernelGGL(hybrid_mean_kernel, dim3(1), dim3(256), 0, s, (const float*)per, B, vb_weight, loss);
+  LGM_LAUNCH_CHECK_AS("hybrid_loss_fwd");
+  return LGM_OK;
+}
+extern "C" int lgm_hybrid_loss_bwd(const float* out, int64_t pitch, const float* target, int64_t target_pitch,
+                                   const float* img, int normalize, const float* xin, int64_t x_pitch, int x_off,
+                                   const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip,
+                                   const float* sqrt_recipm1, const float* loss_weight, const float* tab, int n_table,
+                                   int objective, float vb_weight, const float* gloss, int B, int C, int HW, float* gout,
+                                   void* stream) {
+  const float* tables[4] = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1};
+  LGM_REQUIRE(gloss && gout && gout != out &&
+                  hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, tables, tab, B, C, HW, objective,
+                            n_table),
+              "hybrid_loss_bwd: bad arguments");
+  const HybridTables T = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, loss_weight, tab, n_table};
+  lgm_note_kernel("hybrid_loss_bwd_kernel");
+  hipLaunchKernelGGL(hybrid_loss_bwd_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, out,
+                     (long)pitch, target, (long)target_pitch, img, normalize, xin, (long)x_pitch, x_off, (const long*)t, T,
+                     objective, gloss, vb_weight, B, C, HW, gout);
+  LGM_LAUNCH_CHECK_AS("hybrid_loss_bwd");
+  return LGM_OK;
+}
+
 static int qsample_slice_launch(const float* img, const float* noise, const float* offset, float strength, const int64_t* t,
                                 const float* sqrt_ac, const float* sqrt_1mac, int normalize, int objective, float* xin,
                                 int64_t pitch, int lanes, int x_off, int sc_off, float* target, int64_t target_pitch,
@@ -1650,11 +1892,11 @@ static int sample_step_slice_launch(const float* xin, float* xout, int64_t pitch
                                     int64_t v_pitch, const float* noise, float* x0_out, int64_t x0_pitch, int B, int C,
                                     int HW, const SampleRow& row, const float* table, const int32_t* counter, int objective,
                                     int clip, int rederive, int advance, void* stream, const float* thresh = nullptr,
-                                    const InpaintOps& ip = InpaintOps{}) {
+                                    const InpaintOps& ip = InpaintOps{}, int learned = 0) {
   lgm_note_kernel(LGM_KNAME("sample_step_slice_kernel"));
   hipLaunchKernelGGL(sample_step_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream,
                      xin, xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, B, C, HW, row, table,
-                     (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch, thresh, ip);
+                     (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch, thresh, ip, learned);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("sample_step_slice");
   return LGM_OK;
@@ -1717,6 +1959,30 @@ extern "C" int lgm_sample_step_table_slice(float* x, int64_t pitch, int x_off, i
               "sample_step_table_slice: bad arguments");
   return sample_step_slice_launch(x, x, pitch, x_off, sc_off, v, v_pitch, noise, nullptr, 0, B, C, HW, SampleRow{}, table,
                                   counter, objective, clip, rederive, advance, stream);
+}
+
+// The ancestral step of a learned-variance network: v carries 2 C lanes, the row is (A, Bv, R, Rm1, P1, P2, log beta_t,
+// log beta~_t) with log beta~_t = -inf on the step without noise; the same launch as every other update.
+extern "C" int lgm_sample_step_learned(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
+                                       int64_t v_pitch, const float* noise, float* x0_out, int B, int C, int HW,
+                                       int objective, float A, float Bv, float R, float Rm1, float P1, float P2,
+                                       float log_beta, float log_tilde, void* stream) {
+  LGM_REQUIRE(xin && xout && v && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) && v_pitch >= 2 * (int64_t)C &&
+                  objective_ok(objective) && x0_out != xin && x0_out != xout,
+              "sample_step_learned: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, P1, P2, log_beta, log_tilde}};
+  return sample_step_slice_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, x0_out, pitch, B, C, HW, row, nullptr,
+                                  nullptr, objective, 1, 0, 0, stream, nullptr, InpaintOps{}, 1);
+}
+
+extern "C" int lgm_sample_step_table_learned(float* x, int64_t pitch, int x_off, int sc_off, const float* v, int64_t v_pitch,
+                                             const float* noise, int B, int C, int HW, const float* table,
+                                             const int32_t* counter, int objective, int advance, void* stream) {
+  LGM_REQUIRE(x && v && table && counter && B > 0 && HW > 0 && slices_ok(pitch, x_off, sc_off, C) &&
+                  v_pitch >= 2 * (int64_t)C && objective_ok(objective),
+              "sample_step_table_learned: bad arguments");
+  return sample_step_slice_launch(x, x, pitch, x_off, sc_off, v, v_pitch, noise, nullptr, 0, B, C, HW, SampleRow{}, table,
+                                  counter, objective, 1, 0, advance, stream, nullptr, InpaintOps{}, 1);
 }
 
 // The dynamically thresholded update (thresh [B] from lgm_dyn_thresh): both forms of the row behind one entry point - table
@@ -1876,10 +2142,11 @@ static int vlb_term_launch(const float* img, const float* noise, int normalize, 
                            const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip, const VlbRow& row,
                            const float* table, int stride, const int32_t* counter, int out_row, float* out, int n_rows,
                            int advance, void* stream) {
+  const int v_lanes = v ? (int)(v_pitch < 2 * (int64_t)C ? C : 2 * C) : 0;
   lgm_note_kernel("vlb_term_kernel");
   hipLaunchKernelGGL(vlb_term_kernel, dim3(B), dim3(VLB_THREADS), 0, (hipStream_t)stream, img, noise, normalize, xin,
                      (long)pitch, x_off, v, (long)v_pitch, B, C, HW, row, table, stride, (const int*)counter, out_row,
-                     objective, clip ? 1 : 0, out, n_rows);
+                     objective, clip ? 1 : 0, out, n_rows, v_lanes);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("vlb_term");
   return LGM_OK;
@@ -1906,6 +2173,25 @@ extern "C" int lgm_vlb_term_table(const float* img, const float* noise, int norm
               "vlb_term_table: bad arguments");
   return vlb_term_launch(img, noise, normalize, xin, pitch, x_off, v, v_pitch, B, C, HW, objective, clip, VlbRow{}, table,
                          stride, counter, 0, out, n_rows, advance, stream);
+}
+
+// The term of a learned-variance network (kind 3: KL, 4: decoder; slots 10 / 11 = log beta_t, log beta~_t), both forms of the
+// row behind one entry point like lgm_sample_step_thresh: table != NULL takes row counter[0] of it into output row counter[0].
+// The network output carries 2 C lanes.
+extern "C" int lgm_vlb_term_learned(const float* img, const float* noise, int normalize, const float* xin, int64_t pitch,
+                                    int x_off, const float* v, int64_t v_pitch, int B, int C, int HW, int objective, int clip,
+                                    float A, float S, float R, float Rm1, float P1, float P2, int kind, float log_beta,
+                                    float log_tilde, const float* table, int stride, const int32_t* counter, float* out,
+                                    int n_rows, int out_row, int advance, void* stream) {
+  LGM_REQUIRE((table == nullptr) == (counter == nullptr) && (table || !advance) &&
+                  (table ? stride >= VLB_ROW && out != table && (const void*)out != (const void*)counter
+                         : (kind == 3 || kind == 4) && out_row >= 0 && out_row < n_rows) &&
+                  v_pitch >= 2 * (int64_t)C &&
+                  vlb_operands_ok(img, noise, xin, pitch, x_off, v, v_pitch, B, C, HW, objective, out, n_rows, false),
+              "vlb_term_learned: bad arguments");
+  const VlbRow row = {{A, S, R, Rm1, P1, P2, (float)kind, 0.f, 0.f, 0.f, log_beta, log_tilde}};
+  return vlb_term_launch(img, noise, normalize, xin, pitch, x_off, v, v_pitch, B, C, HW, objective, clip, row, table, stride,
+                         counter, out_row, out, n_rows, advance, stream);
 }
 
 // ---------------------------------------------------------------------------------------

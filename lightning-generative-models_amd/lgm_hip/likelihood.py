@@ -17,7 +17,9 @@ Top down:
   * ``vlb_terms``: the public function behind ``GaussianDiffusion.vlb_terms``; the prior row is one more eager launch, and the
     host reads the [n + 1, 3, B] result once, the only synchronisation.
 
-The model's variance is fixed (the reference's network has no variance head), by Nichol & Dhariwal's two conventions:
+``variance="learned"`` (a ``Unet(learned_variance=True)``): every element's log-variance is interpolated between log beta_t and
+log beta~_t by the network's variance lane (``learned_table``; the device function the hybrid training loss uses).  Otherwise
+the model's variance is fixed, by Nichol & Dhariwal's two conventions:
 ``fixed_small`` = the posterior variance beta~_t, ``fixed_large`` = beta_t, both with t = 0 taking log beta~_1 - not the
 reference's ``posterior_log_variance_clipped[0]`` = log 1e-20, under which the decoder would be a step function.
 """
@@ -36,9 +38,10 @@ import torch
 from . import ops, sampler
 from .flat import _r4
 
-VLB_ROW = 12                                   # floats per row; the kernel reads the first ten
+VLB_ROW = 12                                   # floats per row; the kernel reads the first ten, all twelve of a learned kind
 KL, DECODER, PRIOR = 0, 1, 2                   # row[6]
-VARIANCES = ("fixed_small", "fixed_large")
+KL_LEARNED, DECODER_LEARNED = 3, 4             # row[6] of a learned-variance network's rows (variance="learned")
+VARIANCES = ("fixed_small", "fixed_large")     # the fixed conventions; "learned" is accepted beside them
 VLBTerms = namedtuple("VLBTerms", "total_bpd prior_bpd vb xstart_mse mse timesteps")
 
 
@@ -51,6 +54,22 @@ def _tables64(gd):
     float64, kept in float32 - the values its samplers use), widened"""
     return tuple([float(v) for v in getattr(gd, n).detach().double().cpu().tolist()]
                  for n in ("betas", "alphas_cumprod", "posterior_log_variance_clipped"))
+
+
+def learned_table(gd):
+    """-> T rows of 8 float32 values (log beta_t, log beta~_t, lv_q, P1, P2, 0, 0, 0): the per-t scalars of a learned-variance
+    diffusion, shared by the hybrid loss (``GaussianDiffusion.learned_table``), the ancestral step and the learned rows of
+    ``vlb_plan``.  log beta~_t = ``posterior_log_variance_clipped[t]`` for t >= 1 and log beta~_1 at t = 0 (this module's
+    convention, not the reference's log 1e-20); lv_q = ``posterior_log_variance_clipped[t]``; P1 / P2 =
+    ``posterior_mean_coef1/2[t]``.  The model's log-variance of an element is f log beta_t + (1 - f) log beta~_t with f = (v +
+    1) / 2, v the network's variance lane.  float64 from the diffusion's own tables, rounded once.  Pure Python."""
+    betas, _, lv_q = _tables64(gd)
+    T = len(betas)
+    p1, p2 = ([float(v) for v in getattr(gd, n).detach().double().cpu().tolist()]
+              for n in ("posterior_mean_coef1", "posterior_mean_coef2"))
+    first = lv_q[1] if T > 1 else math.log(betas[0])
+    return [(_f32(math.log(betas[t])), _f32(lv_q[t] if t else first), _f32(lv_q[t]), _f32(p1[t]), _f32(p2[t]), 0.0, 0.0, 0.0)
+            for t in range(T)]
 
 
 def vlb_plan(gd, timesteps=None, variance: str = "fixed_small"):
@@ -67,9 +86,15 @@ def vlb_plan(gd, timesteps=None, variance: str = "fixed_small"):
         PRIOR    slots 10 / 11 hold acp_{T-1} and log(1 - acp_{T-1}); KC = 0.5 (-1 - log(1 - acp) + (1 - acp)) and KW = 0.5 acp,
                  so that the KL per element is KC + KW x0^2 (the sum in KC cancels to about acp^2 / 2: float64 here, not float32
                  on the device).
+    ``variance="learned"`` (a learned-variance network only): kind ``KL_LEARNED`` / ``DECODER_LEARNED``, slots 7 - 9 zero and
+    slots 10 / 11 = (log beta_t, log beta~_t) of ``learned_table``; the kernel forms every element's own log-variance from them
+    and the network's variance lane.  The prior row is the same.
     Everything in float64 from the diffusion's tables, rounded once.  Pure Python: no device, no library."""
-    if variance not in VARIANCES:
-        raise ValueError(f"variance must be one of {VARIANCES}, got {variance!r}")
+    learned = variance == "learned"
+    if learned and not getattr(gd.model, "learned_variance", False):
+        raise ValueError("variance='learned' needs a model built with learned_variance=True")
+    if variance not in VARIANCES and not learned:
+        raise ValueError(f"variance must be one of {VARIANCES + ('learned',)}, got {variance!r}")
     T = int(gd.num_timesteps)
     ts = list(reversed(range(T))) if timesteps is None else [int(t) for t in timesteps]
     if any(not 0 <= t < T for t in ts):
@@ -80,11 +105,14 @@ def vlb_plan(gd, timesteps=None, variance: str = "fixed_small"):
     first = lv_q[1] if T > 1 else math.log(betas[0])
     lv_p = [first] + ([lv_q[t] for t in range(1, T)] if variance == "fixed_small" else [math.log(b) for b in betas[1:]])
     hs = sampler._host_schedule(gd)
+    lt = learned_table(gd) if learned else None
     rows = []
     for t in ts:
         A, Bv, R, Rm1 = sampler._head(hs, t)
         head = (A, -Bv, R, Rm1, float(hs["posterior_mean_coef1"][t]), float(hs["posterior_mean_coef2"][t]))
-        if t == 0:
+        if learned:
+            rows.append(head + (float(KL_LEARNED if t else DECODER_LEARNED), 0.0, 0.0, 0.0, lt[t][0], lt[t][1]))
+        elif t == 0:
             rows.append(head + (float(DECODER), 0.0, 0.0, _f32(math.exp(-0.5 * lv_p[0])), _f32(lv_p[0]), _f32(lv_q[0])))
         else:
             d = lv_q[t] - lv_p[t]
@@ -116,7 +144,18 @@ def _launch_term(gd, img, nz, xin, v, clip: bool, out, *, row=None, at: int = 0,
     B, C, H, W = img.shape
     src = (img.data_ptr(), ops._p(nz), 1 if gd.auto_normalize else 0, ops._p(xin), net.in_pitch, net.x_off, ops._p(v),
            _r4(C) if v is None else ops.pitch(v), B, C, H * W, sampler._objective(gd), 1 if clip else 0)
-    if table is not None:
+    if getattr(net, "learned_variance", False) and v is not None:
+        # a network with the variance head: one entry point for both forms and every kind (the kernel reads the kind from the
+        # row; a fixed-variance row is evaluated as ever, from the prediction lanes alone)
+        if table is not None:
+            ops.lib().lgm_vlb_term_learned(*src, *((0.0,) * 6), 0, 0.0, 0.0, table.data_ptr(), VLB_ROW, counter.data_ptr(),
+                                           out.data_ptr(), out.shape[0], 0, 1, ops.stream())
+        elif int(row[6]) in (KL_LEARNED, DECODER_LEARNED):
+            ops.lib().lgm_vlb_term_learned(*src, *row[:6], int(row[6]), row[10], row[11], None, 0, None, out.data_ptr(),
+                                           out.shape[0], at, 0, ops.stream())
+        else:
+            ops.lib().lgm_vlb_term(*src, *_byval(row), out.data_ptr(), out.shape[0], at, ops.stream())
+    elif table is not None:
         ops.lib().lgm_vlb_term_table(*src, table.data_ptr(), VLB_ROW, counter.data_ptr(), out.data_ptr(), out.shape[0], 1,
                                      ops.stream())
     else:

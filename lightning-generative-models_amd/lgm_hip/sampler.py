@@ -30,7 +30,10 @@ the eager ancestral / DDIM step writes x_start into a buffer of its own, for ``p
 previous step's clipped x0 in ``hist``.  A thresholded step first has one workgroup per sample write s = max(1,
 quantile_p(|x0|)) into ``thresh``; the update then takes clamp(x0, -s, s) / s in place of the static clamp.  A class-conditional
 network reads one label per sample, fixed for the run; labels and guidance scale of a captured step live in static buffers.
-An inpainting chain holds the known image (NHWC, pitch r4(C)) and its mask ([B, HW]); its captured step has them, the two
+The ancestral chain of a learned-variance network (``Unet(learned_variance=True)``) weighs the noise of every element with
+exp(0.5 lv), lv interpolated between log beta_t and log beta~_t by the network's variance lanes: the same launch with the two
+logarithms in the row's last slots (``_p_sample_coeffs``), a graph of its own (``_graph_key``); DDIM and DPM-Solver++ read the
+prediction lanes alone.  An inpainting chain holds the known image (NHWC, pitch r4(C)) and its mask ([B, HW]); its captured step has them, the two
 draws of the tail (eps_k, eps_j) and a second table [max_steps, 4] as static buffers, and draws in the fixed order noise,
 eps_k, eps_j, which the eager loop follows.  A chain longer than the tables is replayed in table-sized segments.
 """
@@ -94,10 +97,29 @@ def _head(hs, t: int):
             _f32(hs["sqrt_recip_alphas_cumprod"][t]), _f32(hs["sqrt_recipm1_alphas_cumprod"][t]))
 
 
+def _learned(gd) -> bool:
+    """the diffusion's network has the variance head (``Unet(learned_variance=True)``)"""
+    return bool(getattr(gd.model, "learned_variance", False))
+
+
+def _learned_rows(gd):
+    """the host copy of ``gd.learned_table``: [T][8] = (log beta_t, log beta~_t, lv_q, P1, P2, 0, 0, 0)"""
+    rows = getattr(gd, "_host_learned", None)
+    if rows is None:
+        rows = gd._host_learned = gd.learned_table.detach().cpu().tolist()
+    return rows
+
+
 def _p_sample_coeffs(gd, t: int):
     """(A, Bv, R, Rm1, C0, C1, C2, C3) of one ancestral step (p_sample :748-757): posterior mean + sigma * noise; sigma is
-    zero at t == 0 and nowhere else (the log variance is clipped at log 1e-20)"""
+    zero at t == 0 and nowhere else (the log variance is clipped at log 1e-20).  A learned-variance network: (A, Bv, R, Rm1,
+    P1, P2, log beta_t, log beta~_t) - the update weighs the noise of an element with exp(0.5 lv), lv interpolated between the
+    two by the network's variance lane; log beta~_t = -inf at t == 0, the step without noise."""
     hs = _host_schedule(gd)
+    if _learned(gd):
+        lb, lt = _learned_rows(gd)[t][:2]
+        return _head(hs, t) + (_f32(hs["posterior_mean_coef1"][t]), _f32(hs["posterior_mean_coef2"][t]), lb,
+                               lt if t > 0 else -math.inf)
     sigma = _f32(torch.as_tensor(0.5 * hs["posterior_log_variance_clipped"][t]).exp()) if t > 0 else 0.0
     return _head(hs, t) + (_f32(hs["posterior_mean_coef1"][t]), _f32(hs["posterior_mean_coef2"][t]), 0.0, sigma)
 
@@ -174,12 +196,20 @@ class _Plan:
     irows: Optional[tuple] = None
     kdraws: tuple = ()
     jdraws: tuple = ()
+    learned: bool = False          # the ancestral chain of a learned-variance network: rows as ``_p_sample_coeffs`` says
 
 
 def _plan_ancestral(gd, start: Optional[int] = None, steps: Optional[int] = None) -> _Plan:
     """p_sample_loop :759-780 from step ``start`` - 1 (default T - 1) down to 0, or its first ``steps`` steps"""
     ts = tuple(reversed(range(gd.num_timesteps if start is None else int(start))))[:steps]
-    return _Plan(ts, tuple(_p_sample_coeffs(gd, t) for t in ts), tuple(t > 0 for t in ts), True)
+    _refuse_learned_dyn(gd)
+    return _Plan(ts, tuple(_p_sample_coeffs(gd, t) for t in ts), tuple(t > 0 for t in ts), True, learned=_learned(gd))
+
+
+def _refuse_learned_dyn(gd):
+    if _learned(gd) and _dyn(gd) is not None:
+        raise NotImplementedError("learned variance on the ancestral chain with dynamic_thresholding=True is not built: the "
+                                  "update kernel has no variant for the combination (DDIM and DPM-Solver++ take both)")
 
 
 def _plan_ddim(gd) -> _Plan:
@@ -278,6 +308,9 @@ def _plan_inpaint(gd, jump_length: int = 1, resamples: int = 1, kind: Optional[s
     kind = _sampler_kind(gd) if kind is None else kind
     if kind not in ("ancestral", "ddim", "dpm"):
         raise ValueError(f"unknown sampler kind {kind!r}")
+    if kind == "ancestral" and _learned(gd):
+        raise NotImplementedError("learned variance on the ancestral chain in inpaint() is not built: the update kernel has "
+                                  "no variant for the combination (DDIM and DPM-Solver++ inpaint with such a model)")
     grid = inpaint_grid(gd, kind)
     steps = inpaint_steps(inpaint_walk(len(grid), jump_length, resamples))
     time = lambda l: grid[l] if l >= 0 else -1  # noqa: E731
@@ -321,7 +354,7 @@ def _launch_thresh(net, shape, objective: int, x, v, head, rank, thresh, table=N
 
 
 def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, hist=None, thresh=None, rank=None, row=None,
-                   table=None, counter=None, rederive: bool = False, dpm: bool = False, inpaint=None):
+                   table=None, counter=None, rederive: bool = False, dpm: bool = False, inpaint=None, learned: bool = False):
     """The update of one step: ``x_next`` <- x slice of ``x``, network output ``v``, ``noise`` (None: none).  The row comes by
     value (``row``, eager launches) or from ``table[counter]`` (the captured step, which also advances the counter and passes
     zeros in the by-value slots).  ``rank`` (dynamic thresholding) puts ``_launch_thresh`` in front.  Every update clips x0.
@@ -334,6 +367,8 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
         DPM               no           by value  either            dpm_step: x0 into ``hist`` (and the slice)
         DPM               no           table     either            dpm_step_table
         DPM               yes          either    either            dpm_step_thresh
+        ancestral, learned variance    by value  either            step_learned (x0 into ``x0`` unless self-conditioned)
+        ancestral, learned variance    table     either            step_table_learned, in place
 
     ``inpaint`` = (known, mask, eps_k, eps_j, irow, itable): the inpainting tail in the same launch, its row of 4 by value
     (``irow``) or from ``itable[counter]``; whatever the other columns say the entry is then step_inpaint / dpm_step_inpaint,
@@ -345,7 +380,14 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
     A, Bv, R, Rm1, W0, W1, W2, W3 = row if not tabled else (0.0,) * 8
     red, tab = 1 if rederive else 0, (p(table), p(counter))
     src = (net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v), p(noise))
-    if inpaint is not None:
+    if learned:
+        assert inpaint is None and rank is None and not dpm, "refused where the plan is made"
+        if tabled:
+            L.lgm_sample_step_table_learned(x.data_ptr(), *src, B, C, H * W, *tab, objective, 1, st)
+        else:
+            L.lgm_sample_step_learned(x.data_ptr(), x_next.data_ptr(), *src, None if net.self_condition else p(x0), B, C,
+                                      H * W, objective, A, Bv, R, Rm1, W0, W1, W2, W3, st)
+    elif inpaint is not None:
         known, mask, eps_k, eps_j, irow, itable = inpaint
         if rank is not None:
             _launch_thresh(net, shape, objective, x, v, (A, Bv, R, Rm1), rank, thresh, table, counter)
@@ -434,7 +476,7 @@ class _Chain:
         return tb
 
     def step(self, t: int, noise: Optional[torch.Tensor], row, rederive: bool = False, dpm: bool = False, irow=None,
-             eps_k: Optional[torch.Tensor] = None, eps_j: Optional[torch.Tensor] = None):
+             eps_k: Optional[torch.Tensor] = None, eps_j: Optional[torch.Tensor] = None, learned: bool = False):
         """One eager step at time t from a row of 8; no noise operand where the row weighs it with zero (t == 0 of the
         ancestral chain, eta == 0, the ODE, a last step that returns x0).  Afterwards ``x`` is the new image and ``x0`` the
         clipped x_start: the self-conditioning slice of ``x``, else ``hist`` (DPM-Solver++), else the buffer of its own.
@@ -447,9 +489,10 @@ class _Chain:
         inpaint = None
         if irow is not None:
             inpaint = (self.known, self.mask, eps_k if irow[1] != 0.0 else None, eps_j if irow[3] != 0.0 else None, irow, None)
-        _launch_update(net, self.shape, _objective(self.gd), v, noise if row[7] != 0.0 else None, x=self.x, x_next=self.x_next,
-                       x0=self.x0, hist=self.hist, thresh=self.thresh, rank=self.dyn, row=row, rederive=rederive, dpm=dpm,
-                       inpaint=inpaint)
+        silent = -math.inf if learned else 0.0       # what the row's last slot holds on a step without noise
+        _launch_update(net, self.shape, _objective(self.gd), v, noise if row[7] != silent else None, x=self.x,
+                       x_next=self.x_next, x0=self.x0, hist=self.hist, thresh=self.thresh, rank=self.dyn, row=row,
+                       rederive=rederive, dpm=dpm, inpaint=inpaint, learned=learned)
         if net.self_condition:
             self.x0 = net.sc_slice(self.x_next)
         elif dpm:
@@ -476,7 +519,7 @@ class _GraphedChain:
     """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it."""
 
     def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096, guided: bool = False,
-                 dpm: bool = False, dyn: Optional[float] = None, inpaint: bool = False):
+                 dpm: bool = False, dyn: Optional[float] = None, inpaint: bool = False, learned: bool = False):
         net = gd.model
         objective = _objective(gd)
         self._net = weakref.ref(net)                 # the cache is keyed weakly on the network: no strong reference here
@@ -526,7 +569,7 @@ class _GraphedChain:
                 tail = (self.known, self.mask, ek, ej, None, self.itable)
             # x (and, self-conditioned, the x_start handed on): the slices of the static buffer, in place
             _launch_update(net, shape, objective, v, nz, x=self.x, x_next=self.x, hist=self.hist, thresh=self.thresh, rank=rank,
-                           table=self.table, counter=self.counter, rederive=rederive, dpm=dpm, inpaint=tail)
+                           table=self.table, counter=self.counter, rederive=rederive, dpm=dpm, inpaint=tail, learned=learned)
 
         net.refresh_derived_weights(False)
         rng_state = torch.cuda.get_rng_state(dev)
@@ -599,7 +642,8 @@ class _GraphedChain:
         return self.x
 
 
-def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: bool, inpaint: bool = False):
+def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: bool, inpaint: bool = False,
+               learned: bool = False):
     """The cache key of a captured step under its network: everything baked into the launches that the network does not fix"""
     key = (tuple(shape), bool(with_noise))
     if gd.objective != "pred_v":                     # two diffusions of other objectives may share one network
@@ -612,11 +656,13 @@ def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: b
         key = ("dynthresh", _dyn(gd)) + key
     if inpaint:                                      # the tail's operands and the 4-wide table in the launch
         key = ("inpaint",) + key
+    if learned:                                      # the learned-variance ancestral step: its own update entry and row
+        key = ("learned",) + key
     return key
 
 
 def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bool = False, dpm: bool = False,
-                 inpaint: bool = False):
+                 inpaint: bool = False, learned: bool = False):
     """-> a _GraphedChain for (network, shape, objective), or None (graph replay disabled / capture failed: eager launches).
     ``rederive``: the DDIM chain's re-derived noise, part of the captured launch for pred_noise / pred_x0.
     ``dpm``: the DPM-Solver++ step (its own update kernel and history buffer): a graph of its own.
@@ -626,7 +672,7 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
     net = gd.model
     net.prepare_hip(gd.betas.device)                 # may rebuild the flat storage (model.to(), new parameter storage)
     per_net = _GRAPHS.setdefault(net, {})
-    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint)
+    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint, learned)
     ent = per_net.get(key)
     if isinstance(ent, _GraphedChain) and not ent.matches(net):
         ent = None                                   # captured against buffers the network no longer uses
@@ -638,7 +684,8 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
         ent = None
     if ent is None:
         try:
-            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd), inpaint=inpaint)
+            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd), inpaint=inpaint,
+                                learned=learned)
         except Exception as e:  # capture is an optimisation
             print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",
                   file=sys.stderr, flush=True)
@@ -650,7 +697,8 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
 
 def p_sample_step(chain: _Chain, t: int, noise: Optional[torch.Tensor]):
     """One ancestral step (p_sample :748-757): clip x0, posterior mean + sigma * noise (t > 0)."""
-    chain.step(t, noise, _p_sample_coeffs(chain.gd, t))
+    _refuse_learned_dyn(chain.gd)
+    chain.step(t, noise, _p_sample_coeffs(chain.gd, t), learned=_learned(chain.gd))
 
 
 def ddim_step(chain: _Chain, t: int, t_next: int, noise: Optional[torch.Tensor], eta: float):
@@ -683,7 +731,7 @@ def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, no
     gc = None
     if plan.times and not return_all_timesteps:
         gc = _graph_chain(gd, shape, plan.with_noise, rederive=plan.rederive, guided=chain.cond_scale != 1.0, dpm=plan.dpm,
-                          inpaint=tail)
+                          inpaint=tail, learned=plan.learned)
     if gc is not None and tail:
         chain.x = gc.run(chain.x, plan.times, plan.rows, noises, chain.classes, chain.cond_scale,
                          inpaint=(chain.known, chain.mask, plan.irows))
@@ -705,7 +753,7 @@ def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, no
             nz = None
             if draws:
                 nz = noises[i] if noises is not None else draw()
-            chain.step(t, nz, row, plan.rederive, plan.dpm)
+            chain.step(t, nz, row, plan.rederive, plan.dpm, learned=plan.learned)
         if return_all_timesteps:
             frames.append(chain.image(False))
     if return_all_timesteps:
@@ -718,7 +766,7 @@ def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, no
 def warm_chain(gd, shape, replays: int = 20) -> bool:
     """Capture the ancestral chain's per-step graph for (network, shape) and run ``replays`` steps of it on noise
     (benchmarks: warm-up without paying a whole 1000-step chain).  False when graph replay is unavailable."""
-    if _graph_chain(gd, shape, True) is None:
+    if _graph_chain(gd, shape, True, learned=_learned(gd)) is None:
         return False
     _run(gd, shape, _plan_ancestral(gd, steps=replays))
     return True

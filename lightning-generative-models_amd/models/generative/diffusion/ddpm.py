@@ -295,12 +295,18 @@ class Unet(nn.Module):
         super().__init__()
         if num_classes is not None and int(num_classes) < 1:
             raise ValueError(f"num_classes must be a positive number of classes, got {num_classes!r}")
-        if learned_variance or learned_sinusoidal_cond or random_fourier_features:
+        if learned_sinusoidal_cond or random_fourier_features:
             raise NotImplementedError("HIP UNet covers the configuration the reference DDPM constructs "
-                                      "(ddpm.py:984-987) and self-conditioning: no learned variance / fourier features")
+                                      "(ddpm.py:984-987), self-conditioning and the learned variance: no fourier features")
+        if learned_variance and self_condition:
+            # tests/test_selfcond_host.py pins this refusal; the hybrid loss's estimate pass is not built for the combination
+            raise NotImplementedError("learned_variance together with self_condition is not built")
         if init_dim not in (None, dim):
             raise NotImplementedError("init_dim != dim")
         self.dim, self.channels = dim, channels
+        # learned variance (:417-418): out_dim = 2 C; lanes [0, C) of the NHWC output are the objective's prediction, lanes
+        # [C, 2 C) the interpolation coefficient v of the model's log-variance (Nichol & Dhariwal 2021, eq. 15)
+        self.learned_variance = bool(learned_variance)
         self.self_condition = bool(self_condition)
         self.random_or_learned_sinusoidal_cond = False
         self.theta = float(sinusoidal_pos_emb_theta)
@@ -344,7 +350,7 @@ class Unet(nn.Module):
             att = Attention(co, heads=h, dim_head=dh) if fa else LinearAttention(co, heads=h, dim_head=dh)
             self.ups.append(nn.ModuleList([rb(co + ci, co), rb(co + ci, co), att,
                                            _Up(co, ci) if not last else _PlainConv(co, ci, 3, padding=1)]))
-        self.out_dim = out_dim if out_dim is not None else channels
+        self.out_dim = out_dim if out_dim is not None else channels * (2 if self.learned_variance else 1)
         self.final_res_block = rb(dim * 2, dim)
         self.final_conv = Conv2d(dim, self.out_dim, 1)
         self._flat: Optional[FlatParams] = None
@@ -539,7 +545,9 @@ class Unet(nn.Module):
             if self.num_classes is None:
                 raise ValueError("cond_scale != 1 needs a Unet built with num_classes")
             null, _ = self.forward_nhwc(x, t, False, False, None)
-            ops.cfg_mix(out, null, cond_scale, self.out_dim, scale_dev)
+            # a learned-variance network mixes its prediction lanes alone: the variance of a guided step is the conditional
+            # forward's (lanes [C, 2 C) of ``out`` stay as that forward wrote them)
+            ops.cfg_mix(out, null, cond_scale, self.channels if self.learned_variance else self.out_dim, scale_dev)
         return out
 
     def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True, classes=None):
@@ -880,7 +888,7 @@ class GaussianDiffusion(nn.Module):
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, cond_drop_prob=None,
                  cond_scale=1.0, sampler="auto", dpm_order=2, dpm_stochastic=False, dynamic_thresholding=False,
-                 dynamic_thresholding_percentile=0.995):
+                 dynamic_thresholding_percentile=0.995, vb_loss_weight=None):
         """``cond_drop_prob`` / ``cond_scale`` (extension, class-conditional ``model`` only): the probability with which
         ``forward`` replaces a training label by the null label, and the classifier-free-guidance scale ``sample`` uses.
         ``cond_drop_prob=None`` is 0.1 on a class-conditional model and 0 on any other.
@@ -889,8 +897,21 @@ class GaussianDiffusion(nn.Module):
         multistep, 1 = DDIM at eta 0), ``dpm_stochastic`` its SDE form.
         ``dynamic_thresholding`` (extension; Saharia et al. 2022, 2.3): wherever sampling clips x0 to [-1, 1] it computes
         ``s = max(1, quantile_p(|x0|))`` per sample instead, p = ``dynamic_thresholding_percentile`` in (0, 1], and takes
-        ``clamp(x0, -s, s) / s``.  Training is untouched."""
+        ``clamp(x0, -s, s) / s``.  Training is untouched.
+        ``vb_loss_weight`` (extension; Nichol & Dhariwal 2021, L_hybrid; a ``Unet(learned_variance=True)`` only, ``None`` =
+        0.001 there): the model trains on mean_b(loss_weight[t_b] mse_b) + vb_loss_weight mean_b(vb_b), vb_b the bound's term at
+        t_b in bits per dimension with the model mean detached; the ancestral chain samples with the learned variance and
+        ``vlb_terms(variance="learned")`` evaluates the bound with it.  DDIM and DPM-Solver++ read no model variance."""
         super().__init__()
+        self.learned_variance = bool(getattr(model, "learned_variance", False))
+        if vb_loss_weight is not None and not self.learned_variance:
+            raise ValueError("vb_loss_weight needs a model built with learned_variance=True")
+        if self.learned_variance and model.out_dim != 2 * model.channels:
+            raise ValueError(f"a learned-variance model has out_dim = 2 * channels, got {model.out_dim}")
+        vb_loss_weight = 0.001 if vb_loss_weight is None else float(vb_loss_weight)
+        if not vb_loss_weight >= 0.0:
+            raise ValueError(f"vb_loss_weight must not be negative, got {vb_loss_weight!r}")
+        self.vb_loss_weight = vb_loss_weight
         p = dynamic_thresholding_percentile
         if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
             raise ValueError(f"dynamic_thresholding_percentile must lie in (0, 1], got {p!r}")
@@ -950,6 +971,11 @@ class GaussianDiffusion(nn.Module):
         reg("posterior_mean_coef2", (1.0 - ac_prev) * torch.sqrt(alphas) / (1.0 - ac))
         reg("loss_weight", {"pred_noise": clipped / snr, "pred_x0": clipped, "pred_v": clipped / (snr + 1)}[objective])
         self.auto_normalize = auto_normalize
+        if self.learned_variance:
+            # the per-t scalars of the hybrid loss, [T, 8] = (log beta_t, log beta~_t, lv_q, P1, P2, 0, 0, 0): float64 from the
+            # tables above, rounded once (lgm_hip.likelihood.learned_table); not part of any state dict
+            from lgm_hip.likelihood import learned_table
+            self.register_buffer("learned_table", torch.tensor(learned_table(self), dtype=torch.float32), persistent=False)
 
     @property
     def device(self):
@@ -1091,6 +1117,8 @@ class GaussianDiffusion(nn.Module):
         else:
             self.model._anchor(x.device)
             v = self.model.run_nchw(x.detach().float(), t.to(x.device), False, x_self_cond, classes, cond_scale)[0]
+        if self.learned_variance:                    # the prediction channels; model_predictions uses no model variance
+            v = v[:, :self.channels].contiguous()
         x = x.detach().float().contiguous()
         B = x.shape[0]
         t = t.to(device=x.device, dtype=torch.long).contiguous()
@@ -1200,7 +1228,8 @@ class GaussianDiffusion(nn.Module):
         prior_bpd`` [B] when all T timesteps were evaluated, else None.  float64 on the host.
         ``img``: [B, C, H, W] in the data range, normalised as ``forward`` normalises.  ``timesteps``: None = T - 1 ... 0, else
         distinct ints in [0, T) in the order to evaluate.  ``noise``: one NCHW draw per evaluated timestep (parity tests).
-        ``variance``: ``"fixed_small"`` (beta~_t) or ``"fixed_large"`` (beta_t), see ``lgm_hip.likelihood``.
+        ``variance``: ``"fixed_small"`` (beta~_t) or ``"fixed_large"`` (beta_t), see ``lgm_hip.likelihood``; ``"learned"`` (a
+        learned-variance model only): the element's own log-variance from the network's variance lanes.
         One forward per timestep, graph-replayed like sampling.  A self-conditioned network is evaluated with a zero
         self-conditioning input at every timestep: that is a Markov model of its own and therefore a valid bound (of that
         model, not of the sampler that feeds x_start forward).  A class-conditional network: ``classes=None`` is the null
@@ -1244,7 +1273,7 @@ def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, sa
             ops.nchw_to_nhwc(self_cond.detach().float().contiguous(), gd.model.sc_slice(xt))
         elif self_cond:
             hip_loss_estimate(gd, xt, t, classes)
-    return hip_loss_network(gd, xt, target, img, t, noise, offset, save, classes)
+    return hip_loss_network(gd, xt, target, img, t, noise, offset, save, classes, normalize)
 
 
 def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None):
@@ -1283,16 +1312,35 @@ def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, of
     return xt, target, img, noise, t, offset
 
 
-def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None):
-    """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx)."""
+def _hybrid_operands(gd: "GaussianDiffusion", out, target, img, normalize: bool, xt, t):
+    """what lgm_hybrid_loss_fwd and lgm_hybrid_loss_bwd share, in their order, up to ``objective``"""
+    net = gd.model
+    return (out.data_ptr(), ops.pitch(out), target.data_ptr(), ops.pitch(target), img.data_ptr(), 1 if normalize else 0,
+            xt.data_ptr(), net.in_pitch, net.x_off, t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
+            gd.sqrt_one_minus_alphas_cumprod.data_ptr(), gd.sqrt_recip_alphas_cumprod.data_ptr(),
+            gd.sqrt_recipm1_alphas_cumprod.data_ptr(), gd.loss_weight.data_ptr(), gd.learned_table.data_ptr(),
+            gd.num_timesteps, OBJECTIVES[gd.objective], float(gd.vb_loss_weight))
+
+
+def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None, normalize=None):
+    """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx).  A learned-variance network: the hybrid
+    loss instead (lgm_hybrid_loss_fwd: the same MSE over the prediction lanes + vb_loss_weight times the bound's term), ``ctx``
+    then ends with the per-sample terms [2, B] = (loss_weight mse_b, vb_b), x_t and ``normalize`` - whether ``img`` is still
+    in the data range (``None``: the diffusion's auto_normalize, what the graph-replayed step hands its q_sample)."""
     net = gd.model
     B, C, H, W = img.shape
     Cp = _r4(C)
     L = ops.lib()
     st = ops.stream()
     out, tape = net.forward_nhwc(xt, t, save, True, classes)
-    per = ops.new((B,), img)
     loss = ops.new((1,), img)
+    if getattr(net, "learned_variance", False):
+        normalize = bool(gd.auto_normalize if normalize is None else normalize)
+        per = ops.new((2, B), img)
+        L.lgm_hybrid_loss_fwd(*_hybrid_operands(gd, out, target, img, normalize, xt, t), B, C, H * W, per.data_ptr(),
+                              loss.data_ptr(), st)
+        return loss, (gd, tape, out, target, t, (B, C, H, W), img, noise, offset, per, xt, normalize)
+    per = ops.new((B,), img)
     L.lgm_weighted_mse_fwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
                            B, C, H * W, Cp, per.data_ptr(), loss.data_ptr(), st)
     return loss, (gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
@@ -1305,6 +1353,13 @@ def hip_loss_backward_begin(ctx, gl):
         raise RuntimeError("p_losses forward ran without saving activations")
     Cp = _r4(C)
     gout = ops.new(out.shape, out)
+    if getattr(gd.model, "learned_variance", False):
+        img, xt, normalize = ctx[6], ctx[10], ctx[11]
+        ops.lib().lgm_hybrid_loss_bwd(*_hybrid_operands(gd, out, target, img, normalize, xt, t), gl.data_ptr(), B, C, H * W,
+                                      gout.data_ptr(), ops.stream())
+        st = gd.model.backward_begin(tape, gout)
+        st.head += (out, target, img, xt)
+        return st
     ops.lib().lgm_weighted_mse_bwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(),
                                    gd.loss_weight.data_ptr(), gl.data_ptr(), B, C, H * W, Cp,
                                    gout.data_ptr(), ops.stream())
@@ -1341,19 +1396,25 @@ class DDPM(LightningModule):
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
                  min_snr_gamma: float = 5, self_condition: bool = False, num_classes: Optional[int] = None,
                  cond_drop_prob: float = 0.1, dynamic_thresholding: bool = False,
-                 dynamic_thresholding_percentile: float = 0.995, cond_scale: float = 1.0, sampler: str = "auto",
+                 dynamic_thresholding_percentile: float = 0.995, learned_variance: bool = False,
+                 vb_loss_weight: float = 0.001, cond_scale: float = 1.0, sampler: str = "auto",
                  dpm_order: int = 2, dpm_stochastic: bool = False):
         """``num_classes`` (extension): class-conditional training on the batches' labels with classifier-free guidance;
         ``cond_drop_prob`` / ``cond_scale`` are read with it only.  ``sampler`` / ``dpm_order`` / ``dpm_stochastic``
         (extension): ``"dpm++"`` samples with DPM-Solver++ in ``sampling_timesteps`` steps (GaussianDiffusion).
         ``dynamic_thresholding`` / ``dynamic_thresholding_percentile`` (extension): the samplers threshold x0 per sample
-        instead of clamping it to [-1, 1] (GaussianDiffusion).  They stand in front of ``cond_scale``: the tail of this
+        instead of clamping it to [-1, 1] (GaussianDiffusion).  ``learned_variance`` / ``vb_loss_weight`` (extension): the
+        network gets the variance head and trains on the hybrid loss (GaussianDiffusion); ``vb_loss_weight`` is read with it
+        only.  They stand in front of ``cond_scale``: the tail of this
         signature is pinned by tests/test_dpmpp_host.py; pass everything from ``num_classes`` on by keyword."""
         super().__init__()
         self.save_hyperparameters()
         self.num_classes = num_classes
-        model = Unet(dim=dim, channels=img_channels, self_condition=self_condition, num_classes=num_classes)
+        model = Unet(dim=dim, channels=img_channels, self_condition=self_condition, num_classes=num_classes,
+                     **(dict(learned_variance=True) if learned_variance else {}))
         cond = dict(cond_drop_prob=cond_drop_prob, cond_scale=cond_scale) if num_classes is not None else {}
+        if learned_variance:
+            cond["vb_loss_weight"] = vb_loss_weight
         diffusion_model = GaussianDiffusion(model, img_size=img_size, timesteps=diffusion_timesteps,
                                             sampling_timesteps=sampling_timesteps, objective=objective,
                                             beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
@@ -1414,6 +1475,8 @@ class DDPM(LightningModule):
     def bits_per_dim(self, img, classes=None, **kw):
         """``GaussianDiffusion.nll_bpd`` of the diffusion ``_log_sample`` samples from (the EMA weights): [B] bits per dimension"""
         self.ema.ema_model.eval()
+        if self.ema.ema_model.learned_variance:      # the variance the model was trained to predict, unless the caller says
+            kw.setdefault("variance", "learned")
         return self.ema.ema_model.nll_bpd(img, classes=classes, **kw)
 
     def training_step(self, batch):
