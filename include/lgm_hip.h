@@ -53,7 +53,7 @@ extern "C" {
                              *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh,
                              *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint, lgm_vlb_term, lgm_vlb_term_table,
                              *  lgm_grad_sqnorm_*, lgm_grad_clip_scale, lgm_adam_step_scaled, lgm_grad_accumulate, lgm_hybrid_loss_fwd,
-                             *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned
+                             *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned, lgm_gn_plan
                              *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -62,7 +62,8 @@ extern "C" {
 int lgm_abi_version(void);
 const char* lgm_last_error(void);
 /* diagnostic: name (as rocprofv3 prints it, without the argument list) of the primary kernel launched by the calling
- * thread's last convolution-family call (lgm_conv_xy / _yx / _wgrad / lgm_conv3x3_wino) */
+ * thread's last convolution-family call (lgm_conv_xy / _yx / _wgrad / lgm_conv3x3_wino) or norm call (lgm_gn_* name the
+ * statistics / one-pass kernel of their plan, lgm_rmsnorm_* their instantiation) */
 const char* lgm_last_kernel(void);
 /* diagnostic: every name lgm_last_kernel() can ever return (one entry per site in the library that notes a name, in link
  * order; duplicates possible).  Each is a prefix of the demangled name of a kernel in liblgm_hip.so - checked on the CPU by
@@ -213,6 +214,10 @@ int lgm_gn_fwd(const float* x, int64_t x_pitch, int B, int HW, int C, int G, flo
 int64_t lgm_gn_planes_supported(int B, int HW, int C, int G);
 /* 1 when lgm_gn_fwd runs its one-pass kernel for this shape (the slices fit a block's registers), 0: two passes over x */
 int64_t lgm_gn_fwd_fused_supported(int B, int HW, int C, int G);
+/* diagnostic (host only, no launch): the launch plan of lgm_gn_fwd (bwd = 0) / lgm_gn_bwd (bwd = 1) for this shape: cb
+ * channels per block, nt threads per block and nv 16-byte values per thread of the one-pass kernel; nv = 0: the two-pass
+ * kernels run, at nt threads.  tests/test_hip_norm_ledger.py checks every row's route against it. */
+int lgm_gn_plan(int B, int HW, int C, int G, int bwd, int* cb, int* nt, int* nv);
 int lgm_gn_fwd_planes(const float* planes, int64_t plane_stride, int splits, const float* conv_bias, float* x,
                       int64_t x_pitch, int B, int HW, int C, int G, float eps, const float* gamma,
                       const float* beta, const float* ss, int64_t ss_pitch, int act, const float* res,

@@ -785,7 +785,17 @@ int gn_check(int B, int HW, int C, int G) {
 struct GnPlan {
   int cb, nt, nv;
 };
-static GnPlan gn_plan_cb(int HW, int cb, bool bwd) {
+// The (nt, nv) pairs of the one-pass kernels: the instantiations the launchers switch over.  nt = 1024 is tried only for
+// HW * cb >= 16384, i.e. nv = HW * cb / 4096 >= 4.  A plan with an even nv at nt threads is also a plan with nv / 2 at 2 nt
+// threads, and that candidate comes first: 128 and 64 threads are reached with nv = 1 only, and nv = 16 at 256 threads
+// (HW * cb = 16384) never, since 1024 threads take that size with nv = 4.  tests/test_hip_norm_ledger.py sweeps lgm_gn_plan
+// and fails when a pair of this list is never returned.
+static bool gn_fused_pair(int nt, int nv) {
+  return (nt == 1024 && (nv == 4 || nv == 8)) || (nt == 256 && (nv == 1 || nv == 2 || nv == 4 || nv == 8)) ||
+         ((nt == 128 || nt == 64) && nv == 1);
+}
+
+static GnPlan gn_plan_cb(int HW, int cb) {
   GnPlan p;
   p.cb = cb;
   p.nt = (long)HW * cb >= 16384 ? 1024 : 256;
@@ -801,7 +811,7 @@ static GnPlan gn_plan_cb(int HW, int cb, bool bwd) {
     const int ppb = nt / tq;
     if (HW % ppb) continue;
     const int nv = HW / ppb;
-    if (nv == 1 || nv == 2 || nv == 4 || nv == 8 || (!bwd && nv == 16 && nt == 256)) {
+    if (gn_fused_pair(nt, nv)) {
       p.nt = nt;
       p.nv = nv;
       return p;
@@ -821,11 +831,21 @@ static GnPlan gn_plan(int B, int HW, int C, int G, bool bwd) {
   static const long want = getenv("LGM_GN_BLOCKS") ? atol(getenv("LGM_GN_BLOCKS")) : 256;
   if (!wide_only)
     while ((long)B * (C / cb) < want && cb > Cg && cb / 2 >= min_cb && (cb / 2) % Cg == 0 && (cb / 2) % 4 == 0) cb /= 2;
-  GnPlan p = gn_plan_cb(HW, cb, bwd);
+  GnPlan p = gn_plan_cb(HW, cb);   // (forward and backward share the plan: `bwd` is kept for the callers)
   // (Large maps - 64 x 64 at 64 channels: 4096 pixels x 32 channels do not fit a block's registers - stay on the two-pass
   // kernels.  Narrowing the block to ONE group so that its slice fits was tried: one pass over x instead of two, but
   // 32-byte rows per pixel; the 64 x 64 DDPM step went from 3,170 to 3,060 images/s.)
   return p;
+}
+
+extern "C" int lgm_gn_plan(int B, int HW, int C, int G, int bwd, int* cb, int* nt, int* nv) {
+  if (int rc = gn_check(B, HW, C, G)) return rc;
+  LGM_REQUIRE(cb && nt && nv, "gn_plan: null pointer");
+  const GnPlan p = gn_plan(B, HW, C, G, bwd != 0);
+  *cb = p.cb;
+  *nt = p.nt;
+  *nv = p.nv;
+  return LGM_OK;
 }
 
 // 1 when the forward runs the one-pass (register-resident) kernel for this shape, 0 when it needs two passes over x
@@ -857,26 +877,25 @@ static int gn_fwd_impl(const float* x, int64_t x_pitch, int B, int HW, int C, in
   static const bool small_only = getenv("LGM_GN_256") != nullptr;   // A/B switch
   if (pln.nv > 0) {   // one-pass kernel: the block's slice fits its registers (NV 16-byte values per thread)
     const int nt = pln.nt, nv = pln.nv;
-#define GN_FUSED(NTV, NVV)                                                                                            \
-  hipLaunchKernelGGL((gn_fused_fwd_kernel<NTV, NVV>), dim3(B * (C / cb)), dim3(NTV), 0, s, x, (long)x_pitch, HW, C, G, \
-                     cb, eps, gamma, beta, ss, (long)ss_pitch, act, res, (long)res_pitch, y, (long)y_pitch, mean,    \
-                     rstd, coefA, coefB, planes, pstride, splits, cbias, (float*)x)
-#define GN_FUSED_NV(NTV)                                                                       \
-  do {                                                                                         \
-    if (nv == 1) GN_FUSED(NTV, 1); else if (nv == 2) GN_FUSED(NTV, 2); else if (nv == 4) GN_FUSED(NTV, 4); \
-    else GN_FUSED(NTV, 8);                                                                     \
+#define GN_FUSED(NTV, NVV)                                                                                                \
+  do {                                                                                                                  \
+    hipLaunchKernelGGL((gn_fused_fwd_kernel<NTV, NVV>), dim3(B * (C / cb)), dim3(NTV), 0, s, x, (long)x_pitch, HW, C, G, \
+                       cb, eps, gamma, beta, ss, (long)ss_pitch, act, res, (long)res_pitch, y, (long)y_pitch, mean,    \
+                       rstd, coefA, coefB, planes, pstride, splits, cbias, (float*)x);                                  \
+    lgm_note_kernel(LGM_KNAME("gn_fused_fwd_kernel<" #NTV ", " #NVV ">"));                                              \
   } while (0)
-    if (nt == 1024) GN_FUSED_NV(1024);
-    else if (nt == 256) { if (nv == 16) GN_FUSED(256, 16); else GN_FUSED_NV(256); }
-    else if (nt == 128) GN_FUSED_NV(128);
-    else GN_FUSED_NV(64);
-#undef GN_FUSED_NV
+    // the pairs of gn_fused_pair, which is all gn_plan returns
+    if (nt == 1024) { if (nv == 4) GN_FUSED(1024, 4); else GN_FUSED(1024, 8); }
+    else if (nt == 256) { if (nv == 1) GN_FUSED(256, 1); else if (nv == 2) GN_FUSED(256, 2); else if (nv == 4) GN_FUSED(256, 4); else GN_FUSED(256, 8); }
+    else if (nt == 128) GN_FUSED(128, 1);
+    else GN_FUSED(64, 1);
 #undef GN_FUSED
     LGM_LAUNCH_CHECK();
     return LGM_OK;
   }
   LGM_REQUIRE(!planes, "gn_fwd_planes: this shape has no one-pass kernel (ask lgm_gn_planes_supported first)");
-  if (!small_only && (long)HW * cb >= 16384)
+  const bool wide = !small_only && (long)HW * cb >= 16384;
+  if (wide)
     hipLaunchKernelGGL(gn_stats_kernel<1024>, dim3(B * (C / cb)), dim3(1024), 0, s, x, (long)x_pitch, HW, C, G, cb, eps,
                        gamma, beta, ss, (long)ss_pitch, mean, rstd, coefA, coefB);
   else
@@ -885,6 +904,7 @@ static int gn_fwd_impl(const float* x, int64_t x_pitch, int B, int HW, int C, in
   const long npix = (long)B * HW;
   hipLaunchKernelGGL(gn_apply_kernel, dim3(lgm_cdiv(npix * (C / 4), 256)), dim3(256), 0, s, x, (long)x_pitch, coefA,
                      coefB, res, (long)res_pitch, y, (long)y_pitch, npix, HW, C, act);
+  lgm_note_kernel(wide ? LGM_KNAME("gn_stats_kernel<1024>") : LGM_KNAME("gn_stats_kernel<256>"));
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1008,6 +1028,7 @@ extern "C" int lgm_gn_fwd_stats(const float* stats, int parts_per_image, const f
   const long npix = (long)B * HW;
   hipLaunchKernelGGL(gn_apply_kernel, dim3(lgm_cdiv(npix * (C / 4), 256)), dim3(256), 0, s, x, (long)x_pitch, coefA, coefB,
                      res, (long)res_pitch, y, (long)y_pitch, npix, HW, C, act);
+  lgm_note_kernel(LGM_KNAME("gn_coef_from_stats_kernel"));
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1058,21 +1079,18 @@ static int gn_bwd_impl(const float* x, int64_t x_pitch, const float* gy, int64_t
   {   // one-pass kernel when the block's x and gy slices fit its registers
     const int nt = pln.nt, nv = pln.nv;
     if (nv > 0) {
-#define GN_FUSED(NTV, NVV)                                                                                             \
-  hipLaunchKernelGGL((gn_fused_bwd_kernel<NTV, NVV>), dim3(B * (C / cb)), dim3(NTV), 0, s, x, (long)x_pitch, gy,        \
-                     (long)gy_pitch, coefA, coefB, mean, rstd, HW, C, G, cb, act, gamma, beta, ss, (long)ss_pitch, gss, \
-                     (long)gss_pitch, gss_beta, S1, S2, gx, (long)gx_pitch, accumulate_gx, rows, planes, pstride, splits, \
-                     add_out, add_pitch)
-#define GN_FUSED_NV(NTV)                                                                       \
-  do {                                                                                         \
-    if (nv == 1) GN_FUSED(NTV, 1); else if (nv == 2) GN_FUSED(NTV, 2); else if (nv == 4) GN_FUSED(NTV, 4); \
-    else GN_FUSED(NTV, 8);                                                                     \
+#define GN_FUSED(NTV, NVV)                                                                                                  \
+  do {                                                                                                                    \
+    hipLaunchKernelGGL((gn_fused_bwd_kernel<NTV, NVV>), dim3(B * (C / cb)), dim3(NTV), 0, s, x, (long)x_pitch, gy,        \
+                       (long)gy_pitch, coefA, coefB, mean, rstd, HW, C, G, cb, act, gamma, beta, ss, (long)ss_pitch, gss, \
+                       (long)gss_pitch, gss_beta, S1, S2, gx, (long)gx_pitch, accumulate_gx, rows, planes, pstride,      \
+                       splits, add_out, add_pitch);                                                                       \
+    lgm_note_kernel(LGM_KNAME("gn_fused_bwd_kernel<" #NTV ", " #NVV ">"));                                                \
   } while (0)
-      if (nt == 1024) GN_FUSED_NV(1024);
-      else if (nt == 256) GN_FUSED_NV(256);
-      else if (nt == 128) GN_FUSED_NV(128);
-      else GN_FUSED_NV(64);
-#undef GN_FUSED_NV
+      if (nt == 1024) { if (nv == 4) GN_FUSED(1024, 4); else GN_FUSED(1024, 8); }
+      else if (nt == 256) { if (nv == 1) GN_FUSED(256, 1); else if (nv == 2) GN_FUSED(256, 2); else if (nv == 4) GN_FUSED(256, 4); else GN_FUSED(256, 8); }
+      else if (nt == 128) GN_FUSED(128, 1);
+      else GN_FUSED(64, 1);
 #undef GN_FUSED
       if (rows && desc) {   // the caller sums the per-image rows of many layers with ONE lgm_wgrad_reduce_batch launch
         union { float f; int64_t i; } bb;
@@ -1089,7 +1107,8 @@ static int gn_bwd_impl(const float* x, int64_t x_pitch, const float* gy, int64_t
     }
   }
   LGM_REQUIRE(!planes, "gn_bwd_planes: this shape has no one-pass kernel (ask lgm_gn_planes_supported first)");
-  if (!small_only && (long)HW * cb >= 16384)
+  const bool wide = !small_only && (long)HW * cb >= 16384;
+  if (wide)
     hipLaunchKernelGGL(gn_bwd_reduce_kernel<1024>, dim3(B * (C / cb)), dim3(1024), 0, s, x, (long)x_pitch, gy,
                        (long)gy_pitch, coefA, coefB, mean, rstd, HW, C, G, cb, act, gamma, beta, ss, (long)ss_pitch, gss,
                        (long)gss_pitch, gss_beta, S1, S2, P, Qc, Rc);
@@ -1103,6 +1122,7 @@ static int gn_bwd_impl(const float* x, int64_t x_pitch, const float* gy, int64_t
                      (long)gy_pitch, coefA, coefB, P, Qc, Rc, gx, (long)gx_pitch, npix, HW, C, act, accumulate_gx,
                      apply_blocks, (const float*)S1, (const float*)S2, ss, (long)ss_pitch, B, ggamma, gbeta,
                      affine_beta, add_out, add_pitch);
+  lgm_note_kernel(wide ? LGM_KNAME("gn_bwd_reduce_kernel<1024>") : LGM_KNAME("gn_bwd_reduce_kernel<256>"));
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1307,6 +1327,7 @@ extern "C" int lgm_rmsnorm_fwd(const float* x, int64_t x_pitch, const float* g, 
                      (long)y_pitch, (long)npix, C, L)
   if (Q == 1) RMS_FWD(1); else if (Q == 2) RMS_FWD(2); else RMS_FWD(4);
 #undef RMS_FWD
+  lgm_note_kernel(Q == 1 ? LGM_KNAME("rmsnorm_fwd_kernel<1>") : Q == 2 ? LGM_KNAME("rmsnorm_fwd_kernel<2>") : LGM_KNAME("rmsnorm_fwd_kernel<4>"));
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1335,15 +1356,19 @@ static int rmsnorm_bwd_impl(const float* x, int64_t x_pitch, const float* gy, in
   if (Q == 1) RMS_BWD(1); else if (Q == 2) RMS_BWD(2); else RMS_BWD(4);
 #undef RMS_BWD
   LGM_LAUNCH_CHECK();
+  const char* kname = Q == 1 ? LGM_KNAME("rmsnorm_bwd_kernel<1>") : Q == 2 ? LGM_KNAME("rmsnorm_bwd_kernel<2>") : LGM_KNAME("rmsnorm_bwd_kernel<4>");
   if (desc) {   // deferred: the per-block partial rows are summed later by lgm_wgrad_reduce_batch (rows = "splits")
     union { float f; int64_t i; } bb;
     bb.i = 0;
     bb.f = gg_beta;
     desc[0] = (int64_t)(uintptr_t)partial; desc[1] = C; desc[2] = (int64_t)(uintptr_t)gg; desc[3] = C;
     desc[4] = 0; desc[5] = 0; desc[6] = nb; desc[7] = bb.i;
+    lgm_note_kernel(kname);
     return LGM_OK;
   }
-  return lgm_colsum(partial, C, nb, C, gg, gg_beta, partial + (long)nb * C, stream);
+  const int rc = lgm_colsum(partial, C, nb, C, gg, gg_beta, partial + (long)nb * C, stream);
+  lgm_note_kernel(kname);       // after the column sum: the name of the call is the RMSNorm kernel's
+  return rc;
 }
 
 extern "C" int lgm_rmsnorm_bwd(const float* x, int64_t x_pitch, const float* gy, int64_t gy_pitch,

@@ -57,6 +57,13 @@ ELSEWHERE = {
     "cfg_mix_kernel": "tests/test_hip_classcond.py",
     "label_emb_fwd_kernel": "tests/test_hip_classcond.py",
     "label_emb_wgrad_kernel": "tests/test_hip_classcond.py",
+    "gn_fused_fwd_kernel": "tests/test_hip_norm_ledger.py",
+    "gn_fused_bwd_kernel": "tests/test_hip_norm_ledger.py",
+    "gn_stats_kernel": "tests/test_hip_norm_ledger.py",
+    "gn_bwd_reduce_kernel": "tests/test_hip_norm_ledger.py",
+    "gn_coef_from_stats_kernel": "tests/test_hip_norm_ledger.py",
+    "rmsnorm_fwd_kernel": "tests/test_hip_norm_ledger.py",
+    "rmsnorm_bwd_kernel": "tests/test_hip_norm_ledger.py",
 }
 
 def R(name, entry, geom, why, env=None, **opts):

@@ -292,8 +292,9 @@ def test_grouped_1x1_weight_gradients(dev, layers):
 
 
 @pytest.mark.parametrize("shape", [(3, 64, 16, 16, 8), (2, 128, 8, 8, 8), (2, 512, 4, 4, 8), (2, 16, 8, 8, 8), (5, 256, 4, 4, 8),
-                                   (2, 64, 32, 32, 8),     # one-pass kernels, 1024-thread blocks
-                                   (1, 64, 64, 64, 8)])    # slice too large for the registers: two-pass kernels
+                                   (2, 64, 32, 32, 8),     # blocks narrowed to one group (cb = 8): one-pass kernels <256, 8>
+                                   (1, 64, 64, 64, 8)])    # cb = 8, 4096 pixels: one-pass kernels <1024, 8> (which kernel runs is
+                                                           # asserted in tests/test_hip_norm_ledger.py, the two-pass ones included)
 @pytest.mark.parametrize("film", [True, False])
 def test_groupnorm_film_silu(dev, shape, film):
     from lgm_hip import ops
