@@ -53,7 +53,8 @@ extern "C" {
                              *  lgm_dyn_thresh, lgm_sample_step_thresh, lgm_dpm_step_thresh, lgm_model_predictions_thresh,
                              *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint, lgm_vlb_term, lgm_vlb_term_table,
                              *  lgm_grad_sqnorm_*, lgm_grad_clip_scale, lgm_adam_step_scaled, lgm_grad_accumulate, lgm_hybrid_loss_fwd,
-                             *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned, lgm_gn_plan
+                             *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned, lgm_gn_plan,
+                             *  lgm_tsampler_draw, lgm_tsampler_update, lgm_weighted_mse_fwd_iw / _bwd_iw, lgm_hybrid_loss_fwd_iw / _bwd_iw
                              *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -696,6 +697,45 @@ int lgm_vlb_term_learned(const float* img, const float* noise, int normalize, co
                          float R, float Rm1, float P1, float P2, int kind, float log_beta, float log_tilde,
                          const float* table, int stride, const int32_t* counter, float* out, int n_rows, int out_row,
                          int advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Timestep samplers of the training step (GaussianDiffusion(t_sampler=...); Nichol & Dhariwal 2021, 3.3 and Kingma et al. 2021,
+ * VDM App. I.1).  State of the loss-aware sampler: history [T][H] float32 (per timestep its last H per-sample losses, oldest
+ * first), counts [T] int32 (entries held, at most H).  The PLAN the next draw reads: cdf [T], iw [T] float32.
+ * lgm_tsampler_draw: t_out [B] int64.  mode 0 (stratified): u [1], u_b = u[0] + (float) b / (float) B (a division, then an add),
+ *   minus 1 where that is >= 1, t_b = min(T - 1, floor((float) T u_b)); cdf is not read.  mode 1 (cdf): u [B], t_b = the first index
+ *   with cdf[t] > u_b by binary search, T - 1 where there is none.  Launches tsampler_draw_kernel.
+ * lgm_tsampler_update: ONE launch of ONE workgroup (tsampler_update_kernel), no atomics.  Phase one: L_b = per[b] (n_terms 1) or
+ *   per[b] + vb_weight * per[B + b] (n_terms 2; product and sum rounded separately) is appended to row t_b in batch order; a row
+ *   keeps its last H entries, counts[t] = min(H, counts[t] + 1); a non-finite L_b or a t_b outside [0, T) is not recorded.  The
+ *   batch is staged in LDS 1024 samples at a time, every thread scans it for the rows it owns (t mod 1024): no two writers per
+ *   row.  Phase two, from the updated state: warm = every counts[t] == H; w_t = sqrt(mean_h history[t][h]^2); not warm, or
+ *   sum(w) zero or not finite: p_t = 1 / T and iw_t = 1.0f exactly; else p_t = (1 - q) w_t / sum(w) + q / T, iw_t = 1 / (T p_t).
+ *   cdf = inclusive prefix sum of p in a fixed two-level sequential order (never decreasing), clamped to 1, cdf[T - 1] = 1.0f.
+ *   Every sum is float32 in a fixed association: replays, eager launches and every CU margin give the same bits.  B == 0 (t and
+ *   per may be NULL) rebuilds the plan only.  cdf must not alias any other operand.  T <= 2^20.
+ * The loss under the plan, mean_b(iw[t_b] L_b): the *_iw forms launch the per-sample kernels of their plain forms unchanged (per
+ *   holds the UNWEIGHTED terms), then iw_mean_kernel, which also writes wb [B] = iw[t_b] (t clamped to [0, n_table)) for the
+ *   backward; the *_bwd_iw forms are the plain launches with every element of sample b multiplied by wb[b] at the end.  With
+ *   iw = 1 the loss and the gradient are the plain forms' bit for bit. */
+int lgm_tsampler_draw(const float* u, const float* cdf, int T, int mode, int64_t* t_out, int B, void* stream);
+int lgm_tsampler_update(const int64_t* t, const float* per, int n_terms, float vb_weight, float* history, int32_t* counts,
+                        int H, float q, int T, int B, float* cdf, float* iw, void* stream);
+int lgm_weighted_mse_fwd_iw(const float* out, const float* target, int64_t pitch, const int64_t* t, const float* loss_weight,
+                            const float* iw, int n_table, int B, int C, int HW, int Cpad, float* per_sample, float* wb,
+                            float* loss, void* stream);
+int lgm_weighted_mse_bwd_iw(const float* out, const float* target, int64_t pitch, const int64_t* t, const float* loss_weight,
+                            const float* wb, const float* gloss, int B, int C, int HW, int Cpad, float* gout, void* stream);
+int lgm_hybrid_loss_fwd_iw(const float* out, int64_t pitch, const float* target, int64_t target_pitch, const float* img,
+                           int normalize, const float* xin, int64_t x_pitch, int x_off, const int64_t* t,
+                           const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                           const float* loss_weight, const float* tab, int n_table, int objective, float vb_weight,
+                           const float* iw, int B, int C, int HW, float* per, float* wb, float* loss, void* stream);
+int lgm_hybrid_loss_bwd_iw(const float* out, int64_t pitch, const float* target, int64_t target_pitch, const float* img,
+                           int normalize, const float* xin, int64_t x_pitch, int x_off, const int64_t* t,
+                           const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip, const float* sqrt_recipm1,
+                           const float* loss_weight, const float* tab, int n_table, int objective, float vb_weight,
+                           const float* wb, const float* gloss, int B, int C, int HW, float* gout, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-fused Winograd engine (csrc/winograd_eng.hip): input transform launch -> ONE batched weight-stationary fp32 MFMA GEMM

@@ -446,7 +446,8 @@ __global__ void mean_kernel(const float* __restrict__ v, int n, float* __restric
 __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ out, const float* __restrict__ target,
                                                       long pitch, const int64_t* __restrict__ t,
                                                       const float* __restrict__ lw, const float* __restrict__ gloss,
-                                                      int B, int C, int HW, int Cpad, float* __restrict__ gout) {
+                                                      int B, int C, int HW, int Cpad, float* __restrict__ gout,
+                                                      const float* __restrict__ wb) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)B * HW * Cpad;
   if (i >= total) return;
@@ -458,8 +459,32 @@ __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ 
     const float w = lw ? lw[t[b]] : 1.f;
     const float scale = gloss[0] * 2.f * w / ((float)C * (float)HW * (float)B);
     g = scale * (out[pix * pitch + c] - target[pix * pitch + c]);
+    if (wb) g = g * wb[b];               // lgm_weighted_mse_bwd_iw: the sample's importance weight, one more rounding
   }
   gout[pix * pitch + c] = g;
+}
+// mean_kernel (n_terms 1) and hybrid_mean_kernel (n_terms 2) under a timestep sampler's plan: every per-sample term times
+// iw[t_b], the same strided partial sums and block sums - with iw = 1 the plain kernels' bits.  wb[b] = iw[t_b] for the backward.
+__global__ void iw_mean_kernel(const float* __restrict__ per, int n_terms, float vb_weight, const long* __restrict__ t,
+                               const float* __restrict__ iw, int T, int B, float* __restrict__ wb, float* __restrict__ loss) {
+#pragma clang fp contract(off)
+  __shared__ float sh[16];
+  float s = 0.f, sv = 0.f;
+  for (int i = threadIdx.x; i < B; i += blockDim.x) {
+    long ti = t[i];
+    ti = ti < 0 ? 0 : (ti >= T ? T - 1 : ti);
+    const float w = iw[ti];
+    wb[i] = w;
+    s += w * per[i];
+    if (n_terms == 2) sv += w * per[B + i];
+  }
+  s = lgm_block_sum(s, sh);
+  if (n_terms == 2) {
+    sv = lgm_block_sum(sv, sh);
+    if (threadIdx.x == 0) loss[0] = s / (float)B + vb_weight * (sv / (float)B);
+  } else if (threadIdx.x == 0) {
+    loss[0] = s / (float)B;
+  }
 }
 
 // GaussianDiffusion's `extract(table, t, shape) * tensor` algebra with a PER-SAMPLE timestep (ddpm.py:673-705, 869-876) on
@@ -1087,7 +1112,8 @@ __global__ __launch_bounds__(256) void hybrid_loss_bwd_kernel(const float* __res
                                                               const float* __restrict__ xin, long x_pitch, int x_off,
                                                               const long* __restrict__ t, HybridTables T, int objective,
                                                               const float* __restrict__ gloss, float vb_weight, int B,
-                                                              int C, int HW, float* __restrict__ gout) {
+                                                              int C, int HW, float* __restrict__ gout,
+                                                              const float* __restrict__ wb) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)B * HW * pitch;
   if (i >= total) return;
@@ -1113,6 +1139,7 @@ __global__ __launch_bounds__(256) void hybrid_loss_bwd_kernel(const float* __res
       const float scale = gloss[0] * vb_weight / ((float)B * ((float)C * (float)HW) * 0.69314718f);
       g = scale * dlv * (0.5f * (row[0] - row[1]));
     }
+    if (wb) g = g * wb[b];               // lgm_hybrid_loss_bwd_iw: the sample's importance weight, as mse_bwd_kernel applies it
   }
   gout[pix * pitch + c] = g;
 }
@@ -1670,6 +1697,173 @@ __global__ __launch_bounds__(256) void tanh_mse_bwd_kernel(const float* __restri
   }
   gpre[pix * pitch + c] = g;
 }
+
+// ---------------------------------------------------------------------------------------
+// Timestep samplers of the diffusion training step (lgm_tsampler_draw / lgm_tsampler_update, include/lgm_hip.h)
+// ---------------------------------------------------------------------------------------
+// mode 0: stratified from ONE uniform (a division, then an add: numpy float32 restates it bit for bit); mode 1: the first
+// index with cdf[t] > u_b.  cdf[T - 1] = 1 > u, so the search ends inside the table for every u < 1; any other u (1, NaN) ends
+// at T - 1 as well, because hi never leaves it.
+__global__ __launch_bounds__(256) void tsampler_draw_kernel(const float* __restrict__ u, const float* __restrict__ cdf, int T,
+                                                            int mode, long* __restrict__ t_out, int B) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  long ti;
+  if (mode == 0) {
+    float ub = u[0] + (float)b / (float)B;
+    if (ub >= 1.f) ub = ub - 1.f;
+    const float f = floorf((float)T * ub);
+    ti = f >= 0.f ? (f < (float)T ? (long)f : (long)T - 1) : 0;      // (a NaN draw: 0)
+  } else {
+    const float ub = u[b];
+    int lo = 0, hi = T - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cdf[mid] > ub) hi = mid;
+      else lo = mid + 1;
+    }
+    ti = lo;
+  }
+  t_out[b] = ti > (long)T - 1 ? (long)T - 1 : ti;
+}
+
+// The loss-second-moment sampler's state update and plan, ONE workgroup.  A thread owns the timesteps t with t mod TS_THREADS ==
+// threadIdx.x: it alone writes their history rows, counts, iw and (first pass) cdf entries, so a batch that repeats a timestep
+// lands in batch order without atomics.  Row update, c entries held, m new ones: the last H of (row[0..c) ++ new) - shift the
+// survivors of the row down by drop = max(0, c + m - H) (ascending, in place), then the k-th new value goes to c - drop + k
+// where that is not negative.  The prefix sum is two-level and sequential at both levels: thread j sums segment j of `seg_len`
+// entries in order, thread 0 sums the segment totals in order, cdf[i] = offset[segment] + local[i].  Rounding is monotone and
+// the next segment's offset is computed exactly as the last entry of this one, so cdf never decreases.
+constexpr int TS_THREADS = 1024;
+__global__ __launch_bounds__(TS_THREADS) void tsampler_update_kernel(const long* __restrict__ t, const float* __restrict__ per,
+                                                                     int n_terms, float vb_weight, float* __restrict__ history,
+                                                                     int* __restrict__ counts, int H, float q, int T, int B,
+                                                                     float* cdf, float* __restrict__ iw, int seg_len) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) int st_t[TS_THREADS];
+  __shared__ float st_l[TS_THREADS];
+  __shared__ float seg[TS_THREADS];
+  __shared__ float sh[16];
+  __shared__ int shi[16];
+  const int tid = threadIdx.x;
+  // ---- phase one: the batch into the rows ----
+  for (int b0 = 0; b0 < B; b0 += TS_THREADS) {
+    const int nb = B - b0 < TS_THREADS ? B - b0 : TS_THREADS;
+    __syncthreads();                                   // the previous chunk has been read by everyone
+    const int nb4 = (nb + 3) & ~3;                     // the scans read four staged timesteps per LDS load: -1 fills the tail
+    if (tid < nb) {
+      const int b = b0 + tid;
+      float L = per[b];
+      if (n_terms == 2) L = L + vb_weight * per[B + b];
+      const long ti = t[b];
+      st_t[tid] = (ti >= 0 && ti < T && isfinite(L)) ? (int)ti : -1;
+      st_l[tid] = L;
+    } else if (tid < nb4) {
+      st_t[tid] = -1;
+    }
+    __syncthreads();
+    for (int row = tid; row < T; row += TS_THREADS) {
+      int m = 0;
+      for (int i = 0; i < nb4; i += 4) {
+        const int4 s4 = *reinterpret_cast<const int4*>(st_t + i);
+        m += (s4.x == row ? 1 : 0) + (s4.y == row ? 1 : 0) + (s4.z == row ? 1 : 0) + (s4.w == row ? 1 : 0);
+      }
+      if (m == 0) continue;
+      float* hr = history + (long)row * H;
+      int c = counts[row];
+      c = c < 0 ? 0 : (c > H ? H : c);
+      const int drop = c + m > H ? c + m - H : 0;
+      // eight loads, then their eight stores: every load of a round reads an index no earlier round and no store of this
+      // round in front of it has written (drop >= 1 here), and the loads of a round are in flight together
+      for (int j = 0; j + drop < c; j += 8) {
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = j + e + drop < c ? hr[j + e + drop] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (j + e + drop < c) hr[j + e] = v[e];
+      }
+      int k = c - drop;
+      for (int i = 0; i < nb4; i += 4) {
+        const int4 s4 = *reinterpret_cast<const int4*>(st_t + i);
+        const int tt[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (tt[e] != row) continue;
+          if (k >= 0) hr[k] = st_l[i + e];
+          ++k;
+        }
+      }
+      counts[row] = c + m > H ? H : c + m;
+    }
+  }
+  // ---- phase two: the plan from the updated rows (every thread reads only what it wrote itself) ----
+  int cmin = H;
+  float wsum = 0.f;
+  for (int row = tid; row < T; row += TS_THREADS) {
+    const int c = counts[row];
+    cmin = c < cmin ? c : cmin;
+    const float* hr = history + (long)row * H;
+    float s = 0.f;
+    for (int h = 0; h < H; ++h) s += hr[h] * hr[h];
+    const float w = sqrtf(s / (float)H);
+    cdf[row] = w;
+    wsum += w;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const int o = __shfl_xor(cmin, off, 64);
+    cmin = o < cmin ? o : cmin;
+  }
+  if ((tid & 63) == 0) shi[tid >> 6] = cmin;
+  const float W = lgm_block_sum(wsum, sh);               // (its barriers also publish shi)
+  for (int i = 0; i < TS_THREADS / 64; ++i) cmin = shi[i] < cmin ? shi[i] : cmin;
+  const bool weighted = cmin >= H && W > 0.f && isfinite(W);
+  const float uniform = 1.f / (float)T;
+  for (int row = tid; row < T; row += TS_THREADS) {
+    float p = uniform, w = 1.f;
+    if (weighted) {
+      p = (1.f - q) * cdf[row] / W + q / (float)T;
+      w = 1.f / ((float)T * p);
+    }
+    cdf[row] = p;
+    iw[row] = w;
+  }
+  __syncthreads();
+  const int nseg = (T + seg_len - 1) / seg_len;          // <= TS_THREADS (the launcher's seg_len)
+  if (tid < nseg) {
+    const int lo = tid * seg_len, hi = lo + seg_len < T ? lo + seg_len : T;
+    float run = 0.f;
+    for (int i0 = lo; i0 < hi; i0 += 8) {                // (loads of a round in front of its stores, as above; the sum stays in order)
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = i0 + e < hi ? cdf[i0 + e] : 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (i0 + e < hi) {
+          run += v[e];
+          cdf[i0 + e] = run;
+        }
+      }
+    }
+    seg[tid] = run;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float off = 0.f;
+    for (int j = 0; j < nseg; ++j) {
+      const float total = seg[j];
+      seg[j] = off;
+      off += total;
+    }
+  }
+  __syncthreads();
+  for (int row = tid; row < T; row += TS_THREADS) {
+    const float v = seg[row / seg_len] + cdf[row];
+    cdf[row] = row == T - 1 ? 1.f : fminf(v, 1.f);
+  }
+}
 }  // namespace
 
 extern "C" int lgm_tanh_mse_fwd(const float* pre, const float* target, int64_t pitch, int B, int C, int HW, int Cpad,
@@ -1714,8 +1908,36 @@ extern "C" int lgm_weighted_mse_bwd(const float* out, const float* target, int64
                                     float* gout, void* stream) {
   LGM_REQUIRE(out && target && gloss && gout && B > 0 && (!loss_weight || t), "weighted_mse_bwd: bad arguments");
   hipLaunchKernelGGL(mse_bwd_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, out,
-                     target, (long)pitch, t, loss_weight, gloss, B, C, HW, Cpad, gout);
+                     target, (long)pitch, t, loss_weight, gloss, B, C, HW, Cpad, gout, (const float*)nullptr);
   LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+// The weighted MSE under a timestep sampler's plan (include/lgm_hip.h, "Timestep samplers"): the plain per-sample launch, then
+// iw_mean_kernel in place of mean_kernel; the backward is the plain launch with the per-sample weights wb the forward left.
+static int iw_mean_launch(const float* per, int n_terms, float vb_weight, const int64_t* t, const float* iw, int n_table, int B,
+                          float* wb, float* loss, hipStream_t s) {
+  hipLaunchKernelGGL(iw_mean_kernel, dim3(1), dim3(256), 0, s, per, n_terms, vb_weight, (const long*)t, iw, n_table, B, wb, loss);
+  return LGM_OK;
+}
+extern "C" int lgm_weighted_mse_fwd_iw(const float* out, const float* target, int64_t pitch, const int64_t* t,
+                                       const float* loss_weight, const float* iw, int n_table, int B, int C, int HW, int Cpad,
+                                       float* per_sample, float* wb, float* loss, void* stream) {
+  LGM_REQUIRE(t && iw && wb && loss && n_table > 0, "weighted_mse_fwd_iw: bad arguments");
+  const int rc = lgm_weighted_mse_fwd(out, target, pitch, t, loss_weight, B, C, HW, Cpad, per_sample, nullptr, stream);
+  if (rc != LGM_OK) return rc;
+  lgm_note_kernel("iw_mean_kernel");
+  iw_mean_launch(per_sample, 1, 0.f, t, iw, n_table, B, wb, loss, (hipStream_t)stream);
+  LGM_LAUNCH_CHECK_AS("weighted_mse_fwd_iw");
+  return LGM_OK;
+}
+extern "C" int lgm_weighted_mse_bwd_iw(const float* out, const float* target, int64_t pitch, const int64_t* t,
+                                       const float* loss_weight, const float* wb, const float* gloss, int B, int C, int HW,
+                                       int Cpad, float* gout, void* stream) {
+  LGM_REQUIRE(out && target && gloss && gout && wb && B > 0 && (!loss_weight || t), "weighted_mse_bwd_iw: bad arguments");
+  hipLaunchKernelGGL(mse_bwd_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, out,
+                     target, (long)pitch, t, loss_weight, gloss, B, C, HW, Cpad, gout, wb);
+  LGM_LAUNCH_CHECK_AS("weighted_mse_bwd_iw");
   return LGM_OK;
 }
 
@@ -1778,8 +2000,71 @@ extern "C" int lgm_hybrid_loss_bwd(const float* out, int64_t pitch, const float*
   lgm_note_kernel("hybrid_loss_bwd_kernel");
   hipLaunchKernelGGL(hybrid_loss_bwd_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, out,
                      (long)pitch, target, (long)target_pitch, img, normalize, xin, (long)x_pitch, x_off, (const long*)t, T,
-                     objective, gloss, vb_weight, B, C, HW, gout);
+                     objective, gloss, vb_weight, B, C, HW, gout, (const float*)nullptr);
   LGM_LAUNCH_CHECK_AS("hybrid_loss_bwd");
+  return LGM_OK;
+}
+// The hybrid loss under a timestep sampler's plan: as lgm_weighted_mse_fwd_iw / _bwd_iw.
+extern "C" int lgm_hybrid_loss_fwd_iw(const float* out, int64_t pitch, const float* target, int64_t target_pitch,
+                                      const float* img, int normalize, const float* xin, int64_t x_pitch, int x_off,
+                                      const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip,
+                                      const float* sqrt_recipm1, const float* loss_weight, const float* tab, int n_table,
+                                      int objective, float vb_weight, const float* iw, int B, int C, int HW, float* per,
+                                      float* wb, float* loss, void* stream) {
+  LGM_REQUIRE(iw && wb && loss, "hybrid_loss_fwd_iw: bad arguments");
+  const int rc = lgm_hybrid_loss_fwd(out, pitch, target, target_pitch, img, normalize, xin, x_pitch, x_off, t, sqrt_ac, sqrt_1mac,
+                                     sqrt_recip, sqrt_recipm1, loss_weight, tab, n_table, objective, vb_weight, B, C, HW, per,
+                                     nullptr, stream);
+  if (rc != LGM_OK) return rc;
+  iw_mean_launch(per, 2, vb_weight, t, iw, n_table, B, wb, loss, (hipStream_t)stream);
+  LGM_LAUNCH_CHECK_AS("hybrid_loss_fwd_iw");
+  return LGM_OK;
+}
+extern "C" int lgm_hybrid_loss_bwd_iw(const float* out, int64_t pitch, const float* target, int64_t target_pitch,
+                                      const float* img, int normalize, const float* xin, int64_t x_pitch, int x_off,
+                                      const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip,
+                                      const float* sqrt_recipm1, const float* loss_weight, const float* tab, int n_table,
+                                      int objective, float vb_weight, const float* wb, const float* gloss, int B, int C, int HW,
+                                      float* gout, void* stream) {
+  const float* tables[4] = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1};
+  LGM_REQUIRE(gloss && gout && gout != out && wb &&
+                  hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, tables, tab, B, C, HW, objective,
+                            n_table),
+              "hybrid_loss_bwd_iw: bad arguments");
+  const HybridTables T = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, loss_weight, tab, n_table};
+  lgm_note_kernel("hybrid_loss_bwd_kernel");
+  hipLaunchKernelGGL(hybrid_loss_bwd_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, out,
+                     (long)pitch, target, (long)target_pitch, img, normalize, xin, (long)x_pitch, x_off, (const long*)t, T,
+                     objective, gloss, vb_weight, B, C, HW, gout, wb);
+  LGM_LAUNCH_CHECK_AS("hybrid_loss_bwd_iw");
+  return LGM_OK;
+}
+
+// Timestep samplers.  The names are noted without a registry entry (no LGM_KNAME), like dpm_step_kernel below: the ledger test
+// lists every registry name with the test file that asserts it; tests/test_hip_tsampler.py asserts these two.
+extern "C" int lgm_tsampler_draw(const float* u, const float* cdf, int T, int mode, int64_t* t_out, int B, void* stream) {
+  LGM_REQUIRE(u && t_out && T > 0 && B > 0 && (mode == 0 || (mode == 1 && cdf)), "tsampler_draw: bad arguments");
+  lgm_note_kernel("tsampler_draw_kernel");
+  hipLaunchKernelGGL(tsampler_draw_kernel, dim3(lgm_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, u, cdf, T, mode,
+                     (long*)t_out, B);
+  LGM_LAUNCH_CHECK_AS("tsampler_draw");
+  return LGM_OK;
+}
+extern "C" int lgm_tsampler_update(const int64_t* t, const float* per, int n_terms, float vb_weight, float* history,
+                                   int32_t* counts, int H, float q, int T, int B, float* cdf, float* iw, void* stream) {
+  LGM_REQUIRE(history && counts && cdf && iw && H >= 1 && T >= 1 && T <= (1 << 20) && B >= 0 && (B == 0 || (t && per)) &&
+                  (n_terms == 1 || n_terms == 2) && q >= 0.f && q <= 1.f,
+              "tsampler_update: bad arguments");
+  LGM_REQUIRE(cdf != iw && cdf != history && (const void*)cdf != (const void*)counts && cdf != per,
+              "tsampler_update: cdf must not alias another operand");
+  // segments of the two-level prefix sum: about sqrt(T) long, and no more of them than the workgroup has threads
+  int seg_len = 1;
+  while ((long)seg_len * seg_len < T) ++seg_len;
+  if (seg_len < lgm_cdiv(T, TS_THREADS)) seg_len = lgm_cdiv(T, TS_THREADS);
+  lgm_note_kernel("tsampler_update_kernel");
+  hipLaunchKernelGGL(tsampler_update_kernel, dim3(1), dim3(TS_THREADS), 0, (hipStream_t)stream, (const long*)t, per, n_terms,
+                     vb_weight, history, (int*)counts, H, q, T, B, cdf, iw, seg_len);
+  LGM_LAUNCH_CHECK_AS("tsampler_update");
   return LGM_OK;
 }
 

@@ -5,8 +5,9 @@ host-bound when issued from Python.  The step is therefore captured ONCE and rep
 backward pass runs in four phases, each of which makes one exchange bucket of the flat gradient buffer final
 (``Unet.BACKWARD_PHASES`` / ``bucket_ranges()``); a LAYOUT says which phases share a graph:
 
-    one rank : ((0, 1, 2, 3),)            ONE graph - t ~ randint, noise ~ randn (a diffusion with offset noise also
-                                          draws its [B, C] offsets, a class-conditional one its label drop), q_sample,
+    one rank : ((0, 1, 2, 3),)            ONE graph - t ~ randint (or the diffusion's timestep sampler: its draw here, its
+                                          state update behind the loss, lgm_hip.tsampler), noise ~ randn (a diffusion with offset
+                                          noise also draws its [B, C] offsets, a class-conditional one its label drop), q_sample,
                                           UNet forward, loss, the whole backward - then fused Adam (1 eager kernel) and
                                           EMA (every 10th step);  ``LGM_ONE_GRAPH=0``: ((0, 1), (2, 3))
     N ranks  : ((0,), (1,), (2,), (3,))   FOUR graphs, cut where a bucket becomes final, with the asynchronous
@@ -260,10 +261,16 @@ class GraphedDDPMStep:
         self.layout = (LAYOUT_BUCKETS if sync is not None or self.pipeline else LAYOUT_ONE if _ONE_GRAPH else LAYOUT_TWO)
         self_cond = bool(net.self_condition)
         self.pre = self.est = None                   # self-conditioned model only: see the class comment
+        # timestep sampler (lgm_hip.tsampler): its draw opens qsample(), its update follows the loss inside hip_loss_network -
+        # both inside the capture, its state on the device.  Warm-up and capture run the step: the state is put back after them.
+        self.ts = ts = gd.active_t_sampler()
 
         def qsample():
             # the draws of GaussianDiffusion.forward / p_losses, in their order, and the q_sample launch
-            self.t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
+            if ts is None:
+                self.t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
+            else:                                    # one launch behind torch.rand, where randint stands
+                self.t = ts.draw(x.shape[0], x.device)
             self.noise = torch.randn_like(self.x)
             self.offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
             if self.y is not None:
@@ -288,6 +295,9 @@ class GraphedDDPMStep:
         # warm-up and capture must not perturb the random stream: a run that captures at batch 0 and a run that
         # resumes from a checkpoint (and captures later) draw the same (t, noise) for the same seed
         rng_state = torch.cuda.get_rng_state(x.device)
+        if ts is not None:
+            ts.ensure_plan()                         # eager, in front of the snapshot: a replay does not pass through Python
+            ts_state = ts.snapshot()
         try:
             _warm_up(whole, warmup)                  # (the WHOLE step: the pieces share workspaces and kernel attributes)
             if self.pipeline:
@@ -319,10 +329,14 @@ class GraphedDDPMStep:
                 self.events = [torch.cuda.Event() for _ in range(4)]
         finally:
             torch.cuda.set_rng_state(rng_state, x.device)
+            if ts is not None:
+                ts.restore(ts_state)
 
     def step(self, batch_idx: int = 0, self_cond: bool = False):
         """``self_cond``: this step's coin (read by a self-conditioned model only)."""
-        if self.pre is not None:                     # draws + q_sample, then the estimate pass when the coin says so
+        if self.ts is not None:
+            self.ts.ensure_plan()                    # a state loaded since the last step: one eager launch, else a host flag
+        if self.pre is not None:                    # draws + q_sample, then the estimate pass when the coin says so
             self.pre.replay()
             if self_cond:
                 self.est.replay()

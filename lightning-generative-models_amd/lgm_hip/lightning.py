@@ -562,6 +562,19 @@ class MiniTrainer:
         if norm is not None:
             model.log("grad_norm", norm)
 
+    def _log_t_sampler(self, model):
+        """``t_sampler_warm`` (the share of timesteps with a full loss history) joins the logged scalars while a loss-aware
+        timestep sampler still draws uniformly; like ``grad_norm`` it is read when the scalars are, not per step"""
+        gd = getattr(getattr(model, "ema", None), "online_model", None)
+        ts = getattr(gd, "_ts", None)
+        if ts is None or not ts.loss_aware:
+            return
+        frac = ts.warm_fraction()
+        if frac < 1.0:
+            model.log("t_sampler_warm", frac)
+        else:
+            model.logged.pop("t_sampler_warm", None)
+
     # -- checkpoints (reference: ModelCheckpoint(dirpath, save_last=True, monitor="val_loss")) ------
     def _save_last(self, model, epoch):
         if self.root and self.rank == 0:
@@ -687,6 +700,7 @@ class MiniTrainer:
                         model.on_train_batch_end(None, batch, batch_idx)
                     if self.log_every and model.global_step % self.log_every == 0:
                         self._log_grad_norm(model)
+                        self._log_t_sampler(model)
                         msg = model.synced_logs()            # collective (sync_dist scalars): every rank takes part
                         if self.rank == 0:
                             print(f"[step {model.global_step}] {msg} ({time.time() - t0:.1f}s)", flush=True)

@@ -888,7 +888,8 @@ class GaussianDiffusion(nn.Module):
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, cond_drop_prob=None,
                  cond_scale=1.0, sampler="auto", dpm_order=2, dpm_stochastic=False, dynamic_thresholding=False,
-                 dynamic_thresholding_percentile=0.995, vb_loss_weight=None):
+                 dynamic_thresholding_percentile=0.995, vb_loss_weight=None, t_sampler="uniform", t_sampler_history=10,
+                 t_sampler_uniform_prob=0.001):
         """``cond_drop_prob`` / ``cond_scale`` (extension, class-conditional ``model`` only): the probability with which
         ``forward`` replaces a training label by the null label, and the classifier-free-guidance scale ``sample`` uses.
         ``cond_drop_prob=None`` is 0.1 on a class-conditional model and 0 on any other.
@@ -901,8 +902,19 @@ class GaussianDiffusion(nn.Module):
         ``vb_loss_weight`` (extension; Nichol & Dhariwal 2021, L_hybrid; a ``Unet(learned_variance=True)`` only, ``None`` =
         0.001 there): the model trains on mean_b(loss_weight[t_b] mse_b) + vb_loss_weight mean_b(vb_b), vb_b the bound's term at
         t_b in bits per dimension with the model mean detached; the ancestral chain samples with the learned variance and
-        ``vlb_terms(variance="learned")`` evaluates the bound with it.  DDIM and DPM-Solver++ read no model variance."""
+        ``vlb_terms(variance="learned")`` evaluates the bound with it.  DDIM and DPM-Solver++ read no model variance.
+        ``t_sampler`` (extension): how a TRAINING-mode forward draws t.  ``"uniform"``: the reference's ``randint``.
+        ``"stratified"``: one uniform per step, t_b = floor(T (u0 + b / B mod 1)) (Kingma et al. 2021, VDM App. I.1).
+        ``"loss_second_moment"`` (Nichol & Dhariwal 2021, 3.3): p_t proportional to the root mean square of the last
+        ``t_sampler_history`` per-sample losses seen at t, mixed with ``t_sampler_uniform_prob`` of the uniform distribution
+        once every t has a full history, and the loss is mean_b(L_b / (T p_t_b)), which leaves its gradient unbiased
+        (``lgm_hip.tsampler``; ``p_losses`` with an explicit t weights and records the same way).  In eval mode every sampler
+        draws uniformly, weights nothing and records nothing.  A deep copy (the EMA shadow) is a ``"uniform"`` diffusion: the
+        state lives with the model that trains, under ``t_sampler.history`` / ``t_sampler.counts`` of its state dict."""
         super().__init__()
+        from lgm_hip import tsampler
+        history, uniform_prob = tsampler.check_arguments(t_sampler, t_sampler_history, t_sampler_uniform_prob)
+        self.t_sampler = t_sampler
         self.learned_variance = bool(getattr(model, "learned_variance", False))
         if vb_loss_weight is not None and not self.learned_variance:
             raise ValueError("vb_loss_weight needs a model built with learned_variance=True")
@@ -976,10 +988,52 @@ class GaussianDiffusion(nn.Module):
             # tables above, rounded once (lgm_hip.likelihood.learned_table); not part of any state dict
             from lgm_hip.likelihood import learned_table
             self.register_buffer("learned_table", torch.tensor(learned_table(self), dtype=torch.float32), persistent=False)
+        # a plain attribute, not a submodule and not buffers: see lgm_hip.tsampler
+        self._ts = None if t_sampler == "uniform" else tsampler.TimestepSampler(t_sampler, self.num_timesteps, history,
+                                                                                uniform_prob)
 
     @property
     def device(self):
         return self.betas.device
+
+    # -- the timestep sampler's state: moved, saved and loaded with the module, never a buffer of it ----------------
+    def active_t_sampler(self):
+        """the sampler a forward in the current mode goes through: None in eval mode and for ``"uniform"``"""
+        return self._ts if self.training else None
+
+    def __deepcopy__(self, memo):
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = None if k == "_ts" else copy.deepcopy(v, memo)
+        new.t_sampler = "uniform"
+        return new
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        if self._ts is not None:
+            self._ts.apply(fn)
+        return self
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        if self._ts is not None:
+            for k, v in self._ts.state().items():
+                destination[f"{prefix}t_sampler.{k}"] = v if keep_vars else v.detach()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        mine = {k: f"{prefix}t_sampler.{k}" for k in (self._ts.state() if self._ts is not None else {})}
+        found = {k: state_dict[key] for k, key in mine.items() if key in state_dict}
+        rest = {k: v for k, v in state_dict.items() if k not in mine.values()} if found else state_dict
+        super()._load_from_state_dict(rest, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        if len(found) == len(mine) and mine:
+            try:
+                self._ts.load_state(found["history"], found["counts"])
+            except ValueError as e:
+                error_msgs.append(str(e))
+        else:
+            missing_keys.extend(key for k, key in mine.items() if k not in found)
 
     def ddim_time_pairs(self):
         times = torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1)
@@ -1029,7 +1083,11 @@ class GaussianDiffusion(nn.Module):
         draws - the stream of a model without classes."""
         b, c, h, w = img.shape
         assert h == self.img_size and w == self.img_size, f"height and width of image must be {self.img_size}"
-        t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()
+        ts = self.active_t_sampler()
+        if ts is None:
+            t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()
+        else:                                        # (its uniforms stand where randint stands in the draw order)
+            t = ts.draw(b, img.device)
         if classes is None:
             return self.p_losses(img, t, *args, _normalize=self.auto_normalize, **kwargs)
         classes = self.model.labels(classes, b, img.device)
@@ -1334,16 +1392,35 @@ def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset,
     st = ops.stream()
     out, tape = net.forward_nhwc(xt, t, save, True, classes)
     loss = ops.new((1,), img)
+    # a loss-aware timestep sampler (training mode): the *_iw forms weight sample b by iw[t_b] and leave that weight in ``wb``
+    # for the backward, then ONE launch records the unweighted per-sample losses and rebuilds the plan of the next draw;
+    # ``ctx`` then ends with ``wb``
+    ts = gd.active_t_sampler()
+    ts = ts if ts is not None and ts.loss_aware else None
+    if ts is not None:
+        ts.ensure_plan()
+        wb = ops.new((B,), img)
     if getattr(net, "learned_variance", False):
         normalize = bool(gd.auto_normalize if normalize is None else normalize)
         per = ops.new((2, B), img)
-        L.lgm_hybrid_loss_fwd(*_hybrid_operands(gd, out, target, img, normalize, xt, t), B, C, H * W, per.data_ptr(),
-                              loss.data_ptr(), st)
-        return loss, (gd, tape, out, target, t, (B, C, H, W), img, noise, offset, per, xt, normalize)
+        head = _hybrid_operands(gd, out, target, img, normalize, xt, t)
+        ctx = (gd, tape, out, target, t, (B, C, H, W), img, noise, offset, per, xt, normalize)
+        if ts is None:
+            L.lgm_hybrid_loss_fwd(*head, B, C, H * W, per.data_ptr(), loss.data_ptr(), st)
+            return loss, ctx
+        L.lgm_hybrid_loss_fwd_iw(*head, ts.iw.data_ptr(), B, C, H * W, per.data_ptr(), wb.data_ptr(), loss.data_ptr(), st)
+        ts.record(t, per, 2, gd.vb_loss_weight)
+        return loss, ctx + (wb,)
     per = ops.new((B,), img)
-    L.lgm_weighted_mse_fwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
-                           B, C, H * W, Cp, per.data_ptr(), loss.data_ptr(), st)
-    return loss, (gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
+    ctx = (gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
+    if ts is None:
+        L.lgm_weighted_mse_fwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
+                               B, C, H * W, Cp, per.data_ptr(), loss.data_ptr(), st)
+        return loss, ctx
+    L.lgm_weighted_mse_fwd_iw(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(), ts.iw.data_ptr(),
+                              gd.num_timesteps, B, C, H * W, Cp, per.data_ptr(), wb.data_ptr(), loss.data_ptr(), st)
+    ts.record(t, per, 1, 0.0)
+    return loss, ctx + (wb,)
 
 
 def hip_loss_backward_begin(ctx, gl):
@@ -1355,16 +1432,23 @@ def hip_loss_backward_begin(ctx, gl):
     gout = ops.new(out.shape, out)
     if getattr(gd.model, "learned_variance", False):
         img, xt, normalize = ctx[6], ctx[10], ctx[11]
-        ops.lib().lgm_hybrid_loss_bwd(*_hybrid_operands(gd, out, target, img, normalize, xt, t), gl.data_ptr(), B, C, H * W,
-                                      gout.data_ptr(), ops.stream())
+        head = _hybrid_operands(gd, out, target, img, normalize, xt, t)
+        if len(ctx) > 12:                # the forward ran under a loss-aware timestep sampler: its per-sample weights
+            ops.lib().lgm_hybrid_loss_bwd_iw(*head, ctx[12].data_ptr(), gl.data_ptr(), B, C, H * W, gout.data_ptr(), ops.stream())
+        else:
+            ops.lib().lgm_hybrid_loss_bwd(*head, gl.data_ptr(), B, C, H * W, gout.data_ptr(), ops.stream())
         st = gd.model.backward_begin(tape, gout)
-        st.head += (out, target, img, xt)
+        st.head += (out, target, img, xt) + tuple(ctx[12:])
         return st
-    ops.lib().lgm_weighted_mse_bwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(),
-                                   gd.loss_weight.data_ptr(), gl.data_ptr(), B, C, H * W, Cp,
-                                   gout.data_ptr(), ops.stream())
+    if len(ctx) > 9:
+        ops.lib().lgm_weighted_mse_bwd_iw(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
+                                          ctx[9].data_ptr(), gl.data_ptr(), B, C, H * W, Cp, gout.data_ptr(), ops.stream())
+    else:
+        ops.lib().lgm_weighted_mse_bwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(),
+                                       gd.loss_weight.data_ptr(), gl.data_ptr(), B, C, H * W, Cp,
+                                       gout.data_ptr(), ops.stream())
     st = gd.model.backward_begin(tape, gout)
-    st.head += (out, target)             # let go of with the phase that reads ``gout``, also when ``ctx`` is gone by then
+    st.head += (out, target) + tuple(ctx[9:])    # let go of with the phase that reads ``gout``, also when ``ctx`` is gone by then
     return st
 
 
@@ -1395,7 +1479,8 @@ class DDPM(LightningModule):
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
                  min_snr_gamma: float = 5, self_condition: bool = False, num_classes: Optional[int] = None,
-                 cond_drop_prob: float = 0.1, dynamic_thresholding: bool = False,
+                 cond_drop_prob: float = 0.1, t_sampler: str = "uniform", t_sampler_history: int = 10,
+                 t_sampler_uniform_prob: float = 0.001, dynamic_thresholding: bool = False,
                  dynamic_thresholding_percentile: float = 0.995, learned_variance: bool = False,
                  vb_loss_weight: float = 0.001, cond_scale: float = 1.0, sampler: str = "auto",
                  dpm_order: int = 2, dpm_stochastic: bool = False):
@@ -1405,8 +1490,12 @@ class DDPM(LightningModule):
         ``dynamic_thresholding`` / ``dynamic_thresholding_percentile`` (extension): the samplers threshold x0 per sample
         instead of clamping it to [-1, 1] (GaussianDiffusion).  ``learned_variance`` / ``vb_loss_weight`` (extension): the
         network gets the variance head and trains on the hybrid loss (GaussianDiffusion); ``vb_loss_weight`` is read with it
-        only.  They stand in front of ``cond_scale``: the tail of this
-        signature is pinned by tests/test_dpmpp_host.py; pass everything from ``num_classes`` on by keyword."""
+        only.  ``t_sampler`` / ``t_sampler_history`` / ``t_sampler_uniform_prob`` (extension): how training draws its
+        timesteps, ``"uniform"``, ``"stratified"`` or ``"loss_second_moment"`` (GaussianDiffusion); the sampler's state belongs
+        to the model that trains - the EMA shadow has none, each rank keeps its own - and is saved under
+        ``ema.online_model.t_sampler.history`` / ``.counts``.  New keywords stand in front of those that tests pin (the tail
+        from ``dynamic_thresholding`` on: tests/test_dpmpp_host.py, tests/test_learned_sigma_host.py); pass everything from
+        ``num_classes`` on by keyword."""
         super().__init__()
         self.save_hyperparameters()
         self.num_classes = num_classes
@@ -1415,6 +1504,7 @@ class DDPM(LightningModule):
         cond = dict(cond_drop_prob=cond_drop_prob, cond_scale=cond_scale) if num_classes is not None else {}
         if learned_variance:
             cond["vb_loss_weight"] = vb_loss_weight
+        cond.update(t_sampler=t_sampler, t_sampler_history=t_sampler_history, t_sampler_uniform_prob=t_sampler_uniform_prob)
         diffusion_model = GaussianDiffusion(model, img_size=img_size, timesteps=diffusion_timesteps,
                                             sampling_timesteps=sampling_timesteps, objective=objective,
                                             beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
