@@ -35,17 +35,17 @@ DIRECT = ("igemm_kernel<", "narrow1x1_", "smalln_yx_", "wgrad_kernel<", "wgrad_g
 
 # every other name (or family prefix): the test file that runs it and asserts lgm_last_kernel
 ELSEWHERE = {
-    "lgmwino::wino_bwd_pair_kernel": "tests/test_hip_winograd.py",
-    "lgmwino::wino_wgrad_kernel": "tests/test_hip_winograd.py",
-    "lgmwino::wino_wgrad2_kernel": "tests/test_hip_winograd.py",
-    "lgmwino::wino_wgrad4_kernel": "tests/test_hip_winograd.py",
-    "lgmwino4::wino4_conv_kernel": "tests/test_hip_winograd.py",
-    "lgmwino4l::wino4l_conv_kernel": "tests/test_hip_winograd.py",
-    "lgmwino4w::wino4_wgrad_kernel": "tests/test_hip_winograd.py",
-    "lgmwino4w::wino4_wgrad2_kernel": "tests/test_hip_winograd.py",
-    "lgmwino4w::wino4_wgrad4_kernel": "tests/test_hip_winograd.py",
-    "lgmwino4w::wino4_wgrad8_kernel": "tests/test_hip_winograd.py",
-    "lgmwino::wino_conv_kernel": "tests/test_hip_winograd.py",
+    "lgmwino::wino_bwd_pair_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino::wino_wgrad_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino::wino_wgrad2_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino::wino_wgrad4_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino4::wino4_conv_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino4l::wino4l_conv_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino4w::wino4_wgrad_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino4w::wino4_wgrad2_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino4w::wino4_wgrad4_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino4w::wino4_wgrad8_kernel": "tests/test_hip_wino_ledger.py",
+    "lgmwino::wino_conv_kernel": "tests/test_hip_wino_ledger.py",
     "lgmweng::weng_gemm_kernel": "tests/test_hip_weng.py",
     "linattn_bwd_fused_kernel": "tests/test_hip_ops.py",
     "linattn_out_fused_kernel": "tests/test_hip_ops.py",
