@@ -1903,12 +1903,17 @@ extern "C" int lgm_weighted_mse_fwd(const float* out, const float* target, int64
   return LGM_OK;
 }
 
+// (wb: the per-sample weights a forward under a timestep sampler's plan left, or nullptr; so in hybrid_bwd_launch)
+static void mse_bwd_launch(const float* out, const float* target, int64_t pitch, const int64_t* t, const float* loss_weight,
+                           const float* wb, const float* gloss, int B, int C, int HW, int Cpad, float* gout, void* stream) {
+  hipLaunchKernelGGL(mse_bwd_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, out,
+                     target, (long)pitch, t, loss_weight, gloss, B, C, HW, Cpad, gout, wb);
+}
 extern "C" int lgm_weighted_mse_bwd(const float* out, const float* target, int64_t pitch, const int64_t* t,
                                     const float* loss_weight, const float* gloss, int B, int C, int HW, int Cpad,
                                     float* gout, void* stream) {
   LGM_REQUIRE(out && target && gloss && gout && B > 0 && (!loss_weight || t), "weighted_mse_bwd: bad arguments");
-  hipLaunchKernelGGL(mse_bwd_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, out,
-                     target, (long)pitch, t, loss_weight, gloss, B, C, HW, Cpad, gout, (const float*)nullptr);
+  mse_bwd_launch(out, target, pitch, t, loss_weight, nullptr, gloss, B, C, HW, Cpad, gout, stream);
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1935,8 +1940,7 @@ extern "C" int lgm_weighted_mse_bwd_iw(const float* out, const float* target, in
                                        const float* loss_weight, const float* wb, const float* gloss, int B, int C, int HW,
                                        int Cpad, float* gout, void* stream) {
   LGM_REQUIRE(out && target && gloss && gout && wb && B > 0 && (!loss_weight || t), "weighted_mse_bwd_iw: bad arguments");
-  hipLaunchKernelGGL(mse_bwd_kernel, dim3(lgm_cdiv((long)B * HW * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, out,
-                     target, (long)pitch, t, loss_weight, gloss, B, C, HW, Cpad, gout, wb);
+  mse_bwd_launch(out, target, pitch, t, loss_weight, wb, gloss, B, C, HW, Cpad, gout, stream);
   LGM_LAUNCH_CHECK_AS("weighted_mse_bwd_iw");
   return LGM_OK;
 }
@@ -1958,13 +1962,11 @@ static bool slices_ok(int64_t pitch, int x_off, int sc_off, int C) {
 // target_pitch], img NCHW (normalised here when `normalize`), x_t in the x slice of xin, tab [T][8] (ddpm.py learned_table),
 // per [2][B] = (lw mse_b, vb_b), loss [1] (optional) = mean_b(per[0]) + vb_weight mean_b(per[1]).
 static bool hybrid_ok(const float* out, int64_t pitch, const float* target, int64_t target_pitch, const float* img,
-                      const float* xin, int64_t x_pitch, int x_off, const int64_t* t, const float* const* tables,
-                      const float* tab, int B, int C, int HW, int objective, int n_table) {
-  if (!out || !target || !img || !xin || !t || !tab || B <= 0 || C <= 0 || HW <= 0 || n_table <= 0) return false;
-  for (int i = 0; i < 4; ++i)
-    if (!tables[i]) return false;
-  return pitch >= 2 * (int64_t)C && target_pitch >= C && slices_ok(x_pitch, x_off, -1, C) && objective_ok(objective) &&
-         (int64_t)B * HW * pitch < ((int64_t)1 << 40);
+                      const float* xin, int64_t x_pitch, int x_off, const int64_t* t, const HybridTables& T, int B, int C, int HW,
+                      int objective) {
+  if (!out || !target || !img || !xin || !t || !T.sa || !T.s1 || !T.r || !T.rm1 || !T.tab || T.n_table <= 0) return false;
+  return B > 0 && C > 0 && HW > 0 && pitch >= 2 * (int64_t)C && target_pitch >= C && slices_ok(x_pitch, x_off, -1, C) &&
+         objective_ok(objective) && (int64_t)B * HW * pitch < ((int64_t)1 << 40);
 }
 extern "C" int lgm_hybrid_loss_fwd(const float* out, int64_t pitch, const float* target, int64_t target_pitch,
                                    const float* img, int normalize, const float* xin, int64_t x_pitch, int x_off,
@@ -1972,11 +1974,9 @@ extern "C" int lgm_hybrid_loss_fwd(const float* out, int64_t pitch, const float*
                                    const float* sqrt_recipm1, const float* loss_weight, const float* tab, int n_table,
                                    int objective, float vb_weight, int B, int C, int HW, float* per, float* loss,
                                    void* stream) {
-  const float* tables[4] = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1};
-  LGM_REQUIRE(per && hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, tables, tab, B, C, HW, objective,
-                               n_table),
-              "hybrid_loss_fwd: bad arguments");
   const HybridTables T = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, loss_weight, tab, n_table};
+  LGM_REQUIRE(per && hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, T, B, C, HW, objective),
+              "hybrid_loss_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   lgm_note_kernel("hybrid_loss_fwd_kernel");
   hipLaunchKernelGGL(hybrid_loss_fwd_kernel, dim3(B), dim3(256), 0, s, out, (long)pitch, target, (long)target_pitch, img,
@@ -1985,22 +1985,27 @@ extern "C" int lgm_hybrid_loss_fwd(const float* out, int64_t pitch, const float*
   LGM_LAUNCH_CHECK_AS("hybrid_loss_fwd");
   return LGM_OK;
 }
+static void hybrid_bwd_launch(const float* out, int64_t pitch, const float* target, int64_t target_pitch, const float* img,
+                              int normalize, const float* xin, int64_t x_pitch, int x_off, const int64_t* t,
+                              const HybridTables& T, int objective, float vb_weight, const float* wb, const float* gloss, int B,
+                              int C, int HW, float* gout, void* stream) {
+  lgm_note_kernel("hybrid_loss_bwd_kernel");
+  hipLaunchKernelGGL(hybrid_loss_bwd_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, out,
+                     (long)pitch, target, (long)target_pitch, img, normalize, xin, (long)x_pitch, x_off, (const long*)t, T,
+                     objective, gloss, vb_weight, B, C, HW, gout, wb);
+}
 extern "C" int lgm_hybrid_loss_bwd(const float* out, int64_t pitch, const float* target, int64_t target_pitch,
                                    const float* img, int normalize, const float* xin, int64_t x_pitch, int x_off,
                                    const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* sqrt_recip,
                                    const float* sqrt_recipm1, const float* loss_weight, const float* tab, int n_table,
                                    int objective, float vb_weight, const float* gloss, int B, int C, int HW, float* gout,
                                    void* stream) {
-  const float* tables[4] = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1};
-  LGM_REQUIRE(gloss && gout && gout != out &&
-                  hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, tables, tab, B, C, HW, objective,
-                            n_table),
-              "hybrid_loss_bwd: bad arguments");
   const HybridTables T = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, loss_weight, tab, n_table};
-  lgm_note_kernel("hybrid_loss_bwd_kernel");
-  hipLaunchKernelGGL(hybrid_loss_bwd_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, out,
-                     (long)pitch, target, (long)target_pitch, img, normalize, xin, (long)x_pitch, x_off, (const long*)t, T,
-                     objective, gloss, vb_weight, B, C, HW, gout, (const float*)nullptr);
+  LGM_REQUIRE(gloss && gout && gout != out &&
+                  hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, T, B, C, HW, objective),
+              "hybrid_loss_bwd: bad arguments");
+  hybrid_bwd_launch(out, pitch, target, target_pitch, img, normalize, xin, x_pitch, x_off, t, T, objective, vb_weight, nullptr,
+                    gloss, B, C, HW, gout, stream);
   LGM_LAUNCH_CHECK_AS("hybrid_loss_bwd");
   return LGM_OK;
 }
@@ -2026,16 +2031,12 @@ extern "C" int lgm_hybrid_loss_bwd_iw(const float* out, int64_t pitch, const flo
                                       const float* sqrt_recipm1, const float* loss_weight, const float* tab, int n_table,
                                       int objective, float vb_weight, const float* wb, const float* gloss, int B, int C, int HW,
                                       float* gout, void* stream) {
-  const float* tables[4] = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1};
-  LGM_REQUIRE(gloss && gout && gout != out && wb &&
-                  hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, tables, tab, B, C, HW, objective,
-                            n_table),
-              "hybrid_loss_bwd_iw: bad arguments");
   const HybridTables T = {sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1, loss_weight, tab, n_table};
-  lgm_note_kernel("hybrid_loss_bwd_kernel");
-  hipLaunchKernelGGL(hybrid_loss_bwd_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream, out,
-                     (long)pitch, target, (long)target_pitch, img, normalize, xin, (long)x_pitch, x_off, (const long*)t, T,
-                     objective, gloss, vb_weight, B, C, HW, gout, wb);
+  LGM_REQUIRE(gloss && gout && gout != out && wb &&
+                  hybrid_ok(out, pitch, target, target_pitch, img, xin, x_pitch, x_off, t, T, B, C, HW, objective),
+              "hybrid_loss_bwd_iw: bad arguments");
+  hybrid_bwd_launch(out, pitch, target, target_pitch, img, normalize, xin, x_pitch, x_off, t, T, objective, vb_weight, wb, gloss,
+                    B, C, HW, gout, stream);
   LGM_LAUNCH_CHECK_AS("hybrid_loss_bwd_iw");
   return LGM_OK;
 }

@@ -278,11 +278,10 @@ class GraphedDDPMStep:
             return hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength)
 
         def estimate(q):
-            hip_loss_estimate(gd, q[0], q[4], self.classes)
+            hip_loss_estimate(gd, q.xt, q.t, self.classes)
 
         def begin(q):                                # the saved forward, the loss, its gradient: the backward is open
-            xt, target, img, noise, t, offset = q
-            loss, ctx = hip_loss_network(gd, xt, target, img, t, noise, offset, True, self.classes)
+            loss, ctx = hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, True, self.classes)
             fp.zero_grad()
             return loss, hip_loss_backward_begin(ctx, self.one)
 

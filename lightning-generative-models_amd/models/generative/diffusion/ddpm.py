@@ -28,6 +28,7 @@ from lgm_hip.optim import EMA, FusedAdam
 
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])     # reference :25
+QSample = namedtuple("QSample", ["xt", "target", "img", "noise", "t", "offset"])     # what hip_loss_qsample returns
 
 
 _NO_RES_FOLD = os.environ.get("LGM_NO_RES_FOLD") is not None       # A/B switch: the identity residual's gradient as its own axpby launch
@@ -624,7 +625,7 @@ class Unet(nn.Module):
         out = self.final_conv.fwd(fin)
         if not save:
             return out, None
-        return out, (time_saved, tape, sm1, sm2, sm3, ups_tape, sf, fin, x, [c[0].shape for c in cats])
+        return out, NetworkTape(time_saved, tape, sm1, sm2, sm3, ups_tape, sf, fin, x, [c[0].shape for c in cats])
 
     def refresh_derived_weights(self, for_backward: bool):
         if self._flat.b3:
@@ -632,9 +633,9 @@ class Unet(nn.Module):
         if self._flat.wino:
             self._flat.refresh_wino(backward_operand=for_backward)   # U = G g G^T of the current weights (one launch)
 
-    def backward_nhwc(self, tape_all, gout):
+    def backward_nhwc(self, tape: "NetworkTape", gout):
         """Hand-written backward pass: parameter gradients into the flat gradient buffer."""
-        self.backward_run(self.backward_begin(tape_all, gout))
+        self.backward_run(self.backward_begin(tape, gout))
 
     def _flush(self, gc: GradCtx, bucket: int):
         """End of an exchange bucket (0: ups + final, 1: mid, 2: init + downs, 3: FiLM + time): the deferred slab / row
@@ -669,9 +670,9 @@ class Unet(nn.Module):
         if bucket == 3:                  # the whole gradient buffer is final
             self._flat.bind_grad_views()
 
-    def backward_begin(self, tape_all, gout):
+    def backward_begin(self, tape: "NetworkTape", gout):
         """The state the phases work on; no phase has run."""
-        return _Backward(self, tape_all, gout)
+        return _Backward(self, tape, gout)
 
     def backward_run(self, st: "_Backward", first: int = 0, last: int = 3):
         """Phases ``first`` .. ``last`` of the backward pass ``backward_begin`` opened."""
@@ -681,8 +682,8 @@ class Unet(nn.Module):
     def _backward_up(self, st: "_Backward"):
         """final conv -> final block -> up path"""
         gc, gsl, k, x_in = st.gc, st.gsl, st.k, st.x_in
-        ups_tape, sf, fin, cat_shapes, gout, *held = st.head
-        st.head = None
+        ups_tape, sf, fin, cat_shapes, gout, held = st.ups, st.final, st.fin, st.cat_shapes, st.gout, st.held
+        st.ups = st.final = st.fin = st.cat_shapes = st.gout = st.held = None
         B, S = x_in.shape[0], x_in.shape[1]
         dim = self.dim
         n = len(self.in_out)
@@ -817,18 +818,25 @@ class Unet(nn.Module):
         return y, tape, out
 
 
+# What ``Unet.forward_nhwc(save=True)`` keeps for the backward pass: per stage of ``downs`` / ``ups`` what its two blocks, its
+# attention and its resampling saved, ``sm1`` .. ``sm3`` the middle blocks', ``final`` / ``fin`` the final block's and its output.
+NetworkTape = namedtuple("NetworkTape", ["time_saved", "downs", "sm1", "sm2", "sm3", "ups", "final", "fin", "x", "cat_shapes"])
+
+
 class _Backward:
     """What the phases of ``Unet``'s backward pass hand to each other: the gradient context, the saved activations the
     later phases read, the gradients of the FiLM projections (``gss_all``, ``gsl`` its per-block views), the running
     resblock index ``k``, the gradient concat buffers (``gcats``, ``gcatF``), the current gradient ``g`` and the
-    network input.  ``head``: what the first phase alone reads, and what else is to live until it returns."""
+    network input.  ``ups`` / ``final`` / ``fin`` / ``cat_shapes`` / ``gout``: what the first phase alone reads; ``held``: what
+    else is to live until that phase returns (callers append).  It takes them all out of here before it starts."""
 
-    def __init__(self, net: Unet, tape_all, gout):
-        time_saved, tape, sm1, sm2, sm3, ups_tape, sf, fin, x_in, cat_shapes = tape_all
+    def __init__(self, net: Unet, tape: NetworkTape, gout):
+        x_in = tape.x
         rbs = net.resblocks()
         self.gc = GradCtx(net._flat, defer=True)     # weight-gradient slabs: one batched reduce per exchange bucket
-        self.time_saved, self.tape, self.mid, self.x_in = time_saved, tape, (sm1, sm2, sm3), x_in
-        self.head = (ups_tape, sf, fin, cat_shapes, gout)
+        self.time_saved, self.tape, self.mid, self.x_in = tape.time_saved, tape.downs, (tape.sm1, tape.sm2, tape.sm3), x_in
+        self.ups, self.final, self.fin, self.cat_shapes, self.gout = tape.ups, tape.final, tape.fin, tape.cat_shapes, gout
+        self.held = []
         self.gss_all = ops.new((x_in.shape[0], net._ss_total), x_in)
         self.gsl = [self.gss_all[:, o:o + 2 * rb.dim_out] for o, rb in zip(net._ss_offsets, rbs)]
         self.k = len(rbs) - 1
@@ -1158,6 +1166,11 @@ class GaussianDiffusion(nn.Module):
             raise ValueError("cond_scale != 1 needs a model built with num_classes")
         return self.model.labels(classes, B, device), scale
 
+    def objective_tables(self):
+        """the four schedule tables the objective's algebra reads, as the entry points take them (sqrt_ac .. sqrt_recipm1)"""
+        return (self.sqrt_alphas_cumprod.data_ptr(), self.sqrt_one_minus_alphas_cumprod.data_ptr(),
+                self.sqrt_recip_alphas_cumprod.data_ptr(), self.sqrt_recipm1_alphas_cumprod.data_ptr())
+
     @torch.no_grad()
     def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, classes=None,
                           cond_scale=1.0):
@@ -1181,8 +1194,7 @@ class GaussianDiffusion(nn.Module):
         B = x.shape[0]
         t = t.to(device=x.device, dtype=torch.long).contiguous()
         pred_noise, x_start = torch.empty_like(x), torch.empty_like(x)
-        tables = (self.sqrt_alphas_cumprod.data_ptr(), self.sqrt_one_minus_alphas_cumprod.data_ptr(),
-                  self.sqrt_recip_alphas_cumprod.data_ptr(), self.sqrt_recipm1_alphas_cumprod.data_ptr())
+        tables = self.objective_tables()
         per = x.numel() // max(B, 1)
         dyn = bool(clip_x_start) and self.dynamic_thresholding and x.numel() > 0
         ops.lib().lgm_model_predictions_obj(x.data_ptr(), v.data_ptr(), t.data_ptr(), *tables, OBJECTIVES[self.objective],
@@ -1324,14 +1336,14 @@ def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, sa
     ``offset`` ([B, C] or None) / ``strength``: offset noise, added to ``noise`` inside the q_sample kernel.
     ``self_cond`` (self-conditioned network only): ``True`` = estimate pass first (``hip_loss_estimate``), a tensor = that
     NCHW estimate.  ``classes``: device labels (``Unet.labels``) both passes of a class-conditional network read."""
-    xt, target, img, noise, t, offset = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength)
+    q = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength)
     if gd.model.self_condition:
         if torch.is_tensor(self_cond):
             assert self_cond.shape == img.shape
-            ops.nchw_to_nhwc(self_cond.detach().float().contiguous(), gd.model.sc_slice(xt))
+            ops.nchw_to_nhwc(self_cond.detach().float().contiguous(), gd.model.sc_slice(q.xt))
         elif self_cond:
-            hip_loss_estimate(gd, xt, t, classes)
-    return hip_loss_network(gd, xt, target, img, t, noise, offset, save, classes, normalize)
+            hip_loss_estimate(gd, q.xt, q.t, classes)
+    return hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, save, classes, normalize)
 
 
 def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None):
@@ -1341,10 +1353,8 @@ def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None):
     B, H, W, _ = xt.shape
     out, _ = net.forward_nhwc(xt, t, False, True, classes)
     ops.lib().lgm_selfcond_estimate(xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off, out.data_ptr(), ops.pitch(out),
-                                    t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
-                                    gd.sqrt_one_minus_alphas_cumprod.data_ptr(), gd.sqrt_recip_alphas_cumprod.data_ptr(),
-                                    gd.sqrt_recipm1_alphas_cumprod.data_ptr(), OBJECTIVES[gd.objective], B, net.channels,
-                                    H * W, gd.num_timesteps, ops.stream())
+                                    t.data_ptr(), *gd.objective_tables(), OBJECTIVES[gd.objective], B, net.channels, H * W,
+                                    gd.num_timesteps, ops.stream())
 
 
 def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, offset=None, strength: float = 0.0):
@@ -1367,88 +1377,77 @@ def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, of
                                        gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
                                        OBJECTIVES[gd.objective], xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
                                        target.data_ptr(), Cp, B, C, H * W, Cp, ops.stream())
-    return xt, target, img, noise, t, offset
+    return QSample(xt, target, img, noise, t, offset)
 
 
-def _hybrid_operands(gd: "GaussianDiffusion", out, target, img, normalize: bool, xt, t):
-    """what lgm_hybrid_loss_fwd and lgm_hybrid_loss_bwd share, in their order, up to ``objective``"""
-    net = gd.model
-    return (out.data_ptr(), ops.pitch(out), target.data_ptr(), ops.pitch(target), img.data_ptr(), 1 if normalize else 0,
-            xt.data_ptr(), net.in_pitch, net.x_off, t.data_ptr(), gd.sqrt_alphas_cumprod.data_ptr(),
-            gd.sqrt_one_minus_alphas_cumprod.data_ptr(), gd.sqrt_recip_alphas_cumprod.data_ptr(),
-            gd.sqrt_recipm1_alphas_cumprod.data_ptr(), gd.loss_weight.data_ptr(), gd.learned_table.data_ptr(),
-            gd.num_timesteps, OBJECTIVES[gd.objective], float(gd.vb_loss_weight))
+class LossContext:
+    """What the loss forward hands to its backward, for all four loss forms.  ``xt`` / ``normalize`` / ``per`` (the per-sample
+    terms [2, B] = (loss_weight mse_b, vb_b)) belong to the hybrid loss of a learned-variance network and stay None for the
+    weighted MSE; ``wb`` ([B], the weights iw[t_b]) is there when the forward ran under a loss-aware timestep sampler.
+    ``shape``: (B, C, H, W) of ``img``; ``tape``: None when the forward saved no activations."""
+    __slots__ = ("gd", "tape", "out", "target", "t", "shape", "img", "noise", "offset", "xt", "normalize", "per", "wb")
+
+    def __init__(self, gd, tape, out, target, t, shape, img, noise, offset):
+        self.gd, self.tape, self.out, self.target, self.t, self.shape = gd, tape, out, target, t, shape
+        self.img, self.noise, self.offset = img, noise, offset
+        self.xt = self.normalize = self.per = self.wb = None
+
+
+def _loss_form(c: LossContext):
+    """-> ((forward, backward) entry point of ``c``'s loss form - the *_iw pair when the forward leaves weights in ``c.wb`` -,
+    the operands the two share in their order (up to ``vb_weight`` / ``loss_weight``), their (B, C, HW[, Cpad]))"""
+    L, gd, (B, C, H, W), weighted = ops.lib(), c.gd, c.shape, c.wb is not None
+    if gd.learned_variance:
+        fns = (L.lgm_hybrid_loss_fwd_iw, L.lgm_hybrid_loss_bwd_iw) if weighted else (L.lgm_hybrid_loss_fwd, L.lgm_hybrid_loss_bwd)
+        return fns, (c.out.data_ptr(), ops.pitch(c.out), c.target.data_ptr(), ops.pitch(c.target), c.img.data_ptr(),
+                     1 if c.normalize else 0, c.xt.data_ptr(), gd.model.in_pitch, gd.model.x_off, c.t.data_ptr(),
+                     *gd.objective_tables(), gd.loss_weight.data_ptr(), gd.learned_table.data_ptr(), gd.num_timesteps,
+                     OBJECTIVES[gd.objective], float(gd.vb_loss_weight)), (B, C, H * W)
+    fns = (L.lgm_weighted_mse_fwd_iw, L.lgm_weighted_mse_bwd_iw) if weighted else (L.lgm_weighted_mse_fwd, L.lgm_weighted_mse_bwd)
+    return fns, (c.out.data_ptr(), c.target.data_ptr(), _r4(C), c.t.data_ptr(), gd.loss_weight.data_ptr()), (B, C, H * W, _r4(C))
 
 
 def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None, normalize=None):
     """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx).  A learned-variance network: the hybrid
     loss instead (lgm_hybrid_loss_fwd: the same MSE over the prediction lanes + vb_loss_weight times the bound's term), ``ctx``
-    then ends with the per-sample terms [2, B] = (loss_weight mse_b, vb_b), x_t and ``normalize`` - whether ``img`` is still
-    in the data range (``None``: the diffusion's auto_normalize, what the graph-replayed step hands its q_sample)."""
-    net = gd.model
+    (``LossContext``) then also holds the per-sample terms, x_t and ``normalize`` - whether ``img`` is still in the data range
+    (``None``: the diffusion's auto_normalize, what the graph-replayed step hands its q_sample)."""
     B, C, H, W = img.shape
-    Cp = _r4(C)
-    L = ops.lib()
-    st = ops.stream()
-    out, tape = net.forward_nhwc(xt, t, save, True, classes)
+    hybrid = gd.learned_variance
+    out, tape = gd.model.forward_nhwc(xt, t, save, True, classes)
     loss = ops.new((1,), img)
+    ctx = LossContext(gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
     # a loss-aware timestep sampler (training mode): the *_iw forms weight sample b by iw[t_b] and leave that weight in ``wb``
-    # for the backward, then ONE launch records the unweighted per-sample losses and rebuilds the plan of the next draw;
-    # ``ctx`` then ends with ``wb``
+    # for the backward, then ONE launch records the unweighted per-sample losses and rebuilds the plan of the next draw
     ts = gd.active_t_sampler()
     ts = ts if ts is not None and ts.loss_aware else None
     if ts is not None:
         ts.ensure_plan()
-        wb = ops.new((B,), img)
-    if getattr(net, "learned_variance", False):
-        normalize = bool(gd.auto_normalize if normalize is None else normalize)
-        per = ops.new((2, B), img)
-        head = _hybrid_operands(gd, out, target, img, normalize, xt, t)
-        ctx = (gd, tape, out, target, t, (B, C, H, W), img, noise, offset, per, xt, normalize)
-        if ts is None:
-            L.lgm_hybrid_loss_fwd(*head, B, C, H * W, per.data_ptr(), loss.data_ptr(), st)
-            return loss, ctx
-        L.lgm_hybrid_loss_fwd_iw(*head, ts.iw.data_ptr(), B, C, H * W, per.data_ptr(), wb.data_ptr(), loss.data_ptr(), st)
-        ts.record(t, per, 2, gd.vb_loss_weight)
-        return loss, ctx + (wb,)
-    per = ops.new((B,), img)
-    ctx = (gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
+        ctx.wb = ops.new((B,), img)
+    per = ops.new((2, B) if hybrid else (B,), img)
+    if hybrid:                                       # (the weighted MSE's backward reads no per-sample term: not kept)
+        ctx.xt, ctx.normalize, ctx.per = xt, bool(gd.auto_normalize if normalize is None else normalize), per
+    (fwd, _), head, dims = _loss_form(ctx)
     if ts is None:
-        L.lgm_weighted_mse_fwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
-                               B, C, H * W, Cp, per.data_ptr(), loss.data_ptr(), st)
-        return loss, ctx
-    L.lgm_weighted_mse_fwd_iw(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(), ts.iw.data_ptr(),
-                              gd.num_timesteps, B, C, H * W, Cp, per.data_ptr(), wb.data_ptr(), loss.data_ptr(), st)
-    ts.record(t, per, 1, 0.0)
-    return loss, ctx + (wb,)
+        fwd(*head, *dims, per.data_ptr(), loss.data_ptr(), ops.stream())
+    else:                                            # (the hybrid operands already hold the tables' length)
+        table = (ts.iw.data_ptr(),) if hybrid else (ts.iw.data_ptr(), gd.num_timesteps)
+        fwd(*head, *table, *dims, per.data_ptr(), ctx.wb.data_ptr(), loss.data_ptr(), ops.stream())
+        ts.record(t, per, 2 if hybrid else 1, gd.vb_loss_weight if hybrid else 0.0)
+    return loss, ctx
 
 
-def hip_loss_backward_begin(ctx, gl):
+def hip_loss_backward_begin(ctx: LossContext, gl):
     """Loss gradient (``gl``: device scalar [1] = dL/dloss) and the opened UNet backward (``Unet.backward_run``)."""
-    gd, tape, out, target, t, (B, C, H, W) = ctx[:6]
-    if tape is None:
+    if ctx.tape is None:
         raise RuntimeError("p_losses forward ran without saving activations")
-    Cp = _r4(C)
-    gout = ops.new(out.shape, out)
-    if getattr(gd.model, "learned_variance", False):
-        img, xt, normalize = ctx[6], ctx[10], ctx[11]
-        head = _hybrid_operands(gd, out, target, img, normalize, xt, t)
-        if len(ctx) > 12:                # the forward ran under a loss-aware timestep sampler: its per-sample weights
-            ops.lib().lgm_hybrid_loss_bwd_iw(*head, ctx[12].data_ptr(), gl.data_ptr(), B, C, H * W, gout.data_ptr(), ops.stream())
-        else:
-            ops.lib().lgm_hybrid_loss_bwd(*head, gl.data_ptr(), B, C, H * W, gout.data_ptr(), ops.stream())
-        st = gd.model.backward_begin(tape, gout)
-        st.head += (out, target, img, xt) + tuple(ctx[12:])
-        return st
-    if len(ctx) > 9:
-        ops.lib().lgm_weighted_mse_bwd_iw(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(), gd.loss_weight.data_ptr(),
-                                          ctx[9].data_ptr(), gl.data_ptr(), B, C, H * W, Cp, gout.data_ptr(), ops.stream())
-    else:
-        ops.lib().lgm_weighted_mse_bwd(out.data_ptr(), target.data_ptr(), Cp, t.data_ptr(),
-                                       gd.loss_weight.data_ptr(), gl.data_ptr(), B, C, H * W, Cp,
-                                       gout.data_ptr(), ops.stream())
-    st = gd.model.backward_begin(tape, gout)
-    st.head += (out, target) + tuple(ctx[9:])    # let go of with the phase that reads ``gout``, also when ``ctx`` is gone by then
+    gout = ops.new(ctx.out.shape, ctx.out)
+    (_, bwd), head, dims = _loss_form(ctx)
+    weights = () if ctx.wb is None else (ctx.wb.data_ptr(),)     # what the forward left under a loss-aware timestep sampler
+    bwd(*head, *weights, gl.data_ptr(), *dims, gout.data_ptr(), ops.stream())
+    st = ctx.gd.model.backward_begin(ctx.tape, gout)
+    # what the launch read: let go of with the phase that reads ``gout``, also when ``ctx`` is gone by then
+    st.held += [ctx.out, ctx.target] + ([ctx.img, ctx.xt] if ctx.gd.learned_variance else []) + [ctx.wb]
     return st
 
 
@@ -1465,7 +1464,7 @@ class _PLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         gl = gloss.detach().float().reshape(1).contiguous()
-        ctx.stuff[0].model.backward_run(hip_loss_backward_begin(ctx.stuff, gl))
+        ctx.stuff.gd.model.backward_run(hip_loss_backward_begin(ctx.stuff, gl))
         ctx.stuff = None
         return None, None, None, None, None, None, None, None, None, None
 

@@ -277,14 +277,14 @@ def test_training_step_matches_fixture(case, parity, gvar_bound):
     from models.generative.diffusion import ddpm as D
     net._flat.zero_grad()
     loss, ctx = D.hip_loss_forward(gd, case.img.to(dev), case.t.to(dev), case.noise.to(dev), True, True)
-    per, out = ctx[9].double().cpu(), ctx[2]
+    per, out = ctx.per.double().cpu(), ctx.out
     parity("unet_out, all 6 channels", rel(out[..., :6].permute(0, 3, 1, 2), fx["unet_out64"]), RTOL)
     parity("loss", abs(float(loss) - float(fx["loss64"])) / float(fx["loss64"]), RTOL)
     for b in range(case.B):
         parity(f"mse_b[{b}]", abs(per[0, b] - fx["mse_b64"][b]) / fx["mse_b64"][b], RTOL)
         parity(f"vb_b[{b}] (t = {int(case.t[b])})", abs(per[1, b] - fx["vb_b64"][b]) / fx["vb_b64"][b], RTOL)
     st = D.hip_loss_backward_begin(ctx, torch.ones(1, device=dev))
-    gout = st.head[4].clone()
+    gout = st.gout.clone()
     net.backward_run(st)
     torch.cuda.synchronize()
     g = gout[..., :6].permute(0, 3, 1, 2).double().cpu()
@@ -343,9 +343,9 @@ def test_final_conv_of_the_64_channel_network_runs_the_narrow_kernels(dev, parit
     assert _last() == "narrow1x1_fwd_kernel"
     net._flat.zero_grad()
     loss, ctx = D.hip_loss_forward(gd, img, t, nz, True, True)
-    fin = ctx[1][7].clone()
+    fin = ctx.tape.fin.clone()
     st = D.hip_loss_backward_begin(ctx, torch.ones(1, device=dev))
-    gout = st.head[4].clone()
+    gout = st.gout.clone()
     fc, fp = net.final_conv, net._flat
     gx = torch.empty_like(fin)
     ops.conv_yx(fc.geom(2, 8, 8), gout, fp.ptr(fc.weight), None, None, gx, fp.tptr(fc.weight))

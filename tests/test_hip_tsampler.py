@@ -240,7 +240,7 @@ def _loss_and_gout(gd, img, t, noise):
     gd.model._flat.zero_grad()
     loss, ctx = D.hip_loss_forward(gd, img, t, noise, True, True)
     st = D.hip_loss_backward_begin(ctx, torch.ones(1, device=img.device))
-    gout = st.head[4].clone()
+    gout = st.gout.clone()
     gd.model.backward_run(st)
     torch.cuda.synchronize()
     return loss.clone(), gout, ctx
@@ -270,12 +270,12 @@ def test_weighted_loss_and_gradient(dev, parity, T, learned):
     assert weighted and iw64[t.cpu().numpy()].max() / iw64[t.cpu().numpy()].min() > 2.0
     # L_b: the unweighted per-sample terms the plain forward left, in float64
     if learned:
-        per = ctx_u[9].double().cpu().numpy()
-        assert torch.equal(ctx[9], ctx_u[9]), "the history records the unweighted terms"
+        per = ctx_u.per.double().cpu().numpy()
+        assert torch.equal(ctx.per, ctx_u.per), "the history records the unweighted terms"
         L64 = per[0] + gd.vb_loss_weight * per[1]
-        L32 = R.per_sample_loss(ctx_u[9].cpu().numpy(), gd.vb_loss_weight)
+        L32 = R.per_sample_loss(ctx_u.per.cpu().numpy(), gd.vb_loss_weight)
     else:
-        out, target = ctx_u[2].double().cpu(), ctx_u[3].double().cpu()
+        out, target = ctx_u.out.double().cpu(), ctx_u.target.double().cpu()
         mse = ((out[..., :3] - target[..., :3]) ** 2).mean(dim=(1, 2, 3)).numpy()
         L64 = gd.loss_weight.double().cpu().numpy()[t.cpu().numpy()] * mse
         L32 = None
@@ -291,7 +291,7 @@ def test_weighted_loss_and_gradient(dev, parity, T, learned):
     for b in range(B):
         e = float((gout_w[b].double().cpu() - g_want[b]).norm() / g_want[b].norm())
         parity(f"T = {T}: output gradient of sample {b} (t = {int(tn[b])})", e, bound)
-    assert torch.equal(ctx[-1].cpu(), torch.as_tensor(iw_dev)[t.cpu()]), "wb = iw[t_b] of the plan the step drew from"
+    assert torch.equal(ctx.wb.cpu(), torch.as_tensor(iw_dev)[t.cpu()]), "wb = iw[t_b] of the plan the step drew from"
     # the step recorded the UNWEIGHTED losses behind the loss, and the plan now belongs to the updated rows
     if L32 is None:                                           # (per [B] is not kept: the rows' newest entries against L_b)
         once = [1, 4, 5, 7]                                   # the samples whose timestep the batch holds once

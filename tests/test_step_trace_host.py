@@ -10,7 +10,8 @@ step then runs on the CPU, and every case pins
   * the memory pool every graph is captured into, the random stream around a capture, and the eager fallback when
     capture fails.
 
-``ModuleFastStep`` and ``WGANFastStep`` are driven with stub modules at the end of the file."""
+A further test pins what the first backward phase is the last holder of, for the four loss forms.  ``ModuleFastStep`` and
+``WGANFastStep`` are driven with stub modules at the end of the file."""
 import contextlib
 
 import pytest
@@ -18,7 +19,10 @@ import torch
 
 B = 2
 KINDS = {"plain": dict(), "selfcond": dict(self_condition=True), "classes": dict(num_classes=3),
-         "offset": dict(offset_noise_strength=0.1)}
+         "offset": dict(offset_noise_strength=0.1),
+         # the other three loss forms: hybrid, weighted MSE and hybrid under a loss-aware timestep sampler (the *_iw entry points)
+         "learned": dict(learned_variance=True), "tsampler": dict(t_sampler="loss_second_moment"),
+         "learned_tsampler": dict(learned_variance=True, t_sampler="loss_second_moment")}
 # layout -> (_ONE_GRAPH, _STEP_PIPELINE, with a gradient exchange, the bucket phases each graph holds)
 WHOLE, HALVES, BUCKETS = ((0, 1, 2, 3),), ((0, 1), (2, 3)), ((0,), (1,), (2,), (3,))
 LAYOUTS = {"one_graph": (True, False, False, WHOLE), "two_graphs": (False, False, False, HALVES),
@@ -348,6 +352,44 @@ def test_failed_capture_falls_back_to_the_eager_step(session, kind, capsys):
     n = _names(eager[1]).index("lgm_adam_step")
     assert _norm(again[:n]) == _norm(eager[1][:n]) and _names(again[n:]) == ["lgm_adam_step"]
     assert capsys.readouterr().err == ""
+
+
+LOSS_FORMS = {"mse": "plain", "mse_iw": "tsampler", "hybrid": "learned", "hybrid_iw": "learned_tsampler"}
+
+
+def _tensors(saved):
+    """every tensor in a nest of tuples and lists"""
+    if torch.is_tensor(saved):
+        return [saved]
+    return [t for s in saved for t in _tensors(s)] if isinstance(saved, (tuple, list)) else []
+
+
+@pytest.mark.parametrize("form", list(LOSS_FORMS))
+def test_first_backward_phase_lets_go_of_what_it_alone_reads(session, form):
+    """With the loss context gone, phase 0 of the backward pass (final conv, final block, up path) is the last holder of the
+    final block's output, the output gradient, the network output, the target, the sampler's per-sample weights and what the
+    up path saved: all of them are dead when it returns.  What the middle and the down path saved lives on for their phases."""
+    import weakref
+    from models.generative.diffusion import ddpm as D
+    m, _, (x, _) = session.ddpm(LOSS_FORMS[form])
+    gd = m.ema.online_model
+    noise = torch.randn(x.shape, generator=torch.Generator().manual_seed(2))
+    _, ctx = D.hip_loss_forward(gd, x, torch.tensor([0, 9]), noise, True, True)
+    assert (ctx.wb is not None) == form.endswith("_iw") and (ctx.per is not None) == form.startswith("hybrid")
+    st = D.hip_loss_backward_begin(ctx, torch.ones(1))
+    tape = ctx.tape
+    later = _tensors([tape.time_saved, tape.downs, tape.sm1, tape.sm2, tape.sm3, tape.x])
+    shared = {t.untyped_storage().data_ptr() for t in later}     # (the concat buffers: the down path wrote their skip halves)
+    up = [t for t in _tensors([tape.ups, tape.final]) if t.untyped_storage().data_ptr() not in shared]
+    assert len(up) > 20 and len(later) > 20
+    dead = [weakref.ref(t) for t in [tape.fin, st.gout, ctx.out, ctx.target] + up + ([] if ctx.wb is None else [ctx.wb])]
+    alive = [weakref.ref(t) for t in _tensors([tape.downs, tape.sm1, tape.sm2, tape.sm3])]
+    del ctx, tape, later, up
+    assert all(r() is not None for r in dead)
+    gd.model.backward_run(st, 0, 0)
+    assert [i for i, r in enumerate(dead) if r() is not None] == []
+    assert all(r() is not None for r in alive)
+    assert st.held is None and st.gout is None and st.fin is None and st.ups is None and st.final is None
 
 
 # ---- ModuleFastStep / WGANFastStep on stub modules ------------------------------------------------------------------

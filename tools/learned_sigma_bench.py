@@ -164,13 +164,16 @@ def measure(a, here):
         nz = torch.randn(B, 3, S, S, generator=gg).to(dev)
         t = torch.randint(0, 1000, (B,), generator=gg).to(dev)
         t[0] = 0
-        xt, target, img, nz, t, _ = D.hip_loss_qsample(gd_l, img, t, nz, True)
+        q = D.hip_loss_qsample(gd_l, img, t, nz, True)
+        target, t = q.target, q.t
         out8 = torch.randn(B, S, S, 8, device=dev)
         out4 = out8[..., :4].contiguous()
         per2, per1, loss = torch.empty(2, B, device=dev), torch.empty(B, device=dev), torch.empty(1, device=dev)
         g8, g4, one = torch.empty_like(out8), torch.empty_like(out4), torch.ones(1, device=dev)
         L, st = ops.lib(), ops.stream()
-        head = D._hybrid_operands(gd_l, out8, target, img, True, xt, t)
+        ctx = D.LossContext(gd_l, None, out8, target, t, tuple(q.img.shape), q.img, q.noise, q.offset)
+        ctx.xt, ctx.normalize = q.xt, True
+        head = D._loss_form(ctx)[1]
         lw = gd_p.loss_weight.data_ptr()
         return {
             "hybrid_fwd_us": alone(torch, lambda: L.lgm_hybrid_loss_fwd(*head, B, 3, S * S, per2.data_ptr(), loss.data_ptr(), st)),

@@ -180,10 +180,12 @@ def measure(a, here):
     gg = torch.Generator().manual_seed(2)
     img, nz = torch.rand(FULL, 3, 32, 32, generator=gg).to(dev), torch.randn(FULL, 3, 32, 32, generator=gg).to(dev)
     t = torch.randint(0, T, (FULL,), generator=gg).to(dev)
-    xt, target, img, nz, t, _ = D.hip_loss_qsample(gd_l, img, t, nz, True)
+    q = D.hip_loss_qsample(gd_l, img, t, nz, True)
     out8 = torch.randn(FULL, 32, 32, 8, device=dev)
     per2, wb, loss = torch.empty(2, FULL, device=dev), torch.empty(FULL, device=dev), torch.empty(1, device=dev)
-    head = D._hybrid_operands(gd_l, out8, target, img, True, xt, t)
+    ctx = D.LossContext(gd_l, None, out8, q.target, q.t, tuple(q.img.shape), q.img, q.noise, q.offset)
+    ctx.xt, ctx.normalize = q.xt, True
+    head = D._loss_form(ctx)[1]
     launches["hybrid_fwd_us"] = alone(torch, lambda: L.lgm_hybrid_loss_fwd(*head, FULL, 3, 32 * 32, per2.data_ptr(), loss.data_ptr(), st))
     launches["hybrid_fwd_iw_us"] = alone(torch, lambda: L.lgm_hybrid_loss_fwd_iw(*head, iw.data_ptr(), FULL, 3, 32 * 32, per2.data_ptr(),
                                                                                  wb.data_ptr(), loss.data_ptr(), st))
