@@ -1139,6 +1139,38 @@ int lgm_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n
                          const float* scale_dev, int decoupled, void* stream);
 int lgm_grad_accumulate(float* dst, const float* src, int64_t n, int overwrite, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Dropout without a mask tensor (additions under ABI 8; csrc/lgm_philox.h).
+ * For an activation [B, HW, C] (C % 4 == 0) the mask is a pure function of (key, layer, pass, element):
+ *   n = (b HW + pix) C + c (the logical index, pitches play no part), q = n >> 2 as a 64-bit number,
+ *   Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) of
+ *   counter (q & 0xffffffff, q >> 32, layer, pass) under key (key[0], key[1]) gives four words = channels c .. c + 3,
+ *   an element is kept iff its word >= thr, thr = min(2^32 - 1, floor(p 2^32)); kept -> fl32(v * scale), dropped -> +0,
+ *   scale = float32(1 / (1 - p)).  `key`: DEVICE pointer to two uint32 (8-byte aligned), read by the kernels, so that a graph
+ *   replay sees the key its own draw wrote.  `thr` crosses as int64 (0 ... 2^32 - 1).
+ * lgm_dropout_fwd / lgm_dropout_bwd: in place on a pitched tensor (the activation / the gradient arriving for it).
+ * lgm_gn_fwd_drop: lgm_gn_fwd (planes == NULL) or lgm_gn_fwd_planes whose stored y goes through the mask, in the same launch on
+ *   the one-pass plans (lgm_gn_plan nv > 0); on the two-pass plans lgm_dropout_fwd's kernel follows on y.
+ * lgm_gn_bwd_drop: lgm_gn_bwd / lgm_gn_bwd_deferred (gy given, gy_planes NULL) or lgm_gn_bwd_planes (gy NULL) whose gy goes
+ *   through the mask as it is loaded (planes: after they are summed).  On the two-pass plans lgm_dropout_bwd's kernel masks
+ *   gy IN PLACE first: gy must be the caller's to overwrite.  rows / desc: both NULL or both given.
+ * ------------------------------------------------------------------------------------- */
+int lgm_dropout_fwd(float* x, int64_t pitch, int B, int HW, int C, const void* key, int layer, int pass, int64_t thr,
+                    float scale, void* stream);
+int lgm_dropout_bwd(float* g, int64_t pitch, int B, int HW, int C, const void* key, int layer, int pass, int64_t thr,
+                    float scale, void* stream);
+int lgm_gn_fwd_drop(const float* planes, int64_t plane_stride, int splits, const float* conv_bias, float* x,
+                    int64_t x_pitch, int B, int HW, int C, int G, float eps, const float* gamma, const float* beta,
+                    const float* ss, int64_t ss_pitch, int act, const float* res, int64_t res_pitch, float* y,
+                    int64_t y_pitch, float* mean, float* rstd, float* coefA, float* coefB, const void* key, int layer,
+                    int pass, int64_t thr, float scale, void* stream);
+int lgm_gn_bwd_drop(const float* x, int64_t x_pitch, float* gy, int64_t gy_pitch, const float* gy_planes,
+                    int64_t plane_stride, int splits, int B, int HW, int C, int G, const float* gamma, const float* beta,
+                    const float* ss, int64_t ss_pitch, int act, const float* mean, const float* rstd, const float* coefA,
+                    const float* coefB, float* gx, int64_t gx_pitch, int accumulate_gx, float* ggamma, float* gbeta,
+                    float affine_beta, float* gss, int64_t gss_pitch, float gss_beta, float* workspace, float* rows,
+                    int64_t* desc, const void* key, int layer, int pass, int64_t thr, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "lgm_common.h"
+#include "lgm_philox.h"
 
 namespace {
 
@@ -186,16 +187,20 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
 // apply pass) and the second launch disappears.  Same thread -> (pixel lane, channel quad) map and
 // the same fixed-order reductions as gn_stats_kernel.
 // ---------------------------------------------------------------------------------------
-template <int NT, int NV>
-__global__ __launch_bounds__(NT) void gn_fused_fwd_kernel(const float* __restrict__ x, long pitch, int HW, int C, int G,
-                                                           int CB, float eps, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ ss,
-                                                           long ss_pitch, int act, const float* __restrict__ res,
-                                                           long res_pitch, float* __restrict__ y, long y_pitch,
-                                                           float* __restrict__ mean, float* __restrict__ rstd,
-                                                           float* __restrict__ A, float* __restrict__ Bc,
-                                                           const float* __restrict__ planes, long pstride, int splits,
-                                                           const float* __restrict__ cbias, float* __restrict__ xw) {
+// DROP: the dropout variant (lgm_philox.h) - the stored value goes through the mask of (key, layer, pass, element) first.
+// The body is shared; gn_fused_fwd_kernel instantiates it with DROP = false, where every dropout statement is discarded
+// at compile time.
+#define GN_FWD_PARAMS                                                                                                      \
+  const float *__restrict__ x, long pitch, int HW, int C, int G, int CB, float eps, const float *__restrict__ gamma,       \
+      const float *__restrict__ beta, const float *__restrict__ ss, long ss_pitch, int act, const float *__restrict__ res, \
+      long res_pitch, float *__restrict__ y, long y_pitch, float *__restrict__ mean, float *__restrict__ rstd,             \
+      float *__restrict__ A, float *__restrict__ Bc, const float *__restrict__ planes, long pstride, int splits,           \
+      const float *__restrict__ cbias, float *__restrict__ xw
+#define GN_FWD_ARGS                                                                                                      \
+  x, pitch, HW, C, G, CB, eps, gamma, beta, ss, ss_pitch, act, res, res_pitch, y, y_pitch, mean, rstd, A, Bc, planes, \
+      pstride, splits, cbias, xw
+template <int NT, int NV, bool DROP>
+__device__ __forceinline__ void gn_fused_fwd_body(GN_FWD_PARAMS, const LgmDrop& dr) {
   __shared__ float sh[NT * 4];
   __shared__ float chs[256];
   __shared__ float gmean[64], grstd[64];
@@ -293,6 +298,11 @@ __global__ __launch_bounds__(NT) void gn_fused_fwd_kernel(const float* __restric
     for (int k = 0; k < NV; ++k)
       r[k] = *reinterpret_cast<const f32x4*>(res + ((long)b * HW + pl + k * ppb) * res_pitch + c0 + q * 4);
   }
+  unsigned dk0 = 0, dk1 = 0;
+  if constexpr (DROP) {
+    dk0 = dr.key[0];
+    dk1 = dr.key[1];
+  }
   float pg = 0.f, pbeta = 0.f, psc = 1.f, psh = 0.f;
   if (tid < CB) {
     pg = gamma[c0 + tid];
@@ -348,8 +358,27 @@ __global__ __launch_bounds__(NT) void gn_fused_fwd_kernel(const float* __restric
       for (int e = 0; e < 4; ++e) z[e] = silu_f(z[e]);
     }
     if (res) z += r[k];
+    if constexpr (DROP) z = lgm_drop4(dr, dk0, dk1, ((long)b * HW + pl + k * ppb) * C + c0 + q * 4, z);
     *reinterpret_cast<f32x4*>(y + ((long)b * HW + pl + k * ppb) * y_pitch + c0 + q * 4) = z;
   }
+}
+
+template <int NT, int NV>
+__global__ __launch_bounds__(NT) void gn_fused_fwd_kernel(const float* __restrict__ x, long pitch, int HW, int C, int G,
+                                                           int CB, float eps, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, const float* __restrict__ ss,
+                                                           long ss_pitch, int act, const float* __restrict__ res,
+                                                           long res_pitch, float* __restrict__ y, long y_pitch,
+                                                           float* __restrict__ mean, float* __restrict__ rstd,
+                                                           float* __restrict__ A, float* __restrict__ Bc,
+                                                           const float* __restrict__ planes, long pstride, int splits,
+                                                           const float* __restrict__ cbias, float* __restrict__ xw) {
+  gn_fused_fwd_body<NT, NV, false>(GN_FWD_ARGS, LgmDrop{});
+}
+
+template <int NT, int NV>
+__global__ __launch_bounds__(NT) void gn_fused_fwd_drop_kernel(GN_FWD_PARAMS, LgmDrop dr) {
+  gn_fused_fwd_body<NT, NV, true>(GN_FWD_ARGS, dr);
 }
 
 // backward pass 1: S1[b,c] = sum_hw gz, S2[b,c] = sum_hw gz * xhat
@@ -565,19 +594,19 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
 // so both are read once instead of twice (reduce pass + apply pass).  Same maps, same fixed-order
 // reductions and the same coefficient algebra as gn_bwd_reduce_kernel + gn_bwd_apply_kernel; the
 // gamma/beta reduction over the batch (needs every block's S1/S2) is the small kernel below.
-template <int NT, int NV>
-__global__ __launch_bounds__(NT) void gn_fused_bwd_kernel(const float* __restrict__ x, long x_pitch,
-                                                           const float* __restrict__ gy, long gy_pitch,
-                                                           const float* __restrict__ A, const float* __restrict__ Bc,
-                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                           int HW, int C, int G, int CB, int act,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           const float* __restrict__ ss, long ss_pitch,
-                                                           float* __restrict__ gss, long gss_pitch, float gss_beta,
-                                                           float* __restrict__ S1, float* __restrict__ S2,
-                                                           float* __restrict__ gx, long gx_pitch, int accumulate,
-                                                           float* __restrict__ T, const float* __restrict__ planes,
-                                                           long pstride, int splits, float* add_out, long add_pitch) {
+// DROP: the dropout variant - gy (summed from its planes first) goes through the mask the forward applied as it is loaded.
+#define GN_BWD_PARAMS                                                                                                       \
+  const float *__restrict__ x, long x_pitch, const float *__restrict__ gy, long gy_pitch, const float *__restrict__ A,      \
+      const float *__restrict__ Bc, const float *__restrict__ mean, const float *__restrict__ rstd, int HW, int C, int G,   \
+      int CB, int act, const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ ss,       \
+      long ss_pitch, float *__restrict__ gss, long gss_pitch, float gss_beta, float *__restrict__ S1, float *__restrict__ S2, \
+      float *__restrict__ gx, long gx_pitch, int accumulate, float *__restrict__ T, const float *__restrict__ planes,        \
+      long pstride, int splits, float *add_out, long add_pitch
+#define GN_BWD_ARGS                                                                                                        \
+  x, x_pitch, gy, gy_pitch, A, Bc, mean, rstd, HW, C, G, CB, act, gamma, beta, ss, ss_pitch, gss, gss_pitch, gss_beta, S1, \
+      S2, gx, gx_pitch, accumulate, T, planes, pstride, splits, add_out, add_pitch
+template <int NT, int NV, bool DROP>
+__device__ __forceinline__ void gn_fused_bwd_body(GN_BWD_PARAMS, const LgmDrop& dr) {
   __shared__ float sh[NT * 8];
   __shared__ float wa1[256], wa2[256];
   __shared__ __align__(16) float cP[256], cQ[256], cR[256];
@@ -623,6 +652,11 @@ __global__ __launch_bounds__(NT) void gn_fused_bwd_kernel(const float* __restric
   } else {
 #pragma unroll
     for (int k = 0; k < NV; ++k) g[k] = *reinterpret_cast<const f32x4*>(gb + (long)(pl + k * ppb) * gy_pitch);
+  }
+  if constexpr (DROP) {
+    const unsigned dk0 = dr.key[0], dk1 = dr.key[1];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) g[k] = lgm_drop4(dr, dk0, dk1, ((long)b * HW + pl + k * ppb) * C + c, g[k]);
   }
   if (add_out) {
     // add_out += gy: the gradient of an identity residual that leaves the block beside this norm (ResnetBlock with
@@ -751,6 +785,46 @@ __global__ __launch_bounds__(NT) void gn_fused_bwd_kernel(const float* __restric
   }
 }
 
+template <int NT, int NV>
+__global__ __launch_bounds__(NT) void gn_fused_bwd_kernel(const float* __restrict__ x, long x_pitch,
+                                                           const float* __restrict__ gy, long gy_pitch,
+                                                           const float* __restrict__ A, const float* __restrict__ Bc,
+                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                           int HW, int C, int G, int CB, int act,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const float* __restrict__ ss, long ss_pitch,
+                                                           float* __restrict__ gss, long gss_pitch, float gss_beta,
+                                                           float* __restrict__ S1, float* __restrict__ S2,
+                                                           float* __restrict__ gx, long gx_pitch, int accumulate,
+                                                           float* __restrict__ T, const float* __restrict__ planes,
+                                                           long pstride, int splits, float* add_out, long add_pitch) {
+  gn_fused_bwd_body<NT, NV, false>(GN_BWD_ARGS, LgmDrop{});
+}
+
+template <int NT, int NV>
+__global__ __launch_bounds__(NT) void gn_fused_bwd_drop_kernel(GN_BWD_PARAMS, LgmDrop dr) {
+  gn_fused_bwd_body<NT, NV, true>(GN_BWD_ARGS, dr);
+}
+
+// Stand-alone dropout, in place on a pitched [npix][C] tensor: the device-level statement of the mask (lgm_philox.h) and the
+// fallback beside the GroupNorm plans without a fused variant.  Forward (activation) and backward (its gradient) are the
+// same map.
+__device__ __forceinline__ void dropout_body(float* __restrict__ x, long pitch, long npix, int C, const LgmDrop& dr) {
+  const int c4n = C / 4;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npix * c4n) return;
+  const long pix = i / c4n;
+  const int c = (int)(i % c4n) * 4;
+  float* p = x + pix * pitch + c;
+  *reinterpret_cast<f32x4*>(p) = lgm_drop4(dr, dr.key[0], dr.key[1], pix * C + c, *reinterpret_cast<const f32x4*>(p));
+}
+__global__ __launch_bounds__(256) void dropout_fwd_kernel(float* __restrict__ x, long pitch, long npix, int C, LgmDrop dr) {
+  dropout_body(x, pitch, npix, C, dr);
+}
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(float* __restrict__ g, long pitch, long npix, int C, LgmDrop dr) {
+  dropout_body(g, pitch, npix, C, dr);
+}
+
 __global__ __launch_bounds__(256) void gn_bwd_affine_kernel(const float* __restrict__ S1, const float* __restrict__ S2,
                                                             const float* __restrict__ ss, long ss_pitch, int B, int C,
                                                             float* __restrict__ ggamma, float* __restrict__ gbeta,
@@ -867,7 +941,7 @@ static int gn_fwd_impl(const float* x, int64_t x_pitch, int B, int HW, int C, in
                        const float* gamma, const float* beta, const float* ss, int64_t ss_pitch,
                        int act, const float* res, int64_t res_pitch, float* y, int64_t y_pitch,
                        float* mean, float* rstd, float* coefA, float* coefB, const float* planes, long pstride,
-                       int splits, const float* cbias, void* stream) {
+                       int splits, const float* cbias, void* stream, const LgmDrop* drop = nullptr) {
   if (int rc = gn_check(B, HW, C, G)) return rc;
   LGM_REQUIRE(x && gamma && beta && y && mean && rstd && coefA && coefB, "gn_fwd: null pointer");
   LGM_REQUIRE(x_pitch % 4 == 0 && y_pitch % 4 == 0 && (!res || res_pitch % 4 == 0), "gn_fwd: pitch %% 4 != 0");
@@ -884,12 +958,25 @@ static int gn_fwd_impl(const float* x, int64_t x_pitch, int B, int HW, int C, in
                        rstd, coefA, coefB, planes, pstride, splits, cbias, (float*)x);                                  \
     lgm_note_kernel(LGM_KNAME("gn_fused_fwd_kernel<" #NTV ", " #NVV ">"));                                              \
   } while (0)
+#define GN_FUSED_DROP(NTV, NVV)                                                                                           \
+  hipLaunchKernelGGL((gn_fused_fwd_drop_kernel<NTV, NVV>), dim3(B * (C / cb)), dim3(NTV), 0, s, x, (long)x_pitch, HW, C,  \
+                     G, cb, eps, gamma, beta, ss, (long)ss_pitch, act, res, (long)res_pitch, y, (long)y_pitch, mean,     \
+                     rstd, coefA, coefB, planes, pstride, splits, cbias, (float*)x, *drop)
+    if (drop) {     // the dropout variants of the same pairs (not noted: the kernel ledgers list the plain kernels)
+      if (nt == 1024) { if (nv == 4) GN_FUSED_DROP(1024, 4); else GN_FUSED_DROP(1024, 8); }
+      else if (nt == 256) { if (nv == 1) GN_FUSED_DROP(256, 1); else if (nv == 2) GN_FUSED_DROP(256, 2); else if (nv == 4) GN_FUSED_DROP(256, 4); else GN_FUSED_DROP(256, 8); }
+      else if (nt == 128) GN_FUSED_DROP(128, 1);
+      else GN_FUSED_DROP(64, 1);
+      LGM_LAUNCH_CHECK();
+      return LGM_OK;
+    }
     // the pairs of gn_fused_pair, which is all gn_plan returns
     if (nt == 1024) { if (nv == 4) GN_FUSED(1024, 4); else GN_FUSED(1024, 8); }
     else if (nt == 256) { if (nv == 1) GN_FUSED(256, 1); else if (nv == 2) GN_FUSED(256, 2); else if (nv == 4) GN_FUSED(256, 4); else GN_FUSED(256, 8); }
     else if (nt == 128) GN_FUSED(128, 1);
     else GN_FUSED(64, 1);
 #undef GN_FUSED
+#undef GN_FUSED_DROP
     LGM_LAUNCH_CHECK();
     return LGM_OK;
   }
@@ -905,6 +992,8 @@ static int gn_fwd_impl(const float* x, int64_t x_pitch, int B, int HW, int C, in
   hipLaunchKernelGGL(gn_apply_kernel, dim3(lgm_cdiv(npix * (C / 4), 256)), dim3(256), 0, s, x, (long)x_pitch, coefA,
                      coefB, res, (long)res_pitch, y, (long)y_pitch, npix, HW, C, act);
   lgm_note_kernel(wide ? LGM_KNAME("gn_stats_kernel<1024>") : LGM_KNAME("gn_stats_kernel<256>"));
+  if (drop)   // two-pass plan: no fused variant, the stand-alone kernel follows on y
+    hipLaunchKernelGGL(dropout_fwd_kernel, dim3(lgm_cdiv(npix * (C / 4), 256)), dim3(256), 0, s, y, (long)y_pitch, npix, C, *drop);
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -1060,7 +1149,7 @@ static int gn_bwd_impl(const float* x, int64_t x_pitch, const float* gy, int64_t
                        int accumulate_gx, float* ggamma, float* gbeta, float affine_beta, float* gss,
                        int64_t gss_pitch, float gss_beta, float* workspace, float* rows, int64_t* desc,
                        void* stream, const float* planes = nullptr, long pstride = 0, int splits = 0,
-                       float* add_out = nullptr, long add_pitch = 0) {
+                       float* add_out = nullptr, long add_pitch = 0, const LgmDrop* drop = nullptr) {
   if (desc) desc[6] = 0;      // nothing deferred unless the one-pass kernel below takes it
   if (int rc = gn_check(B, HW, C, G)) return rc;
   LGM_REQUIRE(x && (gy || planes) && gamma && beta && mean && rstd && coefA && coefB && gx && ggamma && gbeta && workspace,
@@ -1087,11 +1176,23 @@ static int gn_bwd_impl(const float* x, int64_t x_pitch, const float* gy, int64_t
                        splits, add_out, add_pitch);                                                                       \
     lgm_note_kernel(LGM_KNAME("gn_fused_bwd_kernel<" #NTV ", " #NVV ">"));                                                \
   } while (0)
+#define GN_FUSED_DROP(NTV, NVV)                                                                                             \
+  hipLaunchKernelGGL((gn_fused_bwd_drop_kernel<NTV, NVV>), dim3(B * (C / cb)), dim3(NTV), 0, s, x, (long)x_pitch, gy,       \
+                     (long)gy_pitch, coefA, coefB, mean, rstd, HW, C, G, cb, act, gamma, beta, ss, (long)ss_pitch, gss,    \
+                     (long)gss_pitch, gss_beta, S1, S2, gx, (long)gx_pitch, accumulate_gx, rows, planes, pstride, splits,  \
+                     add_out, add_pitch, *drop)
+      if (drop) {
+        if (nt == 1024) { if (nv == 4) GN_FUSED_DROP(1024, 4); else GN_FUSED_DROP(1024, 8); }
+        else if (nt == 256) { if (nv == 1) GN_FUSED_DROP(256, 1); else if (nv == 2) GN_FUSED_DROP(256, 2); else if (nv == 4) GN_FUSED_DROP(256, 4); else GN_FUSED_DROP(256, 8); }
+        else if (nt == 128) GN_FUSED_DROP(128, 1);
+        else GN_FUSED_DROP(64, 1);
+      } else
       if (nt == 1024) { if (nv == 4) GN_FUSED(1024, 4); else GN_FUSED(1024, 8); }
       else if (nt == 256) { if (nv == 1) GN_FUSED(256, 1); else if (nv == 2) GN_FUSED(256, 2); else if (nv == 4) GN_FUSED(256, 4); else GN_FUSED(256, 8); }
       else if (nt == 128) GN_FUSED(128, 1);
       else GN_FUSED(64, 1);
 #undef GN_FUSED
+#undef GN_FUSED_DROP
       if (rows && desc) {   // the caller sums the per-image rows of many layers with ONE lgm_wgrad_reduce_batch launch
         union { float f; int64_t i; } bb;
         bb.i = 0;
@@ -1107,6 +1208,9 @@ static int gn_bwd_impl(const float* x, int64_t x_pitch, const float* gy, int64_t
     }
   }
   LGM_REQUIRE(!planes, "gn_bwd_planes: this shape has no one-pass kernel (ask lgm_gn_planes_supported first)");
+  if (drop)   // two-pass plan: no fused variant, the stand-alone kernel masks gy in place first (the caller's gy is its own)
+    hipLaunchKernelGGL(dropout_bwd_kernel, dim3(lgm_cdiv((long)B * HW * (C / 4), 256)), dim3(256), 0, s, (float*)gy,
+                       (long)gy_pitch, (long)B * HW, C, *drop);
   const bool wide = !small_only && (long)HW * cb >= 16384;
   if (wide)
     hipLaunchKernelGGL(gn_bwd_reduce_kernel<1024>, dim3(B * (C / cb)), dim3(1024), 0, s, x, (long)x_pitch, gy,
@@ -1189,6 +1293,85 @@ extern "C" int lgm_gn_bwd_planes(const float* x, int64_t x_pitch, const float* g
   return gn_bwd_impl(x, x_pitch, nullptr, C, B, HW, C, G, gamma, beta, ss, ss_pitch, act, mean, rstd, coefA, coefB, gx,
                      gx_pitch, accumulate_gx, ggamma, gbeta, affine_beta, gss, gss_pitch, gss_beta, workspace, rows, desc,
                      stream, gy_planes, (long)plane_stride, splits);
+}
+
+// ---------------------------------------------------------------------------------------
+// Dropout (lgm_philox.h).  thr arrives as int64 (0 ... 2^32 - 1), the key as a device pointer to its two 32-bit halves.
+// ---------------------------------------------------------------------------------------
+static int drop_make(LgmDrop* d, const void* key, int layer, int pass, int64_t thr, float scale, const char* who) {
+  LGM_REQUIRE(key && (((uintptr_t)key) & 7u) == 0 && layer >= 0 && pass >= 0 && thr >= 0 && thr <= 0xffffffffLL && scale >= 1.f,
+              "%s: dropout operands (key %p, layer %d, pass %d, thr %lld, scale %g)", who, key, layer, pass, (long long)thr,
+              (double)scale);
+  d->key = (const unsigned*)key;
+  d->layer = (unsigned)layer;
+  d->pass = (unsigned)pass;
+  d->thr = (unsigned)thr;
+  d->scale = scale;
+  return LGM_OK;
+}
+
+static int dropout_impl(bool bwd, float* x, int64_t pitch, int B, int HW, int C, const void* key, int layer, int pass,
+                        int64_t thr, float scale, void* stream) {
+  LGM_REQUIRE(x && lgm_aligned16(x) && B > 0 && HW > 0 && C > 0 && C % 4 == 0 && pitch % 4 == 0 && pitch >= C,
+              "dropout: a 16-byte aligned [B*HW][C] tensor with C %% 4 == 0 and pitch %% 4 == 0, >= C expected");
+  LgmDrop d;
+  if (int rc = drop_make(&d, key, layer, pass, thr, scale, "dropout")) return rc;
+  const long npix = (long)B * HW;
+  const long blocks = (npix * (C / 4) + 255) / 256;
+  LGM_REQUIRE(blocks <= 0x7fffffffL, "dropout: tensor too large for one grid");
+  if (bwd)
+    hipLaunchKernelGGL(dropout_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)pitch, npix, C, d);
+  else
+    hipLaunchKernelGGL(dropout_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)pitch, npix, C, d);
+  LGM_LAUNCH_CHECK_AS(bwd ? "lgm_dropout_bwd" : "lgm_dropout_fwd");
+  return LGM_OK;
+}
+
+extern "C" int lgm_dropout_fwd(float* x, int64_t pitch, int B, int HW, int C, const void* key, int layer, int pass,
+                               int64_t thr, float scale, void* stream) {
+  return dropout_impl(false, x, pitch, B, HW, C, key, layer, pass, thr, scale, stream);
+}
+
+extern "C" int lgm_dropout_bwd(float* g, int64_t pitch, int B, int HW, int C, const void* key, int layer, int pass,
+                               int64_t thr, float scale, void* stream) {
+  return dropout_impl(true, g, pitch, B, HW, C, key, layer, pass, thr, scale, stream);
+}
+
+extern "C" int lgm_gn_fwd_drop(const float* planes, int64_t plane_stride, int splits, const float* conv_bias, float* x,
+                               int64_t x_pitch, int B, int HW, int C, int G, float eps, const float* gamma,
+                               const float* beta, const float* ss, int64_t ss_pitch, int act, const float* res,
+                               int64_t res_pitch, float* y, int64_t y_pitch, float* mean, float* rstd, float* coefA,
+                               float* coefB, const void* key, int layer, int pass, int64_t thr, float scale, void* stream) {
+  LgmDrop d;
+  if (int rc = drop_make(&d, key, layer, pass, thr, scale, "gn_fwd_drop")) return rc;
+  LGM_REQUIRE(y_pitch >= C, "gn_fwd_drop: y pitch < C");
+  if (planes)
+    LGM_REQUIRE(splits >= 1 && plane_stride >= (int64_t)B * HW * C && lgm_aligned16(planes) && plane_stride % 4 == 0 &&
+                    (!conv_bias || lgm_aligned16(conv_bias)), "gn_fwd_drop: bad partial planes");
+  return gn_fwd_impl(x, x_pitch, B, HW, C, G, eps, gamma, beta, ss, ss_pitch, act, res, res_pitch, y, y_pitch, mean, rstd,
+                     coefA, coefB, planes, (long)plane_stride, planes ? splits : 0, planes ? conv_bias : nullptr, stream, &d);
+}
+
+extern "C" int lgm_gn_bwd_drop(const float* x, int64_t x_pitch, float* gy, int64_t gy_pitch, const float* gy_planes,
+                               int64_t plane_stride, int splits, int B, int HW, int C, int G, const float* gamma,
+                               const float* beta, const float* ss, int64_t ss_pitch, int act, const float* mean,
+                               const float* rstd, const float* coefA, const float* coefB, float* gx, int64_t gx_pitch,
+                               int accumulate_gx, float* ggamma, float* gbeta, float affine_beta, float* gss,
+                               int64_t gss_pitch, float gss_beta, float* workspace, float* rows, int64_t* desc,
+                               const void* key, int layer, int pass, int64_t thr, float scale, void* stream) {
+  LgmDrop d;
+  if (int rc = drop_make(&d, key, layer, pass, thr, scale, "gn_bwd_drop")) return rc;
+  LGM_REQUIRE((gy != nullptr) != (gy_planes != nullptr), "gn_bwd_drop: gy as ONE of a tensor and planes");
+  LGM_REQUIRE((!rows && !desc) || (rows && desc && lgm_aligned16(rows) && lgm_aligned16(ggamma) && lgm_aligned16(gbeta)),
+              "gn_bwd_drop: rows / descriptor must come together, gradients 16-byte aligned");
+  if (gy_planes)
+    LGM_REQUIRE(splits >= 1 && plane_stride >= (int64_t)B * HW * C && lgm_aligned16(gy_planes) && plane_stride % 4 == 0,
+                "gn_bwd_drop: bad partial planes");
+  else
+    LGM_REQUIRE(gy_pitch >= C, "gn_bwd_drop: gy pitch < C");
+  return gn_bwd_impl(x, x_pitch, gy, gy_planes ? C : gy_pitch, B, HW, C, G, gamma, beta, ss, ss_pitch, act, mean, rstd, coefA,
+                     coefB, gx, gx_pitch, accumulate_gx, ggamma, gbeta, affine_beta, gss, gss_pitch, gss_beta, workspace, rows,
+                     desc, stream, gy_planes, (long)plane_stride, gy_planes ? splits : 0, nullptr, 0, &d);
 }
 
 // =====================================================================================

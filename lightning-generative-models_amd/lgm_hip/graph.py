@@ -238,7 +238,12 @@ class GraphedDDPMStep:
     offset, the order ``GaussianDiffusion.forward`` draws in.  A model without classes draws nothing more.
 
     ``self.t`` / ``self.noise`` / ``self.offset`` (the [B, C] offset noise of a diffusion with ``offset_noise_strength > 0``)
-    / ``self.classes`` hold what the last replay drew."""
+    / ``self.classes`` hold what the last replay drew.
+
+    Dropout (``Unet(dropout=p)``, p > 0): the step's 64-bit key is drawn inside the graph behind every other draw, into the
+    diffusion's persistent ``dropout_key`` tensor (``self.dropout_key``); the GroupNorm launches of the forward and of the
+    backward graphs read it from the device, so every replay - every accumulation micro-step - runs under its own key.  A
+    self-conditioned model draws it in ``pre``; its estimate pass is pass 1 of the mask.  p == 0: nothing is drawn."""
 
     def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None,
                  accum: Optional[_GradAccumulation] = None):
@@ -251,7 +256,7 @@ class GraphedDDPMStep:
         self.one = torch.ones(1, device=x.device)
         net.grad_sync = None                         # collectives are issued by step(), never captured
         fp = net._flat
-        self.t = self.noise = self.offset = self.classes = None
+        self.t = self.noise = self.offset = self.classes = self.dropout_key = None
         strength = float(gd.offset_noise_strength)
         self.y = net.labels(y, x.shape[0], x.device).clone() if net.num_classes is not None else None
         # (the pipelined variant applies a bucket's Adam slice right behind ITS all-reduce: only with the overlapped exchange)
@@ -275,13 +280,15 @@ class GraphedDDPMStep:
             self.offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
             if self.y is not None:
                 self.classes = gd.drop_labels(self.y)
+            self.dropout_key = gd.draw_dropout_key(x.device)     # None (no launch) unless the network drops
             return hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength)
 
         def estimate(q):
-            hip_loss_estimate(gd, q.xt, q.t, self.classes)
+            hip_loss_estimate(gd, q.xt, q.t, self.classes, self.dropout_key)
 
         def begin(q):                                # the saved forward, the loss, its gradient: the backward is open
-            loss, ctx = hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, True, self.classes)
+            loss, ctx = hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, True, self.classes,
+                                         dropout_key=self.dropout_key)
             fp.zero_grad()
             return loss, hip_loss_backward_begin(ctx, self.one)
 

@@ -388,16 +388,19 @@ class GroupNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(channels))
         self.bias = nn.Parameter(torch.zeros(channels))
 
-    def fwd(self, x, ss, act, res, out=None, planes=None):
+    def fwd(self, x, ss, act, res, out=None, planes=None, drop=None):
         """``planes`` (from Conv2d.fwd_planes): x arrives as split-K partial planes; summed, written to x and
-        normalised in one pass."""
+        normalised in one pass.  ``drop``: the dropout operands of ops.gn_fwd (None: no dropout)."""
         fp = _flat(self.weight)
         y = out if out is not None else ops.new(x.shape, x)
-        sv = ops.gn_fwd(x, self.groups, self.eps, fp.ptr(self.weight), fp.ptr(self.bias), ss, act, res, y, planes=planes)
+        sv = ops.gn_fwd(x, self.groups, self.eps, fp.ptr(self.weight), fp.ptr(self.bias), ss, act, res, y, planes=planes,
+                        drop=drop)
         return y, sv
 
-    def bwd(self, gc: GradCtx, x, gy, ss, act, sv, gss, gx=None, accumulate=False, gy_planes=None, add_gy_to=None):
-        """``add_gy_to``: a tensor that also receives ``+= gy`` in this launch (ops.gn_bwd)."""
+    def bwd(self, gc: GradCtx, x, gy, ss, act, sv, gss, gx=None, accumulate=False, gy_planes=None, add_gy_to=None,
+            drop=None):
+        """``add_gy_to``: a tensor that also receives ``+= gy`` in this launch (ops.gn_bwd).  ``drop``: the dropout operands
+        the forward got - ``gy`` goes through the same mask (ops.gn_bwd)."""
         fp = gc.flat
         if gx is None:
             gx = ops.new(x.shape, x)
@@ -405,7 +408,7 @@ class GroupNorm(nn.Module):
         dfr = gc.defer_for(self.weight)
         ops.gn_bwd(x, gy, self.groups, fp.ptr(self.weight), fp.ptr(self.bias), ss, act, sv, gx, accumulate,
                    fp.gptr(self.weight), fp.gptr(self.bias), gc.beta(self.weight), gss, 0.0, defer=dfr,
-                   gy_planes=gy_planes, add_gy_to=add_gy_to)
+                   gy_planes=gy_planes, add_gy_to=add_gy_to, drop=drop)
         gc.beta(self.bias)
         return gx
 

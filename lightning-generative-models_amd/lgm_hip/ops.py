@@ -7,6 +7,8 @@ slices of a wider buffer (pitch = stride of the pixel dimension).
 from __future__ import annotations
 
 import ctypes
+import math
+import numbers
 from typing import Optional
 
 import torch
@@ -956,20 +958,64 @@ def _gn_scratch(nfloats: int, device) -> torch.Tensor:
     return _grown(_GN_WS, device, 4 * nfloats, max(int(nfloats * 1.25) + 64, 1 << 16))
 
 
-def gn_fwd(x, G, eps, gamma_ptr, beta_ptr, ss, act: bool, res, y, planes=None) -> GNSaved:
+def dropout_operands(p: float):
+    """(thr, scale) of dropout probability ``p``: an element is kept iff its Philox word >= thr = min(2^32 - 1,
+    floor(p 2^32)); kept values are multiplied by scale = float32(1 / (1 - p)), the division in double."""
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 <= p < 1.0:      # (NaN fails the comparison)
+        raise ValueError(f"dropout must be a real number in [0, 1), got {p!r}")
+    thr = min(2 ** 32 - 1, int(math.floor(float(p) * 2.0 ** 32)))
+    return thr, ctypes.c_float(1.0 / (1.0 - float(p))).value
+
+
+class DropOperands(tuple):
+    """(address of the 64-bit key on the device, layer, pass, thr, scale): what the dropout launches take, in the order of
+    the C entry points.  Holds the key TENSOR as well, so that whatever keeps the operands for a backward pass (a ResnetBlock's
+    saved tuple) keeps the memory the backward kernels will read."""
+
+    def __new__(cls, key: torch.Tensor, layer: int, pass_: int, thr: int, scale: float):
+        self = super().__new__(cls, (key.data_ptr(), int(layer), int(pass_), int(thr), float(scale)))
+        self.key = key
+        return self
+
+
+def dropout_fwd(x, drop):
+    """In place: x = kept ? fl32(x * scale) : +0 over the logical elements of the NHWC tensor (or channel slice) ``x``;
+    ``drop`` = (address of the 64-bit key on the device, layer, pass, thr, scale).  No mask tensor (include/lgm_hip.h)."""
+    B, H, W, C = x.shape
+    lib().lgm_dropout_fwd(x.data_ptr(), pitch(x), B, H * W, C, *drop, stream())
+
+
+def dropout_bwd(g, drop):
+    """In place on the gradient arriving for a tensor ``dropout_fwd`` wrote: the same mask, the same scale."""
+    B, H, W, C = g.shape
+    lib().lgm_dropout_bwd(g.data_ptr(), pitch(g), B, H * W, C, *drop, stream())
+
+
+def gn_fwd(x, G, eps, gamma_ptr, beta_ptr, ss, act: bool, res, y, planes=None, drop=None) -> GNSaved:
     """``planes`` = (address, stride, count, conv bias address) from conv_xy(partial=True): x is summed from them,
     WRITTEN to ``x`` and normalised in the same pass; or ("stats", tensor, rows per image, conv bias address) from
-    conv_xy_stats: the statistics come from the convolution's epilogue and x is read once."""
+    conv_xy_stats: the statistics come from the convolution's epilogue and x is read once.
+    ``drop`` (see ``dropout_fwd``): y goes through the dropout mask - inside the one-pass kernels' launch, behind the
+    two-pass kernels and the statistics route as the stand-alone kernel.  None: the launches of a call without it."""
     B, H, W, C = x.shape
     sv = GNSaved()
     stats = new((2, B, G), x)
     coef = new((2, B, C), x)
     sv.mean, sv.rstd, sv.A, sv.Bc = stats[0], stats[1], coef[0], coef[1]
+    if drop is not None and not (planes is not None and planes[0] == "stats"):
+        pl = planes if planes is not None else (None, 0, 0, None)
+        lib().lgm_gn_fwd_drop(pl[0], pl[1], pl[2], pl[3], x.data_ptr(), pitch(x), B, H * W, C, G, eps,
+                              gamma_ptr, beta_ptr, _p(ss), pitch(ss) if ss is not None else 0, 1 if act else 0,
+                              _p(res), pitch(res) if res is not None else 0, y.data_ptr(), pitch(y),
+                              sv.mean.data_ptr(), sv.rstd.data_ptr(), sv.A.data_ptr(), sv.Bc.data_ptr(), *drop, stream())
+        return sv
     if planes is not None and planes[0] == "stats":
         lib().lgm_gn_fwd_stats(planes[1].data_ptr(), planes[2], planes[3], x.data_ptr(), pitch(x), B, H * W, C, G, eps,
                                gamma_ptr, beta_ptr, _p(ss), pitch(ss) if ss is not None else 0, 1 if act else 0,
                                _p(res), pitch(res) if res is not None else 0, y.data_ptr(), pitch(y),
                                sv.mean.data_ptr(), sv.rstd.data_ptr(), sv.A.data_ptr(), sv.Bc.data_ptr(), stream())
+        if drop is not None:
+            dropout_fwd(y, drop)
         return sv
     if planes is not None:
         lib().lgm_gn_fwd_planes(planes[0], planes[1], planes[2], planes[3], x.data_ptr(), pitch(x), B, H * W, C, G, eps,
@@ -985,12 +1031,37 @@ def gn_fwd(x, G, eps, gamma_ptr, beta_ptr, ss, act: bool, res, y, planes=None) -
 
 
 def gn_bwd(x, gy, G, gamma_ptr, beta_ptr, ss, act: bool, sv: GNSaved, gx, accumulate: bool,
-           ggamma_ptr, gbeta_ptr, affine_beta: float, gss, gss_beta: float, defer=None, gy_planes=None, add_gy_to=None):
+           ggamma_ptr, gbeta_ptr, affine_beta: float, gss, gss_beta: float, defer=None, gy_planes=None, add_gy_to=None,
+           drop=None):
     """``gy_planes`` = (address, stride, count, _) from conv_yx(partial=True): gy is summed from them (``gy`` unused).
     ``add_gy_to``: a second tensor that receives ``+= gy`` in the same launch (lgm_gn_bwd_add: an identity residual's
-    gradient beside this norm)."""
+    gradient beside this norm).
+    ``drop`` (the operands the forward got, see ``gn_fwd``): gy goes through the dropout mask as the kernel loads it (planes:
+    once they are summed); the two-pass kernels get it masked IN PLACE by the stand-alone kernel first."""
     B, H, W, C = x.shape
     ws = _gn_scratch(5 * B * C, x.device)
+    if drop is not None:
+        assert add_gy_to is None, "dropout sits in front of block2.proj: no residual gradient rides in this launch"
+        rws, desc = None, None
+        if defer is not None and ggamma_ptr % 16 == 0 and gbeta_ptr % 16 == 0:
+            key = (ggamma_ptr, B * 2 * C)
+            rws = _WGRAD_WS.get(key)
+            if rws is None:
+                rws = torch.empty(B * 2 * C + 4, dtype=torch.float32, device=x.device)
+                _WGRAD_WS[key] = rws
+            desc = (ctypes.c_int64 * 8)()
+        gp = gy_planes if gy_planes is not None else (None, 0, 0)
+        lib().lgm_gn_bwd_drop(x.data_ptr(), pitch(x), None if gy_planes is not None else gy.data_ptr(),
+                              0 if gy_planes is not None else pitch(gy), gp[0], gp[1], gp[2], B, H * W, C, G,
+                              gamma_ptr, beta_ptr, _p(ss), pitch(ss) if ss is not None else 0, 1 if act else 0,
+                              sv.mean.data_ptr(), sv.rstd.data_ptr(), sv.A.data_ptr(), sv.Bc.data_ptr(), gx.data_ptr(),
+                              pitch(gx), 1 if accumulate else 0, ggamma_ptr, gbeta_ptr, affine_beta, _p(gss),
+                              pitch(gss) if gss is not None else 0, gss_beta, ws.data_ptr(),
+                              None if rws is None else rws.data_ptr(), None if desc is None else ctypes.addressof(desc),
+                              *drop, stream())
+        if desc is not None and desc[6] > 0:
+            defer.append(tuple(desc))
+        return
     if add_gy_to is not None:
         assert gy_planes is None and add_gy_to.shape == gy.shape
         rws, desc = None, None

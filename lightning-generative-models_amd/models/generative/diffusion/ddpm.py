@@ -49,7 +49,9 @@ class Block(nn.Module):
 
 
 class ResnetBlock(nn.Module):
-    """conv3x3 -> GN -> FiLM -> SiLU -> conv3x3 -> GN -> SiLU, + res_conv(x)."""
+    """conv3x3 -> GN -> FiLM -> SiLU -> [dropout] -> conv3x3 -> GN -> SiLU, + res_conv(x).
+    Dropout (extension; Ho et al. 2020, upstream's ``Block(dropout=...)``) acts on ``h1``, the tensor ``block2.proj`` reads:
+    ``drop`` = (key address, layer, pass, thr, scale) of ops.gn_fwd, applied inside block1.norm's launches."""
 
     def __init__(self, dim, dim_out, *, time_emb_dim, groups=8):
         super().__init__()
@@ -59,29 +61,32 @@ class ResnetBlock(nn.Module):
         self.block2 = Block(dim_out, dim_out, groups)
         self.res_conv = Conv2d(dim, dim_out, 1) if dim != dim_out else nn.Identity()
 
-    def fwd(self, x, ss, out, save: bool):
+    def fwd(self, x, ss, out, save: bool, drop=None):
         # a 3x3 convolution that splits its reduction (small maps, small batches) leaves partial planes; the
         # GroupNorm behind it sums them while it computes its statistics: no reducer launch, one round trip less
         G = self.block1.norm.groups
         u1, p1 = self.block1.proj.fwd_planes(x, G)
-        h1, sv1 = self.block1.norm.fwd(u1, ss, True, None, planes=p1)
+        h1, sv1 = self.block1.norm.fwd(u1, ss, True, None, planes=p1, drop=drop)
         u2, p2 = self.block2.proj.fwd_planes(h1, G)
         if isinstance(self.res_conv, Conv2d):
             h2, sv2 = self.block2.norm.fwd(u2, None, True, None, planes=p2)
             self.res_conv.fwd(x, out=out, res=h2)
         else:
             _, sv2 = self.block2.norm.fwd(u2, None, True, x, out=out, planes=p2)
-        return (x, ss, u1, sv1, h1, u2, sv2) if save else None
+        if not save:
+            return None
+        return (x, ss, u1, sv1, h1, u2, sv2) if drop is None else (x, ss, u1, sv1, h1, u2, sv2, drop)
 
     def bwd(self, gc: GradCtx, saved, gy, gss, gx, accumulate: bool):
-        x, ss, u1, sv1, h1, u2, sv2 = saved
+        x, ss, u1, sv1, h1, u2, sv2 = saved[:7]
+        drop = saved[7] if len(saved) > 7 else None      # the forward's dropout operands: gh1 goes through the same mask
         # identity residual whose gradient joins a tensor that already holds another branch's (the skip connections of the
         # down path): gx += gy rides in block2's GroupNorm backward, which reads gy anyway (lgm_gn_bwd_add; was an axpby launch)
         fold_res = accumulate and not isinstance(self.res_conv, Conv2d) and not _NO_RES_FOLD
         gu2 = self.block2.norm.bwd(gc, u2, gy, None, True, sv2, None, add_gy_to=gx if fold_res else None)
         gh1, pg = self.block2.proj.bwd(gc, h1, gu2, planes_for_groups=self.block1.norm.groups)
         del gu2
-        gu1 = self.block1.norm.bwd(gc, u1, gh1, ss, True, sv1, gss, gy_planes=pg)
+        gu1 = self.block1.norm.bwd(gc, u1, gh1, ss, True, sv1, gss, gy_planes=pg, drop=drop)
         del gh1
         if isinstance(self.res_conv, Conv2d):
             self.block1.proj.bwd(gc, x, gu1, gx, accumulate)
@@ -292,8 +297,13 @@ class Unet(nn.Module):
                  self_condition=False, resnet_block_groups=8, learned_variance=False,
                  learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32,
-                 attn_heads=4, full_attn=None, flash_attn=False, num_classes=None):
+                 attn_heads=4, full_attn=None, flash_attn=False, num_classes=None, dropout=0.0):
+        """``dropout`` (extension, like upstream's ``Unet(dropout=...)``): the probability with which every ResnetBlock drops
+        the elements of ``h1`` in the network passes of the training loss (``forward_nhwc(dropout_key=...)``; nothing else
+        ever drops).  No parameters, no buffers: state-dict keys and parameter order are those of a model without it."""
         super().__init__()
+        self.drop_thr, self.drop_scale = ops.dropout_operands(dropout)      # ValueError outside [0, 1)
+        self.dropout = float(dropout)
         if num_classes is not None and int(num_classes) < 1:
             raise ValueError(f"num_classes must be a positive number of classes, got {num_classes!r}")
         if learned_sinusoidal_cond or random_fourier_features:
@@ -551,12 +561,25 @@ class Unet(nn.Module):
             ops.cfg_mix(out, null, cond_scale, self.channels if self.learned_variance else self.out_dim, scale_dev)
         return out
 
-    def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True, classes=None):
+    def drop_operands(self, dropout_key, drop_pass: int):
+        """Per resblock (``resblocks()`` order = the mask's ``layer``) the dropout operands of ops.gn_fwd, or None each when
+        this pass does not drop: no key, ``dropout == 0`` or evaluation mode."""
+        n = len(self.resblocks())
+        if dropout_key is None or self.dropout <= 0.0 or not self.training:
+            return [None] * n
+        assert dropout_key.dtype == torch.int64 and dropout_key.numel() == 1 and dropout_key.is_cuda
+        return [ops.DropOperands(dropout_key, k, drop_pass, self.drop_thr, self.drop_scale) for k in range(n)]
+
+    def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True, classes=None, dropout_key=None, drop_pass: int = 0):
         """x: [B, S, S, in_pitch] NHWC (``input_buffer``; pad lanes zero), t: int64 [B].
         Returns (out [B,S,S,r4(out_dim)], tape).  ``refresh_weights=False``: the derived weight copies (Winograd /
         split-precision operands) are known to be current — a sampling chain refreshes them once, not per step.
-        ``classes``: int64 [B] on the device (``Unet.labels``), read by a class-conditional network only; None = null labels."""
+        ``classes``: int64 [B] on the device (``Unet.labels``), read by a class-conditional network only; None = null labels.
+        ``dropout_key`` (int64 [1] on the device, read by the kernels when they run) / ``drop_pass``: the passes of the training
+        loss hand them in - 0 the trained pass, 1 the self-conditioning estimate; a network with ``dropout > 0`` in training mode
+        then drops.  Every other caller (samplers, likelihood, ``forward``) passes none and never drops."""
         B, S, _, _ = x.shape
+        dro = self.drop_operands(dropout_key, drop_pass)
         dim = self.dim
         n = len(self.in_out)
         assert S % (2 ** (n - 1)) == 0, f"input size {S} must be divisible by {2 ** (n - 1)}"
@@ -580,9 +603,9 @@ class Unet(nn.Module):
             cats.append((cat1, cat2))
             ha = _chan(cat2, co, co + ci)
             hb = _chan(cat1, co, co + ci)
-            s1 = b1.fwd(cur, ssl[k], ha, save); k += 1
+            s1 = b1.fwd(cur, ssl[k], ha, save, dro[k]); k += 1
             mid = ops.new((B, res, res, ci), x)
-            s2 = b2.fwd(ha, ssl[k], mid, save); k += 1
+            s2 = b2.fwd(ha, ssl[k], mid, save, dro[k]); k += 1
             s3 = attn.fwd(mid, hb, save)
             last = s == n - 1
             nres = res if last else res // 2
@@ -591,7 +614,7 @@ class Unet(nn.Module):
             tape.append((s1, s2, s3, s4))
             cur, res = nxt, nres
         m1 = ops.new(cur.shape, x)
-        sm1 = self.mid_block1.fwd(cur, ssl[k], m1, save); k += 1
+        sm1 = self.mid_block1.fwd(cur, ssl[k], m1, save, dro[k]); k += 1
         m2 = ops.new(cur.shape, x)
         sm2 = self.mid_attn.fwd(m1, m2, save)
         # mid_block2 writes straight into the first up-stage concat buffer
@@ -602,12 +625,12 @@ class Unet(nn.Module):
             cat1, cat2 = cats[s]
             xa = _chan(cat1, 0, co)
             if u == 0:
-                sm3 = self.mid_block2.fwd(m2, ssl[k], xa, save); k += 1
+                sm3 = self.mid_block2.fwd(m2, ssl[k], xa, save, dro[k]); k += 1
             # (for u > 0 the previous up-stage already wrote xa)
             xb = _chan(cat2, 0, co)
-            s1 = b1.fwd(cat1, ssl[k], xb, save); k += 1
+            s1 = b1.fwd(cat1, ssl[k], xb, save, dro[k]); k += 1
             y2 = ops.new((B, res, res, co), x)
-            s2 = b2.fwd(cat2, ssl[k], y2, save); k += 1
+            s2 = b2.fwd(cat2, ssl[k], y2, save, dro[k]); k += 1
             y3 = ops.new((B, res, res, co), x)
             s3 = attn.fwd(y2, y3, save)
             last = u == n - 1
@@ -621,7 +644,7 @@ class Unet(nn.Module):
                 res *= 2
             ups_tape.append((s1, s2, s3, s4))
         fin = ops.new((B, S, S, dim), x)
-        sf = self.final_res_block.fwd(catF, ssl[k], fin, save); k += 1
+        sf = self.final_res_block.fwd(catF, ssl[k], fin, save, dro[k]); k += 1
         out = self.final_conv.fwd(fin)
         if not save:
             return out, None
@@ -1053,8 +1076,20 @@ class GaussianDiffusion(nn.Module):
         return self.ddim_time_pairs()
 
     # -- training ---------------------------------------------------------------------------
+    def draw_dropout_key(self, device):
+        """The step's 64-bit dropout key: ONE persistent int64 [1] device tensor, refilled in place from torch's device
+        generator (one launch; capturable).  The kernels read it when they run, so the backward pass sees the key of its
+        forward as long as no other loss forward of this diffusion runs in between.  None when the loss passes do not drop
+        (``dropout == 0`` or evaluation mode): nothing is drawn, nothing allocated."""
+        if self.model.dropout <= 0.0 or not self.model.training:
+            return None
+        key = self.__dict__.get("dropout_key")
+        if key is None or key.device != torch.device(device):
+            key = self.__dict__["dropout_key"] = torch.zeros(1, dtype=torch.int64, device=device)
+        return key.random_(-2 ** 63, None)             # all 64 bits
+
     def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, classes=None, *, _offset_noise=None,
-                 _normalize=False, _self_cond=None):
+                 _normalize=False, _self_cond=None, _dropout_key=None):
         """x_start already normalised unless _normalize (reference :878-925).  Offset noise (:885-891): one draw per
         (sample, channel), added to the noise inside the q_sample kernel - the caller's ``noise`` is not written.
         ``_offset_noise`` (extension, for parity tests): the [B, C] draw the reference takes from torch.randn.
@@ -1063,7 +1098,10 @@ class GaussianDiffusion(nn.Module):
         gradient is taken through; no gradient reaches the estimate.  ``_self_cond`` (extension, for parity tests):
         ``True`` / ``False`` is the coin, an NCHW tensor is used as the estimate itself.
         ``classes`` (extension, class-conditional model): the labels as the network gets them - ``forward`` has already
-        replaced the dropped ones by the null label; the estimate pass and the main pass see the same labels."""
+        replaced the dropped ones by the null label; the estimate pass and the main pass see the same labels.
+        Dropout (extension, ``Unet(dropout=p)`` in training mode): the step's key is drawn here behind every other draw (t,
+        noise, offset noise, label drop); ``_dropout_key`` (for parity tests, like ``_offset_noise``): an int64 [1] device
+        tensor used as the key instead, nothing is drawn."""
         classes = self.model.labels(classes, x_start.shape[0], x_start.device)
         if noise is None:
             noise = torch.randn_like(x_start)
@@ -1074,8 +1112,9 @@ class GaussianDiffusion(nn.Module):
         self_cond = False
         if self.self_condition:
             self_cond = (random.random() < 0.5) if _self_cond is None else _self_cond
+        key = _dropout_key if _dropout_key is not None else self.draw_dropout_key(x_start.device)
         anchor = self.model._anchor(x_start.device)
-        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond, classes)
+        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond, classes, key)
 
     def drop_labels(self, classes):
         """Classifier-free guidance training: every label becomes the null label with probability ``cond_drop_prob`` (one
@@ -1331,27 +1370,29 @@ class GaussianDiffusion(nn.Module):
 
 
 def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, save: bool, offset=None,
-                     strength: float = 0.0, self_cond=False, classes=None):
+                     strength: float = 0.0, self_cond=False, classes=None, dropout_key=None):
     """q_sample + UNet + the objective's target + weighted MSE on the HIP engine.  Returns (loss[1], ctx).
     ``offset`` ([B, C] or None) / ``strength``: offset noise, added to ``noise`` inside the q_sample kernel.
     ``self_cond`` (self-conditioned network only): ``True`` = estimate pass first (``hip_loss_estimate``), a tensor = that
-    NCHW estimate.  ``classes``: device labels (``Unet.labels``) both passes of a class-conditional network read."""
+    NCHW estimate.  ``classes``: device labels (``Unet.labels``) both passes of a class-conditional network read.
+    ``dropout_key``: the step's key (``GaussianDiffusion.draw_dropout_key``) both passes read, None = neither drops."""
     q = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength)
     if gd.model.self_condition:
         if torch.is_tensor(self_cond):
             assert self_cond.shape == img.shape
             ops.nchw_to_nhwc(self_cond.detach().float().contiguous(), gd.model.sc_slice(q.xt))
         elif self_cond:
-            hip_loss_estimate(gd, q.xt, q.t, classes)
-    return hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, save, classes, normalize)
+            hip_loss_estimate(gd, q.xt, q.t, classes, dropout_key)
+    return hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, save, classes, normalize, dropout_key)
 
 
-def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None):
+def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None, dropout_key=None):
     """The estimate pass of a self-conditioned training step (:901-905): the network without saved activations on the input
-    buffer whose self-conditioning slice is zero, then ONE launch that writes the unclipped x_start into that slice."""
+    buffer whose self-conditioning slice is zero, then ONE launch that writes the unclipped x_start into that slice.
+    ``dropout_key``: the step's key; this is pass 1 of the dropout mask."""
     net = gd.model
     B, H, W, _ = xt.shape
-    out, _ = net.forward_nhwc(xt, t, False, True, classes)
+    out, _ = net.forward_nhwc(xt, t, False, True, classes, dropout_key, 1)
     ops.lib().lgm_selfcond_estimate(xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off, out.data_ptr(), ops.pitch(out),
                                     t.data_ptr(), *gd.objective_tables(), OBJECTIVES[gd.objective], B, net.channels, H * W,
                                     gd.num_timesteps, ops.stream())
@@ -1407,14 +1448,16 @@ def _loss_form(c: LossContext):
     return fns, (c.out.data_ptr(), c.target.data_ptr(), _r4(C), c.t.data_ptr(), gd.loss_weight.data_ptr()), (B, C, H * W, _r4(C))
 
 
-def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None, normalize=None):
+def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None, normalize=None,
+                     dropout_key=None):
     """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx).  A learned-variance network: the hybrid
     loss instead (lgm_hybrid_loss_fwd: the same MSE over the prediction lanes + vb_loss_weight times the bound's term), ``ctx``
     (``LossContext``) then also holds the per-sample terms, x_t and ``normalize`` - whether ``img`` is still in the data range
-    (``None``: the diffusion's auto_normalize, what the graph-replayed step hands its q_sample)."""
+    (``None``: the diffusion's auto_normalize, what the graph-replayed step hands its q_sample).  ``dropout_key``: the step's key;
+    this is pass 0 of the dropout mask."""
     B, C, H, W = img.shape
     hybrid = gd.learned_variance
-    out, tape = gd.model.forward_nhwc(xt, t, save, True, classes)
+    out, tape = gd.model.forward_nhwc(xt, t, save, True, classes, dropout_key, 0)
     loss = ops.new((1,), img)
     ctx = LossContext(gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
     # a loss-aware timestep sampler (training mode): the *_iw forms weight sample b by iw[t_b] and leave that weight in ``wb``
@@ -1456,9 +1499,9 @@ class _PLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0, self_cond=False,
-                classes=None):
+                classes=None, dropout_key=None):
         loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]), offset, strength,
-                                           self_cond, classes)
+                                           self_cond, classes, dropout_key)
         return loss.view(())
 
     @staticmethod
@@ -1466,7 +1509,7 @@ class _PLossFn(torch.autograd.Function):
         gl = gloss.detach().float().reshape(1).contiguous()
         ctx.stuff.gd.model.backward_run(hip_loss_backward_begin(ctx.stuff, gl))
         ctx.stuff = None
-        return None, None, None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -1477,7 +1520,8 @@ class DDPM(LightningModule):
                  sampling_timesteps: Optional[int] = None, lr: float = 2e-5, betas: Tuple[float, float] = (0.9, 0.99),
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
-                 min_snr_gamma: float = 5, self_condition: bool = False, num_classes: Optional[int] = None,
+                 min_snr_gamma: float = 5, self_condition: bool = False, dropout: float = 0.0,
+                 num_classes: Optional[int] = None,
                  cond_drop_prob: float = 0.1, t_sampler: str = "uniform", t_sampler_history: int = 10,
                  t_sampler_uniform_prob: float = 0.001, dynamic_thresholding: bool = False,
                  dynamic_thresholding_percentile: float = 0.995, learned_variance: bool = False,
@@ -1494,12 +1538,13 @@ class DDPM(LightningModule):
         to the model that trains - the EMA shadow has none, each rank keeps its own - and is saved under
         ``ema.online_model.t_sampler.history`` / ``.counts``.  New keywords stand in front of those that tests pin (the tail
         from ``dynamic_thresholding`` on: tests/test_dpmpp_host.py, tests/test_learned_sigma_host.py); pass everything from
-        ``num_classes`` on by keyword."""
+        ``num_classes`` on by keyword.  ``dropout`` (extension; Ho et al. 2020 use 0.1 on CIFAR-10): the probability with
+        which the ResnetBlocks drop in the network passes of the training loss (``Unet``); the EMA shadow never drops."""
         super().__init__()
         self.save_hyperparameters()
         self.num_classes = num_classes
         model = Unet(dim=dim, channels=img_channels, self_condition=self_condition, num_classes=num_classes,
-                     **(dict(learned_variance=True) if learned_variance else {}))
+                     dropout=dropout, **(dict(learned_variance=True) if learned_variance else {}))
         cond = dict(cond_drop_prob=cond_drop_prob, cond_scale=cond_scale) if num_classes is not None else {}
         if learned_variance:
             cond["vb_loss_weight"] = vb_loss_weight
@@ -1514,6 +1559,7 @@ class DDPM(LightningModule):
         self.channels = img_channels
         self.img_size = img_size
         self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
+        self.ema.ema_model.model.dropout = 0.0       # the shadow is what samples and validates: it never drops
         self.sample_every = 1000          # reference: every 1000 steps on rank 0 (:1025)
         self.bpd_every = 0                # > 0: validation_step also logs val_bpd on every bpd_every-th batch (extension)
         self._val_batches = 0
