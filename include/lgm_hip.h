@@ -54,7 +54,8 @@ extern "C" {
                              *  lgm_sample_step_inpaint, lgm_dpm_step_inpaint, lgm_vlb_term, lgm_vlb_term_table,
                              *  lgm_grad_sqnorm_*, lgm_grad_clip_scale, lgm_adam_step_scaled, lgm_grad_accumulate, lgm_hybrid_loss_fwd,
                              *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned, lgm_gn_plan,
-                             *  lgm_tsampler_draw, lgm_tsampler_update, lgm_weighted_mse_fwd_iw / _bwd_iw, lgm_hybrid_loss_fwd_iw / _bwd_iw
+                             *  lgm_tsampler_draw, lgm_tsampler_update, lgm_weighted_mse_fwd_iw / _bwd_iw, lgm_hybrid_loss_fwd_iw / _bwd_iw,
+                             *  lgm_lowres_cond, lgm_lowres_emb_fwd, lgm_sample_step_extent, lgm_dpm_step_extent
                              *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -533,6 +534,46 @@ int lgm_label_emb_wgrad(const float* gtemb, const int64_t* y, float* gemb, float
                         int num_classes, void* stream);
 int lgm_cfg_mix(float* out_cond, int64_t cond_pitch, const float* out_null, int64_t null_pitch, float scale,
                 const float* scale_dev, int64_t rows, int C, void* stream);
+
+/* Low-resolution conditioning of a cascaded super-resolution stage (csrc/lowres.hip; SR3 / Cascaded Diffusion Models / Imagen;
+ * an extension of the reference).  A conditioned UNet reads cat((lowres_cond_img, x), dim=1) from ONE input buffer [B, H W,
+ * pitch], pitch = r4(2 C): lanes [cond_off, cond_off + C) = the conditioning image (cond_off = 0), lanes [C, 2 C) = x.
+ *
+ * lgm_lowres_cond: the producer of the conditioning slice, one launch.  Exactly one source is non-NULL: img [B, C, H, W]
+ *   (training: the batch q_sample reads) or low [B, C, H / r, W / r] (sampling), both NCHW dense; r in {2, 4, 8} divides H and
+ *   W; C <= 64.  Per element, float32 without contraction, in this order:
+ *     l   = mean of img over the r x r block (img source; each row of r by the halving tree v[i] += v[i + n/2], n = r, r/2, ..,
+ *           the r row sums by the same tree, times 1 / r^2: 2 log2 r roundings)   |   low (low source)
+ *     n   = 2 l - 1 when normalize (1 rounding; applied to the low-resolution value: the bilinear weights sum to one exactly)
+ *     u   = (n00 wx0 + n01 wx1) wy0 + (n10 wx0 + n11 wx1) wy1, the taps of torch's bilinear align_corners=False rule: source
+ *           coordinate (dst + 0.5) / r - 0.5 clamped at 0, the upper tap clamped at the last row / column; the weights are
+ *           exact for these r (4 roundings: tap product, row sum, row product, column sum)
+ *     out = sqrt_ac[s[b]] u + sqrt_1mac[s[b]] eps[b, c, p]  (2 roundings; s int64 [B], clamped to [0, n_table) on the device;
+ *           the s == 0 row is a row like any other)        |   u, bit for bit, when eps == NULL (s and the tables unread)
+ *   out goes to lane cond_off + c of pixel p; no other lane of xin is written.  The low-resolution tile of a workgroup and its
+ *   one-pixel halo are staged in LDS, so img is read about once (x 1.41 at most) and nothing is averaged twice per output.  No
+ *   atomics, no cross-thread sums: the same bits on every run, and from both sources when low holds the averages above.
+ *   Launches lowres_cond_kernel<r>.
+ * lgm_lowres_emb_fwd: temb[b] += add[b], st[b] = SiLU(temb[b]) (st may be NULL) - the augmentation-level embedding joins the
+ *   time embedding behind the time MLP, in place, like lgm_label_emb_fwd.  time_dim % 4 == 0, 16-byte aligned rows.
+ * lgm_sample_step_extent / lgm_dpm_step_extent: the reverse updates of lgm_sample_step_thresh / lgm_dpm_step_thresh (both forms
+ *   of the row; thresh may be NULL: the static clamp; learned != 0: the row and the v lanes of lgm_sample_step_learned) that
+ *   own lanes [lane0, lane0 + lanes) of the pitch only: x in [x_off, x_off + C) inside them, zeros in the rest of them, every
+ *   other lane untouched - the conditioning slice is written once per chain and survives it.  No self-conditioning slice;
+ *   x0_out (optional) has x0_pitch >= lanes and gets x0 in its lanes [0, C).  x0 is always clipped. */
+int lgm_lowres_cond(const float* img, const float* low, const float* eps, const int64_t* s, const float* sqrt_ac,
+                    const float* sqrt_1mac, int n_table, int normalize, float* xin, int64_t pitch, int cond_off, int B, int C,
+                    int H, int W, int r, void* stream);
+int lgm_lowres_emb_fwd(float* temb, float* st, const float* add, int B, int time_dim, void* stream);
+int lgm_sample_step_extent(const float* xin, float* xout, int64_t pitch, int lane0, int lanes, int x_off, const float* v,
+                           int64_t v_pitch, const float* noise, float* x0_out, int64_t x0_pitch, int B, int C, int HW,
+                           int objective, int rederive, float A, float Bv, float R, float Rm1, float C0, float C1, float C2,
+                           float C3, const float* table, const int32_t* counter, int advance, const float* thresh,
+                           int learned, void* stream);
+int lgm_dpm_step_extent(const float* xin, float* xout, int64_t pitch, int lane0, int lanes, int x_off, const float* v,
+                        int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, int objective, float A,
+                        float Bv, float R, float Rm1, float Kx, float K0, float K1, float Kn, const float* table,
+                        const int32_t* counter, int advance, const float* thresh, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * DPM-Solver++(2M) sampling (Lu et al. 2022, data prediction; an extension of the reference).  Buffers as for

@@ -2178,10 +2178,11 @@ static int sample_step_slice_launch(const float* xin, float* xout, int64_t pitch
                                     int64_t v_pitch, const float* noise, float* x0_out, int64_t x0_pitch, int B, int C,
                                     int HW, const SampleRow& row, const float* table, const int32_t* counter, int objective,
                                     int clip, int rederive, int advance, void* stream, const float* thresh = nullptr,
-                                    const InpaintOps& ip = InpaintOps{}, int learned = 0) {
+                                    const InpaintOps& ip = InpaintOps{}, int learned = 0, int lanes = 0) {
   lgm_note_kernel(LGM_KNAME("sample_step_slice_kernel"));
-  hipLaunchKernelGGL(sample_step_slice_kernel, dim3(lgm_cdiv((long)B * HW * pitch, 256)), dim3(256), 0, (hipStream_t)stream,
-                     xin, xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, B, C, HW, row, table,
+  if (lanes == 0) lanes = (int)pitch;                // the whole pitch; the *_extent entry points own fewer lanes
+  hipLaunchKernelGGL(sample_step_slice_kernel, dim3(lgm_cdiv((long)B * HW * lanes, 256)), dim3(256), 0, (hipStream_t)stream,
+                     xin, xout, (long)pitch, lanes, x_off, sc_off, v, (long)v_pitch, noise, B, C, HW, row, table,
                      (const int*)counter, objective, clip, rederive, x0_out, (long)x0_pitch, thresh, ip, learned);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("sample_step_slice");
@@ -2294,11 +2295,12 @@ extern "C" int lgm_sample_step_thresh(const float* xin, float* xout, int64_t pit
 static int dpm_step_launch(const float* xin, float* xout, int64_t pitch, int x_off, int sc_off, const float* v,
                            int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, const SampleRow& row,
                            const float* table, const int32_t* counter, int objective, int clip, int advance, void* stream,
-                           const float* thresh = nullptr, const InpaintOps& ip = InpaintOps{}) {
+                           const float* thresh = nullptr, const InpaintOps& ip = InpaintOps{}, int lanes = 0) {
   lgm_note_kernel("dpm_step_kernel");
-  const long blocks = ((long)B * HW * pitch + 255) / 256;
+  if (lanes == 0) lanes = (int)pitch;
+  const long blocks = ((long)B * HW * lanes + 255) / 256;
   hipLaunchKernelGGL(dpm_step_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream, xin,
-                     xout, (long)pitch, (int)pitch, x_off, sc_off, v, (long)v_pitch, noise, hist, B, C, HW, row, table,
+                     xout, (long)pitch, lanes, x_off, sc_off, v, (long)v_pitch, noise, hist, B, C, HW, row, table,
                      (const int*)counter, objective, clip, thresh, ip);
   if (advance) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)counter);
   LGM_LAUNCH_CHECK_AS("dpm_step");
@@ -2393,6 +2395,45 @@ extern "C" int lgm_dpm_step_inpaint(const float* xin, float* xout, int64_t pitch
   const InpaintOps ip = {known, mask, eps_k, eps_j, itable, {Ma, Mn, Jx, Jn}};
   return dpm_step_launch(xin, xout, pitch, x_off, sc_off, v, v_pitch, noise, hist, B, C, HW, row, table, counter, objective,
                          1, advance, stream, thresh, ip);
+}
+
+// The updates with an EXTENT: the launch owns lanes [lane0, lane0 + lanes) of the pitch - the x slice inside them, zeros in
+// the rest of them - and touches no other lane, so a constant slice outside the extent (the low-resolution conditioning image
+// of a cascaded stage, written once per chain by lgm_lowres_cond) is still there after the last step.  The kernels are the
+// ones above, handed the buffers from lane0 on; no self-conditioning slice.  Both forms of the row (table != NULL: row
+// counter[0]) and the thresholds (or NULL) behind one entry point each, like the *_inpaint ones.
+static bool extent_ok(int64_t pitch, int lane0, int lanes, int x_off, int C) {
+  return C > 0 && lane0 >= 0 && lanes > 0 && lane0 + (int64_t)lanes <= pitch && x_off >= lane0 && x_off + C <= lane0 + lanes;
+}
+
+extern "C" int lgm_sample_step_extent(const float* xin, float* xout, int64_t pitch, int lane0, int lanes, int x_off,
+                                      const float* v, int64_t v_pitch, const float* noise, float* x0_out, int64_t x0_pitch,
+                                      int B, int C, int HW, int objective, int rederive, float A, float Bv, float R, float Rm1,
+                                      float C0, float C1, float C2, float C3, const float* table, const int32_t* counter,
+                                      int advance, const float* thresh, int learned, void* stream) {
+  LGM_REQUIRE(xin && xout && v && B > 0 && HW > 0 && extent_ok(pitch, lane0, lanes, x_off, C) &&
+                  v_pitch >= (learned ? 2 : 1) * (int64_t)C && objective_ok(objective) &&
+                  (table == nullptr) == (counter == nullptr) && (table || !advance) && (!table || xin == xout) &&
+                  x0_out != xin && x0_out != xout && (!x0_out || x0_pitch >= lanes) && !(learned && thresh),
+              "sample_step_extent: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, C0, C1, C2, C3}};
+  return sample_step_slice_launch(xin + lane0, xout + lane0, pitch, x_off - lane0, -1, v, v_pitch, noise, x0_out, x0_pitch, B,
+                                  C, HW, row, table, counter, objective, 1, learned ? 0 : rederive, advance, stream, thresh,
+                                  InpaintOps{}, learned ? 1 : 0, lanes);
+}
+
+extern "C" int lgm_dpm_step_extent(const float* xin, float* xout, int64_t pitch, int lane0, int lanes, int x_off,
+                                   const float* v, int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW,
+                                   int objective, float A, float Bv, float R, float Rm1, float Kx, float K0, float K1,
+                                   float Kn, const float* table, const int32_t* counter, int advance, const float* thresh,
+                                   void* stream) {
+  LGM_REQUIRE(extent_ok(pitch, lane0, lanes, x_off, C) &&
+                  dpm_buffers_ok(xin, xout, pitch, x_off, -1, v, v_pitch, hist, B, C, HW, objective) &&
+                  (table == nullptr) == (counter == nullptr) && (table || !advance) && (!table || xin == xout),
+              "dpm_step_extent: bad arguments");
+  const SampleRow row = {{A, Bv, R, Rm1, Kx, K0, K1, Kn}};
+  return dpm_step_launch(xin + lane0, xout + lane0, pitch, x_off - lane0, -1, v, v_pitch, noise, hist, B, C, HW, row, table,
+                         counter, objective, 1, advance, stream, thresh, InpaintOps{}, lanes);
 }
 
 // Dynamic thresholding: thresh[b] = max(1, lo + w (hi - lo)) with lo, hi the k-th and (k+1)-th smallest |x0| of sample b

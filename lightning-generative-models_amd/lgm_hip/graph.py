@@ -243,7 +243,11 @@ class GraphedDDPMStep:
     Dropout (``Unet(dropout=p)``, p > 0): the step's 64-bit key is drawn inside the graph behind every other draw, into the
     diffusion's persistent ``dropout_key`` tensor (``self.dropout_key``); the GroupNorm launches of the forward and of the
     backward graphs read it from the device, so every replay - every accumulation micro-step - runs under its own key.  A
-    self-conditioned model draws it in ``pre``; its estimate pass is pass 1 of the mask.  p == 0: nothing is drawn."""
+    self-conditioned model draws it in ``pre``; its estimate pass is pass 1 of the mask.  p == 0: nothing is drawn.
+
+    Low-resolution conditioned model (``Unet(lowres_cond=True)``): the augmentation levels s ~ randint(0, lowres_aug_levels) and
+    the augmentation noise are drawn inside the graph behind every other draw (``self.lowres_s`` / ``self.lowres_noise``), and
+    the launch that writes the conditioning slice from the batch follows q_sample's.  Any other model draws nothing more."""
 
     def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None,
                  accum: Optional[_GradAccumulation] = None):
@@ -256,7 +260,7 @@ class GraphedDDPMStep:
         self.one = torch.ones(1, device=x.device)
         net.grad_sync = None                         # collectives are issued by step(), never captured
         fp = net._flat
-        self.t = self.noise = self.offset = self.classes = self.dropout_key = None
+        self.t = self.noise = self.offset = self.classes = self.dropout_key = self.lowres_s = self.lowres_noise = None
         strength = float(gd.offset_noise_strength)
         self.y = net.labels(y, x.shape[0], x.device).clone() if net.num_classes is not None else None
         # (the pipelined variant applies a bucket's Adam slice right behind ITS all-reduce: only with the overlapped exchange)
@@ -281,14 +285,17 @@ class GraphedDDPMStep:
             if self.y is not None:
                 self.classes = gd.drop_labels(self.y)
             self.dropout_key = gd.draw_dropout_key(x.device)     # None (no launch) unless the network drops
-            return hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength)
+            lowres = gd.draw_lowres(self.x)                      # None (no draw) unless low-resolution conditioned
+            if lowres is not None:
+                self.lowres_s, self.lowres_noise = lowres
+            return hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength, lowres)
 
         def estimate(q):
             hip_loss_estimate(gd, q.xt, q.t, self.classes, self.dropout_key)
 
         def begin(q):                                # the saved forward, the loss, its gradient: the backward is open
             loss, ctx = hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, True, self.classes,
-                                         dropout_key=self.dropout_key)
+                                         dropout_key=self.dropout_key, lowres_s=q.lowres_s)
             fp.zero_grad()
             return loss, hip_loss_backward_begin(ctx, self.one)
 
@@ -449,6 +456,8 @@ class DDPMFastStep:
         m = self.model
         x = batch[0]
         y = batch[1] if self.net.num_classes is not None else None      # the labels: read by a class-conditional model only
+        if getattr(m, "lowres_cond", False):
+            m._cond_images = x                       # a super-resolution stage logs samples of the batch at hand
         if m.sample_every and m.global_step % m.sample_every == 0 and _is_master():
             m._log_sample()
         if self.use_graph and self.graphed is None:

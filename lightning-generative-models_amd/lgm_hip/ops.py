@@ -1381,6 +1381,32 @@ def cfg_mix(out_cond, out_null, scale, C, scale_dev=None):
                       _p(scale_dev), rows(out_cond), C, stream())
 
 
+# Low-resolution conditioning of a cascaded super-resolution stage (csrc/lowres.hip)
+LOWRES_FACTORS = (2, 4, 8)
+
+
+def lowres_cond(xin, cond_off, C, r, *, img=None, low=None, eps=None, s=None, sqrt_ac=None, sqrt_1mac=None, normalize=False):
+    """The conditioning slice [cond_off, cond_off + C) of the input buffer ``xin`` [B, H, W, pitch] in one launch: area-average
+    ``img`` [B, C, H, W] over r x r blocks (or take ``low`` [B, C, H / r, W / r]), normalise, upsample bilinearly by r, augment
+    with ``sqrt_ac[s] u + sqrt_1mac[s] eps`` (``eps`` None: no augmentation, nothing else is read).  No other lane is written."""
+    B, H, W, _ = xin.shape
+    src = img if img is not None else low
+    assert (img is None) != (low is None) and src.is_contiguous() and src.dtype == torch.float32
+    assert tuple(src.shape) == ((B, C, H, W) if img is not None else (B, C, H // r, W // r)), tuple(src.shape)
+    n_table = 0
+    if eps is not None:
+        assert eps.is_contiguous() and tuple(eps.shape) == (B, C, H, W) and s.dtype == torch.int64 and tuple(s.shape) == (B,)
+        n_table = sqrt_ac.shape[0]
+    lib().lgm_lowres_cond(_p(img), _p(low), _p(eps), _p(s) if eps is not None else None,
+                          _p(sqrt_ac) if eps is not None else None, _p(sqrt_1mac) if eps is not None else None, n_table,
+                          1 if normalize else 0, xin.data_ptr(), pitch(xin), cond_off, B, C, H, W, r, stream())
+
+
+def lowres_emb_fwd(temb, st, add):
+    """temb += add; st = SiLU(temb) (``st`` None: not written).  Dense [B, time_dim] rows."""
+    lib().lgm_lowres_emb_fwd(temb.data_ptr(), _p(st), add.data_ptr(), temb.shape[0], temb.shape[1], stream())
+
+
 def act_fwd(x, bias_ptr, res, y, act, slope=0.0):
     lib().lgm_act_fwd(x.data_ptr(), pitch(x), bias_ptr, _p(res), pitch(res) if res is not None else 0,
                       y.data_ptr(), pitch(y), rows(x), x.shape[-1], act, slope, stream())

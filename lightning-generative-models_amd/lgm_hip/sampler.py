@@ -36,6 +36,11 @@ logarithms in the row's last slots (``_p_sample_coeffs``), a graph of its own (`
 prediction lanes alone.  An inpainting chain holds the known image (NHWC, pitch r4(C)) and its mask ([B, HW]); its captured step has them, the two
 draws of the tail (eps_k, eps_j) and a second table [max_steps, 4] as static buffers, and draws in the fixed order noise,
 eps_k, eps_j, which the eager loop follows.  A chain longer than the tables is replayed in table-sized segments.
+A low-resolution conditioned network (``Unet(lowres_cond=True)``, a super-resolution stage) has a CONSTANT slice in its input
+buffer: ``_Chain`` writes it once per chain (``lgm_lowres_cond`` from the given low-resolution image: normalise, upsample, augment
+at the chain's level s with one draw behind the initial noise), the updates run in place through the ``*_extent`` entry points,
+which own the lanes from the x slice on and touch nothing else, and every forward embeds s; a captured step holds s in a static
+buffer and has a key of its own.
 """
 from __future__ import annotations
 
@@ -369,6 +374,7 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
         DPM               yes          either    either            dpm_step_thresh
         ancestral, learned variance    by value  either            step_learned (x0 into ``x0`` unless self-conditioned)
         ancestral, learned variance    table     either            step_table_learned, in place
+        any, low-resolution conditioned network                       step_extent / dpm_step_extent (both rows, thresholds or none)
 
     ``inpaint`` = (known, mask, eps_k, eps_j, irow, itable): the inpainting tail in the same launch, its row of 4 by value
     (``irow``) or from ``itable[counter]``; whatever the other columns say the entry is then step_inpaint / dpm_step_inpaint,
@@ -380,7 +386,19 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
     A, Bv, R, Rm1, W0, W1, W2, W3 = row if not tabled else (0.0,) * 8
     red, tab = 1 if rederive else 0, (p(table), p(counter))
     src = (net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v), p(noise))
-    if learned:
+    if getattr(net, "lowres_cond", False):
+        assert inpaint is None, "refused where the chain is made"
+        if rank is not None:
+            _launch_thresh(net, shape, objective, x, v, (A, Bv, R, Rm1), rank, thresh, table, counter)
+        ext = (x.data_ptr(), x_next.data_ptr(), net.in_pitch, *net.x_extent(), net.x_off, v.data_ptr(), ops.pitch(v), p(noise))
+        end = (A, Bv, R, Rm1, W0, W1, W2, W3, *tab, 1 if tabled else 0, p(thresh if rank is not None else None))
+        if dpm:
+            L.lgm_dpm_step_extent(*ext, hist.data_ptr(), B, C, H * W, objective, *end, st)
+        else:
+            x0o = None if tabled else x0
+            L.lgm_sample_step_extent(*ext, p(x0o), 0 if x0o is None else ops.pitch(x0o), B, C, H * W, objective, red, *end,
+                                     1 if learned else 0, st)
+    elif learned:
         assert inpaint is None and rank is None and not dpm, "refused where the plan is made"
         if tabled:
             L.lgm_sample_step_table_learned(x.data_ptr(), *src, B, C, H * W, *tab, objective, 1, st)
@@ -426,7 +444,8 @@ class _Chain:
 
     def __init__(self, gd, shape, init_noise: Optional[torch.Tensor], x_self_cond: Optional[torch.Tensor] = None,
                  classes=None, cond_scale: float = 1.0, known: Optional[torch.Tensor] = None,
-                 mask: Optional[torch.Tensor] = None):
+                 mask: Optional[torch.Tensor] = None, lowres: Optional[torch.Tensor] = None, lowres_aug_t=None,
+                 lowres_noise: Optional[torch.Tensor] = None):
         self.gd = gd
         self.net = net = gd.model
         B, C, H, W = shape
@@ -438,7 +457,24 @@ class _Chain:
         self.Cp = _r4(C)
         if init_noise is None:
             init_noise = torch.randn(shape, device=dev)
-        if net.self_condition:
+        self.lowres_s = None
+        if getattr(net, "lowres_cond", False):
+            # x and the constant conditioning slice in ONE buffer, updated in place: the slice is written here, once
+            if known is not None:
+                raise NotImplementedError("inpaint on a low-resolution conditioned model is not built")
+            low = gd.check_lowres(lowres, B)
+            self.lowres_s = net.aug_levels(gd.lowres_sample_aug_t if lowres_aug_t is None else lowres_aug_t, B, dev)
+            self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)
+            ops.nchw_to_nhwc(init_noise.float().contiguous(), net.x_slice(self.x, pad=True))
+            eps = torch.randn(shape, device=dev) if lowres_noise is None else lowres_noise.to(dev).float().contiguous()
+            ops.lowres_cond(self.x, net.cond_off, C, gd.lowres_factor, low=low, eps=eps, s=self.lowres_s,
+                            sqrt_ac=gd.sqrt_alphas_cumprod, sqrt_1mac=gd.sqrt_one_minus_alphas_cumprod,
+                            normalize=gd.auto_normalize)
+            self.x_next = self.x
+            self.x0 = torch.zeros_like(self.x)
+        elif lowres is not None or lowres_aug_t is not None or lowres_noise is not None:
+            raise ValueError("lowres / lowres_aug_t / lowres_noise were passed to a model built without lowres_cond")
+        elif net.self_condition:
             # both slices live in the input buffer; the update kernel writes the x_start of a step where the next step reads it
             self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)
             ops.nchw_to_nhwc(init_noise.float().contiguous(), net.x_slice(self.x, pad=True))
@@ -485,7 +521,8 @@ class _Chain:
         net = self.net
         if dpm and self.hist is None:
             self.hist = torch.empty((B, H, W, self.Cp), device=self.x.device)
-        v = net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale)
+        lr = {} if self.lowres_s is None else dict(lowres_s=self.lowres_s)      # a conditioned network's levels
+        v = net.forward_guided(self.x, self.times(t), self.classes, self.cond_scale, **lr)
         inpaint = None
         if irow is not None:
             inpaint = (self.known, self.mask, eps_k if irow[1] != 0.0 else None, eps_j if irow[3] != 0.0 else None, irow, None)
@@ -553,12 +590,15 @@ class _GraphedChain:
         self.eps_k = torch.zeros(shape, device=dev) if inpaint else None
         self.eps_j = torch.zeros(shape, device=dev) if inpaint else None
         self.itable = torch.zeros((max_steps, 4), device=dev) if inpaint else None
+        # low-resolution conditioned network: the chain's augmentation levels; the conditioning slice arrives with ``x``
+        self.lowres_s = torch.zeros(B, dtype=torch.long, device=dev) if getattr(net, "lowres_cond", False) else None
         self.inject = False
         self.max_steps = max_steps
 
         def one_step():
             ops.lib().lgm_sampler_time(self.ttable.data_ptr(), self.counter.data_ptr(), self.t.data_ptr(), B, ops.stream())
-            v = net.forward_guided(self.x, self.t, self.classes, 1.0, refresh_weights=False, scale_dev=self.scale)
+            lr = {} if self.lowres_s is None else dict(lowres_s=self.lowres_s)
+            v = net.forward_guided(self.x, self.t, self.classes, 1.0, refresh_weights=False, scale_dev=self.scale, **lr)
             nz = None
             if with_noise:
                 nz = self.noise if self.inject else torch.randn(shape, device=dev)
@@ -598,7 +638,7 @@ class _GraphedChain:
                 and (None if fp.data_uf is None else fp.data_uf.data_ptr()) == uf
                 and (None if fp.data_t is None else fp.data_t.data_ptr()) == dt)
 
-    def run(self, x0_nhwc, times, coeffs, noises, classes=None, cond_scale: float = 1.0, inpaint=None):
+    def run(self, x0_nhwc, times, coeffs, noises, classes=None, cond_scale: float = 1.0, inpaint=None, lowres_s=None):
         """times[i], coeffs[i] (8 floats) per step; noises: None (draw on device) or a list with one NCHW tensor or
         None per step; classes: the run's device labels (class-conditional network).  Returns the final NHWC image (a view
         of the static buffer).  ``inpaint`` (a step captured for inpainting) = (known NHWC, mask [B, HW], rows of 4); an entry
@@ -609,6 +649,8 @@ class _GraphedChain:
             self.classes.copy_(classes)
         if self.scale is not None:
             self.scale.fill_(float(cond_scale))
+        if self.lowres_s is not None:                # (the conditioning slice itself comes with x0_nhwc, below)
+            self.lowres_s.copy_(lowres_s)
         assert (inpaint is not None) == self.inpaint
         if self.inpaint:
             known, mask, irows = inpaint
@@ -658,6 +700,8 @@ def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: b
         key = ("inpaint",) + key
     if learned:                                      # the learned-variance ancestral step: its own update entry and row
         key = ("learned",) + key
+    if getattr(gd.model, "lowres_cond", False):      # the *_extent updates and the level buffer: conditioned networks only
+        key = ("lowres",) + key
     return key
 
 
@@ -712,12 +756,13 @@ def dpm_step(chain: _Chain, t: int, noise: Optional[torch.Tensor], coeffs):
 
 
 def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-         classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None, known=None, mask=None):
+         classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None, known=None, mask=None, lowres=None):
     """One chain of ``plan`` from ``init_noise`` (default: drawn) -> the image, or every image of the chain stacked along
     dim 1.  ``noises``: one NCHW tensor (or None) per step in place of the draws; ``unnormalize``: default = the model's
     auto_normalize (p_sample_loop :779).  No graph for a chain without steps.  An inpainting plan takes ``known`` (NCHW,
     normalised) and ``mask`` ([B, HW] or [B, 1, H, W], 1 = keep); an entry of ``noises`` is then a triple (noise, eps_k,
-    eps_j) with a tensor wherever the plan's draw flag of the step is set; the draws are taken in that order."""
+    eps_j) with a tensor wherever the plan's draw flag of the step is set; the draws are taken in that order.
+    ``lowres`` (a low-resolution conditioned model): a dict of ``_Chain``'s ``lowres`` / ``lowres_aug_t`` / ``lowres_noise``."""
     tail = plan.irows is not None
     if tail and (known is None or mask is None):
         raise ValueError("an inpainting plan needs the known image and its mask")
@@ -726,7 +771,8 @@ def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, no
             flags = (plan.draws[i], plan.kdraws[i], plan.jdraws[i])
             if any(f and (trip is None or trip[k] is None) for k, f in enumerate(flags)):
                 raise ValueError(f"step {i} of the inpainting chain draws {flags}, the injected triple lacks one of them")
-    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale, **(dict(known=known, mask=mask) if tail else {}))
+    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale, **(dict(known=known, mask=mask) if tail else {}),
+                   **(lowres or {}))
     unn = gd.auto_normalize if unnormalize is None else bool(unnormalize)
     gc = None
     if plan.times and not return_all_timesteps:
@@ -737,7 +783,9 @@ def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, no
                          inpaint=(chain.known, chain.mask, plan.irows))
         return chain.image(unn)
     if gc is not None:
-        chain.x = gc.run(chain.x, plan.times, plan.rows, noises if plan.with_noise else None, chain.classes, chain.cond_scale)
+        lr = {} if chain.lowres_s is None else dict(lowres_s=chain.lowres_s)
+        chain.x = gc.run(chain.x, plan.times, plan.rows, noises if plan.with_noise else None, chain.classes, chain.cond_scale,
+                         **lr)
         return chain.image(unn)
     frames = [chain.image(False)] if return_all_timesteps else None
     draw = lambda: torch.randn(shape, device=chain.x.device)  # noqa: E731
@@ -774,24 +822,26 @@ def warm_chain(gd, shape, replays: int = 20) -> bool:
 
 @torch.no_grad()
 def p_sample_loop(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-                  start: Optional[int] = None, unnormalize: Optional[bool] = None, classes=None, cond_scale: float = 1.0):
+                  start: Optional[int] = None, unnormalize: Optional[bool] = None, classes=None, cond_scale: float = 1.0,
+                  lowres=None):
     """``start``: walk the chain from step start - 1 down to 0 (GaussianDiffusion.interpolate :861-865) instead of from
     T - 1; ``unnormalize``: False for interpolate."""
-    return _run(gd, shape, _plan_ancestral(gd, start), return_all_timesteps, init_noise, noises, classes, cond_scale, unnormalize)
+    return _run(gd, shape, _plan_ancestral(gd, start), return_all_timesteps, init_noise, noises, classes, cond_scale, unnormalize,
+                lowres=lowres)
 
 
 @torch.no_grad()
 def ddim_sample(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-                classes=None, cond_scale: float = 1.0):
-    return _run(gd, shape, _plan_ddim(gd), return_all_timesteps, init_noise, noises, classes, cond_scale)
+                classes=None, cond_scale: float = 1.0, lowres=None):
+    return _run(gd, shape, _plan_ddim(gd), return_all_timesteps, init_noise, noises, classes, cond_scale, lowres=lowres)
 
 
 @torch.no_grad()
 def dpm_solver_sample(gd, shape, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-                      classes=None, cond_scale: float = 1.0):
+                      classes=None, cond_scale: float = 1.0, lowres=None):
     """DPM-Solver++(2M) on ``gd.dpm_time_pairs()``, graph-replayed like ``ddim_sample``.  ``noises``: one NCHW tensor per pair
     with t_next >= 0, read by the SDE form only."""
-    return _run(gd, shape, _plan_dpm(gd), return_all_timesteps, init_noise, noises, classes, cond_scale)
+    return _run(gd, shape, _plan_dpm(gd), return_all_timesteps, init_noise, noises, classes, cond_scale, lowres=lowres)
 
 
 @torch.no_grad()

@@ -28,7 +28,8 @@ from lgm_hip.optim import EMA, FusedAdam
 
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])     # reference :25
-QSample = namedtuple("QSample", ["xt", "target", "img", "noise", "t", "offset"])     # what hip_loss_qsample returns
+QSample = namedtuple("QSample", ["xt", "target", "img", "noise", "t", "offset", "lowres_s"],     # what hip_loss_qsample returns
+                     defaults=[None])
 
 
 _NO_RES_FOLD = os.environ.get("LGM_NO_RES_FOLD") is not None       # A/B switch: the identity residual's gradient as its own axpby launch
@@ -297,11 +298,19 @@ class Unet(nn.Module):
                  self_condition=False, resnet_block_groups=8, learned_variance=False,
                  learned_sinusoidal_cond=False, random_fourier_features=False,
                  learned_sinusoidal_dim=16, sinusoidal_pos_emb_theta=10000, attn_dim_head=32,
-                 attn_heads=4, full_attn=None, flash_attn=False, num_classes=None, dropout=0.0):
+                 attn_heads=4, full_attn=None, flash_attn=False, num_classes=None, dropout=0.0, lowres_cond=False):
         """``dropout`` (extension, like upstream's ``Unet(dropout=...)``): the probability with which every ResnetBlock drops
         the elements of ``h1`` in the network passes of the training loss (``forward_nhwc(dropout_key=...)``; nothing else
-        ever drops).  No parameters, no buffers: state-dict keys and parameter order are those of a model without it."""
+        ever drops).  No parameters, no buffers: state-dict keys and parameter order are those of a model without it.
+        ``lowres_cond`` (extension; a super-resolution stage of a cascade - SR3, Cascaded Diffusion Models, Imagen): the network
+        reads ``cat((lowres_cond_img, x), dim=1)``, the conditioning image already at x's size, and adds ``lowres_time_mlp(s)``
+        - an embedding of the conditioning image's noise-augmentation level s with the structure of ``time_mlp``, Imagen's
+        ``to_lowres_time_hiddens`` - to the time embedding.  ``init_conv.weight`` is [dim, 2 C, 7, 7] and every other key is
+        that of the reference's self-conditioned Unet, plus ``lowres_time_mlp.*``."""
         super().__init__()
+        if lowres_cond and self_condition:
+            raise NotImplementedError("lowres_cond together with self_condition is not built: both would take the first C "
+                                      "input channels of init_conv")
         self.drop_thr, self.drop_scale = ops.dropout_operands(dropout)      # ValueError outside [0, 1)
         self.dropout = float(dropout)
         if num_classes is not None and int(num_classes) < 1:
@@ -319,13 +328,18 @@ class Unet(nn.Module):
         # [C, 2 C) the interpolation coefficient v of the model's log-variance (Nichol & Dhariwal 2021, eq. 15)
         self.learned_variance = bool(learned_variance)
         self.self_condition = bool(self_condition)
+        self.lowres_cond = bool(lowres_cond)
         self.random_or_learned_sinusoidal_cond = False
         self.theta = float(sinusoidal_pos_emb_theta)
         # self-conditioned (:300-301, 435): the network reads cat((x_self_cond, x), dim=1) - ONE NHWC buffer of r4(2 C) lanes
         # whose slices [sc_off, sc_off + C) and [x_off, x_off + C) their producers fill; nothing is concatenated
-        self.in_channels = channels * (2 if self.self_condition else 1)
+        # low-resolution conditioned: the same layout with the conditioning image where x_self_cond would stand - a CONSTANT
+        # slice [cond_off, cond_off + C), written once per training step / sampling chain by lgm_lowres_cond; the kernels that
+        # rewrite x own the lanes from x_off on (``x_extent``) and never touch it
+        self.in_channels = channels * (2 if self.self_condition or self.lowres_cond else 1)
         self.in_pitch = _r4(self.in_channels)
-        self.x_off, self.sc_off = (channels, 0) if self.self_condition else (0, -1)
+        self.x_off, self.sc_off = (channels, 0) if self.self_condition else (channels, -1) if self.lowres_cond else (0, -1)
+        self.cond_off = 0 if self.lowres_cond else -1
         self.init_conv = Conv2d(self.in_channels, dim, 7, padding=3)
         dims = [dim, *[dim * m for m in dim_mults]]
         in_out = list(zip(dims[:-1], dims[1:]))
@@ -339,6 +353,8 @@ class Unet(nn.Module):
         if self.num_classes is not None:
             self.label_emb = nn.Embedding(self.num_classes + 1, time_dim)
         self._null_labels = {}
+        if self.lowres_cond:
+            self.lowres_time_mlp = nn.Sequential(nn.Identity(), Linear(dim, time_dim), nn.Identity(), Linear(time_dim, time_dim))
         n = len(in_out)
         if not full_attn:
             full_attn = (*((False,) * (n - 1)), True)
@@ -410,6 +426,10 @@ class Unet(nn.Module):
             first.append((names[id(lin.bias)], lin.bias, "vector"))
         if self.num_classes is not None:                      # dense rows [K + 1, time_dim], final with the time MLP's
             first.append((names[id(self.label_emb.weight)], self.label_emb.weight, "vector"))
+        if self.lowres_cond:                                  # the augmentation-level MLP: backward with the time MLP's
+            for lin in (self.lowres_time_mlp[1], self.lowres_time_mlp[3]):
+                first.append((names[id(lin.weight)], lin.weight, "weight"))
+                first.append((names[id(lin.bias)], lin.bias, "vector"))
         taken = {id(p) for _, p, _ in first}
         rest = [(n, p, param_kind(n, p)) for n, p in named.items() if id(p) not in taken]
         self._flat = FlatParams(first + rest, device)
@@ -470,7 +490,22 @@ class Unet(nn.Module):
             raise ValueError(f"classes must lie in [0, {K}] ({K} = the null label), got [{int(y.min())}, {int(y.max())}]")
         return y.to(device=device, dtype=torch.long).contiguous()
 
-    def _time_fwd(self, t, save, classes=None):
+    def aug_levels(self, lowres_aug_t, B, device):
+        """The int64 [B] device tensor of augmentation levels ``lowres_time_mlp`` embeds, or None for a network without
+        low-resolution conditioning.  ``None`` on a conditioned network = level 0 (no augmentation) for every sample; an int
+        = that level for every sample."""
+        if not self.lowres_cond:
+            if lowres_aug_t is not None:
+                raise ValueError("lowres_aug_t was passed to a Unet built without lowres_cond")
+            return None
+        if lowres_aug_t is None or isinstance(lowres_aug_t, int):
+            return torch.full((B,), int(lowres_aug_t or 0), dtype=torch.long, device=device)
+        s = torch.as_tensor(lowres_aug_t)
+        if s.dtype.is_floating_point or s.dtype == torch.bool or tuple(s.shape) != (B,):
+            raise ValueError(f"lowres_aug_t must be {B} integer levels (one per sample), got {s.dtype} {tuple(s.shape)}")
+        return s.to(device=device, dtype=torch.long).contiguous()
+
+    def _time_fwd(self, t, save, classes=None, lowres_s=None):
         B = t.shape[0]
         fp = self._flat
         l1, l2 = self.time_mlp[1], self.time_mlp[3]
@@ -488,8 +523,21 @@ class Unet(nn.Module):
             ops.conv_xy(l1.geom(B), pe, fp.ptr(l1.weight), fp.ptr(l1.bias), None, a1)
             ops.act_fwd(a1, None, None, h, ops.ACT_GELU)
             ops.conv_xy(l2.geom(B), h, fp.ptr(l2.weight), fp.ptr(l2.bias), None, temb)
-            if self.num_classes is None:
+            if self.num_classes is None and not self.lowres_cond:
                 ops.act_fwd(temb, None, None, st, ops.ACT_SILU)
+        lr_saved = None
+        if self.lowres_cond:
+            # temb += lowres_time_mlp(s), st = SiLU(temb): the MLP on the unfused ops (posemb, linear, GELU, linear: four
+            # launches) and one row-local launch that joins it to the time embedding
+            assert lowres_s is not None, "a low-resolution conditioned network needs its augmentation levels"
+            m1, m2 = self.lowres_time_mlp[1], self.lowres_time_mlp[3]
+            pe_s, a1_s, h_s, emb_s = (ops.new((B, d), t) for d in (self.dim, self.time_dim, self.time_dim, self.time_dim))
+            ops.posemb(lowres_s, self.dim, self.theta, pe_s)
+            ops.conv_xy(m1.geom(B), pe_s, fp.ptr(m1.weight), fp.ptr(m1.bias), None, a1_s)
+            ops.act_fwd(a1_s, None, None, h_s, ops.ACT_GELU)
+            ops.conv_xy(m2.geom(B), h_s, fp.ptr(m2.weight), fp.ptr(m2.bias), None, emb_s)
+            ops.lowres_emb_fwd(temb, None if self.num_classes is not None else st, emb_s)
+            lr_saved = (pe_s, a1_s, h_s)
         if self.num_classes is not None:
             # temb += label_emb[classes], st = SiLU(temb): one row-local launch behind the time MLP
             classes = self.labels(None, B, t.device) if classes is None else classes
@@ -501,10 +549,13 @@ class Unet(nn.Module):
         rb0 = self.resblocks()[0]
         ss_all = ops.new((B, self._ss_total), t)
         ops.conv_xy(g, st, fp.ptr(rb0.mlp[1].weight), fp.ptr(rb0.mlp[1].bias), None, ss_all)
-        return ss_all, ((pe, a1, h, temb, st, classes) if save else None)
+        if not save:
+            return ss_all, None
+        return ss_all, ((pe, a1, h, temb, st, classes) if lr_saved is None else (pe, a1, h, temb, st, classes, lr_saved))
 
     def _time_bwd(self, gc: GradCtx, saved, gss_all):
-        pe, a1, h, temb, st, classes = saved
+        pe, a1, h, temb, st, classes = saved[:6]
+        lr_saved = saved[6] if len(saved) > 6 else None      # a low-resolution conditioned network: its second MLP's activations
         B = pe.shape[0]
         fp = gc.flat
         l1, l2 = self.time_mlp[1], self.time_mlp[3]
@@ -526,9 +577,11 @@ class Unet(nn.Module):
             ops.time_mlp_bwd(gst, pe, a1, h, temb, fp.ptr(l2.weight), self.dim, self.time_dim, gtemb, ga1,
                              fp.gptr(l1.weight), fp.gptr(l1.bias), fp.gptr(l2.weight), fp.gptr(l2.bias), bw)
             self._label_emb_bwd(gc, gtemb, classes)
+            self._lowres_mlp_bwd(gc, gtemb, lr_saved)
             return
         ops.act_bwd(temb, None, gst, gtemb, False, ops.ACT_SILU)
         self._label_emb_bwd(gc, gtemb, classes)
+        self._lowres_mlp_bwd(gc, gtemb, lr_saved)
         gh = ops.new(h.shape, h)
         # weight gradient and input gradient of the second time-MLP linear in one launch (lgm_conv_bwd_pair)
         ops.conv_bwd_generic(l2.geom(B), gtemb, h, fp.ptr(l2.weight), fp.tptr(l2.weight), fp.gptr(l2.weight),
@@ -539,6 +592,23 @@ class Unet(nn.Module):
         ops.conv_wgrad(l1.geom(B), ga1, pe, fp.gptr(l1.weight), gc.beta(l1.weight), fp.gptr(l1.bias))
         gc.beta(l1.bias)
 
+    def _lowres_mlp_bwd(self, gc: GradCtx, gtemb, lr_saved):
+        """temb is a sum: g lowres_time_mlp(s) = g temb.  The MLP's backward on the generic ops, as the time MLP's unfused one:
+        weight + input gradient of the second linear (one launch), GELU', weight gradient of the first."""
+        if lr_saved is None:
+            return
+        pe_s, a1_s, h_s = lr_saved
+        B, fp = pe_s.shape[0], gc.flat
+        m1, m2 = self.lowres_time_mlp[1], self.lowres_time_mlp[3]
+        gh = ops.new(h_s.shape, h_s)
+        ops.conv_bwd_generic(m2.geom(B), gtemb, h_s, fp.ptr(m2.weight), fp.tptr(m2.weight), fp.gptr(m2.weight),
+                             gc.beta(m2.weight), fp.gptr(m2.bias), None, None, gh)
+        gc.beta(m2.bias)
+        ga1 = ops.new(a1_s.shape, a1_s)
+        ops.act_bwd(a1_s, None, gh, ga1, False, ops.ACT_GELU)
+        ops.conv_wgrad(m1.geom(B), ga1, pe_s, fp.gptr(m1.weight), gc.beta(m1.weight), fp.gptr(m1.bias))
+        gc.beta(m1.bias)
+
     def _label_emb_bwd(self, gc: GradCtx, gtemb, classes):
         """g label_emb.weight[k] = sum of g temb[b] over the samples of class k, in ascending b; other rows exactly zero"""
         if self.num_classes is not None:
@@ -546,16 +616,18 @@ class Unet(nn.Module):
             ops.label_emb_wgrad(gtemb, classes, gc.flat.gptr(w), gc.beta(w), self.num_classes)
 
     # ---- network ----------------------------------------------------------------------------
-    def forward_guided(self, x, t, classes=None, cond_scale: float = 1.0, refresh_weights: bool = True, scale_dev=None):
+    def forward_guided(self, x, t, classes=None, cond_scale: float = 1.0, refresh_weights: bool = True, scale_dev=None,
+                       lowres_s=None):
         """The network output a sampler reads (no saved activations).  ``cond_scale == 1``: one forward with ``classes``.
         Otherwise classifier-free guidance: a second forward over the SAME input buffer with the null label, then
         out = out_null + cond_scale * (out - out_null) in place (lgm_cfg_mix); the derived weights are refreshed once.
-        ``scale_dev``: a device float holding the scale (captured steps), which makes the step a guided one."""
-        out, _ = self.forward_nhwc(x, t, False, refresh_weights, classes)
+        ``scale_dev``: a device float holding the scale (captured steps), which makes the step a guided one.
+        ``lowres_s``: the augmentation levels of a low-resolution conditioned network (``aug_levels``), both forwards' alike."""
+        out, _ = self.forward_nhwc(x, t, False, refresh_weights, classes, lowres_s=lowres_s)
         if scale_dev is not None or float(cond_scale) != 1.0:
             if self.num_classes is None:
                 raise ValueError("cond_scale != 1 needs a Unet built with num_classes")
-            null, _ = self.forward_nhwc(x, t, False, False, None)
+            null, _ = self.forward_nhwc(x, t, False, False, None, lowres_s=lowres_s)
             # a learned-variance network mixes its prediction lanes alone: the variance of a guided step is the conditional
             # forward's (lanes [C, 2 C) of ``out`` stay as that forward wrote them)
             ops.cfg_mix(out, null, cond_scale, self.channels if self.learned_variance else self.out_dim, scale_dev)
@@ -570,14 +642,17 @@ class Unet(nn.Module):
         assert dropout_key.dtype == torch.int64 and dropout_key.numel() == 1 and dropout_key.is_cuda
         return [ops.DropOperands(dropout_key, k, drop_pass, self.drop_thr, self.drop_scale) for k in range(n)]
 
-    def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True, classes=None, dropout_key=None, drop_pass: int = 0):
+    def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True, classes=None, dropout_key=None, drop_pass: int = 0,
+                     lowres_s=None):
         """x: [B, S, S, in_pitch] NHWC (``input_buffer``; pad lanes zero), t: int64 [B].
         Returns (out [B,S,S,r4(out_dim)], tape).  ``refresh_weights=False``: the derived weight copies (Winograd /
         split-precision operands) are known to be current — a sampling chain refreshes them once, not per step.
         ``classes``: int64 [B] on the device (``Unet.labels``), read by a class-conditional network only; None = null labels.
         ``dropout_key`` (int64 [1] on the device, read by the kernels when they run) / ``drop_pass``: the passes of the training
         loss hand them in - 0 the trained pass, 1 the self-conditioning estimate; a network with ``dropout > 0`` in training mode
-        then drops.  Every other caller (samplers, likelihood, ``forward``) passes none and never drops."""
+        then drops.  Every other caller (samplers, likelihood, ``forward``) passes none and never drops.
+        ``lowres_s``: int64 [B] on the device (``Unet.aug_levels``), the augmentation levels a low-resolution conditioned
+        network embeds; its conditioning image is in the buffer's slice [cond_off, cond_off + C) already."""
         B, S, _, _ = x.shape
         dro = self.drop_operands(dropout_key, drop_pass)
         dim = self.dim
@@ -585,7 +660,7 @@ class Unet(nn.Module):
         assert S % (2 ** (n - 1)) == 0, f"input size {S} must be divisible by {2 ** (n - 1)}"
         if refresh_weights:
             self.refresh_derived_weights(save)
-        ss_all, time_saved = self._time_fwd(t, save, classes)
+        ss_all, time_saved = self._time_fwd(t, save, classes, lowres_s)
         ssl = [ss_all[:, o:o + 2 * rb.dim_out] for o, rb in zip(self._ss_offsets, self.resblocks())]
         k = 0  # running resblock index
         tape = []
@@ -795,13 +870,24 @@ class Unet(nn.Module):
 
     BACKWARD_PHASES = (_backward_up, _backward_mid, _backward_down, _backward_time)
 
-    def forward(self, x: torch.Tensor, time: torch.Tensor, x_self_cond=None, classes=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, time: torch.Tensor, x_self_cond=None, classes=None, lowres_cond_img=None,
+                lowres_aug_t=None) -> torch.Tensor:
         """NCHW in / NCHW out, like the reference Unet.forward (:428-471); ``x_self_cond`` is a constant (no gradient
         reaches it) and is read by a self-conditioned network only, ``None`` meaning zeros (:434).  ``classes`` (extension):
         one label in [0, num_classes] per sample for a class-conditional network, ``None`` meaning the null label; on a
-        network without classes it raises ValueError."""
+        network without classes it raises ValueError.  ``lowres_cond_img`` / ``lowres_aug_t`` (extension): the conditioning
+        image of a low-resolution conditioned network, already at x's size and in x's range (a constant: no gradient reaches
+        it), and its augmentation levels (``None`` = 0); the image is required there and a ValueError on any other network."""
         classes = self.labels(classes, x.shape[0], x.device)
-        return _UnetFn.apply(self._anchor(x.device), self, x, time, x_self_cond, classes)
+        if self.lowres_cond:
+            if lowres_cond_img is None:
+                raise ValueError("a Unet built with lowres_cond=True needs lowres_cond_img")
+            if tuple(lowres_cond_img.shape) != tuple(x.shape):
+                raise ValueError(f"lowres_cond_img {tuple(lowres_cond_img.shape)} must have the shape of x {tuple(x.shape)}")
+        elif lowres_cond_img is not None:
+            raise ValueError("lowres_cond_img was passed to a Unet built without lowres_cond")
+        s = self.aug_levels(lowres_aug_t, x.shape[0], x.device)
+        return _UnetFn.apply(self._anchor(x.device), self, x, time, x_self_cond, classes, lowres_cond_img, s)
 
     # ---- the input buffer and its two slices ------------------------------------------------------------
     def input_buffer(self, B, H, W, like):
@@ -814,6 +900,14 @@ class Unet(nn.Module):
     def sc_slice(self, xin):
         return _chan(xin, self.sc_off, self.sc_off + self.channels)
 
+    def cond_slice(self, xin):
+        """the lanes of the low-resolution conditioning image"""
+        return _chan(xin, self.cond_off, self.cond_off + self.channels)
+
+    def x_extent(self):
+        """(first lane, lanes) the kernels that rewrite x own in an input buffer of a low-resolution conditioned network"""
+        return self.x_off, self.in_pitch - self.x_off
+
     def _anchor(self, device):
         self.prepare_hip(device)
         a = getattr(self, "_anchor_t", None)
@@ -822,7 +916,8 @@ class Unet(nn.Module):
             self._anchor_t = a
         return a
 
-    def run_nchw(self, x, time, save, x_self_cond=None, classes=None, cond_scale: float = 1.0):
+    def run_nchw(self, x, time, save, x_self_cond=None, classes=None, cond_scale: float = 1.0, lowres_cond_img=None,
+                 lowres_s=None):
         """``classes``: device labels (``Unet.labels``); ``cond_scale != 1`` (without saved activations only): guided output"""
         B, C, H, W = x.shape
         xin = self.input_buffer(B, H, W, x)
@@ -831,11 +926,13 @@ class Unet(nn.Module):
             sc = torch.zeros_like(x) if x_self_cond is None else x_self_cond.detach().float().contiguous()
             assert sc.shape == x.shape, f"x_self_cond {tuple(sc.shape)} must have the shape of x {tuple(x.shape)}"
             ops.nchw_to_nhwc(sc, self.sc_slice(xin))
+        if self.lowres_cond:
+            ops.nchw_to_nhwc(lowres_cond_img.detach().float().contiguous(), self.cond_slice(xin))
         if save:
             assert float(cond_scale) == 1.0, "guidance is a sampling-time mix: no gradient is taken through it"
-            out, tape = self.forward_nhwc(xin, time, True, True, classes)
+            out, tape = self.forward_nhwc(xin, time, True, True, classes, lowres_s=lowres_s)
         else:
-            out, tape = self.forward_guided(xin, time, classes, cond_scale), None
+            out, tape = self.forward_guided(xin, time, classes, cond_scale, lowres_s=lowres_s), None
         y = ops.new((B, self.out_dim, H, W), x)
         ops.nhwc_to_nchw(out, y)
         return y, tape, out
@@ -868,9 +965,9 @@ class _Backward:
 
 class _UnetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, net: Unet, x, time, x_self_cond=None, classes=None):
+    def forward(ctx, anchor, net: Unet, x, time, x_self_cond=None, classes=None, lowres_cond_img=None, lowres_s=None):
         save = bool(ctx.needs_input_grad[0])   # grad mode on at apply() time and anchor requires grad
-        y, tape, _ = net.run_nchw(x.detach().float(), time, save, x_self_cond, classes)
+        y, tape, _ = net.run_nchw(x.detach().float(), time, save, x_self_cond, classes, 1.0, lowres_cond_img, lowres_s)
         ctx.net, ctx.tape = net, tape
         return y
 
@@ -884,7 +981,7 @@ class _UnetFn(torch.autograd.Function):
         ops.nchw_to_nhwc(gy.contiguous(), g)
         net.backward_nhwc(tape, g)
         ctx.tape = None
-        return None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -920,8 +1017,13 @@ class GaussianDiffusion(nn.Module):
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, cond_drop_prob=None,
                  cond_scale=1.0, sampler="auto", dpm_order=2, dpm_stochastic=False, dynamic_thresholding=False,
                  dynamic_thresholding_percentile=0.995, vb_loss_weight=None, t_sampler="uniform", t_sampler_history=10,
-                 t_sampler_uniform_prob=0.001):
-        """``cond_drop_prob`` / ``cond_scale`` (extension, class-conditional ``model`` only): the probability with which
+                 t_sampler_uniform_prob=0.001, lowres_factor=4, lowres_aug_levels=None, lowres_sample_aug_t=None):
+        """``lowres_factor`` / ``lowres_aug_levels`` / ``lowres_sample_aug_t`` (extension, read with a ``Unet(lowres_cond=True)``
+        only - a super-resolution stage of a cascade): the stage conditions on its input area-averaged over ``lowres_factor`` x
+        ``lowres_factor`` blocks (2, 4 or 8), upsampled bilinearly back and noise-augmented (Ho et al. 2021, conditioning
+        augmentation) - c = sqrt_ac[s] u + sqrt_1mac[s] eps with s ~ randint(0, ``lowres_aug_levels``) per sample in training
+        (``None`` = every level, as in Imagen) and s = ``lowres_sample_aug_t`` (``None`` = int(0.2 T)) in ``sample``.
+        ``cond_drop_prob`` / ``cond_scale`` (extension, class-conditional ``model`` only): the probability with which
         ``forward`` replaces a training label by the null label, and the classifier-free-guidance scale ``sample`` uses.
         ``cond_drop_prob=None`` is 0.1 on a class-conditional model and 0 on any other.
         ``sampler`` (extension): ``"auto"`` = the reference's dispatch (DDIM when ``sampling_timesteps < timesteps``, else the
@@ -980,6 +1082,13 @@ class GaussianDiffusion(nn.Module):
         self.channels = model.channels
         self.self_condition = model.self_condition
         self.img_size = img_size
+        self.lowres_cond = bool(getattr(model, "lowres_cond", False))
+        self.lowres_factor = int(lowres_factor)
+        if self.lowres_cond:
+            if self.lowres_factor not in ops.LOWRES_FACTORS:
+                raise ValueError(f"lowres_factor must be one of {ops.LOWRES_FACTORS}, got {lowres_factor!r}")
+            if int(img_size) % self.lowres_factor:
+                raise ValueError(f"lowres_factor {self.lowres_factor} does not divide img_size {img_size}")
         self.objective = objective
         self.offset_noise_strength = offset_noise_strength
         fn = {"linear": _linear_beta_schedule, "cosine": _cosine_beta_schedule, "sigmoid": _sigmoid_beta_schedule}
@@ -990,6 +1099,12 @@ class GaussianDiffusion(nn.Module):
         ac = torch.cumprod(alphas, dim=0)
         ac_prev = torch.nn.functional.pad(ac[:-1], (1, 0), value=1.0)
         self.num_timesteps = int(betas.shape[0])
+        levels = self.num_timesteps if lowres_aug_levels is None else int(lowres_aug_levels)
+        sample_s = int(0.2 * self.num_timesteps) if lowres_sample_aug_t is None else int(lowres_sample_aug_t)
+        if self.lowres_cond and not (1 <= levels <= self.num_timesteps and 0 <= sample_s < self.num_timesteps):
+            raise ValueError(f"lowres_aug_levels must lie in [1, {self.num_timesteps}] and lowres_sample_aug_t in "
+                             f"[0, {self.num_timesteps}), got {lowres_aug_levels!r} and {lowres_sample_aug_t!r}")
+        self.lowres_aug_levels, self.lowres_sample_aug_t = levels, sample_s
         self.sampling_timesteps = sampling_timesteps if sampling_timesteps is not None else self.num_timesteps
         assert self.sampling_timesteps <= self.num_timesteps
         self.is_ddim_sampling = self.sampling_timesteps < self.num_timesteps
@@ -1089,7 +1204,7 @@ class GaussianDiffusion(nn.Module):
         return key.random_(-2 ** 63, None)             # all 64 bits
 
     def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, classes=None, *, _offset_noise=None,
-                 _normalize=False, _self_cond=None, _dropout_key=None):
+                 _normalize=False, _self_cond=None, _dropout_key=None, lowres_aug_t=None, lowres_noise=None):
         """x_start already normalised unless _normalize (reference :878-925).  Offset noise (:885-891): one draw per
         (sample, channel), added to the noise inside the q_sample kernel - the caller's ``noise`` is not written.
         ``_offset_noise`` (extension, for parity tests): the [B, C] draw the reference takes from torch.randn.
@@ -1101,7 +1216,13 @@ class GaussianDiffusion(nn.Module):
         replaced the dropped ones by the null label; the estimate pass and the main pass see the same labels.
         Dropout (extension, ``Unet(dropout=p)`` in training mode): the step's key is drawn here behind every other draw (t,
         noise, offset noise, label drop); ``_dropout_key`` (for parity tests, like ``_offset_noise``): an int64 [1] device
-        tensor used as the key instead, nothing is drawn."""
+        tensor used as the key instead, nothing is drawn.
+        Low-resolution conditioned model (extension): the conditioning slice is made from ``x_start`` itself in one launch
+        (``lgm_lowres_cond``); its augmentation level s ~ randint(0, lowres_aug_levels) per sample and its noise are drawn
+        behind every other draw, so a model without the option draws what it drew; ``lowres_aug_t`` (int64 [B]) /
+        ``lowres_noise`` (NCHW) are used instead when given (parity runs)."""
+        if not self.lowres_cond and (lowres_aug_t is not None or lowres_noise is not None):
+            raise ValueError("lowres_aug_t / lowres_noise were passed to a model built without lowres_cond")
         classes = self.model.labels(classes, x_start.shape[0], x_start.device)
         if noise is None:
             noise = torch.randn_like(x_start)
@@ -1113,8 +1234,23 @@ class GaussianDiffusion(nn.Module):
         if self.self_condition:
             self_cond = (random.random() < 0.5) if _self_cond is None else _self_cond
         key = _dropout_key if _dropout_key is not None else self.draw_dropout_key(x_start.device)
+        lowres = self.draw_lowres(x_start, lowres_aug_t, lowres_noise)
         anchor = self.model._anchor(x_start.device)
-        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond, classes, key)
+        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond, classes, key,
+                              lowres)
+
+    def draw_lowres(self, x_start, lowres_aug_t=None, lowres_noise=None):
+        """(s int64 [B], eps_aug like ``x_start``) of a training step on a low-resolution conditioned model - two draws from
+        torch's device generator unless given -, None on any other model (nothing is drawn)."""
+        if not self.lowres_cond:
+            return None
+        B = x_start.shape[0]
+        if lowres_aug_t is None:
+            s = torch.randint(0, self.lowres_aug_levels, (B,), device=x_start.device).long()
+        else:
+            s = self.model.aug_levels(lowres_aug_t, B, x_start.device)
+        eps = torch.randn_like(x_start) if lowres_noise is None else lowres_noise
+        return s, eps
 
     def drop_labels(self, classes):
         """Classifier-free guidance training: every label becomes the null label with probability ``cond_drop_prob`` (one
@@ -1205,6 +1341,25 @@ class GaussianDiffusion(nn.Module):
             raise ValueError("cond_scale != 1 needs a model built with num_classes")
         return self.model.labels(classes, B, device), scale
 
+    def check_lowres(self, lowres, B):
+        """The low-resolution image of a sampling call as the kernel reads it: float32 [B, C, img_size / r, img_size / r] on
+        the device, in the data range (normalised like a training batch).  ValueError for a model without low-resolution
+        conditioning, a missing image and a wrong shape."""
+        if not self.lowres_cond:
+            raise ValueError("lowres= was passed to a model built without lowres_cond")
+        if lowres is None:
+            raise ValueError("a low-resolution conditioned model samples from a low-resolution image: pass lowres=")
+        n = self.img_size // self.lowres_factor
+        if not torch.is_tensor(lowres) or tuple(lowres.shape) != (B, self.channels, n, n):
+            got = tuple(lowres.shape) if torch.is_tensor(lowres) else type(lowres).__name__
+            raise ValueError(f"lowres must be [{B}, {self.channels}, {n}, {n}] (img_size {self.img_size} / factor "
+                             f"{self.lowres_factor}), got {got}")
+        return lowres.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _refuse_lowres(self, what: str):
+        if self.lowres_cond:
+            raise NotImplementedError(f"{what} on a low-resolution conditioned model is not built")
+
     def objective_tables(self):
         """the four schedule tables the objective's algebra reads, as the entry points take them (sqrt_ac .. sqrt_recipm1)"""
         return (self.sqrt_alphas_cumprod.data_ptr(), self.sqrt_one_minus_alphas_cumprod.data_ptr(),
@@ -1212,7 +1367,7 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, classes=None,
-                          cond_scale=1.0):
+                          cond_scale=1.0, lowres_cond_img=None, lowres_aug_t=None):
         """-> ModelPrediction(pred_noise, pred_x_start), reference :707-734.  ``rederive_pred_noise`` takes effect for
         pred_noise only (with ``clip_x_start``; otherwise pred_noise is the raw network output); for pred_x0 and pred_v the
         noise is always derived from the possibly clipped x_start.  UNet forward on the HIP engine, then ONE launch for
@@ -1223,10 +1378,13 @@ class GaussianDiffusion(nn.Module):
         predictions, ``lgm_dyn_thresh`` over the dense x_start, the predictions again with the thresholds."""
         classes, cond_scale = self._guidance(classes, cond_scale, x.shape[0], x.device)
         if cond_scale == 1.0:
-            v = self.model(x, t, x_self_cond, classes)
+            v = self.model(x, t, x_self_cond, classes, lowres_cond_img, lowres_aug_t)
         else:
             self.model._anchor(x.device)
-            v = self.model.run_nchw(x.detach().float(), t.to(x.device), False, x_self_cond, classes, cond_scale)[0]
+            if self.lowres_cond and lowres_cond_img is None:
+                raise ValueError("a Unet built with lowres_cond=True needs lowres_cond_img")
+            v = self.model.run_nchw(x.detach().float(), t.to(x.device), False, x_self_cond, classes, cond_scale,
+                                    lowres_cond_img, self.model.aug_levels(lowres_aug_t, x.shape[0], x.device))[0]
         if self.learned_variance:                    # the prediction channels; model_predictions uses no model variance
             v = v[:, :self.channels].contiguous()
         x = x.detach().float().contiguous()
@@ -1254,20 +1412,21 @@ class GaussianDiffusion(nn.Module):
         return ModelPrediction(pred_noise, x_start)
 
     @torch.no_grad()
-    def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True, classes=None, cond_scale=1.0):
+    def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True, classes=None, cond_scale=1.0, **lowres):
         x_start = self.model_predictions(x, t, x_self_cond, clip_x_start=clip_denoised, classes=classes,
-                                         cond_scale=cond_scale).pred_x_start
+                                         cond_scale=cond_scale, **lowres).pred_x_start
         mean, var, logvar = self.q_posterior(x_start=x_start, x_t=x, t=t)
         return mean, var, logvar, x_start
 
     # -- sampling: lgm_hip/sampler.py (one fused update kernel per step, graph replay for whole chains) -------------
     @torch.no_grad()
-    def p_sample(self, x, t: int, x_self_cond=None, noise=None, classes=None, cond_scale=1.0):
+    def p_sample(self, x, t: int, x_self_cond=None, noise=None, classes=None, cond_scale=1.0, **lowres):
         """One ancestral step at the shared timestep ``t`` -> (pred_img, x_start), reference :748-757.  ``noise``
         (extension, for parity tests): the draw the reference takes from randn_like.  ``x_self_cond`` (NCHW, ``None`` =
-        zeros): the x_start the previous step returned, for a self-conditioned network."""
+        zeros): the x_start the previous step returned, for a self-conditioned network.  ``lowres`` / ``lowres_aug_t`` /
+        ``lowres_noise`` (keywords, a low-resolution conditioned model): as in ``sample``."""
         from lgm_hip import sampler
-        chain = sampler._Chain(self, tuple(x.shape), x, x_self_cond, classes, cond_scale)
+        chain = sampler._Chain(self, tuple(x.shape), x, x_self_cond, classes, cond_scale, **lowres)
         if noise is None and t > 0:
             noise = torch.randn_like(x)
         sampler.p_sample_step(chain, int(t), noise)
@@ -1276,25 +1435,40 @@ class GaussianDiffusion(nn.Module):
         return chain.image(False), x0
 
     @torch.no_grad()
-    def p_sample_loop(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0):
+    def p_sample_loop(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0, lowres=None):
         from lgm_hip import sampler
-        return sampler.p_sample_loop(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale)
+        return sampler.p_sample_loop(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale,
+                                     lowres=lowres)
 
     @torch.no_grad()
-    def ddim_sample(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0):
+    def ddim_sample(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0, lowres=None):
         from lgm_hip import sampler
-        return sampler.ddim_sample(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale)
+        return sampler.ddim_sample(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale,
+                                   lowres=lowres)
 
     @torch.no_grad()
-    def dpm_solver_sample(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0):
+    def dpm_solver_sample(self, shape, return_all_timesteps=False, classes=None, cond_scale=1.0, lowres=None):
         """DPM-Solver++ on ``dpm_time_pairs()`` (order ``dpm_order``, ``dpm_stochastic``: the SDE form), one forward per step"""
         from lgm_hip import sampler
-        return sampler.dpm_solver_sample(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale)
+        return sampler.dpm_solver_sample(self, tuple(shape), return_all_timesteps, classes=classes, cond_scale=cond_scale,
+                                         lowres=lowres)
 
     @torch.no_grad()
-    def sample(self, batch_size=16, return_all_timesteps=False, classes=None, cond_scale=None):
+    def sample(self, batch_size=None, return_all_timesteps=False, classes=None, cond_scale=None, lowres=None,
+               lowres_aug_t=None, lowres_noise=None):
         """``classes`` (class-conditional model): one label per image, ``None`` = the null label, in one forward per step;
-        ``cond_scale=None`` takes the constructor's."""
+        ``cond_scale=None`` takes the constructor's.  ``batch_size=None``: 16, or the batch of ``lowres``.
+        ``lowres`` (a low-resolution conditioned model; required there, a ValueError elsewhere): [B, C, img_size / r,
+        img_size / r] in the data range.  It is normalised, upsampled and augmented at level ``lowres_aug_t`` (an int or
+        one per sample; ``None`` = the constructor's ``lowres_sample_aug_t``) with one draw (``lowres_noise``, NCHW at
+        ``img_size``, in its place for parity runs) into the conditioning slice, ONCE per chain."""
+        kw = {}
+        if self.lowres_cond or lowres is not None or lowres_aug_t is not None or lowres_noise is not None:
+            if batch_size is None and torch.is_tensor(lowres):
+                batch_size = lowres.shape[0]
+            kw["lowres"] = dict(lowres=self.check_lowres(lowres, 16 if batch_size is None else batch_size),
+                                lowres_aug_t=lowres_aug_t, lowres_noise=lowres_noise)
+        batch_size = 16 if batch_size is None else batch_size
         fn = self.ddim_sample if self.is_ddim_sampling else self.p_sample_loop
         if self.sampler == "dpm++":
             fn = self.dpm_solver_sample
@@ -1303,7 +1477,7 @@ class GaussianDiffusion(nn.Module):
             scale = 1.0                              # out_null + s * (out_null - out_null): the null forward alone
         classes, scale = self._guidance(classes, scale, batch_size, self.device)
         return fn((batch_size, self.channels, self.img_size, self.img_size), return_all_timesteps=return_all_timesteps,
-                  classes=classes, cond_scale=scale)
+                  classes=classes, cond_scale=scale, **kw)
 
     @torch.no_grad()
     def inpaint(self, known, mask, jump_length=1, resamples=1, classes=None, cond_scale=None, return_all_timesteps=False):
@@ -1313,6 +1487,7 @@ class GaussianDiffusion(nn.Module):
         to the step's level, and with ``resamples`` > 1 the chain is walked back up ``jump_length`` levels at a time
         (``lgm_hip.sampler.inpaint_walk``).  ``classes`` / ``cond_scale`` as in ``sample``."""
         from lgm_hip import sampler
+        self._refuse_lowres("inpaint")
         if known.dim() != 4 or tuple(known.shape[1:]) != (self.channels, self.img_size, self.img_size):
             raise ValueError(f"known must be [B, {self.channels}, {self.img_size}, {self.img_size}], got {tuple(known.shape)}")
         b, _, h, w = known.shape
@@ -1344,6 +1519,7 @@ class GaussianDiffusion(nn.Module):
         model, not of the sampler that feeds x_start forward).  A class-conditional network: ``classes=None`` is the null
         label, labels give the conditional bound; there is no guidance here - a guided output is not a probabilistic model."""
         from lgm_hip import likelihood
+        self._refuse_lowres("vlb_terms")
         return likelihood.vlb_terms(self, img, timesteps=timesteps, noise=noise, clip_denoised=clip_denoised,
                                     variance=variance, classes=classes)
 
@@ -1359,6 +1535,7 @@ class GaussianDiffusion(nn.Module):
     def interpolate(self, x1, x2, t=None, lam=0.5, classes=None, cond_scale=1.0):
         """reference :847-867: noise both images to step t, blend, walk the ancestral chain back to 0 (no unnormalise)."""
         from lgm_hip import sampler
+        self._refuse_lowres("interpolate")
         b = x1.shape[0]
         t = self.num_timesteps - 1 if t is None else int(t)
         assert x1.shape == x2.shape
@@ -1370,20 +1547,22 @@ class GaussianDiffusion(nn.Module):
 
 
 def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, save: bool, offset=None,
-                     strength: float = 0.0, self_cond=False, classes=None, dropout_key=None):
+                     strength: float = 0.0, self_cond=False, classes=None, dropout_key=None, lowres=None):
     """q_sample + UNet + the objective's target + weighted MSE on the HIP engine.  Returns (loss[1], ctx).
     ``offset`` ([B, C] or None) / ``strength``: offset noise, added to ``noise`` inside the q_sample kernel.
     ``self_cond`` (self-conditioned network only): ``True`` = estimate pass first (``hip_loss_estimate``), a tensor = that
     NCHW estimate.  ``classes``: device labels (``Unet.labels``) both passes of a class-conditional network read.
-    ``dropout_key``: the step's key (``GaussianDiffusion.draw_dropout_key``) both passes read, None = neither drops."""
-    q = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength)
+    ``dropout_key``: the step's key (``GaussianDiffusion.draw_dropout_key``) both passes read, None = neither drops.
+    ``lowres``: (s, eps_aug) of a low-resolution conditioned network (``GaussianDiffusion.draw_lowres``)."""
+    q = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength, lowres)
     if gd.model.self_condition:
         if torch.is_tensor(self_cond):
             assert self_cond.shape == img.shape
             ops.nchw_to_nhwc(self_cond.detach().float().contiguous(), gd.model.sc_slice(q.xt))
         elif self_cond:
             hip_loss_estimate(gd, q.xt, q.t, classes, dropout_key)
-    return hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, save, classes, normalize, dropout_key)
+    return hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, save, classes, normalize, dropout_key,
+                            q.lowres_s)
 
 
 def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None, dropout_key=None):
@@ -1398,10 +1577,13 @@ def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None, dropout_key=
                                     gd.num_timesteps, ops.stream())
 
 
-def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, offset=None, strength: float = 0.0):
+def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, offset=None, strength: float = 0.0,
+                     lowres=None):
     """x_t into the network's input buffer and the objective's target: one launch.  A self-conditioned network's buffer gets
     x_t in its x slice and zeros in its self-conditioning slice; any other network's buffer is the x slice alone
-    (``in_pitch = r4(C)``, ``x_off = 0``, ``sc_off = -1``)."""
+    (``in_pitch = r4(C)``, ``x_off = 0``, ``sc_off = -1``).  A low-resolution conditioned network (``lowres`` = (s, eps_aug)): a
+    second launch writes the conditioning slice from the same ``img`` - area average, bilinear upsample, normalisation and
+    augmentation in one pass, the low-resolution tensor never reaches memory (lgm_lowres_cond)."""
     net = gd.model
     B, C, H, W = img.shape
     Cp = _r4(C)
@@ -1418,7 +1600,14 @@ def hip_loss_qsample(gd: "GaussianDiffusion", img, t, noise, normalize: bool, of
                                        gd.sqrt_one_minus_alphas_cumprod.data_ptr(), 1 if normalize else 0,
                                        OBJECTIVES[gd.objective], xt.data_ptr(), net.in_pitch, net.x_off, net.sc_off,
                                        target.data_ptr(), Cp, B, C, H * W, Cp, ops.stream())
-    return QSample(xt, target, img, noise, t, offset)
+    if not net.lowres_cond:
+        return QSample(xt, target, img, noise, t, offset)
+    s, eps = lowres
+    s, eps = s.contiguous(), eps.detach().float().contiguous()
+    ops.lowres_cond(xt, net.cond_off, C, gd.lowres_factor, img=img, eps=eps, s=s, sqrt_ac=gd.sqrt_alphas_cumprod,
+                    sqrt_1mac=gd.sqrt_one_minus_alphas_cumprod, normalize=normalize)
+    # (eps is read by this launch alone: nothing behind it keeps it)
+    return QSample(xt, target, img, noise, t, offset, s)
 
 
 class LossContext:
@@ -1449,7 +1638,7 @@ def _loss_form(c: LossContext):
 
 
 def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None, normalize=None,
-                     dropout_key=None):
+                     dropout_key=None, lowres_s=None):
     """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx).  A learned-variance network: the hybrid
     loss instead (lgm_hybrid_loss_fwd: the same MSE over the prediction lanes + vb_loss_weight times the bound's term), ``ctx``
     (``LossContext``) then also holds the per-sample terms, x_t and ``normalize`` - whether ``img`` is still in the data range
@@ -1457,7 +1646,7 @@ def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset,
     this is pass 0 of the dropout mask."""
     B, C, H, W = img.shape
     hybrid = gd.learned_variance
-    out, tape = gd.model.forward_nhwc(xt, t, save, True, classes, dropout_key, 0)
+    out, tape = gd.model.forward_nhwc(xt, t, save, True, classes, dropout_key, 0, lowres_s)
     loss = ops.new((1,), img)
     ctx = LossContext(gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
     # a loss-aware timestep sampler (training mode): the *_iw forms weight sample b by iw[t_b] and leave that weight in ``wb``
@@ -1499,9 +1688,9 @@ class _PLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0, self_cond=False,
-                classes=None, dropout_key=None):
+                classes=None, dropout_key=None, lowres=None):
         loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]), offset, strength,
-                                           self_cond, classes, dropout_key)
+                                           self_cond, classes, dropout_key, lowres)
         return loss.view(())
 
     @staticmethod
@@ -1509,7 +1698,7 @@ class _PLossFn(torch.autograd.Function):
         gl = gloss.detach().float().reshape(1).contiguous()
         ctx.stuff.gd.model.backward_run(hip_loss_backward_begin(ctx.stuff, gl))
         ctx.stuff = None
-        return None, None, None, None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -1521,7 +1710,8 @@ class DDPM(LightningModule):
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
                  min_snr_gamma: float = 5, self_condition: bool = False, dropout: float = 0.0,
-                 num_classes: Optional[int] = None,
+                 lowres_cond: bool = False, lowres_factor: int = 4, lowres_aug_levels: Optional[int] = None,
+                 lowres_sample_aug_t: Optional[int] = None, num_classes: Optional[int] = None,
                  cond_drop_prob: float = 0.1, t_sampler: str = "uniform", t_sampler_history: int = 10,
                  t_sampler_uniform_prob: float = 0.001, dynamic_thresholding: bool = False,
                  dynamic_thresholding_percentile: float = 0.995, learned_variance: bool = False,
@@ -1539,16 +1729,23 @@ class DDPM(LightningModule):
         ``ema.online_model.t_sampler.history`` / ``.counts``.  New keywords stand in front of those that tests pin (the tail
         from ``dynamic_thresholding`` on: tests/test_dpmpp_host.py, tests/test_learned_sigma_host.py); pass everything from
         ``num_classes`` on by keyword.  ``dropout`` (extension; Ho et al. 2020 use 0.1 on CIFAR-10): the probability with
-        which the ResnetBlocks drop in the network passes of the training loss (``Unet``); the EMA shadow never drops."""
+        which the ResnetBlocks drop in the network passes of the training loss (``Unet``); the EMA shadow never drops.
+        ``lowres_cond`` / ``lowres_factor`` / ``lowres_aug_levels`` / ``lowres_sample_aug_t`` (extension): a super-resolution
+        stage of a cascade - the model trains on batches at ``img_size`` and conditions on their own ``lowres_factor`` times
+        smaller, noise-augmented version (``Unet`` / ``GaussianDiffusion``); ``upsample`` super-resolves a given image and
+        ``sample_cascade`` runs a base model and its stages end to end."""
         super().__init__()
         self.save_hyperparameters()
         self.num_classes = num_classes
         model = Unet(dim=dim, channels=img_channels, self_condition=self_condition, num_classes=num_classes,
-                     dropout=dropout, **(dict(learned_variance=True) if learned_variance else {}))
+                     dropout=dropout, **(dict(learned_variance=True) if learned_variance else {}),
+                     **(dict(lowres_cond=True) if lowres_cond else {}))
         cond = dict(cond_drop_prob=cond_drop_prob, cond_scale=cond_scale) if num_classes is not None else {}
         if learned_variance:
             cond["vb_loss_weight"] = vb_loss_weight
         cond.update(t_sampler=t_sampler, t_sampler_history=t_sampler_history, t_sampler_uniform_prob=t_sampler_uniform_prob)
+        if lowres_cond:
+            cond.update(lowres_factor=lowres_factor, lowres_aug_levels=lowres_aug_levels, lowres_sample_aug_t=lowres_sample_aug_t)
         diffusion_model = GaussianDiffusion(model, img_size=img_size, timesteps=diffusion_timesteps,
                                             sampling_timesteps=sampling_timesteps, objective=objective,
                                             beta_schedule=beta_schedule, offset_noise_strength=offset_noise_strength,
@@ -1558,6 +1755,8 @@ class DDPM(LightningModule):
                                             dynamic_thresholding_percentile=dynamic_thresholding_percentile, **cond)
         self.channels = img_channels
         self.img_size = img_size
+        self.lowres_cond, self.lowres_factor = bool(lowres_cond), int(lowres_factor)
+        self._cond_images = None          # a low-resolution conditioned model: the last batch seen, for _log_sample
         self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
         self.ema.ema_model.model.dropout = 0.0       # the shadow is what samples and validates: it never drops
         self.sample_every = 1000          # reference: every 1000 steps on rank 0 (:1025)
@@ -1577,6 +1776,8 @@ class DDPM(LightningModule):
     def _common_step(self, batch, mode: str):
         assert mode in ["train", "val", "test"], f"Invalid mode: {mode}"
         data, y = batch
+        if self.lowres_cond:
+            self._cond_images = data      # what _log_sample super-resolves: the batch at hand, downsampled
         model = self.ema.model if self.training else self.ema.ema_model
         loss = model(data, classes=y) if self.num_classes is not None else model(data)
         self.log(f"{mode}_loss", loss, prog_bar=True, logger=True, sync_dist=multi_rank())
@@ -1587,7 +1788,18 @@ class DDPM(LightningModule):
     @torch.no_grad()
     def _log_sample(self):
         self.ema.ema_model.eval()
-        if self.num_classes is not None:             # every class in turn, at the configured guidance scale
+        if self.lowres_cond:
+            # a super-resolution stage has nothing to sample from without an image: it super-resolves the downsampled
+            # batch of the step that logs (validation_step: the validation batch)
+            if self._cond_images is None:
+                return
+            data = self._cond_images[:64].to(self.ema.ema_model.device).float()
+            low = torch.nn.functional.avg_pool2d(data, self.lowres_factor)
+            kw = {}
+            if self.num_classes is not None:
+                kw["classes"] = torch.arange(low.shape[0], device=low.device) % self.num_classes
+            self.last_samples = self.ema.ema_model.sample(lowres=low, **kw)
+        elif self.num_classes is not None:             # every class in turn, at the configured guidance scale
             classes = torch.arange(64, device=self.ema.ema_model.device) % self.num_classes
             self.last_samples = self.ema.ema_model.sample(batch_size=64, classes=classes)
         else:
@@ -1605,6 +1817,13 @@ class DDPM(LightningModule):
         """``GaussianDiffusion.inpaint`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
         self.ema.ema_model.eval()
         return self.ema.ema_model.inpaint(known, mask, **kw)
+
+    @torch.no_grad()
+    def upsample(self, img_low, **kw):
+        """``GaussianDiffusion.sample(lowres=img_low, **kw)`` of the diffusion ``_log_sample`` samples from (the EMA weights):
+        ``img_low`` [B, C, img_size / lowres_factor, img_size / lowres_factor] in the data range -> [B, C, img_size, img_size]"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model.sample(lowres=img_low, **kw)
 
     @torch.no_grad()
     def bits_per_dim(self, img, classes=None, **kw):
@@ -1638,6 +1857,33 @@ class DDPM(LightningModule):
         bucketed gradient exchange + HIP-graph replay (what bench.py times), eager fallback inside."""
         from lgm_hip.graph import DDPMFastStep
         return DDPMFastStep(self, opt, world, use_graph, accumulate=accumulate)
+
+
+@torch.no_grad()
+def sample_cascade(stages, batch_size, classes=None):
+    """A cascade end to end in the data range: ``stages[0]`` (a ``DDPM`` without low-resolution conditioning) samples
+    ``batch_size`` images, every later stage (``DDPM(lowres_cond=True)`` whose ``img_size / lowres_factor`` is the size of the
+    stage below) super-resolves what the stage below returned (``DDPM.upsample``).  ``classes``: the labels every
+    class-conditional stage samples with.  Everything stays on the device; each stage samples under its EMA weights."""
+    if not stages:
+        raise ValueError("sample_cascade needs at least a base model")
+    base = stages[0]
+    if getattr(base, "lowres_cond", False):
+        raise ValueError("the first stage of a cascade is a base model: it has no low-resolution conditioning")
+    size = base.img_size
+    for k, st in enumerate(stages[1:], 1):
+        if not getattr(st, "lowres_cond", False):
+            raise ValueError(f"stage {k} of the cascade is not a low-resolution conditioned model")
+        if st.img_size != size * st.lowres_factor or st.channels != base.channels:
+            raise ValueError(f"stage {k} upsamples {st.img_size // st.lowres_factor} x {st.img_size // st.lowres_factor} "
+                             f"images of {st.channels} channels, the stage below returns {size} x {size} of {base.channels}")
+        size = st.img_size
+    label = lambda m: dict(classes=classes) if m.num_classes is not None and classes is not None else {}  # noqa: E731
+    base.ema.ema_model.eval()
+    img = base.ema.ema_model.sample(batch_size=batch_size, **label(base))
+    for st in stages[1:]:
+        img = st.upsample(img, **label(st))
+    return img
 
 
 def _is_master() -> bool:
