@@ -55,7 +55,8 @@ extern "C" {
                              *  lgm_grad_sqnorm_*, lgm_grad_clip_scale, lgm_adam_step_scaled, lgm_grad_accumulate, lgm_hybrid_loss_fwd,
                              *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned, lgm_gn_plan,
                              *  lgm_tsampler_draw, lgm_tsampler_update, lgm_weighted_mse_fwd_iw / _bwd_iw, lgm_hybrid_loss_fwd_iw / _bwd_iw,
-                             *  lgm_lowres_cond, lgm_lowres_emb_fwd, lgm_sample_step_extent, lgm_dpm_step_extent
+                             *  lgm_lowres_cond, lgm_lowres_emb_fwd, lgm_sample_step_extent, lgm_dpm_step_extent,
+                             *  lgm_distill_half_step, lgm_distill_target
                              *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -574,6 +575,32 @@ int lgm_dpm_step_extent(const float* xin, float* xout, int64_t pitch, int lane0,
                         int64_t v_pitch, const float* noise, float* hist, int B, int C, int HW, int objective, float A,
                         float Bv, float R, float Rm1, float Kx, float K0, float K1, float Kn, const float* table,
                         const int32_t* counter, int advance, const float* thresh, void* stream);
+
+/* Progressive distillation (csrc/distill.hip; Salimans & Ho 2022, Algorithm 2; an extension of the reference): one DDIM step
+ * t -> t'' of the student is trained to land where two DDIM steps t -> t' -> t'' of a frozen teacher land (eta = 0).  Both
+ * entry points read table [n_table][16] float32 at row t[b] (int64 [B], clamped to [0, n_table) on the device; 16-byte
+ * aligned; lgm_hip.distill.distill_plan, float64 rounded once):
+ *     (A_t, S_t, R_t, Rm1_t,  A_m, S_m, R_m, Rm1_m,  A_n, S_n, cX, cZ,  iS_t, t', den, t'')
+ *   (A, S, R, Rm1) = (sqrt_ac, sqrt_1mac, sqrt_recip, sqrt_recipm1) at t and at t' (m); (A_n, S_n) = (alpha, sigma) at t'', (1, 0)
+ *   for t'' = -1; den = A_n - (S_n / S_t) A_t, cX = 1 / den, cZ = -(S_n / S_t) / den ((1, 0) for t'' = -1); iS_t = 1 / S_t; t' as
+ *   a float.  Buffers are NHWC with their pitch in floats; the x slices are lanes [off, off + C) of their buffer, r4(C) lanes from
+ *   off must lie inside the pitch.  pred(z, o, head) is lgm_model_predictions_obj's branch for the TEACHER's objective with
+ *   rederive_pred_noise set: x0 (clamped to [-1, 1] when clip) and the noise derived from it - what ddim_sample forms.
+ * lgm_distill_half_step: (x1, e1) = pred(z_t, out, head_t), z_t' = A_m x1 + S_m e1 into lanes [mid_off, mid_off + C) of xmid and
+ *   zeros into the r4(C) - C lanes behind them; t_mid[b] = t'.  z_t is read from the x slice of xin; out is the teacher's output at
+ *   (z_t, t).  Launches distill_half_step_kernel.
+ * lgm_distill_target: (x2, e2) = pred(z_t', out, head_m) with out the teacher's output at (z_t', t'), z_t'' = A_n x2 + S_n e2,
+ *   x~ = cX z_t'' + cZ z_t, e~ = (z_t - A_t x~) iS_t; target lanes [0, C) = x~ (student objective 1), e~ (0) or A_t e~ - S_t x~ (2),
+ *   lanes [C, r4(C)) = 0.  Launches distill_target_kernel.
+ * Every product and sum rounds once (no contraction), in the order written.  16-byte accesses when every base is 16-byte aligned
+ * and every pitch and offset a multiple of 4, else one lane per thread: the same bits.  No atomics. */
+int lgm_distill_half_step(const float* xin, int64_t in_pitch, int x_off, const float* out, int64_t out_pitch, const int64_t* t,
+                          const float* table, int n_table, int teacher_objective, int clip, float* xmid, int64_t mid_pitch,
+                          int mid_off, int64_t* t_mid, int B, int C, int HW, void* stream);
+int lgm_distill_target(const float* xin, int64_t in_pitch, int x_off, const float* xmid, int64_t mid_pitch, int mid_off,
+                       const float* out, int64_t out_pitch, const int64_t* t, const float* table, int n_table,
+                       int teacher_objective, int student_objective, int clip, float* target, int64_t target_pitch, int B, int C,
+                       int HW, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * DPM-Solver++(2M) sampling (Lu et al. 2022, data prediction; an extension of the reference).  Buffers as for

@@ -251,8 +251,8 @@ class GraphedDDPMStep:
 
     def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None,
                  accum: Optional[_GradAccumulation] = None):
-        from models.generative.diffusion.ddpm import (hip_loss_backward_begin, hip_loss_estimate, hip_loss_network,
-                                                      hip_loss_qsample)
+        from models.generative.diffusion.ddpm import (hip_loss_backward_begin, hip_loss_distill, hip_loss_estimate,
+                                                      hip_loss_network, hip_loss_qsample)
         self.model, self.opt, self.sync, self.accum = model, opt, sync, accum
         self.gd = gd = model.ema.online_model
         self.net = net = gd.model
@@ -273,10 +273,16 @@ class GraphedDDPMStep:
         # timestep sampler (lgm_hip.tsampler): its draw opens qsample(), its update follows the loss inside hip_loss_network -
         # both inside the capture, its state on the device.  Warm-up and capture run the step: the state is put back after them.
         self.ts = ts = gd.active_t_sampler()
+        # progressive distillation (GaussianDiffusion.distill_from): the teacher's grid, table and weights as they are NOW are
+        # what the graphs hold - a new round (another teacher, another step count) is a new step object
+        distilling = gd._distill is not None
+        self.distill_sig = (gd._distill, gd._distill.table) if distilling else None
 
         def qsample():
             # the draws of GaussianDiffusion.forward / p_losses, in their order, and the q_sample launch
-            if ts is None:
+            if distilling:                           # a level of the student's grid: randint(0, N) and an index into it
+                self.t = gd.draw_distill_t(x.shape[0], x.device)
+            elif ts is None:
                 self.t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
             else:                                    # one launch behind torch.rand, where randint stands
                 self.t = ts.draw(x.shape[0], x.device)
@@ -288,7 +294,10 @@ class GraphedDDPMStep:
             lowres = gd.draw_lowres(self.x)                      # None (no draw) unless low-resolution conditioned
             if lowres is not None:
                 self.lowres_s, self.lowres_noise = lowres
-            return hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength, lowres)
+            q = hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength, lowres)
+            if distilling:                           # two teacher forwards and two launches: the target is the distillation's
+                hip_loss_distill(gd, q, self.classes)
+            return q
 
         def estimate(q):
             hip_loss_estimate(gd, q.xt, q.t, self.classes, self.dropout_key)
@@ -460,6 +469,10 @@ class DDPMFastStep:
             m._cond_images = x                       # a super-resolution stage logs samples of the batch at hand
         if m.sample_every and m.global_step % m.sample_every == 0 and _is_master():
             m._log_sample()
+        d = m.ema.online_model._distill
+        sig = self.graphed.distill_sig if self.graphed is not None else None
+        if self.graphed is not None and ((sig is None) != (d is None) or (d is not None and (sig[0] is not d or sig[1] is not d.table))):
+            self.graphed = None                      # a new distillation round (or none any more): the graphs held the old one's
         if self.use_graph and self.graphed is None:
             self._capture(x, y)
         self_cond = bool(self.coin()) if self.net.self_condition else False

@@ -1407,6 +1407,30 @@ def lowres_emb_fwd(temb, st, add):
     lib().lgm_lowres_emb_fwd(temb.data_ptr(), _p(st), add.data_ptr(), temb.shape[0], temb.shape[1], stream())
 
 
+# Progressive distillation (csrc/distill.hip): the two launches between the teacher's forwards and the student's loss.
+# Buffers [B, H, W, pitch] NHWC, ``*_off`` the first lane of their x slice; ``table`` [T, 16] float32 (lgm_hip.distill).
+def distill_half_step(xin, x_off, out, t, table, teacher_objective: int, clip: bool, xmid, mid_off, t_mid, C):
+    """z_t' into the x slice of ``xmid`` (the teacher's second input buffer) from z_t in ``xin`` and the teacher's output at
+    (z_t, t); ``t_mid`` (int64 [B]) = t'."""
+    B, H, W, _ = xin.shape
+    assert t.dtype == torch.int64 and t_mid.dtype == torch.int64 and tuple(t.shape) == tuple(t_mid.shape) == (B,)
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] == 16
+    lib().lgm_distill_half_step(xin.data_ptr(), pitch(xin), x_off, out.data_ptr(), pitch(out), t.data_ptr(), table.data_ptr(),
+                                table.shape[0], teacher_objective, 1 if clip else 0, xmid.data_ptr(), pitch(xmid), mid_off,
+                                t_mid.data_ptr(), B, C, H * W, stream())
+
+
+def distill_target(xin, x_off, xmid, mid_off, out, t, table, teacher_objective: int, student_objective: int, clip: bool,
+                   target, C):
+    """the distillation target [B, H, W, r4(C)] in the student's objective from z_t, z_t' and the teacher's output at (z_t', t')"""
+    B, H, W, _ = xin.shape
+    assert t.dtype == torch.int64 and tuple(t.shape) == (B,)
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] == 16
+    lib().lgm_distill_target(xin.data_ptr(), pitch(xin), x_off, xmid.data_ptr(), pitch(xmid), mid_off, out.data_ptr(), pitch(out),
+                             t.data_ptr(), table.data_ptr(), table.shape[0], teacher_objective, student_objective,
+                             1 if clip else 0, target.data_ptr(), pitch(target), B, C, H * W, stream())
+
+
 def act_fwd(x, bias_ptr, res, y, act, slope=0.0):
     lib().lgm_act_fwd(x.data_ptr(), pitch(x), bias_ptr, _p(res), pitch(res) if res is not None else 0,
                       y.data_ptr(), pitch(y), rows(x), x.shape[-1], act, slope, stream())

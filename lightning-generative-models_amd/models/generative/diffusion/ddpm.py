@@ -1011,6 +1011,38 @@ def _cosine_beta_schedule(timesteps, s=0.008):
 OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}     # the `objective` argument of the lgm_*_obj entry points
 
 
+class _Distillation:
+    """What ``GaussianDiffusion.distill_from`` attaches: the frozen teacher network (``teacher``, a ``Unet`` of its own flat
+    storage - deliberately no submodule of the student), the teacher's objective, the clip flag, and for the student's step
+    count ``steps``: ``grid`` (the host list G), ``levels`` (int64 [N], G[:-1] on the device: t = levels[i]) and ``table``
+    (float32 [T, 16], ``lgm_hip.distill.distill_plan`` rounded once).  ``stale``: the teacher's derived weight copies (Winograd
+    operands) are to be refreshed by its next forward - set whenever its weights may have changed, never inside a replay."""
+
+    def __init__(self, teacher: Unet, objective: str, clip: bool):
+        self.teacher, self.objective, self.clip = teacher, objective, clip
+        self.steps, self.grid, self.levels, self.table, self.stale = None, None, None, None, True
+
+    def plan(self, gd: "GaussianDiffusion", steps: int):
+        from lgm_hip import distill
+        rows = distill.distill_plan(gd, steps)
+        self.steps, self.grid = int(steps), distill.distill_grid(gd.num_timesteps, steps)[0]
+        self.levels = torch.tensor(self.grid[:-1], dtype=torch.long, device=gd.device)
+        self.table = rows.to(torch.float32).to(gd.device).contiguous()
+
+    def apply(self, fn):
+        self.teacher._apply(fn)
+        self.levels, self.table, self.stale = fn(self.levels), fn(self.table), True
+
+    def load_teacher(self, state):
+        self.teacher.load_state_dict(state, strict=True)
+        fp = self.teacher._flat
+        if fp is not None and fp.device.type == "cuda" and fp.still_bound():
+            self.teacher.refresh_derived_weights(False)      # now: a captured step does not pass through Python again
+            self.stale = False
+        else:
+            self.stale = True
+
+
 class GaussianDiffusion(nn.Module):
     def __init__(self, model: Unet, *, img_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
@@ -1137,10 +1169,56 @@ class GaussianDiffusion(nn.Module):
         # a plain attribute, not a submodule and not buffers: see lgm_hip.tsampler
         self._ts = None if t_sampler == "uniform" else tsampler.TimestepSampler(t_sampler, self.num_timesteps, history,
                                                                                 uniform_prob)
+        # progressive distillation (``distill_from``): None, or the attached teacher - a plain attribute like ``_ts``
+        self._distill: Optional[_Distillation] = None
 
     @property
     def device(self):
         return self.betas.device
+
+    # -- progressive distillation (extension; Salimans & Ho 2022, Algorithm 2; lgm_hip/distill.py) ------------------
+    def distill_from(self, teacher: Optional["GaussianDiffusion"], steps: Optional[int] = None, clip: bool = True):
+        """Attach a frozen copy of ``teacher.model``: from now on the training-mode ``forward`` / ``p_losses``, the eval-mode loss
+        and the graph-replayed step train THIS model so that one of its DDIM steps on the ``steps``-step grid lands where two
+        DDIM steps of the teacher on the 2 ``steps``-step grid land (module text of lgm_hip/distill.py).  The loss draws
+        i ~ randint(0, steps) where randint(0, T) stood and t = G[i]; behind the q_sample launch come the teacher's forward at
+        (z_t, t) without saved activations, ``lgm_distill_half_step``, its forward at (z_t', t') and ``lgm_distill_target``,
+        whose output takes the place of the objective's target; the weighted MSE with this model's ``loss_weight[t]`` and
+        everything behind it are unchanged.  ``clip`` (default True): the teacher's x0 predictions are clamped to [-1, 1] as
+        ``ddim_sample`` clamps them.  A class-conditional teacher sees the labels the student sees (after the drop), unguided.
+        Sets ``sampling_timesteps = steps``, DDIM sampling at eta 0 and ``sampler = "auto"``: ``sample()`` is the distilled sampler.
+        The copy has its own flat storage, is in eval mode, needs no gradient and never drops; its weights are no parameters of
+        this model (not in its flat buffer, gradient, optimizer or EMA shadow) and are saved and loaded under
+        ``distill_teacher.*`` with ``distill_steps`` while attached.  A deep copy of this model carries no teacher.
+        ``distill_from(None)`` detaches (the sampling settings stay).
+        Refused: ``NotImplementedError`` for a student with ``self_condition``, ``learned_variance``, ``lowres_cond``,
+        ``dropout > 0``, ``offset_noise_strength > 0`` or ``t_sampler != "uniform"`` and for a teacher with one of the first
+        three; ``ValueError`` for a teacher whose channels, image size, schedule tables or ``num_classes`` differ, for
+        ``2 * steps > T``, for a (T, steps) whose grids do not nest, and for ``sampler="dpm++"`` on the student."""
+        from lgm_hip import distill
+        if teacher is None:
+            self._distill = None
+            return self
+        import copy
+        N = distill.check_arguments(self, teacher, steps)
+        net = copy.deepcopy(teacher.model)           # Unet.__deepcopy__: plain parameters, flat storage of its own
+        net.eval().requires_grad_(False)
+        net.dropout = 0.0
+        self._distill = _Distillation(net, teacher.objective, bool(clip))
+        self._distill.plan(self, N)
+        self.set_sampling_steps(N)
+        return self
+
+    def set_sampling_steps(self, steps: int):
+        """what ``distill_from`` sets on the student (and ``DDPM`` on its EMA shadow): ``sample()`` = DDIM in ``steps`` steps, eta 0"""
+        self.sampling_timesteps = int(steps)
+        self.is_ddim_sampling = self.sampling_timesteps < self.num_timesteps
+        self.ddim_sampling_eta, self.sampler = 0.0, "auto"
+
+    @property
+    def distill_steps(self) -> Optional[int]:
+        """N while a teacher is attached, else None"""
+        return None if self._distill is None else self._distill.steps
 
     # -- the timestep sampler's state: moved, saved and loaded with the module, never a buffer of it ----------------
     def active_t_sampler(self):
@@ -1152,7 +1230,7 @@ class GaussianDiffusion(nn.Module):
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            new.__dict__[k] = None if k == "_ts" else copy.deepcopy(v, memo)
+            new.__dict__[k] = None if k in ("_ts", "_distill") else copy.deepcopy(v, memo)      # (no teacher either)
         new.t_sampler = "uniform"
         return new
 
@@ -1160,6 +1238,8 @@ class GaussianDiffusion(nn.Module):
         super()._apply(fn, *args, **kwargs)
         if self._ts is not None:
             self._ts.apply(fn)
+        if self._distill is not None:
+            self._distill.apply(fn)
         return self
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
@@ -1167,8 +1247,37 @@ class GaussianDiffusion(nn.Module):
         if self._ts is not None:
             for k, v in self._ts.state().items():
                 destination[f"{prefix}t_sampler.{k}"] = v if keep_vars else v.detach()
+        if self._distill is not None:
+            for k, v in self._distill.teacher.state_dict().items():
+                destination[f"{prefix}distill_teacher.{k}"] = v
+            destination[f"{prefix}distill_steps"] = torch.tensor(self._distill.steps)
+
+    def _load_distillation(self, state_dict, prefix, missing_keys, error_msgs):
+        """With a teacher attached: its weights and the step count out of ``state_dict`` -> the dict without them.  A saved
+        step count other than the attached one re-plans the grid and the table for it (a checkpoint of a later round)."""
+        d, tp, sk = self._distill, f"{prefix}distill_teacher.", f"{prefix}distill_steps"
+        if d is None:
+            return state_dict
+        found = {k[len(tp):]: v for k, v in state_dict.items() if k.startswith(tp)}
+        rest = {k: v for k, v in state_dict.items() if not k.startswith(tp) and k != sk}
+        if not found or sk not in state_dict:
+            if sk not in state_dict:
+                missing_keys.append(sk)
+            if not found:
+                missing_keys.extend(tp + k for k in d.teacher.state_dict())
+            return rest
+        try:
+            d.load_teacher(found)
+            steps = int(state_dict[sk])
+            if steps != d.steps:
+                d.plan(self, steps)
+                self.set_sampling_steps(steps)
+        except (RuntimeError, ValueError) as e:
+            error_msgs.append(f"distill_teacher: {e}")
+        return rest
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        state_dict = self._load_distillation(state_dict, prefix, missing_keys, error_msgs)
         mine = {k: f"{prefix}t_sampler.{k}" for k in (self._ts.state() if self._ts is not None else {})}
         found = {k: state_dict[key] for k, key in mine.items() if key in state_dict}
         rest = {k: v for k, v in state_dict.items() if k not in mine.values()} if found else state_dict
@@ -1204,7 +1313,8 @@ class GaussianDiffusion(nn.Module):
         return key.random_(-2 ** 63, None)             # all 64 bits
 
     def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, classes=None, *, _offset_noise=None,
-                 _normalize=False, _self_cond=None, _dropout_key=None, lowres_aug_t=None, lowres_noise=None):
+                 _normalize=False, _self_cond=None, _dropout_key=None, lowres_aug_t=None, lowres_noise=None,
+                 _t_on_grid=False):
         """x_start already normalised unless _normalize (reference :878-925).  Offset noise (:885-891): one draw per
         (sample, channel), added to the noise inside the q_sample kernel - the caller's ``noise`` is not written.
         ``_offset_noise`` (extension, for parity tests): the [B, C] draw the reference takes from torch.randn.
@@ -1220,13 +1330,22 @@ class GaussianDiffusion(nn.Module):
         Low-resolution conditioned model (extension): the conditioning slice is made from ``x_start`` itself in one launch
         (``lgm_lowres_cond``); its augmentation level s ~ randint(0, lowres_aug_levels) per sample and its noise are drawn
         behind every other draw, so a model without the option draws what it drew; ``lowres_aug_t`` (int64 [B]) /
-        ``lowres_noise`` (NCHW) are used instead when given (parity runs)."""
+        ``lowres_noise`` (NCHW) are used instead when given (parity runs).
+        With a teacher attached (``distill_from``): the target is the distillation target and every ``t_b`` must be a level
+        of the student's grid that has a successor, G[:-1] - ValueError otherwise (``_t_on_grid``: ``forward`` drew them from
+        the grid itself, nothing is read back)."""
         if not self.lowres_cond and (lowres_aug_t is not None or lowres_noise is not None):
             raise ValueError("lowres_aug_t / lowres_noise were passed to a model built without lowres_cond")
+        if self._distill is not None and not _t_on_grid:
+            off = sorted(set(int(v) for v in t.tolist()) - set(self._distill.grid[:-1]))
+            if off:
+                raise ValueError(f"t = {off} is not on the student's {self._distill.steps}-step grid {self._distill.grid[:-1]}")
         classes = self.model.labels(classes, x_start.shape[0], x_start.device)
         if noise is None:
             noise = torch.randn_like(x_start)
         strength = self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
+        if self._distill is not None and strength > 0.0:
+            raise NotImplementedError("offset noise together with a distillation teacher is not built")
         offset = None
         if strength > 0.0:
             offset = _offset_noise if _offset_noise is not None else torch.randn(x_start.shape[:2], device=x_start.device)
@@ -1252,6 +1371,13 @@ class GaussianDiffusion(nn.Module):
         eps = torch.randn_like(x_start) if lowres_noise is None else lowres_noise
         return s, eps
 
+    def draw_distill_t(self, B, device):
+        """t of a distillation step: i ~ randint(0, N) from torch's device generator, t = G[i] by an index into the device copy of
+        the grid (two launches; capturable)."""
+        d = self._distill
+        i = torch.randint(0, d.steps, (B,), device=device).long()
+        return d.levels[i]
+
     def drop_labels(self, classes):
         """Classifier-free guidance training: every label becomes the null label with probability ``cond_drop_prob`` (one
         ``torch.rand(B)`` on the labels' device; nothing is drawn when the probability is 0)."""
@@ -1267,7 +1393,10 @@ class GaussianDiffusion(nn.Module):
         b, c, h, w = img.shape
         assert h == self.img_size and w == self.img_size, f"height and width of image must be {self.img_size}"
         ts = self.active_t_sampler()
-        if ts is None:
+        if self._distill is not None:                # a level of the student's grid, where randint(0, T) stands
+            t = self.draw_distill_t(b, img.device)
+            kwargs["_t_on_grid"] = True
+        elif ts is None:
             t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()
         else:                                        # (its uniforms stand where randint stands in the draw order)
             t = ts.draw(b, img.device)
@@ -1555,6 +1684,8 @@ def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, sa
     ``dropout_key``: the step's key (``GaussianDiffusion.draw_dropout_key``) both passes read, None = neither drops.
     ``lowres``: (s, eps_aug) of a low-resolution conditioned network (``GaussianDiffusion.draw_lowres``)."""
     q = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength, lowres)
+    if gd._distill is not None:
+        hip_loss_distill(gd, q, classes)
     if gd.model.self_condition:
         if torch.is_tensor(self_cond):
             assert self_cond.shape == img.shape
@@ -1563,6 +1694,28 @@ def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, sa
             hip_loss_estimate(gd, q.xt, q.t, classes, dropout_key)
     return hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, save, classes, normalize, dropout_key,
                             q.lowres_s)
+
+
+def hip_loss_distill(gd: "GaussianDiffusion", q: QSample, classes=None):
+    """The distillation target over ``q.target`` (``GaussianDiffusion.distill_from``): the teacher's forward at (z_t, t) on the
+    student's own input buffer - both networks read the same layout -, ``lgm_distill_half_step`` into the teacher's second input
+    buffer, its forward at (z_t', t'), ``lgm_distill_target``.  No activation is saved, nothing is drawn; ``classes``: the device
+    labels the student's pass reads.  The teacher's derived weight copies are refreshed by the first call after its weights
+    were set, not per step: they are frozen."""
+    d, net = gd._distill, gd.model
+    tnet = d.teacher
+    B, H, W, _ = q.xt.shape
+    tnet.prepare_hip(q.xt.device)
+    assert (tnet.in_pitch, tnet.x_off) == (net.in_pitch, net.x_off), "teacher and student read one input layout"
+    to, so = OBJECTIVES[d.objective], OBJECTIVES[gd.objective]
+    out1, _ = tnet.forward_nhwc(q.xt, q.t, False, d.stale, classes)
+    d.stale = False
+    xmid = tnet.input_buffer(B, H, W, q.xt)
+    t_mid = torch.empty_like(q.t)
+    ops.distill_half_step(q.xt, net.x_off, out1, q.t, d.table, to, d.clip, xmid, tnet.x_off, t_mid, net.channels)
+    out2, _ = tnet.forward_nhwc(xmid, t_mid, False, False, classes)
+    ops.distill_target(q.xt, net.x_off, xmid, tnet.x_off, out2, q.t, d.table, to, so, d.clip, q.target, net.channels)
+    return q
 
 
 def hip_loss_estimate(gd: "GaussianDiffusion", xt, t, classes=None, dropout_key=None):
@@ -1711,7 +1864,8 @@ class DDPM(LightningModule):
                  beta_schedule: str = "sigmoid", offset_noise_strength: float = 0.0, min_snr_loss_weight: bool = False,
                  min_snr_gamma: float = 5, self_condition: bool = False, dropout: float = 0.0,
                  lowres_cond: bool = False, lowres_factor: int = 4, lowres_aug_levels: Optional[int] = None,
-                 lowres_sample_aug_t: Optional[int] = None, num_classes: Optional[int] = None,
+                 lowres_sample_aug_t: Optional[int] = None, distill_steps: Optional[int] = None,
+                 num_classes: Optional[int] = None,
                  cond_drop_prob: float = 0.1, t_sampler: str = "uniform", t_sampler_history: int = 10,
                  t_sampler_uniform_prob: float = 0.001, dynamic_thresholding: bool = False,
                  dynamic_thresholding_percentile: float = 0.995, learned_variance: bool = False,
@@ -1733,7 +1887,10 @@ class DDPM(LightningModule):
         ``lowres_cond`` / ``lowres_factor`` / ``lowres_aug_levels`` / ``lowres_sample_aug_t`` (extension): a super-resolution
         stage of a cascade - the model trains on batches at ``img_size`` and conditions on their own ``lowres_factor`` times
         smaller, noise-augmented version (``Unet`` / ``GaussianDiffusion``); ``upsample`` super-resolves a given image and
-        ``sample_cascade`` runs a base model and its stages end to end."""
+        ``sample_cascade`` runs a base model and its stages end to end.
+        ``distill_steps`` (extension; progressive distillation, Salimans & Ho 2022): ``None`` = a plain model; N = the module
+        starts as the student of a round at N sampling steps whose teacher is a frozen copy of its own weights
+        (``start_distillation(N)``) - load the teacher's checkpoint into it, or pass ``--distill_from`` to train.py."""
         super().__init__()
         self.save_hyperparameters()
         self.num_classes = num_classes
@@ -1763,10 +1920,51 @@ class DDPM(LightningModule):
         self.bpd_every = 0                # > 0: validation_step also logs val_bpd on every bpd_every-th batch (extension)
         self._val_batches = 0
         self.last_samples = None
+        if distill_steps is not None:
+            self.start_distillation(distill_steps)
 
     def prepare_hip(self, device):
         self.ema.online_model.model.prepare_hip(device)
         self.ema.ema_model.model.prepare_hip(device)
+        if self.ema.online_model._distill is not None:
+            self.ema.online_model._distill.teacher.prepare_hip(device)
+
+    # -- progressive distillation (extension; GaussianDiffusion.distill_from) ---------------------------------------
+    @torch.no_grad()
+    def start_distillation(self, steps: int, teacher=None, source: str = "ema"):
+        """Begin a round: this module becomes the student at ``steps`` sampling steps of a frozen copy of ``teacher`` - another
+        ``DDPM``, or ``None`` = this module's own weights - taken from its EMA shadow (``source="ema"``) or its online weights
+        (``"online"``).  As in the paper the student starts from the teacher: the online weights AND the EMA shadow are set to
+        the teacher's, the EMA clock starts again and the optimizer moments are dropped.  The refusals are
+        ``GaussianDiffusion.distill_from``'s.  A step object made before (``make_fast_step``) captures its graphs anew."""
+        if source not in ("ema", "online"):
+            raise ValueError(f"source must be 'ema' or 'online', got {source!r}")
+        src = self if teacher is None else teacher
+        tgd = src.ema.ema_model if source == "ema" else src.ema.online_model
+        online, shadow = self.ema.online_model, self.ema.ema_model
+        online.distill_from(tgd, steps)              # (the copy is made here: ``tgd`` may be one of the two set below)
+        weights = online._distill.teacher.state_dict()
+        for gd in (online, shadow):
+            gd.model.load_state_dict(weights)
+        shadow.set_sampling_steps(steps)
+        self.ema.step.zero_()
+        self.ema.initted.fill_(False)
+        self.ema._step_py, self.ema._initted_py = 0, False
+        for o in getattr(self, "_optimizers", None) or []:
+            getattr(o, "_opt", o)._flat_state.clear()            # FusedAdam: the moments and the step count of every flat buffer
+        self.hparams["distill_steps"] = int(steps)
+        return self
+
+    def halve(self, source: str = "online"):
+        """The next round: the current student (its online weights, or ``source="ema"``) becomes the teacher of a student at
+        ``distill_steps // 2``.  ValueError without a teacher attached, at one step, and at an odd step count (the student's grid
+        is then not the one a teacher of ``2 * (steps // 2)`` steps walks)."""
+        n = self.ema.online_model.distill_steps
+        if n is None:
+            raise ValueError("halve() needs a distillation round: call start_distillation first")
+        if n == 1 or n % 2:
+            raise ValueError(f"a student of {n} step{'s' if n > 1 else ''} cannot be halved")
+        return self.start_distillation(n // 2, None, source)
 
     def ddp_buffers(self):
         """Buffers training writes (re-broadcast from rank 0 before every forward, lgm_hip.lightning.BufferSync): none —
@@ -1779,7 +1977,16 @@ class DDPM(LightningModule):
         if self.lowres_cond:
             self._cond_images = data      # what _log_sample super-resolves: the batch at hand, downsampled
         model = self.ema.model if self.training else self.ema.ema_model
-        loss = model(data, classes=y) if self.num_classes is not None else model(data)
+        # a distillation round validates the shadow against the round's teacher: the shadow itself carries none, it borrows the
+        # online model's for the call
+        borrow = model._distill is None and self.ema.online_model._distill is not None
+        if borrow:
+            model._distill = self.ema.online_model._distill
+        try:
+            loss = model(data, classes=y) if self.num_classes is not None else model(data)
+        finally:
+            if borrow:
+                model._distill = None
         self.log(f"{mode}_loss", loss, prog_bar=True, logger=True, sync_dist=multi_rank())
         if self.sample_every and self.global_step % self.sample_every == 0 and _is_master():
             self._log_sample()

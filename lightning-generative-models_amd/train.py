@@ -77,7 +77,15 @@ def setup_arguments(argv=None, print_args=True, save_args=True):
     p.add_argument("--accelerator", type=str, default="auto", help="auto | cpu | gpu")
     p.add_argument("--devices", type=str, default="auto",
                    help="ranks to run as (Lightning's Trainer(devices=...)): auto = every visible GPU, like the reference")
+    p.add_argument("--distill_from", type=str, default=None,
+                   help="progressive distillation: the teacher's checkpoint; the config's model needs distill_steps")
+    p.add_argument("--distill_rounds", type=int, default=None, help="rounds to train, the step count halving between them")
+    p.add_argument("--distill_round_steps", type=int, default=None, help="optimizer steps per round")
     args = p.parse_args(argv)
+    if (args.distill_rounds is None) != (args.distill_round_steps is None):
+        p.error("--distill_rounds and --distill_round_steps go together")
+    if args.distill_rounds is not None and (args.distill_rounds < 1 or args.distill_round_steps < 1):
+        p.error("--distill_rounds and --distill_round_steps must be positive")
     args.precision = check_precision(args.precision)
     args.config = load_config(args.config_path)
     args.experiment_dir = os.path.join(EXPERIMENT_DIR, args.config["model"]["name"], args.experiment_name)
@@ -128,6 +136,36 @@ def maybe_spawn(argv):
     return launch.spawn_ranks(os.path.abspath(__file__), child_argv, n)
 
 
+def distill(args, model, datamodule, make_trainer):
+    """Progressive distillation (``DDPM.start_distillation`` / ``halve``): ``--distill_from CKPT`` loads the teacher's checkpoint
+    into the module and starts the round the config names (``distill_steps``) from its EMA weights; ``--distill_rounds R
+    --distill_round_steps S`` trains R rounds of S optimizer steps each, the student of one round becoming the teacher of
+    the next at half the steps.  Every round is a ``fit`` of its own: pending accumulation micro-batches are stepped at its
+    end (``flush``), the optimizer starts without moments, and the step is captured anew - the table, the grid and the
+    teacher's weights are baked into the graphs.  ``last.ckpt`` holds the round's teacher and its step count."""
+    if not hasattr(model, "start_distillation") or model.ema.online_model.distill_steps is None:
+        raise SystemExit("--distill_from / --distill_rounds need a DDPM config whose model args set distill_steps")
+    steps = model.ema.online_model.distill_steps
+    if args.distill_from is not None:
+        state = torch.load(args.distill_from, map_location="cpu", weights_only=False)["state_dict"]
+        if "ema.online_model.distill_steps" not in state:        # a plain model's checkpoint: it becomes the teacher
+            model.ema.online_model.distill_from(None)
+            model.load_state_dict(state)
+            model.start_distillation(steps)
+        else:                                                    # a round's checkpoint: its teacher, its step count
+            model.load_state_dict(state)
+    rounds = args.distill_rounds or 1
+    per_round = args.distill_round_steps if args.distill_round_steps is not None else args.max_steps
+    for r in range(rounds):
+        n = model.ema.online_model.distill_steps
+        if int(os.environ.get("RANK", "0")) == 0:
+            print(f"[distill] round {r + 1}/{rounds}: {2 * n} -> {n} sampling steps", flush=True)
+        make_trainer(model.global_step + per_round if per_round > 0 else -1).fit(
+            model, datamodule=datamodule, ckpt_path=args.ckpt_path if r == 0 else None)
+        if r < rounds - 1:
+            model.halve()
+
+
 def main(argv=None):
     rc = maybe_spawn(argv)
     if rc is not None:
@@ -143,11 +181,16 @@ def main(argv=None):
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     else:
         device = torch.device("cpu")
-    trainer = MiniTrainer(max_epochs=args.max_epochs, max_steps=args.max_steps, default_root_dir=args.experiment_dir,
-                          accumulate_grad_batches=args.accumulate_grad_batches, device=device,
-                          gradient_clip_val=args.gradient_clip_val, gradient_clip_algorithm=args.gradient_clip_algorithm,
-                          check_val_every_n_epoch=args.check_val_every_n_epoch)   # reference train.py: Trainer(...)
-    trainer.fit(model, datamodule=datamodule, ckpt_path=args.ckpt_path)
+    def make_trainer(max_steps):
+        return MiniTrainer(max_epochs=args.max_epochs, max_steps=max_steps, default_root_dir=args.experiment_dir,
+                           accumulate_grad_batches=args.accumulate_grad_batches, device=device,
+                           gradient_clip_val=args.gradient_clip_val, gradient_clip_algorithm=args.gradient_clip_algorithm,
+                           check_val_every_n_epoch=args.check_val_every_n_epoch)   # reference train.py: Trainer(...)
+
+    if args.distill_from is not None or args.distill_rounds is not None:
+        distill(args, model, datamodule, make_trainer)
+    else:
+        make_trainer(args.max_steps).fit(model, datamodule=datamodule, ckpt_path=args.ckpt_path)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
