@@ -56,7 +56,7 @@ extern "C" {
                              *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned, lgm_gn_plan,
                              *  lgm_tsampler_draw, lgm_tsampler_update, lgm_weighted_mse_fwd_iw / _bwd_iw, lgm_hybrid_loss_fwd_iw / _bwd_iw,
                              *  lgm_lowres_cond, lgm_lowres_emb_fwd, lgm_sample_step_extent, lgm_dpm_step_extent,
-                             *  lgm_distill_half_step, lgm_distill_target
+                             *  lgm_distill_half_step, lgm_distill_target, lgm_slerp, lgm_slerp_span, lgm_slerp_partials
                              *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -601,6 +601,25 @@ int lgm_distill_target(const float* xin, int64_t in_pitch, int x_off, const floa
                        const float* out, int64_t out_pitch, const int64_t* t, const float* table, int n_table,
                        int teacher_objective, int student_objective, int clip, float* target, int64_t target_pitch, int B, int C,
                        int HW, void* stream);
+
+/* Spherical interpolation of two latents (csrc/slerp.hip; the latent interpolation of Song et al. 2021, fig. 6; an extension
+ * of the reference).  a, b, out: NHWC [B, HW, pitch] with C live lanes from lane `off` on (off + C <= pitch), so each may be
+ * the x slice of a network input buffer; out may be a or b.  lam: float[B] on the device.  Per sample, in double:
+ *     c = a.b / sqrt(a.a b.b), clamped to [-1, 1]
+ *     (c0, c1) = (1 - lam, lam) when 1 - c^2 < 1e-3 or a norm is 0, else (sin((1 - lam) W), sin(lam W)) / sin W, W = acos c
+ *   each rounded once to float32, then out = fmaf(c1, b, c0 * a): three roundings per element on the way from (c0, c1).
+ *   Lanes of out outside [off, off + C) are not written.  coef_out (optional): float[B][2] = (c0, c1).
+ * Two launches, no atomics: slerp_partial_kernel (grid (spans, B): a workgroup reduces lgm_slerp_span() pixels of one sample
+ * to the three doubles a.a, b.b, a.b, products and sums in double in a fixed order) into partials, then slerp_blend_kernel
+ * (grid (spans, B): every workgroup sums its sample's partials in index order and blends its span).  partials: the caller's,
+ * lgm_slerp_partials(B, HW) = 3 B ceil(HW / span) doubles, 8-byte aligned.  Both queries are host-only and depend on their
+ * arguments alone (not on lgm_cu_margin()).  16-byte accesses when every base is 16-byte aligned, every pitch and offset a
+ * multiple of 4 and r4(C) lanes from off lie inside the pitch, else one float at a time: the same bits. */
+int64_t lgm_slerp_span(void);
+int64_t lgm_slerp_partials(int64_t B, int64_t HW);
+int lgm_slerp(const float* a, int64_t a_pitch, int a_off, const float* b, int64_t b_pitch, int b_off, const float* lam,
+              float* out, int64_t out_pitch, int out_off, double* partials, float* coef_out, int B, int C, int HW,
+              void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * DPM-Solver++(2M) sampling (Lu et al. 2022, data prediction; an extension of the reference).  Buffers as for

@@ -1431,6 +1431,41 @@ def distill_target(xin, x_off, xmid, mid_off, out, t, table, teacher_objective: 
                              1 if clip else 0, target.data_ptr(), pitch(target), B, C, H * W, stream())
 
 
+# Spherical interpolation of latents (csrc/slerp.hip): a per-sample reduction into the caller's partials, then the blend.
+def slerp_span() -> int:
+    """pixels one workgroup of either slerp launch covers (a constant of the library)"""
+    return int(lib().lgm_slerp_span())
+
+
+def slerp_partials(B: int, HW: int) -> int:
+    """doubles the slerp launches need as workspace for B samples of HW pixels: 3 per (sample, span)"""
+    return int(lib().lgm_slerp_partials(B, HW))
+
+
+def slerp(a, b, lam, out=None, coef_out=None, partials=None):
+    """out = c0 a + c1 b per sample, (c0, c1) the slerp weights of ``lam`` ([B] float32 on the device) between the samples of
+    ``a`` and ``b`` (lerp where they are nearly parallel or one is zero; include/lgm_hip.h has the rule).  ``a``, ``b``, ``out``:
+    NHWC [B, H, W, C], each possibly the lanes of a wider buffer (a network input buffer's x slice); ``out`` may be ``a`` or
+    ``b``, default: a new dense tensor; lanes of its buffer outside the C it shows are not written.  ``coef_out``: [B, 2]
+    float32, receives (c0, c1).  ``partials``: float64 workspace of ``slerp_partials(B, H W)`` values (default: allocated; a
+    captured call passes its own).  Two launches, no atomics."""
+    B, H, W, C = a.shape
+    if out is None:
+        out = torch.empty((B, H, W, C), device=a.device, dtype=torch.float32)
+    assert tuple(b.shape) == tuple(out.shape) == (B, H, W, C), (tuple(a.shape), tuple(b.shape), tuple(out.shape))
+    assert a.dtype == b.dtype == out.dtype == lam.dtype == torch.float32
+    assert tuple(lam.shape) == (B,) and lam.is_contiguous() and lam.device == a.device
+    n = slerp_partials(B, H * W)
+    if partials is None:
+        partials = torch.empty(n, device=a.device, dtype=torch.float64)
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= n
+    if coef_out is not None:
+        assert coef_out.dtype == torch.float32 and coef_out.is_contiguous() and tuple(coef_out.shape) == (B, 2)
+    lib().lgm_slerp(a.data_ptr(), pitch(a), 0, b.data_ptr(), pitch(b), 0, lam.data_ptr(), out.data_ptr(), pitch(out), 0,
+                    partials.data_ptr(), _p(coef_out), B, C, H * W, stream())
+    return out
+
+
 def act_fwd(x, bias_ptr, res, y, act, slope=0.0):
     lib().lgm_act_fwd(x.data_ptr(), pitch(x), bias_ptr, _p(res), pitch(res) if res is not None else 0,
                       y.data_ptr(), pitch(y), rows(x), x.shape[-1], act, slope, stream())

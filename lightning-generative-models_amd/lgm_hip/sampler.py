@@ -20,6 +20,10 @@ Top down:
     step (M_a, M_n, J_x, J_n); the update launch then also blends the known image, noised to the level the step lands on, into
     the known region and, after a step that is followed by a jump, re-noises the result up to the jump's level
     (``_plan_inpaint``, ``inpaint``).  A chain without a known image takes the path, key, buffers and launches it took.
+  * Editing (extensions; Song et al. 2021 4.3 and fig. 6, Meng et al. 2022): ``ddim_inverse_pairs`` / ``_plan_ddim_inverse``
+    walk the DDIM grid upwards with the same rows and the clip off (``_Plan.clip``; a graph key of its own), ``_plan_decode``
+    walks it down from a given level, ``_plan_img2img`` is the last steps of any of the three samplers; ``encode``, ``decode``,
+    ``img2img``, ``interpolate_ddim`` (``ops.slerp`` into the decoding chain's x slice) run them from a given state.
   * ``_run``: a chain of a plan.  Graph replay when only the final image is wanted, eager launches otherwise
     (``return_all_timesteps``, ``LGM_NO_SAMPLER_GRAPH=1``, no device, capture failed); bit-identical (tests/test_hip_unet.py).
 
@@ -135,7 +139,8 @@ def _ddim_coeffs(gd, t: int, t_next: int, eta: float):
     if t_next < 0:
         return _head(hs, t) + (1.0, 0.0, 0.0, 0.0)
     a, an = hs["alphas_cumprod"][t], hs["alphas_cumprod"][t_next]
-    sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt()
+    # eta == 0 also takes t_next > t (the inverse step), where the root below is of a negative number; 0 * root is the same 0
+    sigma = eta * ((1 - a / an) * (1 - an) / (1 - a)).sqrt() if eta != 0.0 else torch.zeros_like(an)
     c = (1 - an - sigma ** 2).sqrt()
     return _head(hs, t) + (_f32(an.sqrt()), 0.0, _f32(c), _f32(sigma))
 
@@ -202,6 +207,7 @@ class _Plan:
     kdraws: tuple = ()
     jdraws: tuple = ()
     learned: bool = False          # the ancestral chain of a learned-variance network: rows as ``_p_sample_coeffs`` says
+    clip: bool = True              # x0 is clipped (or thresholded); False: the inverse chain and its exact way back
 
 
 def _plan_ancestral(gd, start: Optional[int] = None, steps: Optional[int] = None) -> _Plan:
@@ -217,17 +223,99 @@ def _refuse_learned_dyn(gd):
                                   "update kernel has no variant for the combination (DDIM and DPM-Solver++ take both)")
 
 
-def _plan_ddim(gd) -> _Plan:
-    eta, pairs = gd.ddim_sampling_eta, gd.ddim_time_pairs()
+def _plan_ddim(gd, pairs=None, eta: Optional[float] = None, clip: bool = True) -> _Plan:
+    """``ddim_sample`` on ``pairs`` (default: the whole grid) at ``eta`` (default: the diffusion's)"""
+    eta = gd.ddim_sampling_eta if eta is None else float(eta)
+    pairs = gd.ddim_time_pairs() if pairs is None else pairs
     return _Plan(tuple(t for t, _ in pairs), tuple(_ddim_coeffs(gd, t, t_next, eta) for t, t_next in pairs),
-                 tuple(t_next >= 0 and eta != 0.0 for _, t_next in pairs), eta != 0.0, rederive=True)
+                 tuple(t_next >= 0 and eta != 0.0 for _, t_next in pairs), eta != 0.0, rederive=True, clip=clip)
 
 
-def _plan_dpm(gd) -> _Plan:
-    """``gd.dpm_order`` 1 or 2, ``gd.dpm_stochastic``: the SDE form, the only one that takes noise"""
-    stochastic, pairs = bool(gd.dpm_stochastic), gd.dpm_time_pairs()
+def _plan_dpm(gd, pairs=None) -> _Plan:
+    """``gd.dpm_order`` 1 or 2, ``gd.dpm_stochastic``: the SDE form, the only one that takes noise; on ``pairs`` (default: the
+    whole grid) as a chain of its own: its first step is first-order and reads no history"""
+    stochastic, pairs = bool(gd.dpm_stochastic), gd.dpm_time_pairs() if pairs is None else pairs
     return _Plan(tuple(t for t, _ in pairs), tuple(dpm_coeffs(gd, pairs, gd.dpm_order, stochastic)),
                  tuple(t_next >= 0 and stochastic for _, t_next in pairs), stochastic, dpm=True)
+
+
+def _ddim_grid(gd, steps: Optional[int] = None):
+    """g_0 < g_1 < .. < g_{N-1}: the times ``ddim_time_pairs()`` visits on ``steps`` steps (default: ``sampling_timesteps``)"""
+    pairs = gd.ddim_time_pairs() if steps is None else gd.ddim_time_pairs(int(steps))
+    return sorted({int(t) for t, _ in pairs})
+
+
+def _check_grid_steps(gd, steps: Optional[int]):
+    """the step count of an inversion grid: ``None`` is ``sampling_timesteps`` and must lie below T (a diffusion that samples
+    on the ancestral chain has no DDIM grid to invert); all T steps only when asked for by number"""
+    T = gd.num_timesteps
+    if steps is None:
+        if not 1 <= gd.sampling_timesteps < T:
+            raise ValueError(f"encode / decode need a DDIM grid: sampling_timesteps = {gd.sampling_timesteps} is not below "
+                             f"T = {T}; pass steps= (steps={T} for the full grid)")
+        return None
+    if int(steps) != steps or not 1 <= int(steps) <= T:
+        raise ValueError(f"steps must be an integer in [1, {T}], got {steps!r}")
+    return int(steps)
+
+
+def ddim_inverse_pairs(gd, upto: Optional[int] = None, steps: Optional[int] = None):
+    """The (t, u) pairs of DDIM inversion (Song et al. 2021, 4.3; guided-diffusion's ``ddim_reverse_sample``), u > t: with g_0 <
+    .. < g_{N-1} the times of the sampler's grid, [(g_0, g_1), .., (g_{N-2}, g_{N-1})].  The clean image is taken as the state
+    at level g_0 (guided-diffusion's convention; DESIGN section 6 has the size of that approximation).  ``upto`` = k, 1 <= k <=
+    N - 1: the first k pairs, ending at level g_k.  Pure Python: no device, no library."""
+    g = _ddim_grid(gd, steps)
+    pairs = list(zip(g[:-1], g[1:]))
+    if upto is None:
+        return pairs
+    if int(upto) != upto or not 1 <= int(upto) <= len(pairs):
+        raise ValueError(f"upto must be an integer in [1, {len(pairs)}] (the grid has {len(g)} levels), got {upto!r}")
+    return pairs[:int(upto)]
+
+
+def _plan_ddim_inverse(gd, upto: Optional[int] = None, steps: Optional[int] = None) -> _Plan:
+    """The inverse chain: step (t, u) reads the network at t and lands on u > t with the row ``_ddim_coeffs(gd, t, u, 0.0)`` =
+    head(t) + (sqrt(acp_u), 0, sqrt(1 - acp_u), 0).  Deterministic (no draws, no noise operand), and x0 is taken as predicted:
+    neither clipped nor thresholded, whatever the diffusion's sampler does - the map has to be undone step by step."""
+    pairs = ddim_inverse_pairs(gd, upto, steps)
+    return _Plan(tuple(t for t, _ in pairs), tuple(_ddim_coeffs(gd, t, u, 0.0) for t, u in pairs), (False,) * len(pairs), False,
+                 rederive=True, clip=False)
+
+
+def _plan_decode(gd, from_level: Optional[int] = None, steps: Optional[int] = None, clip: bool = True) -> _Plan:
+    """``ddim_sample`` at eta 0 from level index ``from_level`` of the grid (default N - 1, its top) down to the image: the pairs
+    (g_L, g_{L-1}), .., (g_1, g_0), (g_0, -1)"""
+    g = _ddim_grid(gd, steps)
+    L = len(g) - 1 if from_level is None else from_level
+    if int(L) != L or not 0 <= int(L) <= len(g) - 1:
+        raise ValueError(f"from_level must be an integer in [0, {len(g) - 1}] (the grid has {len(g)} levels), got {from_level!r}")
+    down = g[int(L)::-1]
+    return _plan_ddim(gd, list(zip(down, down[1:] + [-1])), 0.0, clip)
+
+
+def img2img_steps(n: int, strength: float) -> int:
+    """how many of a sampler's n steps an img2img chain runs: max(1, round(strength n)), strength in (0, 1]"""
+    if not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f"strength must lie in (0, 1], got {strength!r}")
+    return max(1, int(round(float(strength) * n)))
+
+
+def _plan_img2img(gd, strength: float, kind: Optional[str] = None):
+    """-> (plan, t_start): the last ``img2img_steps(N, strength)`` steps of the sampler ``kind`` (default: the one ``sample``
+    dispatches to) and the time of the first of them, the level the image is noised to (SDEdit, Meng et al. 2022).
+    DPM-Solver++ is planned on the truncated pairs, a chain of its own, as the monotone runs of ``inpaint`` are."""
+    kind = _sampler_kind(gd) if kind is None else kind
+    if kind == "ancestral":
+        plan = _plan_ancestral(gd, start=img2img_steps(gd.num_timesteps, strength))
+    elif kind == "ddim":
+        pairs = gd.ddim_time_pairs()
+        plan = _plan_ddim(gd, pairs[len(pairs) - img2img_steps(len(pairs), strength):])
+    elif kind == "dpm":
+        pairs = gd.dpm_time_pairs()
+        plan = _plan_dpm(gd, pairs[len(pairs) - img2img_steps(len(pairs), strength):])
+    else:
+        raise ValueError(f"unknown sampler kind {kind!r}")
+    return plan, plan.times[0]
 
 
 def inpaint_walk(n: int, jump_length: int, resamples: int) -> List[int]:
@@ -359,10 +447,12 @@ def _launch_thresh(net, shape, objective: int, x, v, head, rank, thresh, table=N
 
 
 def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, hist=None, thresh=None, rank=None, row=None,
-                   table=None, counter=None, rederive: bool = False, dpm: bool = False, inpaint=None, learned: bool = False):
+                   table=None, counter=None, rederive: bool = False, dpm: bool = False, inpaint=None, learned: bool = False,
+                   clip: bool = True):
     """The update of one step: ``x_next`` <- x slice of ``x``, network output ``v``, ``noise`` (None: none).  The row comes by
     value (``row``, eager launches) or from ``table[counter]`` (the captured step, which also advances the counter and passes
-    zeros in the by-value slots).  ``rank`` (dynamic thresholding) puts ``_launch_thresh`` in front.  Every update clips x0.
+    zeros in the by-value slots).  ``rank`` (dynamic thresholding) puts ``_launch_thresh`` in front.  Every update clips x0
+    unless ``clip`` is False (``_plan_ddim_inverse`` and the decode that undoes it: the plain entries only, no thresholds).
 
         solver            thresholded  row       self-conditioned  kernel entry
         ancestral / DDIM  no           by value  yes               step_slice: x0 into the self-conditioning slice
@@ -384,7 +474,9 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
     L, st, p = ops.lib(), ops.stream(), ops._p
     tabled = table is not None
     A, Bv, R, Rm1, W0, W1, W2, W3 = row if not tabled else (0.0,) * 8
-    red, tab = 1 if rederive else 0, (p(table), p(counter))
+    red, tab, cl = 1 if rederive else 0, (p(table), p(counter)), 1 if clip else 0
+    assert clip or (rank is None and inpaint is None and not learned and not getattr(net, "lowres_cond", False)), \
+        "an unclipped step runs on the plain update entries only: refused where the plan is made"
     src = (net.in_pitch, net.x_off, net.sc_off, v.data_ptr(), ops.pitch(v), p(noise))
     if getattr(net, "lowres_cond", False):
         assert inpaint is None, "refused where the chain is made"
@@ -425,18 +517,18 @@ def _launch_update(net, shape, objective: int, v, noise, *, x, x_next, x0=None, 
             L.lgm_sample_step_thresh(x.data_ptr(), x_next.data_ptr(), *src, None if net.self_condition or tabled else p(x0),
                                      B, C, H * W, objective, red, *end)
     elif dpm and tabled:
-        L.lgm_dpm_step_table(x.data_ptr(), *src, hist.data_ptr(), B, C, H * W, *tab, objective, 1, 1, st)
+        L.lgm_dpm_step_table(x.data_ptr(), *src, hist.data_ptr(), B, C, H * W, *tab, objective, cl, 1, st)
     elif dpm:
-        L.lgm_dpm_step(x.data_ptr(), x_next.data_ptr(), *src, hist.data_ptr(), B, C, H * W, objective, A, Bv, 1, R, Rm1, W0, W1,
+        L.lgm_dpm_step(x.data_ptr(), x_next.data_ptr(), *src, hist.data_ptr(), B, C, H * W, objective, A, Bv, cl, R, Rm1, W0, W1,
                        W2, W3, st)
     elif tabled:
-        L.lgm_sample_step_table_slice(x.data_ptr(), *src, B, C, H * W, *tab, objective, 1, red, 1, st)
+        L.lgm_sample_step_table_slice(x.data_ptr(), *src, B, C, H * W, *tab, objective, cl, red, 1, st)
     elif net.self_condition:
-        L.lgm_sample_step_slice(x.data_ptr(), x_next.data_ptr(), *src, B, C, H * W, objective, A, Bv, 1, red, R, Rm1, W0, W1,
+        L.lgm_sample_step_slice(x.data_ptr(), x_next.data_ptr(), *src, B, C, H * W, objective, A, Bv, cl, red, R, Rm1, W0, W1,
                                 W2, W3, st)
     else:
         L.lgm_sample_step_obj(x.data_ptr(), v.data_ptr(), p(noise), x_next.data_ptr(), x0.data_ptr(), B, C, H * W, _r4(C),
-                              objective, A, Bv, 1, red, R, Rm1, W0, W1, W2, W3, st)
+                              objective, A, Bv, cl, red, R, Rm1, W0, W1, W2, W3, st)
 
 
 class _Chain:
@@ -512,10 +604,12 @@ class _Chain:
         return tb
 
     def step(self, t: int, noise: Optional[torch.Tensor], row, rederive: bool = False, dpm: bool = False, irow=None,
-             eps_k: Optional[torch.Tensor] = None, eps_j: Optional[torch.Tensor] = None, learned: bool = False):
+             eps_k: Optional[torch.Tensor] = None, eps_j: Optional[torch.Tensor] = None, learned: bool = False,
+             clip: bool = True):
         """One eager step at time t from a row of 8; no noise operand where the row weighs it with zero (t == 0 of the
         ancestral chain, eta == 0, the ODE, a last step that returns x0).  Afterwards ``x`` is the new image and ``x0`` the
-        clipped x_start: the self-conditioning slice of ``x``, else ``hist`` (DPM-Solver++), else the buffer of its own.
+        clipped x_start (``clip`` False: as predicted, neither clipped nor thresholded): the self-conditioning slice of ``x``,
+        else ``hist`` (DPM-Solver++), else the buffer of its own.
         ``irow`` (an inpainting chain): the step's (M_a, M_n, J_x, J_n); ``eps_k`` / ``eps_j`` go in where M_n / J_n is not zero."""
         B, C, H, W = self.shape
         net = self.net
@@ -528,8 +622,8 @@ class _Chain:
             inpaint = (self.known, self.mask, eps_k if irow[1] != 0.0 else None, eps_j if irow[3] != 0.0 else None, irow, None)
         silent = -math.inf if learned else 0.0       # what the row's last slot holds on a step without noise
         _launch_update(net, self.shape, _objective(self.gd), v, noise if row[7] != silent else None, x=self.x,
-                       x_next=self.x_next, x0=self.x0, hist=self.hist, thresh=self.thresh, rank=self.dyn, row=row,
-                       rederive=rederive, dpm=dpm, inpaint=inpaint, learned=learned)
+                       x_next=self.x_next, x0=self.x0, hist=self.hist, thresh=self.thresh, rank=self.dyn if clip else None,
+                       row=row, rederive=rederive, dpm=dpm, inpaint=inpaint, learned=learned, clip=clip)
         if net.self_condition:
             self.x0 = net.sc_slice(self.x_next)
         elif dpm:
@@ -556,8 +650,10 @@ class _GraphedChain:
     """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it."""
 
     def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096, guided: bool = False,
-                 dpm: bool = False, dyn: Optional[float] = None, inpaint: bool = False, learned: bool = False):
+                 dpm: bool = False, dyn: Optional[float] = None, inpaint: bool = False, learned: bool = False,
+                 clip: bool = True):
         net = gd.model
+        dyn = dyn if clip else None                  # an unclipped step is not thresholded either
         objective = _objective(gd)
         self._net = weakref.ref(net)                 # the cache is keyed weakly on the network: no strong reference here
         B, C, H, W = shape
@@ -609,7 +705,8 @@ class _GraphedChain:
                 tail = (self.known, self.mask, ek, ej, None, self.itable)
             # x (and, self-conditioned, the x_start handed on): the slices of the static buffer, in place
             _launch_update(net, shape, objective, v, nz, x=self.x, x_next=self.x, hist=self.hist, thresh=self.thresh, rank=rank,
-                           table=self.table, counter=self.counter, rederive=rederive, dpm=dpm, inpaint=tail, learned=learned)
+                           table=self.table, counter=self.counter, rederive=rederive, dpm=dpm, inpaint=tail, learned=learned,
+                           clip=clip)
 
         net.refresh_derived_weights(False)
         rng_state = torch.cuda.get_rng_state(dev)
@@ -685,8 +782,10 @@ class _GraphedChain:
 
 
 def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: bool, inpaint: bool = False,
-               learned: bool = False):
+               learned: bool = False, clip: bool = True):
     """The cache key of a captured step under its network: everything baked into the launches that the network does not fix"""
+    if not clip:                                     # the unclipped (and unthresholded) update: no other key changes
+        return ("noclip",) + _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint, learned)
     key = (tuple(shape), bool(with_noise))
     if gd.objective != "pred_v":                     # two diffusions of other objectives may share one network
         key += (gd.objective, bool(rederive))
@@ -706,7 +805,7 @@ def _graph_key(gd, shape, with_noise: bool, rederive: bool, guided: bool, dpm: b
 
 
 def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bool = False, dpm: bool = False,
-                 inpaint: bool = False, learned: bool = False):
+                 inpaint: bool = False, learned: bool = False, clip: bool = True):
     """-> a _GraphedChain for (network, shape, objective), or None (graph replay disabled / capture failed: eager launches).
     ``rederive``: the DDIM chain's re-derived noise, part of the captured launch for pred_noise / pred_x0.
     ``dpm``: the DPM-Solver++ step (its own update kernel and history buffer): a graph of its own.
@@ -716,7 +815,7 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
     net = gd.model
     net.prepare_hip(gd.betas.device)                 # may rebuild the flat storage (model.to(), new parameter storage)
     per_net = _GRAPHS.setdefault(net, {})
-    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint, learned)
+    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint, learned, clip)
     ent = per_net.get(key)
     if isinstance(ent, _GraphedChain) and not ent.matches(net):
         ent = None                                   # captured against buffers the network no longer uses
@@ -729,7 +828,7 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
     if ent is None:
         try:
             ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd), inpaint=inpaint,
-                                learned=learned)
+                                learned=learned, clip=clip)
         except Exception as e:  # capture is an optimisation
             print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",
                   file=sys.stderr, flush=True)
@@ -756,9 +855,12 @@ def dpm_step(chain: _Chain, t: int, noise: Optional[torch.Tensor], coeffs):
 
 
 def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, noises: Optional[List[torch.Tensor]] = None,
-         classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None, known=None, mask=None, lowres=None):
+         classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None, known=None, mask=None, lowres=None,
+         chain: Optional[_Chain] = None):
     """One chain of ``plan`` from ``init_noise`` (default: drawn) -> the image, or every image of the chain stacked along
-    dim 1.  ``noises``: one NCHW tensor (or None) per step in place of the draws; ``unnormalize``: default = the model's
+    dim 1.  The start is a STATE, not necessarily noise: ``init_noise`` is whatever the chain's first step reads (NCHW: a
+    latent for ``decode``, a noised image for ``img2img``, an image for ``encode``), or the caller hands over a ``chain`` whose
+    x slice it has filled on the device (``interpolate_ddim``), eager and replayed alike.  ``noises``: one NCHW tensor (or None) per step in place of the draws; ``unnormalize``: default = the model's
     auto_normalize (p_sample_loop :779).  No graph for a chain without steps.  An inpainting plan takes ``known`` (NCHW,
     normalised) and ``mask`` ([B, HW] or [B, 1, H, W], 1 = keep); an entry of ``noises`` is then a triple (noise, eps_k,
     eps_j) with a tensor wherever the plan's draw flag of the step is set; the draws are taken in that order.
@@ -771,13 +873,14 @@ def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, no
             flags = (plan.draws[i], plan.kdraws[i], plan.jdraws[i])
             if any(f and (trip is None or trip[k] is None) for k, f in enumerate(flags)):
                 raise ValueError(f"step {i} of the inpainting chain draws {flags}, the injected triple lacks one of them")
-    chain = _Chain(gd, shape, init_noise, None, classes, cond_scale, **(dict(known=known, mask=mask) if tail else {}),
-                   **(lowres or {}))
+    if chain is None:
+        chain = _Chain(gd, shape, init_noise, None, classes, cond_scale, **(dict(known=known, mask=mask) if tail else {}),
+                       **(lowres or {}))
     unn = gd.auto_normalize if unnormalize is None else bool(unnormalize)
     gc = None
     if plan.times and not return_all_timesteps:
         gc = _graph_chain(gd, shape, plan.with_noise, rederive=plan.rederive, guided=chain.cond_scale != 1.0, dpm=plan.dpm,
-                          inpaint=tail, learned=plan.learned)
+                          inpaint=tail, learned=plan.learned, clip=plan.clip)
     if gc is not None and tail:
         chain.x = gc.run(chain.x, plan.times, plan.rows, noises, chain.classes, chain.cond_scale,
                          inpaint=(chain.known, chain.mask, plan.irows))
@@ -801,7 +904,7 @@ def _run(gd, shape, plan: _Plan, return_all_timesteps=False, init_noise=None, no
             nz = None
             if draws:
                 nz = noises[i] if noises is not None else draw()
-            chain.step(t, nz, row, plan.rederive, plan.dpm, learned=plan.learned)
+            chain.step(t, nz, row, plan.rederive, plan.dpm, learned=plan.learned, clip=plan.clip)
         if return_all_timesteps:
             frames.append(chain.image(False))
     if return_all_timesteps:
@@ -854,3 +957,61 @@ def inpaint(gd, known, mask, jump_length: int = 1, resamples: int = 1, return_al
     shape = tuple(known.shape)
     return _run(gd, shape, _plan_inpaint(gd, jump_length, resamples, kind), return_all_timesteps, init_noise, noises, classes,
                 cond_scale, unnormalize, known=known, mask=mask)
+
+
+@torch.no_grad()
+def encode(gd, img, steps: Optional[int] = None, upto: Optional[int] = None, return_all_timesteps=False, classes=None,
+           cond_scale: float = 1.0):
+    """DDIM inversion (Song et al. 2021, 4.3 and 5.4): the deterministic chain of ``_plan_ddim_inverse`` from ``img`` (NCHW,
+    normalised), taken as the state at the grid's lowest level, up to its top (or ``upto`` pairs) -> the latent, NCHW, as the
+    chain holds it.  Per step one forward (two and the mix when guided) and the ONE update launch of ``ddim_sample``, with the
+    clip off; graph-replayed like it."""
+    plan = _plan_ddim_inverse(gd, upto, _check_grid_steps(gd, steps))
+    return _run(gd, tuple(img.shape), plan, return_all_timesteps, img, None, classes, cond_scale, unnormalize=False)
+
+
+@torch.no_grad()
+def decode(gd, latent, from_level: Optional[int] = None, steps: Optional[int] = None, clip: bool = True,
+           return_all_timesteps=False, classes=None, cond_scale: float = 1.0, unnormalize: Optional[bool] = None, chain=None):
+    """``ddim_sample`` at eta 0 started from ``latent`` (NCHW; or a ``chain`` that holds it) at level index ``from_level`` of the
+    grid (default: its top).  ``clip=False``: x0 as predicted, the exact way back along ``encode``'s chain."""
+    plan = _plan_decode(gd, from_level, _check_grid_steps(gd, steps), clip)
+    shape = tuple(latent.shape) if chain is None else chain.shape
+    return _run(gd, shape, plan, return_all_timesteps, latent, None, classes, cond_scale, unnormalize, chain=chain)
+
+
+@torch.no_grad()
+def img2img(gd, img, strength: float = 0.5, noise=None, return_all_timesteps=False, noises=None, classes=None,
+            cond_scale: float = 1.0, kind: Optional[str] = None):
+    """SDEdit (Meng et al. 2022): ``img`` (NCHW, normalised) noised to the level of the first of the sampler's last
+    ``img2img_steps(N, strength)`` steps (``q_sample`` with ``noise``, default: drawn), then those steps.  ``noises``: one NCHW
+    tensor (or None) per step of the truncated chain in place of its draws."""
+    plan, t0 = _plan_img2img(gd, strength, kind)
+    tb = torch.full((img.shape[0],), t0, device=img.device, dtype=torch.long)
+    return _run(gd, tuple(img.shape), plan, return_all_timesteps, gd.q_sample(img, tb, noise), noises, classes, cond_scale)
+
+
+@torch.no_grad()
+def interpolate_ddim(gd, x1, x2, lam=0.5, steps: Optional[int] = None, classes=None, cond_scale: float = 1.0,
+                     upto: Optional[int] = None):
+    """The latent interpolation of Song et al. 2021, fig. 6: ``encode`` both images (NCHW, normalised), slerp the two latents
+    with ``lam`` (a float or one value per sample) straight into the x slice of the decoding chain (``ops.slerp``: two launches),
+    ``decode`` without the clip.  ``upto``: blend at level index ``upto`` of the grid, not at its top.  Deterministic; no
+    unnormalise, like the stochastic form."""
+    grid_steps = _check_grid_steps(gd, steps)
+    if tuple(x1.shape) != tuple(x2.shape):
+        raise ValueError(f"the two images must have one shape, got {tuple(x1.shape)} and {tuple(x2.shape)}")
+    B, C, H, W = x1.shape
+    za = encode(gd, x1, grid_steps, upto, False, classes, cond_scale)
+    zb = encode(gd, x2, grid_steps, upto, False, classes, cond_scale)
+    chain = _Chain(gd, (B, C, H, W), za, None, classes, cond_scale)
+    other = torch.empty((B, H, W, _r4(C)), device=za.device)
+    ops.nchw_to_nhwc(zb.contiguous(), other)
+    lam = torch.as_tensor(lam, dtype=torch.float32, device=za.device)
+    if lam.dim() == 0:
+        lam = lam.expand(B)
+    if tuple(lam.shape) != (B,):
+        raise ValueError(f"lam must be a float or one value per sample ([{B}]), got shape {tuple(lam.shape)}")
+    x = chain.net.x_slice(chain.x)
+    ops.slerp(x, other[..., :C], lam.contiguous(), out=x)
+    return decode(gd, None, upto, grid_steps, False, False, classes, cond_scale, unnormalize=False, chain=chain)

@@ -1290,8 +1290,9 @@ class GaussianDiffusion(nn.Module):
         else:
             missing_keys.extend(key for k, key in mine.items() if k not in found)
 
-    def ddim_time_pairs(self):
-        times = torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1)
+    def ddim_time_pairs(self, steps=None):
+        """the reference's DDIM grid (:785-787) on ``steps`` steps (default: ``sampling_timesteps``)"""
+        times = torch.linspace(-1, self.num_timesteps - 1, steps=(self.sampling_timesteps if steps is None else steps) + 1)
         times = list(reversed(times.int().tolist()))
         return list(zip(times[:-1], times[1:]))
 
@@ -1660,10 +1661,84 @@ class GaussianDiffusion(nn.Module):
             raise ValueError("nll_bpd evaluates every timestep; use vlb_terms for a subset")
         return self.vlb_terms(img, **kw).total_bpd
 
+    def _edit_args(self, what: str, img, classes, cond_scale, selfcond_ok: bool = False):
+        """the checks every editing call makes before anything runs -> (img on the device in float32, labels, scale)"""
+        self._refuse_lowres(what)
+        if self.self_condition and not selfcond_ok:
+            raise NotImplementedError(f"{what} on a self-conditioned model is not built: the inverse step has no x_start to "
+                                      "hand on")
+        want = (self.channels, self.img_size, self.img_size)
+        if not torch.is_tensor(img) or img.dim() != 4 or tuple(img.shape[1:]) != want:
+            got = tuple(img.shape) if torch.is_tensor(img) else type(img).__name__
+            raise ValueError(f"{what} takes [B, {want[0]}, {want[1]}, {want[2]}], got {got}")
+        scale = self.cond_scale if cond_scale is None else cond_scale
+        if classes is None:
+            scale = 1.0                              # the null forward alone, as in ``sample``
+        classes, scale = self._guidance(classes, scale, img.shape[0], self.device)
+        return img.to(self.device).float().contiguous(), classes, scale
+
     @torch.no_grad()
-    def interpolate(self, x1, x2, t=None, lam=0.5, classes=None, cond_scale=1.0):
-        """reference :847-867: noise both images to step t, blend, walk the ancestral chain back to 0 (no unnormalise)."""
+    def encode(self, img, steps=None, upto=None, classes=None, cond_scale=1.0, return_all_timesteps=False):
+        """DDIM inversion (extension; Song et al. 2021, 4.3 and 5.4; guided-diffusion's ``ddim_reverse_sample``): the
+        deterministic map from ``img`` ([B, C, S, S] in the data range, normalised as ``forward`` normalises) to the latent
+        that ``decode`` turns back into it -> [B, C, S, S], the chain's state, not unnormalised.  The grid is the DDIM
+        sampler's on ``steps`` steps (``None``: ``sampling_timesteps``, which must then lie below T; all T steps only by
+        ``steps=T``), walked upwards (``lgm_hip.sampler.ddim_inverse_pairs``); the image is taken as the state at the grid's
+        lowest level.  ``upto=k`` stops after k pairs, at level index k.  x0 is neither clipped nor thresholded on the way,
+        whatever the sampler does.  ``classes`` / ``cond_scale`` as in ``sample`` (``cond_scale=None``: the constructor's): a
+        guided encode is two forwards and the mix per step.  Graph-replayed like sampling."""
         from lgm_hip import sampler
+        img, classes, scale = self._edit_args("encode", img, classes, cond_scale)
+        return sampler.encode(self, self.normalize(img), steps, upto, return_all_timesteps, classes, scale)
+
+    @torch.no_grad()
+    def decode(self, latent, from_level=None, classes=None, cond_scale=None, steps=None, clip=True,
+               return_all_timesteps=False):
+        """``ddim_sample`` at eta 0 started from ``latent`` ([B, C, S, S], a state of the chain: ``encode``'s result, a slerp of
+        two, noise) at level index ``from_level`` of the grid on ``steps`` steps (default: its top; ``steps`` as in ``encode``)
+        -> the image in the data range.  ``clip=False`` takes x0 as predicted, as ``encode`` does: the exact way back.
+        ``classes`` / ``cond_scale`` as in ``sample``."""
+        from lgm_hip import sampler
+        latent, classes, scale = self._edit_args("decode", latent, classes, cond_scale)
+        return sampler.decode(self, latent, from_level, steps, clip, return_all_timesteps, classes, scale)
+
+    @torch.no_grad()
+    def reconstruct(self, img, steps=None, upto=None, classes=None, cond_scale=1.0):
+        """``decode(encode(img))`` on one grid with the clip off both ways: what the DDIM ODE loses on ``steps`` steps"""
+        z = self.encode(img, steps=steps, upto=upto, classes=classes, cond_scale=cond_scale)
+        return self.decode(z, from_level=upto, classes=classes, cond_scale=cond_scale, steps=steps, clip=False)
+
+    @torch.no_grad()
+    def img2img(self, img, strength=0.5, noise=None, classes=None, cond_scale=None, return_all_timesteps=False):
+        """SDEdit (extension; Meng et al. 2022): noise ``img`` ([B, C, S, S] in the data range, normalised as ``forward``
+        normalises) part of the way and run the rest of the sampler ``sample`` dispatches to - the last max(1, round(strength
+        N)) of its N steps, ``strength`` in (0, 1]; 1 keeps nothing of the image but its low frequencies at level T - 1.
+        ``noise``: the draw of the noising ([B, C, S, S]; default: drawn).  Dynamic thresholding, guidance and learned
+        variance work as they do in ``sample``; ``classes`` / ``cond_scale`` as there."""
+        from lgm_hip import sampler
+        img, classes, scale = self._edit_args("img2img", img, classes, cond_scale, selfcond_ok=True)
+        if noise is not None:
+            if tuple(noise.shape) != tuple(img.shape):
+                raise ValueError(f"noise must be {tuple(img.shape)}, got {tuple(noise.shape)}")
+            noise = noise.to(self.device).float().contiguous()
+        return sampler.img2img(self, self.normalize(img), strength, noise, return_all_timesteps, classes=classes,
+                               cond_scale=scale)
+
+    @torch.no_grad()
+    def interpolate(self, x1, x2, t=None, lam=0.5, classes=None, cond_scale=1.0, method="stochastic", steps=None,
+                    upto=None):
+        """reference :847-867: noise both images to step t, blend, walk the ancestral chain back to 0 (no unnormalise).
+        ``method="ddim"`` (extension; Song et al. 2021, fig. 6): ``encode`` both images (given as the reference's form takes
+        them: already normalised), slerp the latents with ``lam`` (a float or a [B] tensor) on the device, ``decode`` with the
+        clip off - deterministic, and the blend keeps the latents' norm, which a lerp at ``lam = 0.5`` does not.  ``t`` is
+        not read there; ``steps`` and ``upto`` as in ``encode`` (``upto``: blend at that level of the grid, not at its top)."""
+        from lgm_hip import sampler
+        if method not in ("stochastic", "ddim"):
+            raise ValueError(f"method must be 'stochastic' or 'ddim', got {method!r}")
+        if method == "ddim":
+            x1, classes_d, scale = self._edit_args("interpolate(method='ddim')", x1, classes, cond_scale)
+            x2 = self._edit_args("interpolate(method='ddim')", x2, classes, cond_scale)[0]
+            return sampler.interpolate_ddim(self, x1, x2, lam, steps, classes_d, scale, upto)
         self._refuse_lowres("interpolate")
         b = x1.shape[0]
         t = self.num_timesteps - 1 if t is None else int(t)
@@ -2024,6 +2099,30 @@ class DDPM(LightningModule):
         """``GaussianDiffusion.inpaint`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
         self.ema.ema_model.eval()
         return self.ema.ema_model.inpaint(known, mask, **kw)
+
+    @torch.no_grad()
+    def encode(self, img, **kw):
+        """``GaussianDiffusion.encode`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model.encode(img, **kw)
+
+    @torch.no_grad()
+    def decode(self, latent, **kw):
+        """``GaussianDiffusion.decode`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model.decode(latent, **kw)
+
+    @torch.no_grad()
+    def reconstruct(self, img, **kw):
+        """``GaussianDiffusion.reconstruct`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model.reconstruct(img, **kw)
+
+    @torch.no_grad()
+    def img2img(self, img, **kw):
+        """``GaussianDiffusion.img2img`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model.img2img(img, **kw)
 
     @torch.no_grad()
     def upsample(self, img_low, **kw):
