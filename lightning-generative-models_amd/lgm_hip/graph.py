@@ -28,6 +28,7 @@ from typing import Optional
 import torch
 
 from . import ops
+from .captured import _warm_up
 from .lightning import multi_rank
 
 
@@ -71,18 +72,6 @@ class _TrainingState:
             m.logged.clear()
             m.logged.update(lg)
         torch.cuda.set_rng_state(self.rng, self.device)
-
-
-def _warm_up(fn, n: int):
-    """``n`` eager runs of ``fn`` on a side stream (they size workspaces and set kernel attributes), joined before return."""
-    cur = torch.cuda.current_stream()
-    side = torch.cuda.Stream()
-    side.wait_stream(cur)
-    with torch.cuda.stream(side):
-        for _ in range(n):
-            fn()
-    cur.wait_stream(side)
-    torch.cuda.synchronize()
 
 
 def _capture(fn, warmup: int, pool=None):

@@ -28,14 +28,13 @@ from __future__ import annotations
 import math
 import os
 import struct
-import sys
-import weakref
 from collections import namedtuple
 from typing import List, Optional
 
 import torch
 
 from . import ops, sampler
+from .captured import _CapturedStep, _cached_step
 from .flat import _r4
 
 VLB_ROW = 12                                   # floats per row; the kernel reads the first ten, all twelve of a learned kind
@@ -178,35 +177,25 @@ def _eager_terms(gd, img, times, rows, noises, classes, clip: bool):
     return out
 
 
-class _GraphedVLB:
-    """One captured evaluation step for a (network, batch shape, objective, clip); replayed once per timestep.  Static
-    buffers: the image, the noise, the network's input buffer, the schedule's two q_sample tables, the time and row tables,
-    the counter and the [max_steps, 3, B] output.  Capture, warm-up, RNG-state restore and ``matches`` as ``_GraphedChain``."""
-
-    matches = sampler._GraphedChain.matches
+class _GraphedVLB(_CapturedStep):
+    """A ``_CapturedStep`` of one evaluation step for a (network, batch shape, objective, clip), its rows ``VLB_ROW`` wide.  It
+    adds the static image, noise and input buffer, the schedule's two q_sample tables and the [max_steps, 3, B] output, whose
+    rows ``run`` copies out behind every segment."""
 
     def __init__(self, gd, shape, clip: bool, max_steps: int = 4096):
         net = gd.model
-        self._net = weakref.ref(net)
         B, C, H, W = shape
         dev = gd.betas.device
-        self.shape, self.max_steps = shape, max_steps
-        fp = net._flat
-        self._bound = (weakref.ref(fp), fp.data.data_ptr(),
-                       None if fp.data_uf is None else fp.data_uf.data_ptr(),
-                       None if fp.data_t is None else fp.data_t.data_ptr())
+        super().__init__(net, dev, max_steps, VLB_ROW)
+        self.shape = shape
         self.img = torch.zeros(shape, device=dev)
         self.noise = torch.zeros(shape, device=dev)                   # injected noise goes here
         self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)
         self.t = torch.zeros(B, dtype=torch.long, device=dev)
         self.sa = torch.zeros(gd.num_timesteps, device=dev)           # a diffusion's tables are copied in per run: two
         self.sb = torch.zeros(gd.num_timesteps, device=dev)           # diffusions of one length may share the step
-        self.table = torch.zeros((max_steps, VLB_ROW), device=dev)
-        self.ttable = torch.zeros(max_steps, dtype=torch.long, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.out = torch.zeros((max_steps, 3, B), device=dev)
         self.classes = net.labels(None, B, dev).clone() if net.num_classes is not None else None
-        self.inject = False
 
         def one_step():
             ops.lib().lgm_sampler_time(self.ttable.data_ptr(), self.counter.data_ptr(), self.t.data_ptr(), B, ops.stream())
@@ -215,46 +204,21 @@ class _GraphedVLB:
             v = net.forward_guided(self.x, self.t, self.classes, 1.0, refresh_weights=False)
             _launch_term(gd, self.img, nz, self.x, v, clip, self.out, table=self.table, counter=self.counter)
 
-        net.refresh_derived_weights(False)
-        rng_state = torch.cuda.get_rng_state(dev)
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):            # eager warm-up (sizes workspaces, sets kernel attributes)
-            for _ in range(2):
-                one_step()
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        self.graphs = {}
-        for inject in (False, True):
-            self.inject = inject
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                one_step()
-            self.graphs[inject] = g
-        torch.cuda.set_rng_state(rng_state, dev)     # capture leaves the random stream where it was
+        self._capture(one_step, (False, True), dev)
 
     def run(self, gd, img, times, rows, noises, classes=None):
         """times[i], rows[i] (``VLB_ROW`` floats) per timestep; noises: None (draw on the device) or one NCHW tensor per
         timestep.  -> [n, 3, B] on the device.  More timesteps than table rows are replayed in table-sized segments."""
-        n = len(times)
         if self.classes is not None:
             self.classes.copy_(classes)
         self._net().refresh_derived_weights(False)   # the weights may have moved since the last evaluation (EMA updates)
         self.img.copy_(img)
         self.sa.copy_(gd.sqrt_alphas_cumprod)
         self.sb.copy_(gd.sqrt_one_minus_alphas_cumprod)
-        res = torch.empty((n, 3, self.shape[0]), device=img.device)
+        res = torch.empty((len(times), 3, self.shape[0]), device=img.device)
         inject = noises is not None
-        for lo, hi in sampler._segments(n, self.max_steps):
-            self.table[:hi - lo].copy_(torch.tensor(rows[lo:hi], dtype=torch.float32))
-            self.ttable[:hi - lo].copy_(torch.tensor(times[lo:hi], dtype=torch.long))
-            self.counter.zero_()
-            for i in range(lo, hi):
-                if inject:
-                    self.noise.copy_(noises[i])
-                self.graphs[inject].replay()
-            res[lo:hi].copy_(self.out[:hi - lo])
+        self._replay(times, rows, inject, before=(lambda i: self.noise.copy_(noises[i])) if inject else None,
+                     after=lambda lo, hi: res[lo:hi].copy_(self.out[:hi - lo]))
         return res
 
 
@@ -265,33 +229,13 @@ def _vlb_key(gd, shape, clip: bool):
 
 
 def _graph_vlb(gd, shape, clip: bool) -> Optional[_GraphedVLB]:
-    """-> the network's ``_GraphedVLB`` for the key, or None (graph replay disabled, no device, capture failed: eager launches);
-    invalidation and the retry after a failed capture as ``sampler._graph_chain``"""
+    """-> the network's ``_GraphedVLB`` under ``_vlb_key`` from ``_cached_step``, or None (graph replay disabled, no device,
+    capture failed: eager launches)"""
     if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or gd.betas.device.type != "cuda":
         return None
     net = gd.model
     net.prepare_hip(gd.betas.device)
-    per_net = sampler._GRAPHS.setdefault(net, {})
-    key = _vlb_key(gd, shape, clip)
-    ent = per_net.get(key)
-    if isinstance(ent, _GraphedVLB) and not ent.matches(net):
-        ent = None
-        per_net.pop(key, None)
-    if isinstance(ent, int):
-        if ent > 0:
-            per_net[key] = ent - 1
-            return None
-        ent = None
-    if ent is None:
-        try:
-            ent = _GraphedVLB(gd, tuple(shape), clip)
-        except Exception as e:  # capture is an optimisation
-            print(f"[lgm_hip] likelihood graph capture unavailable ({type(e).__name__}: {e}); eager launches",
-                  file=sys.stderr, flush=True)
-            per_net[key] = sampler._CAPTURE_RETRY_AFTER
-            return None
-        per_net[key] = ent
-    return ent
+    return _cached_step(net, _vlb_key(gd, shape, clip), lambda: _GraphedVLB(gd, tuple(shape), clip), "likelihood")
 
 
 @torch.no_grad()

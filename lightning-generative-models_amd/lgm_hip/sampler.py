@@ -50,14 +50,13 @@ from __future__ import annotations
 
 import math
 import os
-import sys
-import weakref
 from dataclasses import dataclass
 from typing import List, Optional
 
 import torch
 
 from . import ops
+from .captured import _CAPTURE_RETRY_AFTER, _GRAPHS, _CapturedStep, _cached_step, _segments  # noqa: F401 (their users' names)
 from .flat import _r4
 
 
@@ -431,13 +430,6 @@ def _plan_inpaint(gd, jump_length: int = 1, resamples: int = 1, kind: Optional[s
                  kdraws=tuple(r[1] != 0.0 for r in irows), jdraws=tuple(r[3] != 0.0 for r in irows))
 
 
-def _segments(n: int, max_steps: int):
-    """[(lo, hi)]: the steps of a chain of n in table-sized pieces, in order; a chain is never truncated to its tables"""
-    if max_steps < 1:
-        raise ValueError(f"max_steps must be at least 1, got {max_steps}")
-    return [(lo, min(lo + max_steps, n)) for lo in range(0, n, max_steps)]
-
-
 def _launch_thresh(net, shape, objective: int, x, v, head, rank, thresh, table=None, counter=None):
     """s[b] of a step into ``thresh``: from the x slice of ``x``, the network output ``v`` and the head (A, Bv, R, Rm1) by
     value, or from the row ``table[counter]`` (the by-value slots are then zero); ``rank`` = ``dyn_rank`` of a sample"""
@@ -638,16 +630,9 @@ class _Chain:
         return out
 
 
-# net -> {_graph_key(...): _GraphedChain}.  Weak on the network: a sampled model that goes away takes its graphs
-# (and their memory pool) with it.  Every entry remembers which flat parameter storage its launches were captured
-# against (see _GraphedChain.matches): a graph bakes buffer ADDRESSES in, so after prepare_hip() rebuilt the flat
-# storage (model.to(), replaced parameter storage) the entry is dropped and the step recaptured.
-_GRAPHS = weakref.WeakKeyDictionary()
-_CAPTURE_RETRY_AFTER = 8      # a failed capture is retried after this many eager chains, not cached for ever
-
-
-class _GraphedChain:
-    """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it."""
+class _GraphedChain(_CapturedStep):
+    """One captured sampling step for a (network, batch shape); replayed once per step of any chain on it.  Binding, capture
+    and segmented replay are ``_CapturedStep``'s; the cache entry under ``_graph_key`` in ``_GRAPHS[net]`` is ``_cached_step``'s."""
 
     def __init__(self, gd, shape, with_noise: bool, rederive: bool = False, max_steps: int = 4096, guided: bool = False,
                  dpm: bool = False, dyn: Optional[float] = None, inpaint: bool = False, learned: bool = False,
@@ -655,21 +640,13 @@ class _GraphedChain:
         net = gd.model
         dyn = dyn if clip else None                  # an unclipped step is not thresholded either
         objective = _objective(gd)
-        self._net = weakref.ref(net)                 # the cache is keyed weakly on the network: no strong reference here
         B, C, H, W = shape
         dev = gd.betas.device
+        super().__init__(net, dev, max_steps, 8)
         self.shape, self.with_noise, self.inpaint = shape, with_noise, inpaint
-        fp = net._flat
-        # identity of everything whose address the captured launches carry: the flat object and its buffers
-        self._bound = (weakref.ref(fp), fp.data.data_ptr(),
-                       None if fp.data_uf is None else fp.data_uf.data_ptr(),
-                       None if fp.data_t is None else fp.data_t.data_ptr())
         self.x = torch.zeros((B, H, W, net.in_pitch), device=dev)     # static input buffer (both slices when self-conditioned)
         self.t = torch.zeros(B, dtype=torch.long, device=dev)
         self.noise = torch.zeros(shape, device=dev) if with_noise else None     # injected noise goes here
-        self.table = torch.zeros((max_steps, 8), device=dev)
-        self.ttable = torch.zeros(max_steps, dtype=torch.long, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         # class-conditional network: the run's labels; guided step: its scale, read on the device by the mix
         self.classes = net.labels(None, B, dev).clone() if net.num_classes is not None else None
         self.scale = torch.ones(1, device=dev) if guided else None
@@ -688,8 +665,6 @@ class _GraphedChain:
         self.itable = torch.zeros((max_steps, 4), device=dev) if inpaint else None
         # low-resolution conditioned network: the chain's augmentation levels; the conditioning slice arrives with ``x``
         self.lowres_s = torch.zeros(B, dtype=torch.long, device=dev) if getattr(net, "lowres_cond", False) else None
-        self.inject = False
-        self.max_steps = max_steps
 
         def one_step():
             ops.lib().lgm_sampler_time(self.ttable.data_ptr(), self.counter.data_ptr(), self.t.data_ptr(), B, ops.stream())
@@ -708,32 +683,7 @@ class _GraphedChain:
                            table=self.table, counter=self.counter, rederive=rederive, dpm=dpm, inpaint=tail, learned=learned,
                            clip=clip)
 
-        net.refresh_derived_weights(False)
-        rng_state = torch.cuda.get_rng_state(dev)
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):            # eager warm-up (sizes workspaces, sets kernel attributes)
-            for _ in range(2):
-                one_step()
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        self.graphs = {}
-        for inject in ((False, True) if with_noise or inpaint else (False,)):
-            self.inject = inject
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                one_step()
-            self.graphs[inject] = g
-        torch.cuda.set_rng_state(rng_state, dev)     # capture leaves the random stream where it was
-
-    def matches(self, net) -> bool:
-        """True while the network still owns the flat storage this step was captured against."""
-        fp = net._flat
-        ref, data, uf, dt = self._bound
-        return (fp is not None and ref() is fp and fp.still_bound() and fp.data.data_ptr() == data
-                and (None if fp.data_uf is None else fp.data_uf.data_ptr()) == uf
-                and (None if fp.data_t is None else fp.data_t.data_ptr()) == dt)
+        self._capture(one_step, (False, True) if with_noise or inpaint else (False,), dev)
 
     def run(self, x0_nhwc, times, coeffs, noises, classes=None, cond_scale: float = 1.0, inpaint=None, lowres_s=None):
         """times[i], coeffs[i] (8 floats) per step; noises: None (draw on device) or a list with one NCHW tensor or
@@ -741,7 +691,6 @@ class _GraphedChain:
         of the static buffer).  ``inpaint`` (a step captured for inpainting) = (known NHWC, mask [B, HW], rows of 4); an entry
         of ``noises`` is then a triple (noise, eps_k, eps_j) or None.  A chain longer than the tables is replayed in table-
         sized segments: refill the tables, zero the counter."""
-        n = len(times)
         if self.classes is not None:
             self.classes.copy_(classes)
         if self.scale is not None:
@@ -765,19 +714,17 @@ class _GraphedChain:
                 buf.copy_(value)
             elif buf is not None:
                 buf.zero_()
-        for lo, hi in _segments(n, self.max_steps):
-            self.table[:hi - lo].copy_(torch.tensor(coeffs[lo:hi], dtype=torch.float32), non_blocking=False)
-            self.ttable[:hi - lo].copy_(torch.tensor(times[lo:hi], dtype=torch.long))
+
+        def refill(lo, hi):
+            self.itable[:hi - lo].copy_(torch.tensor(irows[lo:hi], dtype=torch.float32))
+
+        def before(i):
             if self.inpaint:
-                self.itable[:hi - lo].copy_(torch.tensor(irows[lo:hi], dtype=torch.float32))
-            self.counter.zero_()
-            for i in range(lo, hi):
-                if inject and self.inpaint:
-                    nz, ek, ej = noises[i] if noises[i] is not None else (None, None, None)
-                    put(self.noise, nz), put(self.eps_k, ek), put(self.eps_j, ej)
-                elif inject:
-                    put(self.noise, noises[i])
-                self.graphs[inject].replay()
+                nz, ek, ej = noises[i] if noises[i] is not None else (None, None, None)
+                put(self.noise, nz), put(self.eps_k, ek), put(self.eps_j, ej)
+            else:
+                put(self.noise, noises[i])
+        self._replay(times, coeffs, inject, refill if self.inpaint else None, before if inject else None)
         return self.x
 
 
@@ -814,28 +761,9 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
         return None
     net = gd.model
     net.prepare_hip(gd.betas.device)                 # may rebuild the flat storage (model.to(), new parameter storage)
-    per_net = _GRAPHS.setdefault(net, {})
-    key = _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint, learned, clip)
-    ent = per_net.get(key)
-    if isinstance(ent, _GraphedChain) and not ent.matches(net):
-        ent = None                                   # captured against buffers the network no longer uses
-        per_net.pop(key, None)
-    if isinstance(ent, int):                         # a capture failed earlier: eager for a while, then try again
-        if ent > 0:
-            per_net[key] = ent - 1
-            return None
-        ent = None
-    if ent is None:
-        try:
-            ent = _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd), inpaint=inpaint,
-                                learned=learned, clip=clip)
-        except Exception as e:  # capture is an optimisation
-            print(f"[lgm_hip] sampler graph capture unavailable ({type(e).__name__}: {e}); eager launches",
-                  file=sys.stderr, flush=True)
-            per_net[key] = _CAPTURE_RETRY_AFTER
-            return None
-        per_net[key] = ent
-    return ent
+    return _cached_step(net, _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint, learned, clip),
+                        lambda: _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd),
+                                              inpaint=inpaint, learned=learned, clip=clip), "sampler")
 
 
 def p_sample_step(chain: _Chain, t: int, noise: Optional[torch.Tensor]):

@@ -505,6 +505,18 @@ class Unet(nn.Module):
             raise ValueError(f"lowres_aug_t must be {B} integer levels (one per sample), got {s.dtype} {tuple(s.shape)}")
         return s.to(device=device, dtype=torch.long).contiguous()
 
+    def _emb_mlp_fwd(self, mlp, t, out=None):
+        """``time_mlp`` / ``lowres_time_mlp`` over the integer input ``t`` on the unfused ops: posemb, linear, GELU, linear
+        (four launches) -> (pe, a1, h, emb), in ``out`` where the caller owns the four buffers"""
+        B, fp = t.shape[0], self._flat
+        l1, l2 = mlp[1], mlp[3]
+        pe, a1, h, emb = out or (ops.new((B, d), t) for d in (self.dim, self.time_dim, self.time_dim, self.time_dim))
+        ops.posemb(t, self.dim, self.theta, pe)
+        ops.conv_xy(l1.geom(B), pe, fp.ptr(l1.weight), fp.ptr(l1.bias), None, a1)
+        ops.act_fwd(a1, None, None, h, ops.ACT_GELU)
+        ops.conv_xy(l2.geom(B), h, fp.ptr(l2.weight), fp.ptr(l2.bias), None, emb)
+        return pe, a1, h, emb
+
     def _time_fwd(self, t, save, classes=None, lowres_s=None):
         B = t.shape[0]
         fp = self._flat
@@ -519,25 +531,17 @@ class Unet(nn.Module):
             ops.time_mlp_fwd(t, self.dim, self.theta, fp.ptr(l1.weight), fp.ptr(l1.bias), fp.ptr(l2.weight),
                              fp.ptr(l2.bias), self.time_dim, pe, a1, h, temb, st)
         else:
-            ops.posemb(t, self.dim, self.theta, pe)
-            ops.conv_xy(l1.geom(B), pe, fp.ptr(l1.weight), fp.ptr(l1.bias), None, a1)
-            ops.act_fwd(a1, None, None, h, ops.ACT_GELU)
-            ops.conv_xy(l2.geom(B), h, fp.ptr(l2.weight), fp.ptr(l2.bias), None, temb)
+            self._emb_mlp_fwd(self.time_mlp, t, (pe, a1, h, temb))
             if self.num_classes is None and not self.lowres_cond:
                 ops.act_fwd(temb, None, None, st, ops.ACT_SILU)
-        lr_saved = None
+        lowres = None
         if self.lowres_cond:
-            # temb += lowres_time_mlp(s), st = SiLU(temb): the MLP on the unfused ops (posemb, linear, GELU, linear: four
-            # launches) and one row-local launch that joins it to the time embedding
+            # temb += lowres_time_mlp(s), st = SiLU(temb): the MLP on the unfused ops and one row-local launch that joins it
+            # to the time embedding
             assert lowres_s is not None, "a low-resolution conditioned network needs its augmentation levels"
-            m1, m2 = self.lowres_time_mlp[1], self.lowres_time_mlp[3]
-            pe_s, a1_s, h_s, emb_s = (ops.new((B, d), t) for d in (self.dim, self.time_dim, self.time_dim, self.time_dim))
-            ops.posemb(lowres_s, self.dim, self.theta, pe_s)
-            ops.conv_xy(m1.geom(B), pe_s, fp.ptr(m1.weight), fp.ptr(m1.bias), None, a1_s)
-            ops.act_fwd(a1_s, None, None, h_s, ops.ACT_GELU)
-            ops.conv_xy(m2.geom(B), h_s, fp.ptr(m2.weight), fp.ptr(m2.bias), None, emb_s)
+            pe_s, a1_s, h_s, emb_s = self._emb_mlp_fwd(self.lowres_time_mlp, lowres_s)
             ops.lowres_emb_fwd(temb, None if self.num_classes is not None else st, emb_s)
-            lr_saved = (pe_s, a1_s, h_s)
+            lowres = (pe_s, a1_s, h_s)
         if self.num_classes is not None:
             # temb += label_emb[classes], st = SiLU(temb): one row-local launch behind the time MLP
             classes = self.labels(None, B, t.device) if classes is None else classes
@@ -549,14 +553,11 @@ class Unet(nn.Module):
         rb0 = self.resblocks()[0]
         ss_all = ops.new((B, self._ss_total), t)
         ops.conv_xy(g, st, fp.ptr(rb0.mlp[1].weight), fp.ptr(rb0.mlp[1].bias), None, ss_all)
-        if not save:
-            return ss_all, None
-        return ss_all, ((pe, a1, h, temb, st, classes) if lr_saved is None else (pe, a1, h, temb, st, classes, lr_saved))
+        return ss_all, (TimeTape(pe, a1, h, temb, st, classes, lowres) if save else None)
 
-    def _time_bwd(self, gc: GradCtx, saved, gss_all):
-        pe, a1, h, temb, st, classes = saved[:6]
-        lr_saved = saved[6] if len(saved) > 6 else None      # a low-resolution conditioned network: its second MLP's activations
-        B = pe.shape[0]
+    def _time_bwd(self, gc: GradCtx, saved: "TimeTape", gss_all):
+        st = saved.st
+        B = st.shape[0]
         fp = gc.flat
         l1, l2 = self.time_mlp[1], self.time_mlp[3]
         rbs = self.resblocks()
@@ -568,23 +569,29 @@ class Unet(nn.Module):
         gst = ops.new(st.shape, st)
         ops.conv_yx(g, gss_all, fp.ptr(rbs[0].mlp[1].weight), None, None, gst)
         gtemb = ops.new(st.shape, st)
-        if ops.time_mlp_ok(self.dim, self.time_dim, l1, l2):
+        fused = ops.time_mlp_ok(self.dim, self.time_dim, l1, l2)
+        if fused:
             # SiLU' -> (weight / bias gradient, input gradient) of the second linear -> GELU' -> weight / bias gradient of the
             # first: two launches (row-local chain, batch reductions in row order) instead of six
             bw = gc.beta(l2.weight)
             assert bw == gc.beta(l2.bias) == gc.beta(l1.weight) == gc.beta(l1.bias)
-            ga1 = ops.new(a1.shape, a1)
-            ops.time_mlp_bwd(gst, pe, a1, h, temb, fp.ptr(l2.weight), self.dim, self.time_dim, gtemb, ga1,
-                             fp.gptr(l1.weight), fp.gptr(l1.bias), fp.gptr(l2.weight), fp.gptr(l2.bias), bw)
-            self._label_emb_bwd(gc, gtemb, classes)
-            self._lowres_mlp_bwd(gc, gtemb, lr_saved)
-            return
-        ops.act_bwd(temb, None, gst, gtemb, False, ops.ACT_SILU)
-        self._label_emb_bwd(gc, gtemb, classes)
-        self._lowres_mlp_bwd(gc, gtemb, lr_saved)
+            ga1 = ops.new(saved.a1.shape, saved.a1)
+            ops.time_mlp_bwd(gst, saved.pe, saved.a1, saved.h, saved.temb, fp.ptr(l2.weight), self.dim, self.time_dim, gtemb,
+                             ga1, fp.gptr(l1.weight), fp.gptr(l1.bias), fp.gptr(l2.weight), fp.gptr(l2.bias), bw)
+        else:
+            ops.act_bwd(saved.temb, None, gst, gtemb, False, ops.ACT_SILU)
+        self._label_emb_bwd(gc, gtemb, saved.classes)
+        self._lowres_mlp_bwd(gc, gtemb, saved.lowres)
+        if not fused:
+            self._emb_mlp_bwd(gc, self.time_mlp, gtemb, saved.pe, saved.a1, saved.h)
+
+    def _emb_mlp_bwd(self, gc: GradCtx, mlp, gemb, pe, a1, h):
+        """The backward of ``_emb_mlp_fwd`` from the gradient of its output: weight + input gradient of the second linear in
+        one launch (lgm_conv_bwd_pair), GELU', weight gradient of the first."""
+        B, fp = pe.shape[0], gc.flat
+        l1, l2 = mlp[1], mlp[3]
         gh = ops.new(h.shape, h)
-        # weight gradient and input gradient of the second time-MLP linear in one launch (lgm_conv_bwd_pair)
-        ops.conv_bwd_generic(l2.geom(B), gtemb, h, fp.ptr(l2.weight), fp.tptr(l2.weight), fp.gptr(l2.weight),
+        ops.conv_bwd_generic(l2.geom(B), gemb, h, fp.ptr(l2.weight), fp.tptr(l2.weight), fp.gptr(l2.weight),
                              gc.beta(l2.weight), fp.gptr(l2.bias), None, None, gh)
         gc.beta(l2.bias)
         ga1 = ops.new(a1.shape, a1)
@@ -592,22 +599,10 @@ class Unet(nn.Module):
         ops.conv_wgrad(l1.geom(B), ga1, pe, fp.gptr(l1.weight), gc.beta(l1.weight), fp.gptr(l1.bias))
         gc.beta(l1.bias)
 
-    def _lowres_mlp_bwd(self, gc: GradCtx, gtemb, lr_saved):
-        """temb is a sum: g lowres_time_mlp(s) = g temb.  The MLP's backward on the generic ops, as the time MLP's unfused one:
-        weight + input gradient of the second linear (one launch), GELU', weight gradient of the first."""
-        if lr_saved is None:
-            return
-        pe_s, a1_s, h_s = lr_saved
-        B, fp = pe_s.shape[0], gc.flat
-        m1, m2 = self.lowres_time_mlp[1], self.lowres_time_mlp[3]
-        gh = ops.new(h_s.shape, h_s)
-        ops.conv_bwd_generic(m2.geom(B), gtemb, h_s, fp.ptr(m2.weight), fp.tptr(m2.weight), fp.gptr(m2.weight),
-                             gc.beta(m2.weight), fp.gptr(m2.bias), None, None, gh)
-        gc.beta(m2.bias)
-        ga1 = ops.new(a1_s.shape, a1_s)
-        ops.act_bwd(a1_s, None, gh, ga1, False, ops.ACT_GELU)
-        ops.conv_wgrad(m1.geom(B), ga1, pe_s, fp.gptr(m1.weight), gc.beta(m1.weight), fp.gptr(m1.bias))
-        gc.beta(m1.bias)
+    def _lowres_mlp_bwd(self, gc: GradCtx, gtemb, lowres):
+        """temb is a sum: g lowres_time_mlp(s) = g temb"""
+        if lowres is not None:
+            self._emb_mlp_bwd(gc, self.lowres_time_mlp, gtemb, *lowres)
 
     def _label_emb_bwd(self, gc: GradCtx, gtemb, classes):
         """g label_emb.weight[k] = sum of g temb[b] over the samples of class k, in ascending b; other rows exactly zero"""
@@ -941,6 +936,9 @@ class Unet(nn.Module):
 # What ``Unet.forward_nhwc(save=True)`` keeps for the backward pass: per stage of ``downs`` / ``ups`` what its two blocks, its
 # attention and its resampling saved, ``sm1`` .. ``sm3`` the middle blocks', ``final`` / ``fin`` the final block's and its output.
 NetworkTape = namedtuple("NetworkTape", ["time_saved", "downs", "sm1", "sm2", "sm3", "ups", "final", "fin", "x", "cat_shapes"])
+# ``time_saved``, what ``Unet._time_fwd(save=True)`` keeps: the time MLP's activations, the embedding sum and its SiLU, the labels
+# (None without classes) and ``lowres`` = (pe_s, a1_s, h_s) of ``lowres_time_mlp`` (None without low-resolution conditioning).
+TimeTape = namedtuple("TimeTape", ["pe", "a1", "h", "temb", "st", "classes", "lowres"])
 
 
 class _Backward:

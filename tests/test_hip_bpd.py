@@ -403,6 +403,40 @@ def test_sampling_chains_beside_an_evaluation_keep_their_bits(fx, dev, monkeypat
         assert torch.equal(a, b), "a sampling chain changed its bits beside an evaluation"
 
 
+def test_evaluation_step_is_recaptured_when_the_parameter_storage_is_replaced(fx, dev, monkeypatch):
+    """the likelihood's twin of tests/test_hip_unet.py's invalidation: after every parameter got new storage prepare_hip()
+    rebuilds the flat buffers, the step captured against the old ones is dropped and recaptured, and the evaluation reads the
+    NEW weights (a stale graph would go on reading the old buffers)"""
+    from lgm_hip import likelihood as LK, sampler
+    from models.generative.diffusion.ddpm import GaussianDiffusion, Unet
+    from oracle import diffusion as OD
+    net = Unet(dim=16, channels=3)
+    net.load_state_dict(OD.unet_init(dim=16, channels=3, seed=int(fx["seed"])), strict=True)
+    gd = GaussianDiffusion(net, img_size=16, timesteps=12).to(dev)
+    shape = (2, 3, 16, 16)
+    g = torch.Generator().manual_seed(9)
+    img = torch.rand(shape, generator=g).to(dev)
+    nz = [torch.randn(shape, generator=g).to(dev) for _ in range(2)]
+    run = lambda: gd.vlb_terms(img, timesteps=[5, 0], noise=nz)  # noqa: E731
+    key = LK._vlb_key(gd, shape, True)
+    monkeypatch.setenv("LGM_NO_SAMPLER_GRAPH", "0")
+    first = run()
+    old = sampler._GRAPHS[net].get(key)
+    assert isinstance(old, LK._GraphedVLB), "graph capture of the evaluation step did not happen"
+    with torch.no_grad():
+        for p in net.parameters():
+            p.data = (p.data * 1.01).clone()            # new storage, different values
+    assert not net._flat.still_bound()
+    second = run()
+    new = sampler._GRAPHS[net][key]
+    assert isinstance(new, LK._GraphedVLB) and new is not old and new.matches(net)
+    monkeypatch.setenv("LGM_NO_SAMPLER_GRAPH", "1")
+    eager = run()
+    for name in ("vb", "xstart_mse", "mse", "prior_bpd"):
+        assert torch.equal(getattr(second, name), getattr(eager, name)), f"{name}: the recaptured step differs from eager launches"
+    assert not torch.equal(second.vb, first.vb), "the evaluation still reads the old weights"
+
+
 def test_drawn_noise_and_the_public_methods(nets, dev, monkeypatch):
     """``noise=None``: two calls under one seed agree and capture leaves the random stream where it was; ``nll_bpd``,
     ``DDPM.bits_per_dim`` and ``validation_step`` under ``bpd_every``; shape mismatches raise"""
