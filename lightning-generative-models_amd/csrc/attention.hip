@@ -472,6 +472,7 @@ extern "C" int lgm_linattn_fwd(const float* qkv, int64_t qkv_pitch, const float*
   if (int rc = lgm_linattn_ctx_launch(0, qkv, (long)qkv_pitch, mem_kv, nullptr, 0L, nullptr, B, n, heads, M, scale, ctx,
                                       kmax, ksum, nullptr, s))
     return rc;
+  lgm_note_kernel(LGM_KNAME("linattn_out_kernel"));
   hipLaunchKernelGGL(linattn_out_kernel, dim3(B * heads, lgm_cdiv(n, TI)), dim3(256), 0, s, qkv, (long)qkv_pitch,
                      (const float*)ctx, n, heads, scale, out, (long)out_pitch);
   LGM_LAUNCH_CHECK();
@@ -659,13 +660,16 @@ extern "C" int lgm_attn_fwd(const float* qkv, int64_t qkv_pitch, const float* me
                           (int)(sa_fwd_floats(SA_MAXN, 16) * sizeof(float)));
       attr = true;
     }
+    lgm_note_kernel(LGM_KNAME("attn_small_fwd_kernel"));
     hipLaunchKernelGGL(attn_small_fwd_kernel, dim3(B * heads), dim3(256), sa_fwd_floats(n, M) * sizeof(float),
                        (hipStream_t)stream, qkv, (long)qkv_pitch, mem_kv, n, heads, M, 1.f / sqrtf((float)dim_head), out,
                        (long)out_pitch, lse);
   }
-  else
+  else {
+    lgm_note_kernel(LGM_KNAME("attn_fwd_kernel"));
     hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * heads), dim3(128), smem, (hipStream_t)stream, qkv, (long)qkv_pitch,
                        mem_kv, n, heads, M, 1.f / sqrtf((float)dim_head), out, (long)out_pitch, lse);
+  }
   LGM_LAUNCH_CHECK();
   return LGM_OK;
 }
@@ -722,14 +726,17 @@ int attn_bwd_impl(const float* qkv, int64_t qkv_pitch, const float* mem_kv, cons
                           (int)(sa_bwd_floats(SA_MAXN, 16) * sizeof(float)));
       attr = true;
     }
+    lgm_note_kernel(LGM_KNAME("attn_small_bwd_kernel"));
     hipLaunchKernelGGL(attn_small_bwd_kernel, dim3(B * heads), dim3(256), sa_bwd_floats(n, M) * sizeof(float),
                        (hipStream_t)stream, qkv, (long)qkv_pitch, mem_kv, out, (long)out_pitch, gout, (long)gout_pitch, lse, n,
                        heads, M, 1.f / sqrtf((float)dim_head), gqkv, (long)gqkv_pitch, part);
   }
-  else
+  else {
+    lgm_note_kernel(LGM_KNAME("attn_bwd_kernel"));
     hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * heads), dim3(192), smem, (hipStream_t)stream, qkv, (long)qkv_pitch,
                        mem_kv, out, (long)out_pitch, gout, (long)gout_pitch, lse, n, heads, M,
                        1.f / sqrtf((float)dim_head), gqkv, (long)gqkv_pitch, part);
+  }
   LGM_LAUNCH_CHECK();
   return attn_bwd_mem_reduce(part, ncols, B, gmem_kv, gmem_beta, gmem_desc, stream);
 }

@@ -264,6 +264,7 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_kernel(const float* __rest
 int lgm_attn_tiled_fwd_launch(const float* qkv, long pitch, const float* mem_kv, int B, int n, int heads, int M,
                               float scale, float* out, long out_pitch, float* lse, hipStream_t s) {
   LGM_REQUIRE(lgm_cdiv(n, TT) <= 65535, "attn_fwd: n=%d too large", n);
+  lgm_note_kernel(LGM_KNAME("attn_tiled_fwd_kernel"));
   hipLaunchKernelGGL(attn_tiled_fwd_kernel, dim3(B * heads, lgm_cdiv(n, TT)), dim3(256), 0, s, qkv, pitch, mem_kv, n,
                      heads, M, scale, out, out_pitch, lse);
   LGM_LAUNCH_CHECK();
@@ -275,6 +276,7 @@ int lgm_attn_tiled_bwd_launch(const float* qkv, long pitch, const float* mem_kv,
                               float scale, float* gqkv, long gq_pitch, float* gmem_partial, hipStream_t s) {
   const int nqt = lgm_cdiv(n, TT), nkt = lgm_cdiv(n + M, TT);
   LGM_REQUIRE(nqt + nkt <= 65535, "attn_bwd: n=%d too large", n);
+  lgm_note_kernel(LGM_KNAME("attn_tiled_bwd_kernel"));
   hipLaunchKernelGGL(attn_tiled_bwd_kernel, dim3(B * heads, nqt + nkt), dim3(256), 0, s, qkv, pitch, mem_kv, out,
                      out_pitch, gout, gout_pitch, lse, n, heads, M, scale, nqt, gqkv, gq_pitch, gmem_partial);
   LGM_LAUNCH_CHECK();

@@ -390,6 +390,7 @@ int lgm_linattn_ctx_launch(int mode, const float* qkv, long pitch, const float* 
                            const float* kmax_in, const float* ksum_in, float* gmem_partial) {
   LGM_REQUIRE(pitch % 4 == 0 && lgm_aligned16(qkv) && (mode == 0 || (gout_pitch % 4 == 0 && lgm_aligned16(gout))),
               "linattn_ctx: 16-byte aligned rows required");
+  lgm_note_kernel(mode == 0 ? LGM_KNAME("linattn_ctx_mfma<0>") : LGM_KNAME("linattn_ctx_mfma<1>"));
   if (mode == 0)
     hipLaunchKernelGGL(linattn_ctx_mfma<0>, dim3(B * heads), dim3(256), 0, s, qkv, pitch, mem_kv, gout, gout_pitch,
                        ctx_in, n, heads, M, scale, ctx_out, kmax, ksum, r_out, kmax_in, ksum_in, gmem_partial);
@@ -415,6 +416,7 @@ int lgm_linattn_bwd_launch(const float* qkv, long pitch, const float* mem_kv, co
     attr = true;
   }
   // gmem_partial == nullptr: the memory columns' gradient came out of the gctx launch (linattn_ctx_mfma<1>'s epilogue)
+  lgm_note_kernel(LGM_KNAME("linattn_bwd_mfma"));
   hipLaunchKernelGGL(linattn_bwd_mfma, dim3(B * heads, lgm_cdiv(n, TP) + (M > 0 && gmem_partial ? 1 : 0)), dim3(256), smem, s, qkv,
                      pitch, mem_kv, gout, gout_pitch, ctx, gctx, kmax, ksum, rvec, n, heads, M, scale, gqkv, gq_pitch,
                      gmem_partial);

@@ -47,8 +47,17 @@ ELSEWHERE = {
     "lgmwino4w::wino4_wgrad8_kernel": "tests/test_hip_wino_ledger.py",
     "lgmwino::wino_conv_kernel": "tests/test_hip_wino_ledger.py",
     "lgmweng::weng_gemm_kernel": "tests/test_hip_weng.py",
-    "linattn_bwd_fused_kernel": "tests/test_hip_ops.py",
-    "linattn_out_fused_kernel": "tests/test_hip_ops.py",
+    "linattn_bwd_fused_kernel": "tests/test_hip_attention_ledger.py",
+    "linattn_out_fused_kernel": "tests/test_hip_attention_ledger.py",
+    "linattn_out_kernel": "tests/test_hip_attention_ledger.py",
+    "linattn_bwd_mfma": "tests/test_hip_attention_ledger.py",
+    "linattn_ctx_mfma": "tests/test_hip_attention_ledger.py",
+    "attn_small_fwd_kernel": "tests/test_hip_attention_ledger.py",
+    "attn_small_bwd_kernel": "tests/test_hip_attention_ledger.py",
+    "attn_fwd_kernel": "tests/test_hip_attention_ledger.py",
+    "attn_bwd_kernel": "tests/test_hip_attention_ledger.py",
+    "attn_tiled_fwd_kernel": "tests/test_hip_attention_ledger.py",
+    "attn_tiled_bwd_kernel": "tests/test_hip_attention_ledger.py",
     "rms_qkv_fused_kernel": "tests/test_hip_ops.py",
     "resstack_fwd_kernel": "tests/test_hip_ops.py",
     "qsample_slice_kernel": "tests/test_hip_selfcond.py",
