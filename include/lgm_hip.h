@@ -56,7 +56,9 @@ extern "C" {
                              *  lgm_hybrid_loss_bwd, lgm_sample_step_learned, lgm_sample_step_table_learned, lgm_vlb_term_learned, lgm_gn_plan,
                              *  lgm_tsampler_draw, lgm_tsampler_update, lgm_weighted_mse_fwd_iw / _bwd_iw, lgm_hybrid_loss_fwd_iw / _bwd_iw,
                              *  lgm_lowres_cond, lgm_lowres_emb_fwd, lgm_sample_step_extent, lgm_dpm_step_extent,
-                             *  lgm_distill_half_step, lgm_distill_target, lgm_slerp, lgm_slerp_span, lgm_slerp_partials
+                             *  lgm_distill_half_step, lgm_distill_target, lgm_slerp, lgm_slerp_span, lgm_slerp_partials,
+                             *  lgm_edm_qsample, lgm_edm_qsample_sigma, lgm_edm_pre, lgm_edm_euler, lgm_edm_heun, lgm_fourier_emb_fwd,
+                             *  lgm_fourier_emb_bwd
                              *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -1257,6 +1259,55 @@ int lgm_gn_bwd_drop(const float* x, int64_t x_pitch, float* gy, int64_t gy_pitch
                     const float* coefB, float* gx, int64_t gx_pitch, int accumulate_gx, float* ggamma, float* gbeta,
                     float affine_beta, float* gss, int64_t gss_pitch, float gss_beta, float* workspace, float* rows,
                     int64_t* desc, const void* key, int layer, int pass, int64_t thr, float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Elucidated diffusion (csrc/edm.hip; Karras et al. 2022, Table 1 "Ours" and Algorithm 2; an extension of the reference) and
+ * the reference's random / learned Fourier embedding of a real-valued time (ddpm.py:135-151) its network reads.  With
+ * s_d = sigma_data: c_in = 1 / sqrt(s^2 + s_d^2), c_skip = s_d^2 / (s^2 + s_d^2), c_out = s s_d / sqrt(s^2 + s_d^2), c_noise = ln(s) / 4,
+ * D(x, s) = c_skip x + c_out F(c_in x, c_noise).  Buffers are NHWC with their pitch in floats; the network's input buffer holds
+ * c_in x in lanes [x_off, x_off + C) (r4(C) lanes from x_off must lie inside the pitch, the padding behind the C lanes is zeroed);
+ * the target, the sample state x, x^ and d are buffers of their own with r4(C) written lanes a pixel (padding zero); img and
+ * noise are dense NCHW.  Every product, quotient and sum rounds once (no contraction), in the order written.  16-byte accesses
+ * when every base is 16-byte aligned and every pitch and offset a multiple of 4, else one lane per thread: the same bits.
+ * No atomics.  B <= 65535.
+ * lgm_edm_qsample: s_b = exp(P_mean + P_std n_b), c_noise_b = (P_mean + P_std n_b) / 4 from the normal draw n [B]; y = img
+ *   (2 img - 1 when normalize), x = y + s eps; c_in x into the input buffer, F* = (y - c_skip x) / c_out into the target, s and
+ *   c_noise into sigma_out / cnoise_out [B].  lgm_edm_qsample_sigma: the same with s [B] given, c_noise = log(s) / 4.  Both launch
+ *   edm_qsample_kernel.
+ * A sampling step's row is 16 floats (lgm_hip.edm.edm_plan, float64 rounded once):
+ *     (s_i, s^, coef = sqrt(s^^2 - s_i^2) S_noise, s',  c_in, c_noise, c_skip, c_out at s^,  the same four at s' (zeros when s' = 0),
+ *      dt = s' - s^, gamma, 0, 0)
+ *   by value (`row`, 16 host floats) or row counter[0] of the 16-byte aligned device `table`; exactly one of the two is given.
+ * lgm_edm_pre: x^ = x + coef eps where noise is given and coef != 0, else x^ = x; c_in(s^) x^ into the input buffer, cnoise[b] =
+ *   c_noise(s^).  xhat is a buffer of its own (not x).  Launches edm_pre_kernel.
+ * lgm_edm_euler: D = c_skip(s^) x^ + c_out(s^) F (clamped to [-1, 1] when clip), d = (x^ - D) / s^, x' = x^ + dt d into the state x.
+ *   second: also d, c_in(s') x' into the input buffer and cnoise[b] = c_noise(s') (d, xin, cnoise may be NULL otherwise).  advance
+ *   (table form, not with second): counter[0] += 1 behind the launch.  Launches edm_euler_kernel.
+ * lgm_edm_heun: D' = c_skip(s') x' + c_out(s') F' with x' read from the state (clamped when clip), d' = (x' - D') / s',
+ *   x_next = x^ + dt ((d + d') / 2) into the state.  advance as above.  Launches edm_heun_kernel.
+ * lgm_fourier_emb_fwd: out[b] = (x_b, sin(f_b0) .. sin(f_b,half-1), cos(f_b0) .. cos(f_b,half-1)), f_bd = ((x_b w_d) 2) pi in
+ *   float32, lanes [2 half + 1, pitch) zero; x [B] float32.  Launches fourier_emb_fwd_kernel.
+ * lgm_fourier_emb_bwd: gweights[d] = beta gweights[d] + 2 pi sum_b x_b (cos_bd g_sin_bd - sin_bd g_cos_bd) from the forward's own
+ *   rows `emb` and the gradient rows `gemb`, summed over b in ascending order by one workgroup: the same bits on every run.
+ *   Launches fourier_emb_bwd_kernel.
+ * ------------------------------------------------------------------------------------- */
+int lgm_edm_qsample(const float* img, const float* noise, const float* n, float P_mean, float P_std, float sigma_data,
+                    int normalize, float* xin, int64_t pitch, int x_off, float* target, int64_t target_pitch, float* sigma_out,
+                    float* cnoise_out, int B, int C, int HW, void* stream);
+int lgm_edm_qsample_sigma(const float* img, const float* noise, const float* sigma, float sigma_data, int normalize, float* xin,
+                          int64_t pitch, int x_off, float* target, int64_t target_pitch, float* sigma_out, float* cnoise_out,
+                          int B, int C, int HW, void* stream);
+int lgm_edm_pre(const float* x, int64_t state_pitch, const float* noise, const float* row, const float* table,
+                const int32_t* counter, float* xhat, float* xin, int64_t pitch, int x_off, float* cnoise, int B, int C, int HW,
+                void* stream);
+int lgm_edm_euler(const float* F, int64_t f_pitch, const float* xhat, int64_t state_pitch, const float* row, const float* table,
+                  int32_t* counter, int clip, int second, float* x, float* d, float* xin, int64_t pitch, int x_off, float* cnoise,
+                  int advance, int B, int C, int HW, void* stream);
+int lgm_edm_heun(const float* F, int64_t f_pitch, const float* xhat, const float* d, int64_t state_pitch, const float* row,
+                 const float* table, int32_t* counter, int clip, float* x, int advance, int B, int C, int HW, void* stream);
+int lgm_fourier_emb_fwd(const float* x, const float* weights, int B, int half, float* out, int64_t pitch, void* stream);
+int lgm_fourier_emb_bwd(const float* emb, int64_t pitch, const float* gemb, int64_t gpitch, int B, int half, float* gweights,
+                        float beta, void* stream);
 
 #ifdef __cplusplus
 }

@@ -236,7 +236,16 @@ class GraphedDDPMStep:
 
     Low-resolution conditioned model (``Unet(lowres_cond=True)``): the augmentation levels s ~ randint(0, lowres_aug_levels) and
     the augmentation noise are drawn inside the graph behind every other draw (``self.lowres_s`` / ``self.lowres_noise``), and
-    the launch that writes the conditioning slice from the batch follows q_sample's.  Any other model draws nothing more."""
+    the launch that writes the conditioning slice from the batch follows q_sample's.  Any other model draws nothing more.
+
+    The ``step_qsample`` protocol.  A diffusion that is no ``GaussianDiffusion`` rides this step by defining
+    ``step_qsample(step) -> QSample``: its draws, in the order its own ``forward`` takes them, left in ``step.t`` / ``step.noise`` /
+    ``step.classes`` (from ``step.y``) / ``step.dropout_key``, and its q_sample launch over ``step.x``.  ``QSample.t`` indexes the
+    diffusion's ``loss_weight`` table, ``QSample.net_t`` (when not None) is the time the network reads.  Besides the hook the
+    step reads ``model``, ``auto_normalize``, ``loss_weight``, ``learned_variance``, ``offset_noise_strength``, ``_distill``,
+    ``active_t_sampler()`` of the diffusion.  ``ElucidatedDiffusion`` (models/generative/diffusion/edm.py) is the one user: n ~
+    randn(B) stands where randint stood (``step.t`` holds it), then noise, the label drop and the dropout key, then
+    ``lgm_edm_qsample``.  Everything behind q_sample is the plain step."""
 
     def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None,
                  accum: Optional[_GradAccumulation] = None):
@@ -266,9 +275,13 @@ class GraphedDDPMStep:
         # what the graphs hold - a new round (another teacher, another step count) is a new step object
         distilling = gd._distill is not None
         self.distill_sig = (gd._distill, gd._distill.table) if distilling else None
+        # a diffusion with a q_sample of its own (the ``step_qsample`` protocol, below): it differs here and nowhere else
+        own_qsample = getattr(gd, "step_qsample", None)
 
         def qsample():
             # the draws of GaussianDiffusion.forward / p_losses, in their order, and the q_sample launch
+            if own_qsample is not None:
+                return own_qsample(self)
             if distilling:                           # a level of the student's grid: randint(0, N) and an index into it
                 self.t = gd.draw_distill_t(x.shape[0], x.device)
             elif ts is None:
@@ -293,7 +306,7 @@ class GraphedDDPMStep:
 
         def begin(q):                                # the saved forward, the loss, its gradient: the backward is open
             loss, ctx = hip_loss_network(gd, q.xt, q.target, q.img, q.t, q.noise, q.offset, True, self.classes,
-                                         dropout_key=self.dropout_key, lowres_s=q.lowres_s)
+                                         dropout_key=self.dropout_key, lowres_s=q.lowres_s, net_t=q.net_t)
             fp.zero_grad()
             return loss, hip_loss_backward_begin(ctx, self.one)
 

@@ -1431,6 +1431,76 @@ def distill_target(xin, x_off, xmid, mid_off, out, t, table, teacher_objective: 
                              1 if clip else 0, target.data_ptr(), pitch(target), B, C, H * W, stream())
 
 
+# Elucidated diffusion (csrc/edm.hip).  ``xin`` [B, H, W, pitch] is the network's input buffer (c_in x in its x slice); the
+# target, the state ``x``, ``xhat`` and ``d`` are [B, H, W, r4(C)] buffers of their own; ``img`` / ``noise`` dense NCHW.  A step's
+# operands are either ``row`` (16 host floats, lgm_hip.edm.edm_plan) or ``table`` [n, 16] float32 with its int32 ``counter``.
+def edm_qsample(img, noise, xin, x_off, target, sigma_out, cnoise_out, sigma_data, normalize, *, n=None, sigma=None,
+                P_mean=0.0, P_std=0.0):
+    """c_in (y + s eps) into ``xin``, F* into ``target``, s and c_noise per sample; s = exp(P_mean + P_std n) or ``sigma``"""
+    B, C, H, W = img.shape
+    assert (n is None) != (sigma is None) and img.is_contiguous() and noise.is_contiguous() and noise.shape == img.shape
+    assert tuple(xin.shape[:3]) == tuple(target.shape[:3]) == (B, H, W)
+    for v in (n, sigma, sigma_out, cnoise_out):
+        assert v is None or (v.dtype == torch.float32 and tuple(v.shape) == (B,) and v.is_contiguous())
+    tail = (float(sigma_data), 1 if normalize else 0, xin.data_ptr(), pitch(xin), x_off, target.data_ptr(), pitch(target),
+            sigma_out.data_ptr(), cnoise_out.data_ptr(), B, C, H * W, stream())
+    if n is not None:
+        lib().lgm_edm_qsample(img.data_ptr(), noise.data_ptr(), n.data_ptr(), float(P_mean), float(P_std), *tail)
+    else:
+        lib().lgm_edm_qsample_sigma(img.data_ptr(), noise.data_ptr(), sigma.data_ptr(), *tail)
+
+
+def _edm_row(row, table, counter):
+    assert (row is None) != (table is None) and (table is None) == (counter is None)
+    if row is not None:
+        assert len(row) == 16
+        return (ctypes.c_float * 16)(*[float(v) for v in row]), None, None
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] == 16 and counter.dtype == torch.int32
+    return None, table.data_ptr(), counter.data_ptr()
+
+
+def edm_pre(x, noise, xhat, xin, x_off, cnoise, C, *, row=None, table=None, counter=None):
+    """x^ = x + coef eps (``noise`` NCHW or None: x^ = x), c_in(s^) x^ into ``xin``, c_noise(s^) into ``cnoise`` [B]"""
+    B, H, W, _ = x.shape
+    assert xhat.shape == x.shape and pitch(xhat) == pitch(x) and cnoise.dtype == torch.float32 and tuple(cnoise.shape) == (B,)
+    assert noise is None or (noise.is_contiguous() and tuple(noise.shape) == (B, C, H, W))
+    lib().lgm_edm_pre(x.data_ptr(), pitch(x), _p(noise), *_edm_row(row, table, counter), xhat.data_ptr(), xin.data_ptr(),
+                      pitch(xin), x_off, cnoise.data_ptr(), B, C, H * W, stream())
+
+
+def edm_euler(F, xhat, x, C, clip: bool, *, d=None, xin=None, x_off=0, cnoise=None, second: bool = False, advance: bool = False,
+              row=None, table=None, counter=None):
+    """x' into the state ``x`` from the network output ``F`` at (x^, s^); ``second``: also ``d``, c_in(s') x' into ``xin`` and
+    c_noise(s') into ``cnoise`` for the second evaluation"""
+    B, H, W, _ = x.shape
+    assert xhat.shape == x.shape and pitch(xhat) == pitch(x) and tuple(F.shape[:3]) == (B, H, W)
+    assert not second or (d is not None and d.shape == x.shape and pitch(d) == pitch(x) and xin is not None and cnoise is not None)
+    lib().lgm_edm_euler(F.data_ptr(), pitch(F), xhat.data_ptr(), pitch(x), *_edm_row(row, table, counter), 1 if clip else 0,
+                        1 if second else 0, x.data_ptr(), _p(d), _p(xin), pitch(xin) if xin is not None else 0, x_off,
+                        _p(cnoise), 1 if advance else 0, B, C, H * W, stream())
+
+
+def edm_heun(F, xhat, d, x, C, clip: bool, *, advance: bool = False, row=None, table=None, counter=None):
+    """x_next into the state ``x`` (which holds x') from the network output ``F`` at (x', s')"""
+    B, H, W, _ = x.shape
+    assert xhat.shape == x.shape == d.shape and pitch(xhat) == pitch(x) == pitch(d) and tuple(F.shape[:3]) == (B, H, W)
+    lib().lgm_edm_heun(F.data_ptr(), pitch(F), xhat.data_ptr(), d.data_ptr(), pitch(x), *_edm_row(row, table, counter),
+                       1 if clip else 0, x.data_ptr(), 1 if advance else 0, B, C, H * W, stream())
+
+
+def fourier_emb_fwd(x, weights_ptr: int, half: int, out):
+    """out[b] = (x_b, sin(2 pi x_b w), cos(2 pi x_b w)), the lanes behind them zero; ``x`` float32 [B]"""
+    assert x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous() and out.shape[0] == x.shape[0]
+    lib().lgm_fourier_emb_fwd(x.data_ptr(), weights_ptr, x.shape[0], half, out.data_ptr(), pitch(out), stream())
+
+
+def fourier_emb_bwd(emb, gemb, half: int, gweights_ptr: int, beta: float):
+    """gweights = beta gweights + 2 pi sum_b x_b (cos g_sin - sin g_cos), rows in ascending order"""
+    assert emb.shape[0] == gemb.shape[0]
+    lib().lgm_fourier_emb_bwd(emb.data_ptr(), pitch(emb), gemb.data_ptr(), pitch(gemb), emb.shape[0], half, gweights_ptr,
+                              float(beta), stream())
+
+
 # Spherical interpolation of latents (csrc/slerp.hip): a per-sample reduction into the caller's partials, then the blend.
 def slerp_span() -> int:
     """pixels one workgroup of either slerp launch covers (a constant of the library)"""

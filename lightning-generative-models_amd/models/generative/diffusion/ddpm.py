@@ -28,8 +28,9 @@ from lgm_hip.optim import EMA, FusedAdam
 
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])     # reference :25
-QSample = namedtuple("QSample", ["xt", "target", "img", "noise", "t", "offset", "lowres_s"],     # what hip_loss_qsample returns
-                     defaults=[None])
+# what hip_loss_qsample returns; ``net_t``: the time the network reads where it is not ``t`` (elucidated diffusion: c_noise,
+# while ``t`` indexes the loss weights)
+QSample = namedtuple("QSample", ["xt", "target", "img", "noise", "t", "offset", "lowres_s", "net_t"], defaults=[None, None])
 
 
 _NO_RES_FOLD = os.environ.get("LGM_NO_RES_FOLD") is not None       # A/B switch: the identity residual's gradient as its own axpby launch
@@ -277,6 +278,16 @@ class _Up(nn.Module):
         return gx
 
 
+class FourierPosEmb(nn.Module):
+    """RandomOrLearnedSinusoidalPosEmb (:135-151): the parameter alone, key ``time_mlp.0.weights`` [dim / 2]; the row is
+    written by ``lgm_fourier_emb_fwd`` (``Unet._emb_mlp_fwd``)."""
+
+    def __init__(self, dim, is_random=False):
+        super().__init__()
+        self.is_random = bool(is_random)
+        self.weights = nn.Parameter(torch.randn(dim // 2), requires_grad=not is_random)
+
+
 class _PlainConv(Conv2d):
     """Last-stage 3x3 conv used in place of Down/Up (:377, :413)."""
 
@@ -306,7 +317,12 @@ class Unet(nn.Module):
         reads ``cat((lowres_cond_img, x), dim=1)``, the conditioning image already at x's size, and adds ``lowres_time_mlp(s)``
         - an embedding of the conditioning image's noise-augmentation level s with the structure of ``time_mlp``, Imagen's
         ``to_lowres_time_hiddens`` - to the time embedding.  ``init_conv.weight`` is [dim, 2 C, 7, 7] and every other key is
-        that of the reference's self-conditioned Unet, plus ``lowres_time_mlp.*``."""
+        that of the reference's self-conditioned Unet, plus ``lowres_time_mlp.*``.
+        ``learned_sinusoidal_cond`` / ``random_fourier_features`` / ``learned_sinusoidal_dim`` (the reference's, :315-326): the
+        network embeds a REAL-valued time - float32 [B] in ``forward`` / ``forward_nhwc`` / ``forward_guided`` - through
+        ``time_mlp.0.weights`` [learned_sinusoidal_dim / 2], trained when learned and a saved constant when random; what
+        ``ElucidatedDiffusion`` (edm.py) is built around.  NotImplementedError together with ``self_condition``,
+        ``learned_variance`` or ``lowres_cond``."""
         super().__init__()
         if lowres_cond and self_condition:
             raise NotImplementedError("lowres_cond together with self_condition is not built: both would take the first C "
@@ -315,9 +331,13 @@ class Unet(nn.Module):
         self.dropout = float(dropout)
         if num_classes is not None and int(num_classes) < 1:
             raise ValueError(f"num_classes must be a positive number of classes, got {num_classes!r}")
-        if learned_sinusoidal_cond or random_fourier_features:
-            raise NotImplementedError("HIP UNet covers the configuration the reference DDPM constructs "
-                                      "(ddpm.py:984-987), self-conditioning and the learned variance: no fourier features")
+        fourier = bool(learned_sinusoidal_cond or random_fourier_features)
+        if fourier and (self_condition or learned_variance or lowres_cond):
+            # tests/test_selfcond_host.py and tests/test_learned_sigma_host.py pin the first two refusals
+            raise NotImplementedError("the random / learned fourier time embedding together with self_condition, "
+                                      "learned_variance or lowres_cond is not built")
+        if fourier and (int(learned_sinusoidal_dim) < 2 or int(learned_sinusoidal_dim) % 2):
+            raise ValueError(f"learned_sinusoidal_dim must be a positive even number, got {learned_sinusoidal_dim!r}")
         if learned_variance and self_condition:
             # tests/test_selfcond_host.py pins this refusal; the hybrid loss's estimate pass is not built for the combination
             raise NotImplementedError("learned_variance together with self_condition is not built")
@@ -329,7 +349,11 @@ class Unet(nn.Module):
         self.learned_variance = bool(learned_variance)
         self.self_condition = bool(self_condition)
         self.lowres_cond = bool(lowres_cond)
-        self.random_or_learned_sinusoidal_cond = False
+        # the reference's RandomOrLearnedSinusoidalPosEmb (:135-151, 315-326): the network reads a REAL-valued time (float32 [B])
+        # through the row (x, sin(2 pi x w), cos(2 pi x w)) of learned_sinusoidal_dim + 1 lanes; ``weights`` is trained when
+        # learned and a constant - never written by the optimizer, copied by the EMA, saved - when random
+        self.random_or_learned_sinusoidal_cond = fourier
+        self.fourier_half = int(learned_sinusoidal_dim) // 2 if fourier else 0
         self.theta = float(sinusoidal_pos_emb_theta)
         # self-conditioned (:300-301, 435): the network reads cat((x_self_cond, x), dim=1) - ONE NHWC buffer of r4(2 C) lanes
         # whose slices [sc_off, sc_off + C) and [x_off, x_off + C) their producers fill; nothing is concatenated
@@ -346,7 +370,12 @@ class Unet(nn.Module):
         self.in_out = in_out
         time_dim = dim * 4
         self.time_dim = time_dim
-        self.time_mlp = nn.Sequential(nn.Identity(), Linear(dim, time_dim), nn.Identity(), Linear(time_dim, time_dim))
+        if fourier:
+            self.time_mlp = nn.Sequential(FourierPosEmb(int(learned_sinusoidal_dim), bool(random_fourier_features)),
+                                          Linear(int(learned_sinusoidal_dim) + 1, time_dim), nn.Identity(),
+                                          Linear(time_dim, time_dim))
+        else:
+            self.time_mlp = nn.Sequential(nn.Identity(), Linear(dim, time_dim), nn.Identity(), Linear(time_dim, time_dim))
         # class-conditional (extension): temb = time_mlp(t) + label_emb.weight[classes], row num_classes = the null label
         # classifier-free guidance trains and samples with; N(0, 1) like nn.Embedding, dense under Adam and the EMA
         self.num_classes = None if num_classes is None else int(num_classes)
@@ -424,6 +453,8 @@ class Unet(nn.Module):
         for lin in (self.time_mlp[1], self.time_mlp[3]):      # their gradients are produced last, too
             first.append((names[id(lin.weight)], lin.weight, "weight"))
             first.append((names[id(lin.bias)], lin.bias, "vector"))
+        if self.random_or_learned_sinusoidal_cond:            # the fourier frequencies: their gradient ends the time phase
+            first.append((names[id(self.time_mlp[0].weights)], self.time_mlp[0].weights, "vector"))
         if self.num_classes is not None:                      # dense rows [K + 1, time_dim], final with the time MLP's
             first.append((names[id(self.label_emb.weight)], self.label_emb.weight, "vector"))
         if self.lowres_cond:                                  # the augmentation-level MLP: backward with the time MLP's
@@ -510,23 +541,55 @@ class Unet(nn.Module):
         (four launches) -> (pe, a1, h, emb), in ``out`` where the caller owns the four buffers"""
         B, fp = t.shape[0], self._flat
         l1, l2 = mlp[1], mlp[3]
-        pe, a1, h, emb = out or (ops.new((B, d), t) for d in (self.dim, self.time_dim, self.time_dim, self.time_dim))
-        ops.posemb(t, self.dim, self.theta, pe)
+        pe, a1, h, emb = out or (ops.new((B, d), t) for d in (self._pe_width(mlp), self.time_dim, self.time_dim, self.time_dim))
+        if self._is_fourier(mlp):
+            # the real-valued time's row at the pitch ``l1.geom`` reads (r4(learned_sinusoidal_dim + 1) lanes, padding zero)
+            ops.fourier_emb_fwd(t, fp.ptr(mlp[0].weights), self.fourier_half, pe)
+        else:
+            ops.posemb(t, self.dim, self.theta, pe)
         ops.conv_xy(l1.geom(B), pe, fp.ptr(l1.weight), fp.ptr(l1.bias), None, a1)
         ops.act_fwd(a1, None, None, h, ops.ACT_GELU)
         ops.conv_xy(l2.geom(B), h, fp.ptr(l2.weight), fp.ptr(l2.bias), None, emb)
         return pe, a1, h, emb
 
+    def _is_fourier(self, mlp) -> bool:
+        """``mlp`` is the time MLP of a network with the random / learned fourier embedding (``lowres_time_mlp`` never is)"""
+        return self.random_or_learned_sinusoidal_cond and mlp is self.time_mlp
+
+    def _pe_width(self, mlp) -> int:
+        return _r4(2 * self.fourier_half + 1) if self._is_fourier(mlp) else self.dim
+
+    def _time_mlp_fused(self) -> bool:
+        """The time MLP runs on the fused sinusoidal kernels (``lgm_time_mlp_fwd`` / ``_bwd``, opt-in).  ONE decision for the forward
+        and the backward: a network with the fourier embedding never does, whatever the switch says - those kernels embed an
+        integer time and read a [B, dim] row, its row is [B, r4(learned_sinusoidal_dim + 1)]."""
+        if self.random_or_learned_sinusoidal_cond:
+            return False
+        return ops.time_mlp_ok(self.dim, self.time_dim, self.time_mlp[1], self.time_mlp[3])
+
+    def check_time(self, time):
+        """TypeError by name unless ``time`` has the type this network embeds: float32 [B] with the fourier embedding (a
+        real-valued time), an integer tensor with the sinusoidal one"""
+        if self.random_or_learned_sinusoidal_cond:
+            if not torch.is_tensor(time) or not time.dtype.is_floating_point:
+                raise TypeError("a Unet with the random / learned fourier embedding takes a floating-point time [B], got "
+                                f"{time.dtype if torch.is_tensor(time) else type(time).__name__}")
+            return time.detach().to(torch.float32).contiguous()
+        if not torch.is_tensor(time) or time.dtype.is_floating_point:
+            raise TypeError("a Unet with the sinusoidal embedding takes an integer time [B], got "
+                            f"{time.dtype if torch.is_tensor(time) else type(time).__name__}")
+        return time
+
     def _time_fwd(self, t, save, classes=None, lowres_s=None):
         B = t.shape[0]
         fp = self._flat
         l1, l2 = self.time_mlp[1], self.time_mlp[3]
-        pe = ops.new((B, self.dim), t)
+        pe = ops.new((B, self._pe_width(self.time_mlp)), t)
         a1 = ops.new((B, self.time_dim), t)
         h = ops.new((B, self.time_dim), t)
         temb = ops.new((B, self.time_dim), t)
         st = ops.new((B, self.time_dim), t)
-        if ops.time_mlp_ok(self.dim, self.time_dim, l1, l2):
+        if self._time_mlp_fused():
             # posemb -> Linear -> GELU -> Linear -> SiLU in ONE launch (was six: csrc/elementwise.hip time_mlp_fwd_kernel)
             ops.time_mlp_fwd(t, self.dim, self.theta, fp.ptr(l1.weight), fp.ptr(l1.bias), fp.ptr(l2.weight),
                              fp.ptr(l2.bias), self.time_dim, pe, a1, h, temb, st)
@@ -569,7 +632,7 @@ class Unet(nn.Module):
         gst = ops.new(st.shape, st)
         ops.conv_yx(g, gss_all, fp.ptr(rbs[0].mlp[1].weight), None, None, gst)
         gtemb = ops.new(st.shape, st)
-        fused = ops.time_mlp_ok(self.dim, self.time_dim, l1, l2)
+        fused = self._time_mlp_fused()           # the forward's decision: the tape holds what that path saved
         if fused:
             # SiLU' -> (weight / bias gradient, input gradient) of the second linear -> GELU' -> weight / bias gradient of the
             # first: two launches (row-local chain, batch reductions in row order) instead of six
@@ -583,7 +646,16 @@ class Unet(nn.Module):
         self._label_emb_bwd(gc, gtemb, saved.classes)
         self._lowres_mlp_bwd(gc, gtemb, saved.lowres)
         if not fused:
-            self._emb_mlp_bwd(gc, self.time_mlp, gtemb, saved.pe, saved.a1, saved.h)
+            ga1 = self._emb_mlp_bwd(gc, self.time_mlp, gtemb, saved.pe, saved.a1, saved.h)
+            pos = self.time_mlp[0]
+            if self.random_or_learned_sinusoidal_cond and not pos.is_random:
+                # learned frequencies: the first linear's input gradient, then g_w summed over the batch in row order by one
+                # workgroup (the forward's own row holds x, sin and cos).  Random features get no launch: their gradient
+                # slot stays zero, and Adam leaves a parameter with m = v = g = 0 as it is.
+                l1 = self.time_mlp[1]
+                gpe = ops.new(saved.pe.shape, saved.pe)
+                ops.conv_yx(l1.geom(B), ga1, fp.ptr(l1.weight), None, None, gpe, wt_ptr=fp.tptr(l1.weight))
+                ops.fourier_emb_bwd(saved.pe, gpe, self.fourier_half, fp.gptr(pos.weights), gc.beta(pos.weights))
 
     def _emb_mlp_bwd(self, gc: GradCtx, mlp, gemb, pe, a1, h):
         """The backward of ``_emb_mlp_fwd`` from the gradient of its output: weight + input gradient of the second linear in
@@ -598,6 +670,7 @@ class Unet(nn.Module):
         ops.act_bwd(a1, None, gh, ga1, False, ops.ACT_GELU)
         ops.conv_wgrad(l1.geom(B), ga1, pe, fp.gptr(l1.weight), gc.beta(l1.weight), fp.gptr(l1.bias))
         gc.beta(l1.bias)
+        return ga1
 
     def _lowres_mlp_bwd(self, gc: GradCtx, gtemb, lowres):
         """temb is a sum: g lowres_time_mlp(s) = g temb"""
@@ -639,7 +712,8 @@ class Unet(nn.Module):
 
     def forward_nhwc(self, x, t, save: bool, refresh_weights: bool = True, classes=None, dropout_key=None, drop_pass: int = 0,
                      lowres_s=None):
-        """x: [B, S, S, in_pitch] NHWC (``input_buffer``; pad lanes zero), t: int64 [B].
+        """x: [B, S, S, in_pitch] NHWC (``input_buffer``; pad lanes zero), t: int64 [B] - float32 [B], a real-valued time, on a
+        network with the random / learned fourier embedding (``check_time``: the other type is a TypeError).
         Returns (out [B,S,S,r4(out_dim)], tape).  ``refresh_weights=False``: the derived weight copies (Winograd /
         split-precision operands) are known to be current — a sampling chain refreshes them once, not per step.
         ``classes``: int64 [B] on the device (``Unet.labels``), read by a class-conditional network only; None = null labels.
@@ -649,6 +723,7 @@ class Unet(nn.Module):
         ``lowres_s``: int64 [B] on the device (``Unet.aug_levels``), the augmentation levels a low-resolution conditioned
         network embeds; its conditioning image is in the buffer's slice [cond_off, cond_off + C) already."""
         B, S, _, _ = x.shape
+        t = self.check_time(t)
         dro = self.drop_operands(dropout_key, drop_pass)
         dim = self.dim
         n = len(self.in_out)
@@ -873,6 +948,7 @@ class Unet(nn.Module):
         network without classes it raises ValueError.  ``lowres_cond_img`` / ``lowres_aug_t`` (extension): the conditioning
         image of a low-resolution conditioned network, already at x's size and in x's range (a constant: no gradient reaches
         it), and its augmentation levels (``None`` = 0); the image is required there and a ValueError on any other network."""
+        time = self.check_time(time)       # here too: the refusal comes before any storage is bound (forward_nhwc serves the samplers)
         classes = self.labels(classes, x.shape[0], x.device)
         if self.lowres_cond:
             if lowres_cond_img is None:
@@ -1076,6 +1152,9 @@ class GaussianDiffusion(nn.Module):
         state lives with the model that trains, under ``t_sampler.history`` / ``t_sampler.counts`` of its state dict."""
         super().__init__()
         from lgm_hip import tsampler
+        if getattr(model, "random_or_learned_sinusoidal_cond", False):       # the reference asserts the same (:555)
+            raise ValueError("GaussianDiffusion walks integer timesteps: a Unet with the random / learned fourier embedding "
+                             "reads a real-valued time (models.generative.diffusion.edm.ElucidatedDiffusion)")
         history, uniform_prob = tsampler.check_arguments(t_sampler, t_sampler_history, t_sampler_uniform_prob)
         self.t_sampler = t_sampler
         self.learned_variance = bool(getattr(model, "learned_variance", False))
@@ -1864,15 +1943,15 @@ def _loss_form(c: LossContext):
 
 
 def hip_loss_network(gd: "GaussianDiffusion", xt, target, img, t, noise, offset, save: bool, classes=None, normalize=None,
-                     dropout_key=None, lowres_s=None):
+                     dropout_key=None, lowres_s=None, net_t=None):
     """The pass the gradient is taken through + weighted MSE.  Returns (loss[1], ctx).  A learned-variance network: the hybrid
     loss instead (lgm_hybrid_loss_fwd: the same MSE over the prediction lanes + vb_loss_weight times the bound's term), ``ctx``
     (``LossContext``) then also holds the per-sample terms, x_t and ``normalize`` - whether ``img`` is still in the data range
     (``None``: the diffusion's auto_normalize, what the graph-replayed step hands its q_sample).  ``dropout_key``: the step's key;
-    this is pass 0 of the dropout mask."""
+    this is pass 0 of the dropout mask.  ``net_t``: the time the network reads where it is not ``t`` (``QSample.net_t``)."""
     B, C, H, W = img.shape
     hybrid = gd.learned_variance
-    out, tape = gd.model.forward_nhwc(xt, t, save, True, classes, dropout_key, 0, lowres_s)
+    out, tape = gd.model.forward_nhwc(xt, t if net_t is None else net_t, save, True, classes, dropout_key, 0, lowres_s)
     loss = ops.new((1,), img)
     ctx = LossContext(gd, tape, out, target, t, (B, C, H, W), img, noise, offset)
     # a loss-aware timestep sampler (training mode): the *_iw forms weight sample b by iw[t_b] and leave that weight in ``wb``
