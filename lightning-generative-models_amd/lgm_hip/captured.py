@@ -2,6 +2,7 @@
 kept per network by ``_cached_step``.  ``_warm_up`` also serves the training steps of ``graph.py``."""
 from __future__ import annotations
 
+import os
 import sys
 import weakref
 
@@ -94,10 +95,13 @@ class _CapturedStep:
                 after(lo, hi)
 
 
-def _cached_step(net, key, build, what: str):
+def _cached_step(net, key, build, what: str, dev):
     """-> the network's captured step under ``key``, built by ``build()`` on first use and again once the entry no longer
-    ``matches`` the network, or None: ``build`` raised (one line on stderr, ``what`` in it) now or at one of the last
+    ``matches`` the network, or None: graph replay is disabled (``LGM_NO_SAMPLER_GRAPH=1``) or ``dev`` is no GPU - nothing is
+    looked up or built then -, or ``build`` raised (one line on stderr, ``what`` in it) now or at one of the last
     ``_CAPTURE_RETRY_AFTER`` calls for this key.  The caller then goes on with eager launches."""
+    if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or dev.type != "cuda":
+        return None
     per_net = _GRAPHS.setdefault(net, {})
     ent = per_net.get(key)
     if isinstance(ent, int):                         # a capture failed earlier: eager for a while, then try again

@@ -238,19 +238,18 @@ class GraphedDDPMStep:
     the augmentation noise are drawn inside the graph behind every other draw (``self.lowres_s`` / ``self.lowres_noise``), and
     the launch that writes the conditioning slice from the batch follows q_sample's.  Any other model draws nothing more.
 
-    The ``step_qsample`` protocol.  A diffusion that is no ``GaussianDiffusion`` rides this step by defining
-    ``step_qsample(step) -> QSample``: its draws, in the order its own ``forward`` takes them, left in ``step.t`` / ``step.noise`` /
-    ``step.classes`` (from ``step.y``) / ``step.dropout_key``, and its q_sample launch over ``step.x``.  ``QSample.t`` indexes the
-    diffusion's ``loss_weight`` table, ``QSample.net_t`` (when not None) is the time the network reads.  Besides the hook the
-    step reads ``model``, ``auto_normalize``, ``loss_weight``, ``learned_variance``, ``offset_noise_strength``, ``_distill``,
-    ``active_t_sampler()`` of the diffusion.  ``ElucidatedDiffusion`` (models/generative/diffusion/edm.py) is the one user: n ~
-    randn(B) stands where randint stood (``step.t`` holds it), then noise, the label drop and the dropout key, then
-    ``lgm_edm_qsample``.  Everything behind q_sample is the plain step."""
+    The protocol (``models.generative.diffusion.ddpm.Diffusion``).  Every diffusion rides this step through the two methods its
+    eager ``forward`` goes through: ``draw(x, labels) -> StepDraws``, the one place its draw order is written, and
+    ``qsample(x, draws, normalize) -> QSample``, its launches up to the input buffer and the target.  The record is left in
+    ``self.t`` / ``self.noise`` / ``self.offset`` / ``self.classes`` / ``self.dropout_key`` / ``self.lowres_s`` /
+    ``self.lowres_noise``.  ``QSample.t`` indexes the diffusion's ``loss_weight`` table, ``QSample.net_t`` (when not None) is the
+    time the network reads.  ``ElucidatedDiffusion`` (models/generative/diffusion/edm.py): n ~ randn(B) stands where randint
+    stood (``self.t`` holds it), then noise, the label drop and the dropout key, then ``lgm_edm_qsample``.  Everything behind
+    q_sample is the plain step."""
 
     def __init__(self, model, opt, x: torch.Tensor, sync=None, warmup: int = 3, y: Optional[torch.Tensor] = None,
                  accum: Optional[_GradAccumulation] = None):
-        from models.generative.diffusion.ddpm import (hip_loss_backward_begin, hip_loss_distill, hip_loss_estimate,
-                                                      hip_loss_network, hip_loss_qsample)
+        from models.generative.diffusion.ddpm import hip_loss_backward_begin, hip_loss_estimate, hip_loss_network
         self.model, self.opt, self.sync, self.accum = model, opt, sync, accum
         self.gd = gd = model.ema.online_model
         self.net = net = gd.model
@@ -259,7 +258,6 @@ class GraphedDDPMStep:
         net.grad_sync = None                         # collectives are issued by step(), never captured
         fp = net._flat
         self.t = self.noise = self.offset = self.classes = self.dropout_key = self.lowres_s = self.lowres_noise = None
-        strength = float(gd.offset_noise_strength)
         self.y = net.labels(y, x.shape[0], x.device).clone() if net.num_classes is not None else None
         # (the pipelined variant applies a bucket's Adam slice right behind ITS all-reduce: only with the overlapped exchange)
         # (and a slice cannot be updated before the whole gradient norm exists, or before the last micro-batch)
@@ -273,33 +271,14 @@ class GraphedDDPMStep:
         self.ts = ts = gd.active_t_sampler()
         # progressive distillation (GaussianDiffusion.distill_from): the teacher's grid, table and weights as they are NOW are
         # what the graphs hold - a new round (another teacher, another step count) is a new step object
-        distilling = gd._distill is not None
-        self.distill_sig = (gd._distill, gd._distill.table) if distilling else None
-        # a diffusion with a q_sample of its own (the ``step_qsample`` protocol, below): it differs here and nowhere else
-        own_qsample = getattr(gd, "step_qsample", None)
+        self.distill_sig = (gd._distill, gd._distill.table) if gd._distill is not None else None
 
         def qsample():
-            # the draws of GaussianDiffusion.forward / p_losses, in their order, and the q_sample launch
-            if own_qsample is not None:
-                return own_qsample(self)
-            if distilling:                           # a level of the student's grid: randint(0, N) and an index into it
-                self.t = gd.draw_distill_t(x.shape[0], x.device)
-            elif ts is None:
-                self.t = torch.randint(0, gd.num_timesteps, (x.shape[0],), device=x.device).long()
-            else:                                    # one launch behind torch.rand, where randint stands
-                self.t = ts.draw(x.shape[0], x.device)
-            self.noise = torch.randn_like(self.x)
-            self.offset = torch.randn(x.shape[:2], device=x.device) if strength > 0.0 else None
-            if self.y is not None:
-                self.classes = gd.drop_labels(self.y)
-            self.dropout_key = gd.draw_dropout_key(x.device)     # None (no launch) unless the network drops
-            lowres = gd.draw_lowres(self.x)                      # None (no draw) unless low-resolution conditioned
-            if lowres is not None:
-                self.lowres_s, self.lowres_noise = lowres
-            q = hip_loss_qsample(gd, self.x, self.t, self.noise, gd.auto_normalize, self.offset, strength, lowres)
-            if distilling:                           # two teacher forwards and two launches: the target is the distillation's
-                hip_loss_distill(gd, q, self.classes)
-            return q
+            # the diffusion's draws, in the order its forward takes them, and its q_sample launches (the class comment)
+            d = gd.draw(self.x, self.y)
+            self.t, self.noise, self.offset, self.classes, self.dropout_key = d[:5]
+            self.lowres_s, self.lowres_noise = d.lowres or (None, None)
+            return gd.qsample(self.x, d, gd.auto_normalize)
 
         def estimate(q):
             hip_loss_estimate(gd, q.xt, q.t, self.classes, self.dropout_key)

@@ -26,7 +26,6 @@ reference's ``posterior_log_variance_clipped[0]`` = log 1e-20, under which the d
 from __future__ import annotations
 
 import math
-import os
 import struct
 from collections import namedtuple
 from typing import List, Optional
@@ -231,11 +230,10 @@ def _vlb_key(gd, shape, clip: bool):
 def _graph_vlb(gd, shape, clip: bool) -> Optional[_GraphedVLB]:
     """-> the network's ``_GraphedVLB`` under ``_vlb_key`` from ``_cached_step``, or None (graph replay disabled, no device,
     capture failed: eager launches)"""
-    if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or gd.betas.device.type != "cuda":
-        return None
     net = gd.model
     net.prepare_hip(gd.betas.device)
-    return _cached_step(net, _vlb_key(gd, shape, clip), lambda: _GraphedVLB(gd, tuple(shape), clip), "likelihood")
+    return _cached_step(net, _vlb_key(gd, shape, clip), lambda: _GraphedVLB(gd, tuple(shape), clip), "likelihood",
+                        gd.betas.device)
 
 
 @torch.no_grad()

@@ -49,7 +49,6 @@ buffer and has a key of its own.
 from __future__ import annotations
 
 import math
-import os
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -757,13 +756,11 @@ def _graph_chain(gd, shape, with_noise: bool, rederive: bool = False, guided: bo
     ``rederive``: the DDIM chain's re-derived noise, part of the captured launch for pred_noise / pred_x0.
     ``dpm``: the DPM-Solver++ step (its own update kernel and history buffer): a graph of its own.
     ``inpaint``: the step with the inpainting tail (its operands are static buffers of the graph): a graph of its own."""
-    if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or gd.betas.device.type != "cuda":
-        return None
     net = gd.model
     net.prepare_hip(gd.betas.device)                 # may rebuild the flat storage (model.to(), new parameter storage)
     return _cached_step(net, _graph_key(gd, shape, with_noise, rederive, guided, dpm, inpaint, learned, clip),
                         lambda: _GraphedChain(gd, tuple(shape), with_noise, rederive, guided=guided, dpm=dpm, dyn=_dyn(gd),
-                                              inpaint=inpaint, learned=learned, clip=clip), "sampler")
+                                              inpaint=inpaint, learned=learned, clip=clip), "sampler", gd.betas.device)
 
 
 def p_sample_step(chain: _Chain, t: int, noise: Optional[torch.Tensor]):

@@ -31,6 +31,12 @@ ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"]) 
 # what hip_loss_qsample returns; ``net_t``: the time the network reads where it is not ``t`` (elucidated diffusion: c_noise,
 # while ``t`` indexes the loss weights)
 QSample = namedtuple("QSample", ["xt", "target", "img", "noise", "t", "offset", "lowres_s", "net_t"], defaults=[None, None])
+# The random operands of one training step, in the order a diffusion's ``draw`` takes them from torch's device generator - the
+# bits of the loss depend on it, and the graph-replayed step is tested bit for bit against the eager one.  ``t``: the timesteps
+# (elucidated diffusion: the normal draw n that sets sigma; None where sigma was given), ``offset``: the [B, C] offset noise,
+# ``classes``: the labels as the network gets them (behind the label drop), ``lowres``: (s, eps_aug).  None = the diffusion
+# does not have the feature: nothing was drawn for it.
+StepDraws = namedtuple("StepDraws", ["t", "noise", "offset", "classes", "dropout_key", "lowres"])
 
 
 _NO_RES_FOLD = os.environ.get("LGM_NO_RES_FOLD") is not None       # A/B switch: the identity residual's gradient as its own axpby launch
@@ -1117,7 +1123,62 @@ class _Distillation:
             self.stale = True
 
 
-class GaussianDiffusion(nn.Module):
+class Diffusion(nn.Module):
+    """What ``GaussianDiffusion`` and ``ElucidatedDiffusion`` (edm.py) share, and the protocol of the training step - eager
+    (``forward`` / ``p_losses``) and graph-replayed (``lgm_hip.graph.GraphedDDPMStep``) alike: a diffusion defines
+    ``draw(x, labels, ...) -> StepDraws``, the ONE place its draw order is written, and ``qsample(x, draws, normalize) ->
+    QSample``, its launches up to the network's input buffer and the target.  Everything behind them (``hip_loss_network``)
+    reads ``model``, ``auto_normalize``, ``loss_weight`` and what stands below.  Registers no parameter, buffer or submodule."""
+    learned_variance = False                         # hip_loss_network: the hybrid loss
+    _distill = None                                  # DDPMFastStep.step, DDPM.prepare_hip: the attached teacher
+
+    @property
+    def device(self):
+        return self.loss_weight.device
+
+    def active_t_sampler(self):
+        """the timestep sampler a forward in the current mode goes through (``lgm_hip.tsampler``), or None"""
+        return None
+
+    def draw_dropout_key(self, device):
+        """The step's 64-bit dropout key: ONE persistent int64 [1] device tensor, refilled in place from torch's device
+        generator (one launch; capturable).  The kernels read it when they run, so the backward pass sees the key of its
+        forward as long as no other loss forward of this diffusion runs in between.  None when the loss passes do not drop
+        (``dropout == 0`` or evaluation mode): nothing is drawn, nothing allocated."""
+        if self.model.dropout <= 0.0 or not self.model.training:
+            return None
+        key = self.__dict__.get("dropout_key")
+        if key is None or key.device != torch.device(device):
+            key = self.__dict__["dropout_key"] = torch.zeros(1, dtype=torch.int64, device=device)
+        return key.random_(-2 ** 63, None)             # all 64 bits
+
+    def drop_labels(self, classes):
+        """Classifier-free guidance training: every label becomes the null label with probability ``cond_drop_prob`` (one
+        ``torch.rand(B)`` on the labels' device; nothing is drawn when the probability is 0)."""
+        if self.cond_drop_prob <= 0.0:
+            return classes
+        drop = torch.rand(classes.shape[0], device=classes.device) < self.cond_drop_prob
+        return torch.where(drop, torch.full_like(classes, self.num_classes), classes)
+
+    def step_labels(self, labels, classes, B, device):
+        """The labels the network gets: the batch's ``labels`` behind the label drop (drawn here), or - no labels given -
+        ``classes`` as they are (``Unet.labels``: None on a class-conditional network = the null label, nothing is drawn)."""
+        if labels is None:
+            return self.model.labels(classes, B, device)
+        return self.drop_labels(self.model.labels(labels, B, device))
+
+    def normalize(self, img):
+        return img * 2 - 1 if self.auto_normalize else img
+
+    def unnormalize(self, t):
+        return (t + 1) * 0.5 if self.auto_normalize else t
+
+    def _loss(self, img, loss_forward):
+        """``loss_forward(save) -> (loss[1], LossContext)`` under the hand-written backward"""
+        return _LossFn.apply(self.model._anchor(img.device), loss_forward)
+
+
+class GaussianDiffusion(Diffusion):
     def __init__(self, model: Unet, *, img_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=None, ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, cond_drop_prob=None,
@@ -1249,10 +1310,6 @@ class GaussianDiffusion(nn.Module):
         # progressive distillation (``distill_from``): None, or the attached teacher - a plain attribute like ``_ts``
         self._distill: Optional[_Distillation] = None
 
-    @property
-    def device(self):
-        return self.betas.device
-
     # -- progressive distillation (extension; Salimans & Ho 2022, Algorithm 2; lgm_hip/distill.py) ------------------
     def distill_from(self, teacher: Optional["GaussianDiffusion"], steps: Optional[int] = None, clip: bool = True):
         """Attach a frozen copy of ``teacher.model``: from now on the training-mode ``forward`` / ``p_losses``, the eval-mode loss
@@ -1378,17 +1435,43 @@ class GaussianDiffusion(nn.Module):
         return self.ddim_time_pairs()
 
     # -- training ---------------------------------------------------------------------------
-    def draw_dropout_key(self, device):
-        """The step's 64-bit dropout key: ONE persistent int64 [1] device tensor, refilled in place from torch's device
-        generator (one launch; capturable).  The kernels read it when they run, so the backward pass sees the key of its
-        forward as long as no other loss forward of this diffusion runs in between.  None when the loss passes do not drop
-        (``dropout == 0`` or evaluation mode): nothing is drawn, nothing allocated."""
-        if self.model.dropout <= 0.0 or not self.model.training:
-            return None
-        key = self.__dict__.get("dropout_key")
-        if key is None or key.device != torch.device(device):
-            key = self.__dict__["dropout_key"] = torch.zeros(1, dtype=torch.int64, device=device)
-        return key.random_(-2 ** 63, None)             # all 64 bits
+    def draw(self, x_start, labels=None, *, t=None, noise=None, offset=None, classes=None, dropout_key=None, lowres_aug_t=None,
+             lowres_noise=None, offset_noise_strength=None) -> StepDraws:
+        """The random operands of a training step on the batch ``x_start``: what is given is used, the rest is drawn from
+        torch's device generator in THIS order, and nothing is drawn for a feature the diffusion does not have -
+        t (a level of the student's grid under a teacher, the timestep sampler's draw in training mode, else randint),
+        noise, the offset noise (strength > 0 only; ``offset_noise_strength`` overrides the attribute), the label drop
+        (``labels`` given and ``cond_drop_prob > 0``; ``classes``: the labels as the network gets them, never dropped), the
+        dropout key (``dropout > 0`` in training mode), the low-resolution level and noise (conditioned model)."""
+        B, dev = x_start.shape[0], x_start.device
+        if t is None:
+            ts = self.active_t_sampler()
+            if self._distill is not None:            # a level of the student's grid, where randint(0, T) stands
+                t = self.draw_distill_t(B, dev)
+            elif ts is None:
+                t = torch.randint(0, self.num_timesteps, (B,), device=dev).long()
+            else:                                    # (its uniforms stand where randint stands in the draw order)
+                t = ts.draw(B, dev)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        if not self._strength(offset_noise_strength) > 0.0:
+            offset = None
+        elif offset is None:
+            offset = torch.randn(x_start.shape[:2], device=dev)
+        classes = self.step_labels(labels, classes, B, dev)
+        key = dropout_key if dropout_key is not None else self.draw_dropout_key(dev)
+        return StepDraws(t, noise, offset, classes, key, self.draw_lowres(x_start, lowres_aug_t, lowres_noise))
+
+    def qsample(self, x_start, d: StepDraws, normalize: bool, offset_noise_strength=None) -> QSample:
+        """x_t, the objective's target and the conditioning slice from the batch and its draws (``hip_loss_qsample``); under a
+        teacher the distillation target over the objective's (``hip_loss_distill``)."""
+        q = hip_loss_qsample(self, x_start, d.t, d.noise, normalize, d.offset, self._strength(offset_noise_strength), d.lowres)
+        if self._distill is not None:
+            hip_loss_distill(self, q, d.classes)
+        return q
+
+    def _strength(self, offset_noise_strength=None):
+        return self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
 
     def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, classes=None, *, _offset_noise=None,
                  _normalize=False, _self_cond=None, _dropout_key=None, lowres_aug_t=None, lowres_noise=None,
@@ -1411,35 +1494,28 @@ class GaussianDiffusion(nn.Module):
         ``lowres_noise`` (NCHW) are used instead when given (parity runs).
         With a teacher attached (``distill_from``): the target is the distillation target and every ``t_b`` must be a level
         of the student's grid that has a successor, G[:-1] - ValueError otherwise (``_t_on_grid``: ``forward`` drew them from
-        the grid itself, nothing is read back)."""
-        if not self.lowres_cond and (lowres_aug_t is not None or lowres_noise is not None):
-            raise ValueError("lowres_aug_t / lowres_noise were passed to a model built without lowres_cond")
+        the grid itself, nothing is read back).  Whatever is not given is drawn by ``draw``, in its order."""
         if self._distill is not None and not _t_on_grid:
             off = sorted(set(int(v) for v in t.tolist()) - set(self._distill.grid[:-1]))
             if off:
                 raise ValueError(f"t = {off} is not on the student's {self._distill.steps}-step grid {self._distill.grid[:-1]}")
-        classes = self.model.labels(classes, x_start.shape[0], x_start.device)
-        if noise is None:
-            noise = torch.randn_like(x_start)
-        strength = self.offset_noise_strength if offset_noise_strength is None else offset_noise_strength
-        if self._distill is not None and strength > 0.0:
+        if self._distill is not None and self._strength(offset_noise_strength) > 0.0:
             raise NotImplementedError("offset noise together with a distillation teacher is not built")
-        offset = None
-        if strength > 0.0:
-            offset = _offset_noise if _offset_noise is not None else torch.randn(x_start.shape[:2], device=x_start.device)
+        d = self.draw(x_start, None, t=t, noise=noise, offset=_offset_noise, classes=classes, dropout_key=_dropout_key,
+                      lowres_aug_t=lowres_aug_t, lowres_noise=lowres_noise, offset_noise_strength=offset_noise_strength)
         self_cond = False
         if self.self_condition:
             self_cond = (random.random() < 0.5) if _self_cond is None else _self_cond
-        key = _dropout_key if _dropout_key is not None else self.draw_dropout_key(x_start.device)
-        lowres = self.draw_lowres(x_start, lowres_aug_t, lowres_noise)
-        anchor = self.model._anchor(x_start.device)
-        return _PLossFn.apply(anchor, self, x_start, t, noise, _normalize, offset, float(strength), self_cond, classes, key,
-                              lowres)
+        strength = float(self._strength(offset_noise_strength))
+        return self._loss(x_start, lambda save: hip_loss_forward(self, x_start, d.t, d.noise, _normalize, save, d.offset,
+                                                                 strength, self_cond, d.classes, d.dropout_key, d.lowres))
 
     def draw_lowres(self, x_start, lowres_aug_t=None, lowres_noise=None):
         """(s int64 [B], eps_aug like ``x_start``) of a training step on a low-resolution conditioned model - two draws from
-        torch's device generator unless given -, None on any other model (nothing is drawn)."""
+        torch's device generator unless given -, None on any other model (nothing is drawn; given operands are a ValueError)."""
         if not self.lowres_cond:
+            if lowres_aug_t is not None or lowres_noise is not None:
+                raise ValueError("lowres_aug_t / lowres_noise were passed to a model built without lowres_cond")
             return None
         B = x_start.shape[0]
         if lowres_aug_t is None:
@@ -1456,47 +1532,21 @@ class GaussianDiffusion(nn.Module):
         i = torch.randint(0, d.steps, (B,), device=device).long()
         return d.levels[i]
 
-    def drop_labels(self, classes):
-        """Classifier-free guidance training: every label becomes the null label with probability ``cond_drop_prob`` (one
-        ``torch.rand(B)`` on the labels' device; nothing is drawn when the probability is 0)."""
-        if self.cond_drop_prob <= 0.0:
-            return classes
-        drop = torch.rand(classes.shape[0], device=classes.device) < self.cond_drop_prob
-        return torch.where(drop, torch.full_like(classes, self.num_classes), classes)
-
     def forward(self, img, *args, classes=None, **kwargs):
-        """``classes`` (keyword, class-conditional model): the batch's labels.  The draws are then taken here, in the order
-        the graph-replayed step takes them: t, noise, offset noise, label drop.  Without labels: t, then what p_losses
-        draws - the stream of a model without classes."""
+        """``classes`` (keyword, class-conditional model): the batch's labels, which go through the label drop.  Every draw
+        is ``draw``'s, in the order the graph-replayed step takes them; ``p_losses`` gets every operand and draws nothing."""
         b, c, h, w = img.shape
         assert h == self.img_size and w == self.img_size, f"height and width of image must be {self.img_size}"
-        ts = self.active_t_sampler()
-        if self._distill is not None:                # a level of the student's grid, where randint(0, T) stands
-            t = self.draw_distill_t(b, img.device)
-            kwargs["_t_on_grid"] = True
-        elif ts is None:
-            t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()
-        else:                                        # (its uniforms stand where randint stands in the draw order)
-            t = ts.draw(b, img.device)
-        if classes is None:
-            return self.p_losses(img, t, *args, _normalize=self.auto_normalize, **kwargs)
-        classes = self.model.labels(classes, b, img.device)
         noise, strength = (list(args) + [None, None])[:2]
-        noise = kwargs.pop("noise", noise)
-        strength = kwargs.pop("offset_noise_strength", strength)
-        if noise is None:
-            noise = torch.randn_like(img)
-        if (self.offset_noise_strength if strength is None else strength) > 0.0 and kwargs.get("_offset_noise") is None:
-            kwargs["_offset_noise"] = torch.randn(img.shape[:2], device=img.device)
-        return self.p_losses(img, t, noise, strength, self.drop_labels(classes), _normalize=self.auto_normalize, **kwargs)
+        noise, strength = kwargs.pop("noise", noise), kwargs.pop("offset_noise_strength", strength)
+        d = self.draw(img, classes, noise=noise, offset=kwargs.pop("_offset_noise", None), offset_noise_strength=strength,
+                      dropout_key=kwargs.pop("_dropout_key", None), lowres_aug_t=kwargs.pop("lowres_aug_t", None),
+                      lowres_noise=kwargs.pop("lowres_noise", None))
+        s, eps = d.lowres or (None, None)
+        return self.p_losses(img, d.t, d.noise, strength, d.classes, _offset_noise=d.offset, _dropout_key=d.dropout_key,
+                             lowres_aug_t=s, lowres_noise=eps, _normalize=self.auto_normalize, _t_on_grid=True, **kwargs)
 
     # -- the reference's per-sample-timestep algebra (:673-705, 869-876): one lgm_extract_axpby launch each ---------
-    def normalize(self, img):
-        return img * 2 - 1 if self.auto_normalize else img
-
-    def unnormalize(self, t):
-        return (t + 1) * 0.5 if self.auto_normalize else t
-
     def _axpby(self, ta, tb, td, t, x, y, sb=1.0, clip=False):
         """out = clamp?((ta[t] * x + sb * tb[t] * y) / td[t]) on dense NCHW tensors, t per sample ([B] int64)."""
         x = x.detach().float().contiguous()
@@ -1835,9 +1885,7 @@ def hip_loss_forward(gd: "GaussianDiffusion", img, t, noise, normalize: bool, sa
     NCHW estimate.  ``classes``: device labels (``Unet.labels``) both passes of a class-conditional network read.
     ``dropout_key``: the step's key (``GaussianDiffusion.draw_dropout_key``) both passes read, None = neither drops.
     ``lowres``: (s, eps_aug) of a low-resolution conditioned network (``GaussianDiffusion.draw_lowres``)."""
-    q = hip_loss_qsample(gd, img, t, noise, normalize, offset, strength, lowres)
-    if gd._distill is not None:
-        hip_loss_distill(gd, q, classes)
+    q = gd.qsample(img, StepDraws(t, noise, offset, classes, dropout_key, lowres), normalize, strength)
     if gd.model.self_condition:
         if torch.is_tensor(self_cond):
             assert self_cond.shape == img.shape
@@ -1988,14 +2036,13 @@ def hip_loss_backward_begin(ctx: LossContext, gl):
     return st
 
 
-class _PLossFn(torch.autograd.Function):
-    """q_sample + UNet + the objective's target + weighted MSE, forward and hand-written backward."""
+class _LossFn(torch.autograd.Function):
+    """A diffusion's training loss - ``loss_forward(save) -> (loss[1], LossContext)``: ``hip_loss_forward``, or
+    ``edm.edm_loss_forward`` - with the hand-written backward."""
 
     @staticmethod
-    def forward(ctx, anchor, gd: GaussianDiffusion, img, t, noise, normalize, offset=None, strength=0.0, self_cond=False,
-                classes=None, dropout_key=None, lowres=None):
-        loss, ctx.stuff = hip_loss_forward(gd, img, t, noise, normalize, bool(ctx.needs_input_grad[0]), offset, strength,
-                                           self_cond, classes, dropout_key, lowres)
+    def forward(ctx, anchor, loss_forward):
+        loss, ctx.stuff = loss_forward(bool(ctx.needs_input_grad[0]))
         return loss.view(())
 
     @staticmethod
@@ -2003,13 +2050,82 @@ class _PLossFn(torch.autograd.Function):
         gl = gloss.detach().float().reshape(1).contiguous()
         ctx.stuff.gd.model.backward_run(hip_loss_backward_begin(ctx.stuff, gl))
         ctx.stuff = None
-        return None, None, None, None, None, None, None, None, None, None, None, None
+        return None, None
 
 
 # ----------------------------------------------------------------------------------------
 # LightningModule  (reference :949-1094)
 # ----------------------------------------------------------------------------------------
-class DDPM(LightningModule):
+class DiffusionModule(LightningModule):
+    """What ``DDPM`` and ``EDM`` (edm.py) share: the EMA around the diffusion (keys ``ema.online_model.*`` /
+    ``ema.ema_model.*``), the training and validation loss, logging, periodic sampling, the optimizer and the graph-replayed
+    step.  A subclass's ``__init__`` calls ``save_hyperparameters()`` (it reads the caller's arguments) and ``_wrap``."""
+
+    def _wrap(self, diffusion, img_channels, img_size, ema_decay, ema_update_every):
+        self.channels, self.img_size = img_channels, img_size
+        self.ema = EMA(diffusion, beta=ema_decay, update_every=ema_update_every)
+        self.ema.ema_model.model.dropout = 0.0       # the shadow is what samples and validates: it never drops
+        self.sample_every = 1000          # reference: every 1000 steps on rank 0 (:1025)
+        self.last_samples = None
+
+    def prepare_hip(self, device):
+        self.ema.online_model.model.prepare_hip(device)
+        self.ema.ema_model.model.prepare_hip(device)
+        if self.ema.online_model._distill is not None:
+            self.ema.online_model._distill.teacher.prepare_hip(device)
+
+    def ddp_buffers(self):
+        """Buffers training writes (re-broadcast from rank 0 before every forward, lgm_hip.lightning.BufferSync): none —
+        the 13 schedule tables are constants and the EMA shadow is updated identically on every rank."""
+        return []
+
+    def _shadow(self):
+        """the diffusion ``_log_sample`` samples from - the EMA weights -, in evaluation mode"""
+        self.ema.ema_model.eval()
+        return self.ema.ema_model
+
+    def _batch_loss(self, model, data, y):
+        return model(data, classes=y) if self.num_classes is not None else model(data)
+
+    def _common_step(self, batch, mode: str):
+        assert mode in ["train", "val", "test"], f"Invalid mode: {mode}"
+        data, y = batch
+        loss = self._batch_loss(self.ema.model if self.training else self.ema.ema_model, data, y)
+        self.log(f"{mode}_loss", loss, prog_bar=True, logger=True, sync_dist=multi_rank())
+        if self.sample_every and self.global_step % self.sample_every == 0 and _is_master():
+            self._log_sample()
+        return loss
+
+    def _log_images(self):
+        """``last_samples`` to the logger, where there is one that takes images"""
+        logger = getattr(self, "logger", None)
+        if logger is not None and hasattr(logger, "experiment"):
+            try:  # W&B is optional
+                import wandb  # type: ignore
+                logger.experiment.log({"Random Generation": [wandb.Image(self.last_samples)]}, step=self.global_step)
+            except Exception:  # noqa
+                pass
+
+    def training_step(self, batch):
+        return self._common_step(batch, "train")
+
+    def on_train_batch_end(self, outputs, batch, batch_idx):
+        self.ema.update()
+
+    def validation_step(self, batch):
+        return self._common_step(batch, "val")
+
+    def configure_optimizers(self):
+        return FusedAdam(self.ema.model.parameters(), lr=self.hparams.lr, betas=self.hparams.betas)
+
+    def make_fast_step(self, opt, world: int = 1, use_graph: bool = True, accumulate: int = 1):
+        """The step object ``MiniTrainer.fit`` drives instead of training_step/backward/step: overlapped
+        bucketed gradient exchange + HIP-graph replay (what bench.py times), eager fallback inside."""
+        from lgm_hip.graph import DDPMFastStep
+        return DDPMFastStep(self, opt, world, use_graph, accumulate=accumulate)
+
+
+class DDPM(DiffusionModule):
     def __init__(self, img_channels: int = 3, img_size: int = 64, dim: int = 64, diffusion_timesteps: int = 1000,
                  sampling_timesteps: Optional[int] = None, lr: float = 2e-5, betas: Tuple[float, float] = (0.9, 0.99),
                  ema_update_every: int = 10, ema_decay: float = 0.995, objective: str = "pred_v",
@@ -2062,24 +2178,13 @@ class DDPM(LightningModule):
                                             sampler=sampler, dpm_order=dpm_order, dpm_stochastic=dpm_stochastic,
                                             dynamic_thresholding=dynamic_thresholding,
                                             dynamic_thresholding_percentile=dynamic_thresholding_percentile, **cond)
-        self.channels = img_channels
-        self.img_size = img_size
         self.lowres_cond, self.lowres_factor = bool(lowres_cond), int(lowres_factor)
         self._cond_images = None          # a low-resolution conditioned model: the last batch seen, for _log_sample
-        self.ema = EMA(diffusion_model, beta=ema_decay, update_every=ema_update_every)
-        self.ema.ema_model.model.dropout = 0.0       # the shadow is what samples and validates: it never drops
-        self.sample_every = 1000          # reference: every 1000 steps on rank 0 (:1025)
+        self._wrap(diffusion_model, img_channels, img_size, ema_decay, ema_update_every)
         self.bpd_every = 0                # > 0: validation_step also logs val_bpd on every bpd_every-th batch (extension)
         self._val_batches = 0
-        self.last_samples = None
         if distill_steps is not None:
             self.start_distillation(distill_steps)
-
-    def prepare_hip(self, device):
-        self.ema.online_model.model.prepare_hip(device)
-        self.ema.ema_model.model.prepare_hip(device)
-        if self.ema.online_model._distill is not None:
-            self.ema.online_model._distill.teacher.prepare_hip(device)
 
     # -- progressive distillation (extension; GaussianDiffusion.distill_from) ---------------------------------------
     @torch.no_grad()
@@ -2118,112 +2223,85 @@ class DDPM(LightningModule):
             raise ValueError(f"a student of {n} step{'s' if n > 1 else ''} cannot be halved")
         return self.start_distillation(n // 2, None, source)
 
-    def ddp_buffers(self):
-        """Buffers training writes (re-broadcast from rank 0 before every forward, lgm_hip.lightning.BufferSync): none —
-        the 13 schedule tables are constants and the EMA shadow is updated identically on every rank."""
-        return []
-
     def _common_step(self, batch, mode: str):
-        assert mode in ["train", "val", "test"], f"Invalid mode: {mode}"
-        data, y = batch
         if self.lowres_cond:
-            self._cond_images = data      # what _log_sample super-resolves: the batch at hand, downsampled
-        model = self.ema.model if self.training else self.ema.ema_model
+            self._cond_images = batch[0]  # what _log_sample super-resolves: the batch at hand, downsampled
+        return super()._common_step(batch, mode)
+
+    def _batch_loss(self, model, data, y):
         # a distillation round validates the shadow against the round's teacher: the shadow itself carries none, it borrows the
         # online model's for the call
         borrow = model._distill is None and self.ema.online_model._distill is not None
         if borrow:
             model._distill = self.ema.online_model._distill
         try:
-            loss = model(data, classes=y) if self.num_classes is not None else model(data)
+            return super()._batch_loss(model, data, y)
         finally:
             if borrow:
                 model._distill = None
-        self.log(f"{mode}_loss", loss, prog_bar=True, logger=True, sync_dist=multi_rank())
-        if self.sample_every and self.global_step % self.sample_every == 0 and _is_master():
-            self._log_sample()
-        return loss
 
     @torch.no_grad()
     def _log_sample(self):
-        self.ema.ema_model.eval()
+        shadow = self._shadow()
         if self.lowres_cond:
             # a super-resolution stage has nothing to sample from without an image: it super-resolves the downsampled
             # batch of the step that logs (validation_step: the validation batch)
             if self._cond_images is None:
                 return
-            data = self._cond_images[:64].to(self.ema.ema_model.device).float()
+            data = self._cond_images[:64].to(shadow.device).float()
             low = torch.nn.functional.avg_pool2d(data, self.lowres_factor)
             kw = {}
             if self.num_classes is not None:
                 kw["classes"] = torch.arange(low.shape[0], device=low.device) % self.num_classes
-            self.last_samples = self.ema.ema_model.sample(lowres=low, **kw)
+            self.last_samples = shadow.sample(lowres=low, **kw)
         elif self.num_classes is not None:             # every class in turn, at the configured guidance scale
-            classes = torch.arange(64, device=self.ema.ema_model.device) % self.num_classes
-            self.last_samples = self.ema.ema_model.sample(batch_size=64, classes=classes)
+            classes = torch.arange(64, device=shadow.device) % self.num_classes
+            self.last_samples = shadow.sample(batch_size=64, classes=classes)
         else:
-            self.last_samples = self.ema.ema_model.sample(batch_size=64)
-        logger = getattr(self, "logger", None)
-        if logger is not None and hasattr(logger, "experiment"):
-            try:  # W&B is optional
-                import wandb  # type: ignore
-                logger.experiment.log({"Random Generation": [wandb.Image(self.last_samples)]}, step=self.global_step)
-            except Exception:  # noqa
-                pass
+            self.last_samples = shadow.sample(batch_size=64)
+        self._log_images()
 
     @torch.no_grad()
     def inpaint(self, known, mask, **kw):
         """``GaussianDiffusion.inpaint`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
-        self.ema.ema_model.eval()
-        return self.ema.ema_model.inpaint(known, mask, **kw)
+        return self._shadow().inpaint(known, mask, **kw)
 
     @torch.no_grad()
     def encode(self, img, **kw):
         """``GaussianDiffusion.encode`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
-        self.ema.ema_model.eval()
-        return self.ema.ema_model.encode(img, **kw)
+        return self._shadow().encode(img, **kw)
 
     @torch.no_grad()
     def decode(self, latent, **kw):
         """``GaussianDiffusion.decode`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
-        self.ema.ema_model.eval()
-        return self.ema.ema_model.decode(latent, **kw)
+        return self._shadow().decode(latent, **kw)
 
     @torch.no_grad()
     def reconstruct(self, img, **kw):
         """``GaussianDiffusion.reconstruct`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
-        self.ema.ema_model.eval()
-        return self.ema.ema_model.reconstruct(img, **kw)
+        return self._shadow().reconstruct(img, **kw)
 
     @torch.no_grad()
     def img2img(self, img, **kw):
         """``GaussianDiffusion.img2img`` of the diffusion ``_log_sample`` samples from (the EMA weights)"""
-        self.ema.ema_model.eval()
-        return self.ema.ema_model.img2img(img, **kw)
+        return self._shadow().img2img(img, **kw)
 
     @torch.no_grad()
     def upsample(self, img_low, **kw):
         """``GaussianDiffusion.sample(lowres=img_low, **kw)`` of the diffusion ``_log_sample`` samples from (the EMA weights):
         ``img_low`` [B, C, img_size / lowres_factor, img_size / lowres_factor] in the data range -> [B, C, img_size, img_size]"""
-        self.ema.ema_model.eval()
-        return self.ema.ema_model.sample(lowres=img_low, **kw)
+        return self._shadow().sample(lowres=img_low, **kw)
 
     @torch.no_grad()
     def bits_per_dim(self, img, classes=None, **kw):
         """``GaussianDiffusion.nll_bpd`` of the diffusion ``_log_sample`` samples from (the EMA weights): [B] bits per dimension"""
-        self.ema.ema_model.eval()
-        if self.ema.ema_model.learned_variance:      # the variance the model was trained to predict, unless the caller says
+        shadow = self._shadow()
+        if shadow.learned_variance:                  # the variance the model was trained to predict, unless the caller says
             kw.setdefault("variance", "learned")
-        return self.ema.ema_model.nll_bpd(img, classes=classes, **kw)
-
-    def training_step(self, batch):
-        return self._common_step(batch, "train")
-
-    def on_train_batch_end(self, outputs, batch, batch_idx):
-        self.ema.update()
+        return shadow.nll_bpd(img, classes=classes, **kw)
 
     def validation_step(self, batch):
-        loss = self._common_step(batch, "val")
+        loss = super().validation_step(batch)
         if self.bpd_every > 0:
             if self._val_batches % self.bpd_every == 0:
                 data, y = batch
@@ -2231,15 +2309,6 @@ class DDPM(LightningModule):
                 self.log("val_bpd", bpd.mean().float(), prog_bar=True, logger=True, sync_dist=multi_rank())
             self._val_batches += 1
         return loss
-
-    def configure_optimizers(self):
-        return FusedAdam(self.ema.model.parameters(), lr=self.hparams.lr, betas=self.hparams.betas)
-
-    def make_fast_step(self, opt, world: int = 1, use_graph: bool = True, accumulate: int = 1):
-        """The step object ``MiniTrainer.fit`` drives instead of training_step/backward/step: overlapped
-        bucketed gradient exchange + HIP-graph replay (what bench.py times), eager fallback inside."""
-        from lgm_hip.graph import DDPMFastStep
-        return DDPMFastStep(self, opt, world, use_graph, accumulate=accumulate)
 
 
 @torch.no_grad()

@@ -7,25 +7,22 @@ The network is a ``Unet(learned_sinusoidal_cond=True | random_fourier_features=T
 real-valued time.  Definitions, host planning and the row layout: ``lgm_hip/edm.py``; the elementwise launches around the
 network's forwards: ``csrc/edm.hip``.  Training runs on the machinery of the DDPM step (``lgm_hip.graph``) - the saved forward,
 the weighted MSE over a one-entry weight table, the four backward phases, Adam and the EMA are untouched; only the draws and
-the q_sample launch differ."""
+the q_sample launch differ (``ElucidatedDiffusion.draw`` / ``.qsample``: the protocol of ``ddpm.Diffusion``)."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
 
 import torch
-from torch import nn
 
 from lgm_hip import edm as plan
 from lgm_hip import ops
 from lgm_hip.captured import _CapturedStep, _cached_step
 from lgm_hip.flat import _r4
-from lgm_hip.lightning import LightningModule, multi_rank
-from lgm_hip.optim import EMA, FusedAdam
 
-from .ddpm import QSample, Unet, _is_master, hip_loss_backward_begin, hip_loss_network
+from .ddpm import Diffusion, DiffusionModule, QSample, StepDraws, Unet, hip_loss_network
 
 
-class ElucidatedDiffusion(nn.Module):
+class ElucidatedDiffusion(Diffusion):
     """``ElucidatedDiffusion(model, img_size=...)`` around a fourier ``Unet`` (anything else is a ValueError).
 
     Training: n_b ~ N(0, 1), sigma_b = exp(P_mean + P_std n_b), x = y + sigma_b eps, loss = mean_b mean_elem lambda(sigma_b)
@@ -38,11 +35,6 @@ class ElucidatedDiffusion(nn.Module):
     coefficients for both.
 
     ``distill_from``, ``inpaint``, ``vlb_terms`` and ``encode`` do not exist here: they are built on the discrete-time chain."""
-
-    # What the graph-replayed DDPM step reads of a diffusion besides the ``step_qsample`` hook (the protocol is stated in
-    # ``lgm_hip.graph.GraphedDDPMStep``): ``model``, ``auto_normalize``, ``loss_weight``, ``active_t_sampler()`` and these,
-    # which this diffusion does not have
-    offset_noise_strength, learned_variance, self_condition, lowres_cond, _distill = 0.0, False, False, False, None
 
     def __init__(self, model: Unet, *, img_size, num_sample_steps=32, sigma_min=0.002, sigma_max=80.0, sigma_data=0.5,
                  rho=7.0, P_mean=-1.2, P_std=1.2, S_churn=0.0, S_tmin=0.05, S_tmax=50.0, S_noise=1.003, auto_normalize=True,
@@ -73,22 +65,6 @@ class ElucidatedDiffusion(nn.Module):
         self.register_buffer("loss_weight", torch.ones(1), persistent=False)
         self._zero_index = {}
 
-    @property
-    def device(self):
-        return self.loss_weight.device
-
-    def active_t_sampler(self):
-        return None
-
-    def draw_lowres(self, x_start, lowres_aug_t=None, lowres_noise=None):
-        return None
-
-    def normalize(self, img):
-        return img * 2 - 1 if self.auto_normalize else img
-
-    def unnormalize(self, t):
-        return (t + 1) * 0.5 if self.auto_normalize else t
-
     # -- the definitions on the host (float64) --------------------------------------------------------------------------
     def coefficients(self, sigma: float):
         """(c_in, c_noise, c_skip, c_out) at ``sigma``"""
@@ -105,22 +81,6 @@ class ElucidatedDiffusion(nn.Module):
                              S_tmin=self.S_tmin, S_tmax=self.S_tmax, S_noise=self.S_noise)
 
     # -- training -------------------------------------------------------------------------------------------------------
-    def draw_dropout_key(self, device):
-        """``GaussianDiffusion.draw_dropout_key``: the step's 64-bit dropout key in ONE persistent int64 [1] device tensor"""
-        if self.model.dropout <= 0.0 or not self.model.training:
-            return None
-        key = self.__dict__.get("dropout_key")
-        if key is None or key.device != torch.device(device):
-            key = self.__dict__["dropout_key"] = torch.zeros(1, dtype=torch.int64, device=device)
-        return key.random_(-2 ** 63, None)
-
-    def drop_labels(self, classes):
-        """``GaussianDiffusion.drop_labels``: every label becomes the null label with probability ``cond_drop_prob``"""
-        if self.cond_drop_prob <= 0.0:
-            return classes
-        drop = torch.rand(classes.shape[0], device=classes.device) < self.cond_drop_prob
-        return torch.where(drop, torch.full_like(classes, self.num_classes), classes)
-
     def zero_index(self, B, device):
         """the all-zero int64 [B] index into the one-entry weight table, made once per (B, device)"""
         key = (B, torch.device(device))
@@ -129,48 +89,42 @@ class ElucidatedDiffusion(nn.Module):
             z = self._zero_index[key] = torch.zeros(B, dtype=torch.long, device=device)
         return z
 
+    def draw(self, img, labels=None, *, t=None, sigma=None, noise=None, classes=None, dropout_key=None) -> StepDraws:
+        """The random operands of a training step on the batch ``img``: what is given is used, the rest is drawn from torch's
+        device generator in THIS order - n ~ randn(B) (``t`` of the record; not with ``sigma`` given), noise ~ randn_like(img),
+        the label drop (``labels`` given and ``cond_drop_prob > 0``; ``classes``: the labels as the network gets them), the
+        dropout key (``dropout > 0`` in training mode)."""
+        B, dev = img.shape[0], img.device
+        if t is None and sigma is None:
+            t = torch.randn(B, device=dev)
+        if noise is None:
+            noise = torch.randn_like(img)
+        classes = self.step_labels(labels, classes, B, dev)
+        key = dropout_key if dropout_key is not None else self.draw_dropout_key(dev)
+        return StepDraws(t, noise, None, classes, key, None)
+
+    def qsample(self, img, d: StepDraws, normalize: bool, sigma=None) -> QSample:
+        """``edm_loss_qsample`` from the batch and its draws (``d.t``: the normal draw n), or at the given ``sigma``"""
+        return edm_loss_qsample(self, img, d.noise, normalize, d.t, sigma)
+
     def forward(self, img, classes=None):
-        """The training loss of a batch in the data range.  The draws, in the order the graph-replayed step takes them:
-        n ~ randn(B), noise ~ randn_like(img), the label drop (class-conditional model, labels given), the dropout key."""
+        """The training loss of a batch in the data range; ``classes``: its labels, which go through the label drop"""
         b, c, h, w = img.shape
         assert h == self.img_size and w == self.img_size, f"height and width of image must be {self.img_size}"
-        n = torch.randn(b, device=img.device)
-        noise = torch.randn_like(img)
-        labels = self.model.labels(classes, b, img.device)
-        if classes is not None:
-            labels = self.drop_labels(labels)
-        return self._loss(img, noise, n, None, labels, self.auto_normalize, self.draw_dropout_key(img.device))
-
-    def step_qsample(self, step):
-        """The hook of the graph-replayed step (``lgm_hip.graph.GraphedDDPMStep``): the draws of ``forward``, in their order,
-        left in the step object, and the ``lgm_edm_qsample`` launch over its static batch.  ``step.t`` holds the normal draw
-        n [B] that sets sigma where the timesteps stood."""
-        x = step.x
-        step.t = torch.randn(x.shape[0], device=x.device)
-        step.noise = torch.randn_like(x)
-        if step.y is not None:
-            step.classes = self.drop_labels(step.y)
-        step.dropout_key = self.draw_dropout_key(x.device)
-        return edm_loss_qsample(self, x, step.noise, self.auto_normalize, n=step.t)
+        return self._loss_of(img, self.draw(img, classes), None, self.auto_normalize)
 
     def p_losses(self, img, sigma=None, noise=None, classes=None, *, _normalize=False, _dropout_key=None):
         """``img`` already normalised unless ``_normalize``.  ``sigma`` (float32 [B]) / ``noise`` / ``classes`` (the labels as
-        the network gets them): explicit operands for parity tests; what is not given is drawn - sigma through its normal."""
-        b = img.shape[0]
-        n = None
-        if sigma is None:
-            n = torch.randn(b, device=img.device)
-        else:
-            sigma = torch.as_tensor(sigma, dtype=torch.float32, device=img.device).reshape(-1).expand(b).contiguous()
-        if noise is None:
-            noise = torch.randn_like(img)
-        labels = self.model.labels(classes, b, img.device)
-        key = _dropout_key if _dropout_key is not None else self.draw_dropout_key(img.device)
-        return self._loss(img, noise, n, sigma, labels, _normalize, key)
+        the network gets them): explicit operands for parity tests; what is not given is drawn (``draw``) - sigma through its
+        normal."""
+        if sigma is not None:
+            sigma = torch.as_tensor(sigma, dtype=torch.float32, device=img.device).reshape(-1).expand(img.shape[0]).contiguous()
+        d = self.draw(img, None, sigma=sigma, noise=noise, classes=classes, dropout_key=_dropout_key)
+        return self._loss_of(img, d, sigma, _normalize)
 
-    def _loss(self, img, noise, n, sigma, labels, normalize, key):
-        anchor = self.model._anchor(img.device)
-        return _EDMLossFn.apply(anchor, self, img, noise, n, sigma, bool(normalize), labels, key)
+    def _loss_of(self, img, d: StepDraws, sigma, normalize):
+        return self._loss(img, lambda save: edm_loss_forward(self, img, d.noise, d.t, sigma, bool(normalize), save, d.classes,
+                                                             d.dropout_key))
 
     # -- the denoiser ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -237,26 +191,9 @@ def edm_loss_qsample(ed: ElucidatedDiffusion, img, noise, normalize: bool, n=Non
 
 def edm_loss_forward(ed: ElucidatedDiffusion, img, noise, n, sigma, normalize: bool, save: bool, classes=None, dropout_key=None):
     """q_sample + UNet + MSE(F, F*) on the HIP engine -> (loss[1], ctx): ``hip_loss_network`` behind ``edm_loss_qsample``"""
-    q = edm_loss_qsample(ed, img, noise, normalize, n, sigma)
+    q = ed.qsample(img, StepDraws(n, noise, None, classes, dropout_key, None), normalize, sigma)
     return hip_loss_network(ed, q.xt, q.target, q.img, q.t, q.noise, q.offset, save, classes, normalize, dropout_key,
                             net_t=q.net_t)
-
-
-class _EDMLossFn(torch.autograd.Function):
-    """the elucidated loss, forward and hand-written backward (``ddpm._PLossFn`` with the other q_sample)"""
-
-    @staticmethod
-    def forward(ctx, anchor, ed, img, noise, n, sigma, normalize, classes=None, dropout_key=None):
-        loss, ctx.stuff = edm_loss_forward(ed, img, noise, n, sigma, normalize, bool(ctx.needs_input_grad[0]), classes,
-                                           dropout_key)
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gloss):
-        gl = gloss.detach().float().reshape(1).contiguous()
-        ctx.stuff.gd.model.backward_run(hip_loss_backward_begin(ctx.stuff, gl))
-        ctx.stuff = None
-        return None, None, None, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------
@@ -323,13 +260,10 @@ class _GraphedEdmStep(_CapturedStep):
 
 
 def _graphed_step(ed, net, shape, second, guided, clip, with_noise):
-    import os
     dev = ed.device
-    if os.environ.get("LGM_NO_SAMPLER_GRAPH", "0") == "1" or dev.type != "cuda":
-        return None
     key = ("edm", tuple(shape), bool(second), bool(guided), bool(clip), bool(with_noise))
     return _cached_step(net, key, lambda: _GraphedEdmStep(net, tuple(shape), second, guided, clip, with_noise, dev),
-                        "elucidated sampler")
+                        "elucidated sampler", dev)
 
 
 def _run_chain(ed: ElucidatedDiffusion, shape, rows, heun: bool, classes, scale, clip, return_all, init_noise, noises):
@@ -385,7 +319,7 @@ def _run_chain(ed: ElucidatedDiffusion, shape, rows, heun: bool, classes, scale,
 # ----------------------------------------------------------------------------------------
 # LightningModule
 # ----------------------------------------------------------------------------------------
-class EDM(LightningModule):
+class EDM(DiffusionModule):
     """``DDPM``'s training surface around ``ElucidatedDiffusion``: the same EMA (keys ``ema.online_model.*`` /
     ``ema.ema_model.*``), optimizer, logging and graph-replayed step (``make_fast_step``); ``sample`` samples under the EMA
     weights."""
@@ -407,29 +341,8 @@ class EDM(LightningModule):
         diffusion = ElucidatedDiffusion(model, img_size=img_size, num_sample_steps=num_sample_steps, sigma_min=sigma_min,
                                         sigma_max=sigma_max, sigma_data=sigma_data, rho=rho, P_mean=P_mean, P_std=P_std,
                                         S_churn=S_churn, S_tmin=S_tmin, S_tmax=S_tmax, S_noise=S_noise, sampler=sampler, **cond)
-        self.channels, self.img_size = img_channels, img_size
         self.lowres_cond = False
-        self.ema = EMA(diffusion, beta=ema_decay, update_every=ema_update_every)
-        self.ema.ema_model.model.dropout = 0.0       # the shadow is what samples and validates: it never drops
-        self.sample_every = 1000
-        self.last_samples = None
-
-    def prepare_hip(self, device):
-        self.ema.online_model.model.prepare_hip(device)
-        self.ema.ema_model.model.prepare_hip(device)
-
-    def ddp_buffers(self):
-        return []
-
-    def _common_step(self, batch, mode: str):
-        assert mode in ["train", "val", "test"], f"Invalid mode: {mode}"
-        data, y = batch
-        model = self.ema.model if self.training else self.ema.ema_model
-        loss = model(data, classes=y) if self.num_classes is not None else model(data)
-        self.log(f"{mode}_loss", loss, prog_bar=True, logger=True, sync_dist=multi_rank())
-        if self.sample_every and self.global_step % self.sample_every == 0 and _is_master():
-            self._log_sample()
-        return loss
+        self._wrap(diffusion, img_channels, img_size, ema_decay, ema_update_every)
 
     @torch.no_grad()
     def _log_sample(self):
@@ -437,34 +350,9 @@ class EDM(LightningModule):
         if self.num_classes is not None:             # every class in turn, at the configured guidance scale
             kw["classes"] = torch.arange(64, device=self.ema.ema_model.device) % self.num_classes
         self.last_samples = self.sample(batch_size=64, **kw)
-        logger = getattr(self, "logger", None)
-        if logger is not None and hasattr(logger, "experiment"):
-            try:  # W&B is optional
-                import wandb  # type: ignore
-                logger.experiment.log({"Random Generation": [wandb.Image(self.last_samples)]}, step=self.global_step)
-            except Exception:  # noqa
-                pass
+        self._log_images()
 
     @torch.no_grad()
     def sample(self, *a, **kw):
         """``ElucidatedDiffusion.sample`` under the EMA weights"""
-        self.ema.ema_model.eval()
-        return self.ema.ema_model.sample(*a, **kw)
-
-    def training_step(self, batch):
-        return self._common_step(batch, "train")
-
-    def on_train_batch_end(self, outputs, batch, batch_idx):
-        self.ema.update()
-
-    def validation_step(self, batch):
-        return self._common_step(batch, "val")
-
-    def configure_optimizers(self):
-        return FusedAdam(self.ema.model.parameters(), lr=self.hparams.lr, betas=self.hparams.betas)
-
-    def make_fast_step(self, opt, world: int = 1, use_graph: bool = True, accumulate: int = 1):
-        """``DDPM.make_fast_step``: the same step object, which draws n ~ randn(B) where randint stood and launches
-        ``lgm_edm_qsample`` (``lgm_hip.graph.GraphedDDPMStep``)"""
-        from lgm_hip.graph import DDPMFastStep
-        return DDPMFastStep(self, opt, world, use_graph, accumulate=accumulate)
+        return self._shadow().sample(*a, **kw)
