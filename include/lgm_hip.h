@@ -11,10 +11,10 @@
  *     lgm_last_error() returns a thread-local description;
  *   - re-entrant per THREAD (safe from the autograd thread next to the main thread): an entry point keeps no state
  *     between calls.  What the library does hold, exactly:
- *       . thread-local: the last error string, the last kernel name (lgm_last_error / lgm_last_kernel), and - only
- *         INSIDE lgm_conv_bwd_pair[_post] - the pair-recording context in which that call's own input-gradient and
- *         weight-gradient dispatchers record instead of launching; it is opened and closed by the same call on the same
- *         thread and never visible between calls;
+ *       . thread-local: the last error string, the last kernel name (lgm_last_error / lgm_last_kernel) and the
+ *         weight-gradient queue a caller switches on itself (lgm_wgrad_queue_enable, below).  What ONE call asks of its
+ *         launch sites - a post-op, the record in which lgm_conv_bwd_pair[_post]'s own input-gradient and weight-gradient
+ *         dispatchers record instead of launching - lives on that call's stack and travels as an argument;
  *       . process-wide, written once: hipFuncSetAttribute one-shot flags per kernel (idempotent: a race sets the same
  *         attribute twice) and `static const` switches read from the environment on first use;
  *       . process-wide, diagnostics only: the cycle-stamp buffers of lgm_wino_set_debug_buffer /

@@ -13,7 +13,6 @@
 // element s of that float4 from both operands (the k -> (half, step) assignment is arbitrary as
 // long as A and B agree; fp32 accumulation order inside a chunk is fixed => deterministic).
 #include <stdlib.h>
-#include <string.h>
 
 #include "lgm_common.h"
 
@@ -101,6 +100,23 @@ struct IgemmArgs {
   const float* bn_mean;
   const float* bn_rstd;
   float* bn_part;
+};
+
+// arguments of the generic weight-gradient kernels (below, "Weight gradient"); up here so that the pair record of the
+// backward pair can hold them by type
+struct WgradArgs {
+  const float* y;  // [P, Nw] rows
+  const float* x;  // X-side NHWC
+  float* out;      // gw (splits == 1) or workspace [splits][Nw*Q + Nw]
+  float* bias_out; // gbias (splits == 1), workspace slab tail (splits > 1), or null
+  float beta;      // only for splits == 1
+  long slab;       // floats per split slab in the workspace
+  long y_pitch, x_pitch;
+  int B, H, W, Cw, Ho, Wo, Nw, KH, KW, stride, pad;
+  int P, Q;        // pixels, T*Cw
+  int tiles_m, tiles_n, splits, chunk;  // chunk = pixels per split (multiple of WBK)
+  int swz;         // stand-alone launches: XCD-aware block order (wgrad_kernel)
+  int lWo, lHo, lW, lH;                 // FAST: log2 of the (power-of-two) map sizes
 };
 
 __device__ __forceinline__ float lgm_post_act(float v, int act, float slope) {
@@ -611,25 +627,50 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs p) {
   igemm_body<MODE, BM, BN, TM, TN, UNI>(p, p.swz ? lgm_xcd_swizzle((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x);
 }
 
-// ---- backward pair of the generic layers (1x1 convolutions, linears): lgm_conv_bwd_pair ---------------------------------
-// While the context is active, the two launch sites that can share a grid - the 64 x 64 uniform-tap input-gradient
-// GEMM and the generic weight-gradient kernel - RECORD their arguments instead of launching, and the reducers that would
-// follow them are stashed; lgm_conv_bwd_pair then issues ONE launch for both (or each alone when only one recorded) and
-// the stashed reducers after it.  Every other path launches as usual: whatever the dispatchers pick, nothing is lost.
-struct PairCtx {
-  bool active, rec_i, rec_w, red_i, red_w;
-  IgemmArgs ig;
-  size_t ig_smem;
-  unsigned ig_blocks, wg_blocks;
-  alignas(16) unsigned char wg[320];        // WgradArgs (defined below)
-  // stashed split-K reducer of the input gradient
-  const float* r_ws; long r_stride; int r_splits; const float* r_bias; const float* r_res; long r_res_pitch;
-  float* r_out; long r_out_pitch; long r_M; int r_N;
-  bool r_post; int r_act; float r_slope; const float* r_mask; long r_mask_pitch; float r_mask_slope;
-  // stashed slab reducer of the weight gradient (non-deferred form)
-  const float* w_ws; long w_slab; float* w_gw; long w_nw; float* w_gb; long w_nb; int w_splits; float w_beta;
+// ---- call context: what an entry point asks of the launch sites below it, handed down as an argument ------------------
+// The two reducers a backward pair may have to hold back until its one launch has been issued (see PairRecord).
+struct SplitkReduce {      // sum of an implicit GEMM's split-K planes + bias + residual, with the dispatch's post-op if any
+  bool present, post;
+  IgemmArgs a;             // the GEMM whose planes these are: ws, splits, M, N, bias, res, out and the post-op's fields
+  int launch(hipStream_t s) const;
 };
-static thread_local PairCtx t_pair = {};
+struct SlabReduce {        // sum of a weight gradient's slabs: gw = beta * gw + sum (lgm_wgrad_reduce_launch)
+  bool present;
+  const float* ws; long slab; float* gw; long n_w; float* gb; long n_b; int splits; float beta;
+  int launch(hipStream_t s) const { return lgm_wgrad_reduce_launch(ws, slab, gw, n_w, gb, n_b, splits, beta, s); }
+  // the same reduction as a row of the caller's table: many layers' slabs in ONE lgm_wgrad_reduce_batch launch
+  void describe(int64_t* desc) const {
+    union { float f; int64_t i; } bb;
+    bb.i = 0;
+    bb.f = beta;
+    desc[0] = (int64_t)(uintptr_t)ws; desc[1] = slab; desc[2] = (int64_t)(uintptr_t)gw; desc[3] = n_w;
+    desc[4] = (int64_t)(uintptr_t)gb; desc[5] = n_b; desc[6] = splits; desc[7] = bb.i;
+  }
+};
+
+// Backward pair of the generic layers (1x1 convolutions, linears): lgm_conv_bwd_pair.  Where a context carries this
+// record, the two launch sites that can share a grid - the 64 x 64 uniform-tap input-gradient GEMM and the generic
+// weight-gradient kernel - RECORD their prepared arguments here instead of launching, and the reducers that would follow
+// them are held back; lgm_conv_bwd_pair then issues ONE launch for both (or each alone when only one recorded) and the
+// reducers after it.  Every other path launches as usual: whatever the dispatchers pick, nothing is lost.
+struct PairRecord {
+  bool rec_i, rec_w;
+  IgemmArgs ig;            // swz unset: the pair kernel passes blockIdx.x straight through
+  size_t ig_smem;
+  WgradArgs wg;
+  unsigned ig_blocks, wg_blocks;
+  SplitkReduce red_i;
+  SlabReduce red_w;
+};
+
+// A record the entry point owns, on its stack, for ONE dispatch: nothing ambient, every launch site sees it in its
+// signature.  Plain entry points hand in an empty one.
+struct CallCtx {
+  const LgmPostOp* post;   // post-op asked of this dispatch or null (lgm_conv_*_post): the launch paths that can apply it in
+  bool post_done;          // their epilogue (implicit-GEMM kernels, their split-K reducer) do and say so here; for every
+                           // other path the entry point runs post_kernel over the finished output - same result either way
+  PairRecord* pair;        // null: launch everything at once
+};
 
 struct IgemmName { char c[64]; };
 constexpr IgemmName igemm_name(int mode, int bm, int bn, int tm, int tn, bool uni) {
@@ -651,34 +692,49 @@ constexpr IgemmName igemm_name(int mode, int bm, int bn, int tm, int tn, bool un
   return r;
 }
 
+// prepare: tile counts, the instantiation's shared-memory size (returned; opted into once) and its name noted
 template <int MODE, int BM, int BN, int TM, int TN, bool UNI>
-int launch_igemm_t(IgemmArgs& a, hipStream_t s) {
+size_t prepare_igemm_t(IgemmArgs& a) {
   a.tiles_m = lgm_cdiv(a.M, BM);
   a.tiles_n = lgm_cdiv(a.N, BN);
   constexpr int A_TILE = BM * LDA;
   constexpr int B_TILE = (MODE == MODE_XY) ? BN * LDA : BK * BN;
   const size_t smem = 2 * (A_TILE + B_TILE) * sizeof(float);
-  auto kern = igemm_kernel<MODE, BM, BN, TM, TN, UNI>;
   static bool attr_set = false;
   if (!attr_set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_kernel<MODE, BM, BN, TM, TN, UNI>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
   // the instantiation's name as the profiler prints it, built at compile time so that it can sit in the name registry
   static constexpr IgemmName name = igemm_name(MODE, BM, BN, TM, TN, UNI);
   static const char* const name_reg __attribute__((section("lgm_knames"), used)) = name.c;
   lgm_note_kernel(name_reg);
-  if (MODE == MODE_YX && BM == 64 && BN == 64 && UNI && t_pair.active && !t_pair.rec_i && !a.stats) {
-    t_pair.ig = a;                                   // launched by lgm_conv_bwd_pair, together with the weight gradient
-    t_pair.ig_smem = smem;
-    t_pair.ig_blocks = (unsigned)(a.tiles_m * a.tiles_n * a.splits * a.phases);
-    t_pair.rec_i = true;
+  return smem;
+}
+
+// launch prepared arguments as a kernel of their own
+template <int MODE, int BM, int BN, int TM, int TN, bool UNI>
+int run_igemm_t(IgemmArgs& a, size_t smem, hipStream_t s) {
+  a.swz = swz_on();
+  hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, TM, TN, UNI>), dim3((unsigned)(a.tiles_m * a.tiles_n * a.splits * a.phases)),
+                     dim3(256), smem, s, a);
+  LGM_LAUNCH_CHECK_AS("launch_igemm_t");
+  return LGM_OK;
+}
+
+template <int MODE, int BM, int BN, int TM, int TN, bool UNI>
+int launch_igemm_t(IgemmArgs& a, CallCtx& ctx, hipStream_t s) {
+  const size_t smem = prepare_igemm_t<MODE, BM, BN, TM, TN, UNI>(a);
+  PairRecord* const pr = ctx.pair;
+  if (MODE == MODE_YX && BM == 64 && BN == 64 && UNI && pr && !pr->rec_i && !a.stats) {
+    pr->ig = a;                                      // launched by lgm_conv_bwd_pair, together with the weight gradient
+    pr->ig_smem = smem;
+    pr->ig_blocks = (unsigned)(a.tiles_m * a.tiles_n * a.splits * a.phases);
+    pr->rec_i = true;
     return LGM_OK;
   }
-  a.swz = swz_on();
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.tiles_m * a.tiles_n * a.splits * a.phases)), dim3(256), smem, s, a);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
+  return run_igemm_t<MODE, BM, BN, TM, TN, UNI>(a, smem, s);
 }
 
 // UNI (uniform-tap chunks, buffer loads): gathered channel count a multiple of BK, strided input gradients only in
@@ -689,13 +745,13 @@ static bool igemm_uni_enabled() {
 }
 
 template <int MODE, int BM, int BN, int TM, int TN>
-int launch_igemm(IgemmArgs& a, hipStream_t s) {
+int launch_igemm(IgemmArgs& a, CallCtx& ctx, hipStream_t s) {
   const long gathered = MODE == MODE_XY ? (long)a.B * a.H * a.W : (long)a.B * a.Ho * a.Wo;
   const long span = (gathered + (long)(a.KH + 2) * (a.W > a.Wo ? a.W : a.Wo) + a.KW) * a.a_pitch * 4;
   const bool uni = igemm_uni_enabled() && a.Cg % BK == 0 && a.K % BK == 0 && span < (1L << 31) &&
                    (long)a.Nw * a.KH * a.KW * a.Cw * 4 < (1L << 31) &&
                    (MODE == MODE_XY || a.stride == 1 || a.phases > 1);
-  return uni ? launch_igemm_t<MODE, BM, BN, TM, TN, true>(a, s) : launch_igemm_t<MODE, BM, BN, TM, TN, false>(a, s);
+  return uni ? launch_igemm_t<MODE, BM, BN, TM, TN, true>(a, ctx, s) : launch_igemm_t<MODE, BM, BN, TM, TN, false>(a, ctx, s);
 }
 
 // Split-K plan of the generic path: a GEMM with few output tiles and a long reduction (the fused FiLM
@@ -719,16 +775,7 @@ int igemm_splits(long M, int N, int K, int* kchunk) {
   return lgm_cdiv(nk, per);
 }
 
-// ---- post-op plumbing (lgm_conv_xy_post / lgm_conv_yx_post) -----------------------------------------------------------
-// The entry points park the caller's post-op here for the duration of ONE call on this thread; the launch paths that
-// can apply it in their epilogue (implicit-GEMM kernels, their split-K reducer) take it and set `done`; for every
-// other path the entry point runs post_kernel over the finished output, so the result is the same either way.
-struct PostState {
-  const LgmPostOp* post;
-  bool done;
-};
-static thread_local PostState t_post = {nullptr, false};
-
+// ---- post-op kernels (lgm_conv_xy_post / lgm_conv_yx_post; see CallCtx) ----------------------------------------------
 __global__ __launch_bounds__(256) void splitk_reduce_post_kernel(const float* __restrict__ ws, long ws_stride, int splits,
                                                                  const float* __restrict__ bias,
                                                                  const float* __restrict__ res, long res_pitch,
@@ -766,23 +813,41 @@ __global__ __launch_bounds__(256) void post_kernel(float* __restrict__ out, long
   if (mask) v *= mask[m * mask_pitch + n] > 0.f ? 1.f : mask_slope;
   out[m * out_pitch + n] = v;
 }
+int post_launch(const LgmPostOp* post, float* out, long out_pitch, long M, int N, hipStream_t s) {
+  hipLaunchKernelGGL(post_kernel, dim3((unsigned)lgm_cdiv(M * N, 256)), dim3(256), 0, s, out, out_pitch, M, N, post->act,
+                     post->slope, post->mask, (long)post->mask_pitch, post->mask_slope);
+  LGM_LAUNCH_CHECK();
+  return LGM_OK;
+}
+
+int SplitkReduce::launch(hipStream_t s) const {
+  if (!post)
+    return lgm_splitk_reduce_launch(a.ws, (long)a.M * a.N, a.splits, a.bias, a.res, a.res_pitch, a.out, a.out_pitch, a.M,
+                                    a.N, s);
+  const long items = (long)a.M * (a.N / 4);
+  hipLaunchKernelGGL(splitk_reduce_post_kernel, dim3((unsigned)lgm_cdiv(items, 256)), dim3(256), 0, s, (const float*)a.ws,
+                     (long)a.M * a.N, a.splits, a.bias, a.res, a.res_pitch, a.out, a.out_pitch, (long)a.M, a.N, a.act,
+                     a.slope, a.mask, a.mask_pitch, a.mask_slope);
+  LGM_LAUNCH_CHECK_AS("splitk_reduce_post");
+  return LGM_OK;
+}
 
 // stats / stats_tiles (optional): request the BatchNorm statistics of the output from the epilogue; *stats_tiles = the
 // number of row tiles written (0: this launch could not produce them - split-K, ragged tiles, bias / residual)
 template <int MODE>
-int dispatch_igemm(IgemmArgs& a, void* workspace, int64_t workspace_bytes, bool wide, hipStream_t s,
+int dispatch_igemm(IgemmArgs& a, CallCtx& ctx, void* workspace, int64_t workspace_bytes, bool wide, hipStream_t s,
                    float* stats = nullptr, int* stats_tiles = nullptr) {
   a.wide = wide && a.N % 4 == 0 ? 1 : 0;
   a.phases = 1;
   a.KHs = a.KH;
   a.KWs = a.KW;
   a.act = 0; a.slope = 0.f; a.mask = nullptr; a.mask_pitch = 0; a.mask_slope = 0.f;
-  const LgmPostOp* post = t_post.post;
+  const LgmPostOp* post = ctx.post;
   a.bn_a = nullptr; a.bn_a_pitch = 0; a.bn_mean = a.bn_rstd = nullptr; a.bn_part = nullptr;
   if (post) {          // every launch of this dispatcher applies it: in the epilogue, or in the split-K reducer
     a.act = post->act; a.slope = post->slope; a.mask = post->mask; a.mask_pitch = post->mask_pitch;
     a.mask_slope = post->mask_slope;
-    t_post.done = true;
+    ctx.post_done = true;
   }
   // BatchNorm backward sums from the epilogue: full tiles of the kernel this dispatcher is about to pick, no split-K
   auto want_bn = [&](int bm, int bn) {
@@ -819,12 +884,12 @@ int dispatch_igemm(IgemmArgs& a, void* workspace, int64_t workspace_bytes, bool 
   if (a.N > 64 && t128 * lgm_cdiv(a.N, 128) >= 384) {
     want_stats(128, 128);
     want_bn(128, 128);
-    return launch_igemm<MODE, 128, 128, 2, 2>(a, s);
+    return launch_igemm<MODE, 128, 128, 2, 2>(a, ctx, s);
   }
   if (t128 * lgm_cdiv(a.N, 64) >= 384) {
     want_stats(128, 64);
     want_bn(128, 64);
-    return launch_igemm<MODE, 128, 64, 2, 1>(a, s);
+    return launch_igemm<MODE, 128, 64, 2, 1>(a, ctx, s);
   }
   int kchunk;
   const int splits = a.phases > 1 ? 1 : igemm_splits(a.M, a.N, a.K, &kchunk);
@@ -832,30 +897,18 @@ int dispatch_igemm(IgemmArgs& a, void* workspace, int64_t workspace_bytes, bool 
     a.splits = splits;
     a.kchunk = kchunk;
     a.ws = (float*)workspace;
-    if (int rc = launch_igemm<MODE, 64, 64, 1, 1>(a, s)) return rc;      // partial products: the kernel skips the epilogue ops
-    if (t_pair.active && t_pair.rec_i && t_pair.ig.ws == a.ws) {   // recorded, not launched: reduce after the pair
-      t_pair.red_i = true;
-      t_pair.r_ws = a.ws; t_pair.r_stride = (long)a.M * a.N; t_pair.r_splits = splits; t_pair.r_bias = a.bias;
-      t_pair.r_res = a.res; t_pair.r_res_pitch = a.res_pitch; t_pair.r_out = a.out; t_pair.r_out_pitch = a.out_pitch;
-      t_pair.r_M = a.M; t_pair.r_N = a.N;
-      t_pair.r_post = post != nullptr; t_pair.r_act = a.act; t_pair.r_slope = a.slope; t_pair.r_mask = a.mask;
-      t_pair.r_mask_pitch = a.mask_pitch; t_pair.r_mask_slope = a.mask_slope;
+    if (int rc = launch_igemm<MODE, 64, 64, 1, 1>(a, ctx, s)) return rc;   // partial products: the kernel skips the epilogue ops
+    const SplitkReduce red{true, post != nullptr, a};
+    PairRecord* const pr = ctx.pair;
+    if (pr && pr->rec_i && pr->ig.ws == a.ws) {      // recorded, not launched: reduce after the pair
+      pr->red_i = red;
       return LGM_OK;
     }
-    if (post) {
-      const long items = (long)a.M * (a.N / 4);
-      hipLaunchKernelGGL(splitk_reduce_post_kernel, dim3((unsigned)lgm_cdiv(items, 256)), dim3(256), 0, s,
-                         (const float*)a.ws, (long)a.M * a.N, splits, a.bias, a.res, a.res_pitch, a.out, a.out_pitch,
-                         (long)a.M, a.N, a.act, a.slope, a.mask, a.mask_pitch, a.mask_slope);
-      LGM_LAUNCH_CHECK();
-      return LGM_OK;
-    }
-    return lgm_splitk_reduce_launch(a.ws, (long)a.M * a.N, splits, a.bias, a.res, a.res_pitch, a.out, a.out_pitch, a.M,
-                                    a.N, s);
+    return red.launch(s);
   }
   want_stats(64, 64);
   want_bn(64, 64);
-  return launch_igemm<MODE, 64, 64, 1, 1>(a, s);
+  return launch_igemm<MODE, 64, 64, 1, 1>(a, ctx, s);
 }
 
 int check_geom(const LgmConvGeom* g) {
@@ -989,7 +1042,7 @@ unsigned narrow1x1_blocks(long P) {
 }
 }  // namespace
 
-static int conv_xy_impl(const LgmConvGeom* g, const float* x, int64_t x_pitch, const float* w,
+static int conv_xy_impl(CallCtx& ctx, const LgmConvGeom* g, const float* x, int64_t x_pitch, const float* w,
                         const float* bias, const float* res, int64_t res_pitch, float* y,
                         int64_t y_pitch, void* workspace, int64_t workspace_bytes, float* stats, int* stats_tiles,
                         void* stream) {
@@ -1000,7 +1053,7 @@ static int conv_xy_impl(const LgmConvGeom* g, const float* x, int64_t x_pitch, c
   LGM_REQUIRE(x_pitch % 4 == 0 && x_pitch >= g->Cw && lgm_aligned16(x) && lgm_aligned16(w),
               "conv_xy: x/w must be 16B aligned with pitch %% 4 == 0");
   LGM_REQUIRE(y_pitch >= g->Nw && (!res || res_pitch >= g->Nw), "conv_xy: output pitch < Nw");
-  if (use_3x3() && narrow1x1_geom(g) && !res && !stats && !t_post.post && wide_ok(y, y_pitch, nullptr, 0, bias)) {
+  if (use_3x3() && narrow1x1_geom(g) && !res && !stats && !ctx.post && wide_ok(y, y_pitch, nullptr, 0, bias)) {
     const long P = (long)g->B * g->H * g->W;
     lgm_note_kernel(LGM_KNAME("narrow1x1_fwd_kernel"));
     if (g->Nw == 8)
@@ -1013,7 +1066,7 @@ static int conv_xy_impl(const LgmConvGeom* g, const float* x, int64_t x_pitch, c
     return LGM_OK;
   }
   static const bool post_3x3 = lgm_env_set("LGM_POST_VIA_3X3");   // A/B switch: direct 3x3 kernel + elementwise post-op
-  if (use_3x3() && (!t_post.post || post_3x3) && wide_ok(y, y_pitch, res, res_pitch, bias) && lgm_conv3x3_supported(g, g->Cw, g->Nw) &&
+  if (use_3x3() && (!ctx.post || post_3x3) && wide_ok(y, y_pitch, res, res_pitch, bias) && lgm_conv3x3_supported(g, g->Cw, g->Nw) &&
       ((long)g->B * g->H * g->W + g->W + 1) * x_pitch < (1L << 29))   // buffer offsets (bytes) below 2^31
     return lgm_conv3x3_launch(0, g, x, x_pitch, w, bias, res, res_pitch, y, y_pitch, workspace, workspace_bytes,
                               (hipStream_t)stream);
@@ -1031,14 +1084,15 @@ static int conv_xy_impl(const LgmConvGeom* g, const float* x, int64_t x_pitch, c
   a.B = g->B; a.H = g->H; a.W = g->W; a.Cw = g->Cw; a.Ho = g->Ho; a.Wo = g->Wo; a.Nw = g->Nw;
   a.KH = g->KH; a.KW = g->KW; a.stride = g->stride; a.pad = g->pad;
   a.M = g->B * g->Ho * g->Wo; a.N = g->Nw; a.K = g->KH * g->KW * g->Cw; a.Cg = g->Cw;
-  return dispatch_igemm<MODE_XY>(a, workspace, workspace_bytes, wide_ok(y, y_pitch, res, res_pitch, bias),
+  return dispatch_igemm<MODE_XY>(a, ctx, workspace, workspace_bytes, wide_ok(y, y_pitch, res, res_pitch, bias),
                                  (hipStream_t)stream, stats, stats_tiles);
 }
 
 extern "C" int lgm_conv_xy(const LgmConvGeom* g, const float* x, int64_t x_pitch, const float* w,
                            const float* bias, const float* res, int64_t res_pitch, float* y,
                            int64_t y_pitch, void* workspace, int64_t workspace_bytes, void* stream) {
-  return conv_xy_impl(g, x, x_pitch, w, bias, res, res_pitch, y, y_pitch, workspace, workspace_bytes, nullptr, nullptr,
+  CallCtx ctx{};
+  return conv_xy_impl(ctx, g, x, x_pitch, w, bias, res, res_pitch, y, y_pitch, workspace, workspace_bytes, nullptr, nullptr,
                       stream);
 }
 
@@ -1048,22 +1102,15 @@ static int post_check(const LgmPostOp* post, const char* who) {
   return LGM_OK;
 }
 
-// runs `call` with the post-op parked for the launch paths; applies it with one elementwise launch when the path
-// taken had no epilogue hook
+// runs `call` with a context that carries the post-op to the launch paths; applies it with one elementwise launch when
+// the path taken had no epilogue hook
 template <typename F>
 static int with_post(const LgmPostOp* post, float* out, int64_t out_pitch, long M, int N, void* stream, F call) {
-  if (post && post->bn_tiles) *post->bn_tiles = 0;      // set by the dispatcher when the epilogue takes the sums
-  t_post.post = post;
-  t_post.done = false;
-  const int rc = call();
-  const bool done = t_post.done;
-  t_post.post = nullptr;
-  t_post.done = false;
-  if (rc != LGM_OK || done || (post->act == 0 && !post->mask)) return rc;
-  hipLaunchKernelGGL(post_kernel, dim3((unsigned)lgm_cdiv(M * N, 256)), dim3(256), 0, (hipStream_t)stream, out,
-                     (long)out_pitch, M, N, post->act, post->slope, post->mask, (long)post->mask_pitch, post->mask_slope);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
+  if (post->bn_tiles) *post->bn_tiles = 0;      // set by the dispatcher when the epilogue takes the sums
+  CallCtx ctx{post, false, nullptr};
+  const int rc = call(ctx);
+  if (rc != LGM_OK || ctx.post_done || (post->act == 0 && !post->mask)) return rc;
+  return post_launch(post, out, (long)out_pitch, M, N, (hipStream_t)stream);
 }
 
 extern "C" int lgm_conv_xy_post(const LgmConvGeom* g, const float* x, int64_t x_pitch, const float* w,
@@ -1071,8 +1118,8 @@ extern "C" int lgm_conv_xy_post(const LgmConvGeom* g, const float* x, int64_t x_
                                 void* workspace, int64_t workspace_bytes, const LgmPostOp* post, void* stream) {
   if (int rc = post_check(post, "conv_xy_post")) return rc;
   if (int rc = check_geom(g)) return rc;
-  return with_post(post, y, y_pitch, (long)g->B * g->Ho * g->Wo, g->Nw, stream, [&] {
-    return conv_xy_impl(g, x, x_pitch, w, bias, res, res_pitch, y, y_pitch, workspace, workspace_bytes, nullptr, nullptr,
+  return with_post(post, y, y_pitch, (long)g->B * g->Ho * g->Wo, g->Nw, stream, [&](CallCtx& ctx) {
+    return conv_xy_impl(ctx, g, x, x_pitch, w, bias, res, res_pitch, y, y_pitch, workspace, workspace_bytes, nullptr, nullptr,
                         stream);
   });
 }
@@ -1084,8 +1131,9 @@ extern "C" int lgm_conv_xy_stats(const LgmConvGeom* g, const float* x, int64_t x
                                  int64_t y_pitch, void* workspace, int64_t workspace_bytes, float* stats,
                                  int* stats_tiles, void* stream) {
   LGM_REQUIRE(stats && stats_tiles, "conv_xy_stats: null statistics buffer");
-  return conv_xy_impl(g, x, x_pitch, w, nullptr, nullptr, 0, y, y_pitch, workspace, workspace_bytes, stats, stats_tiles,
-                      stream);
+  CallCtx ctx{};
+  return conv_xy_impl(ctx, g, x, x_pitch, w, nullptr, nullptr, 0, y, y_pitch, workspace, workspace_bytes, stats,
+                      stats_tiles, stream);
 }
 
 extern "C" int64_t lgm_conv_stats_floats(const LgmConvGeom* g, int yx) {
@@ -1342,7 +1390,7 @@ __global__ __launch_bounds__(256) void smalln_yx_lp_kernel(const SmallNArgs p, i
 }
 }  // namespace
 
-static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, const float* w,
+static int conv_yx_impl(CallCtx& ctx, const LgmConvGeom* g, const float* y, int64_t y_pitch, const float* w,
                         const float* w_t, const float* bias, const float* res, int64_t res_pitch, float* x,
                         int64_t x_pitch, void* workspace, int64_t workspace_bytes, float* stats, int* stats_tiles,
                         void* stream) {
@@ -1353,7 +1401,7 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
   LGM_REQUIRE(y_pitch % 4 == 0 && y_pitch >= g->Nw && lgm_aligned16(y) && lgm_aligned16(w),
               "conv_yx: y/w must be 16B aligned with pitch %% 4 == 0");
   LGM_REQUIRE(x_pitch >= g->Cw && (!res || res_pitch >= g->Cw), "conv_yx: output pitch < Cw");
-  if (use_3x3() && narrow1x1_geom(g) && !res && !bias && !stats && !t_post.post && wide_ok(x, x_pitch, nullptr, 0, nullptr)) {
+  if (use_3x3() && narrow1x1_geom(g) && !res && !bias && !stats && !ctx.post && wide_ok(x, x_pitch, nullptr, 0, nullptr)) {
     const long P = (long)g->B * g->H * g->W;
     lgm_note_kernel(LGM_KNAME("narrow1x1_dgrad_kernel"));
     if (g->Nw == 8)
@@ -1366,7 +1414,7 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
     return LGM_OK;
   }
   static const bool post_3x3 = lgm_env_set("LGM_POST_VIA_3X3");   // A/B switch (see conv_xy_impl)
-  if (use_3x3() && (!t_post.post || post_3x3) && wide_ok(x, x_pitch, res, res_pitch, bias) && lgm_conv3x3_supported(g, g->Nw, g->Cw) &&
+  if (use_3x3() && (!ctx.post || post_3x3) && wide_ok(x, x_pitch, res, res_pitch, bias) && lgm_conv3x3_supported(g, g->Nw, g->Cw) &&
       ((long)g->B * g->H * g->W + g->W + 1) * y_pitch < (1L << 29))
     return lgm_conv3x3_launch(w_t ? 2 : 1, g, y, y_pitch, w_t ? w_t : w, bias, res, res_pitch, x, x_pitch, workspace,
                               workspace_bytes, (hipStream_t)stream);
@@ -1420,14 +1468,15 @@ static int conv_yx_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, c
   a.B = g->B; a.H = g->H; a.W = g->W; a.Cw = g->Cw; a.Ho = g->Ho; a.Wo = g->Wo; a.Nw = g->Nw;
   a.KH = g->KH; a.KW = g->KW; a.stride = g->stride; a.pad = g->pad;
   a.M = g->B * g->H * g->W; a.N = g->Cw; a.K = g->KH * g->KW * g->Nw; a.Cg = g->Nw;
-  return dispatch_igemm<MODE_YX>(a, workspace, workspace_bytes, wide_ok(x, x_pitch, res, res_pitch, bias),
+  return dispatch_igemm<MODE_YX>(a, ctx, workspace, workspace_bytes, wide_ok(x, x_pitch, res, res_pitch, bias),
                                  (hipStream_t)stream, stats, stats_tiles);
 }
 
 extern "C" int lgm_conv_yx(const LgmConvGeom* g, const float* y, int64_t y_pitch, const float* w,
                            const float* w_t, const float* bias, const float* res, int64_t res_pitch, float* x,
                            int64_t x_pitch, void* workspace, int64_t workspace_bytes, void* stream) {
-  return conv_yx_impl(g, y, y_pitch, w, w_t, bias, res, res_pitch, x, x_pitch, workspace, workspace_bytes, nullptr,
+  CallCtx ctx{};
+  return conv_yx_impl(ctx, g, y, y_pitch, w, w_t, bias, res, res_pitch, x, x_pitch, workspace, workspace_bytes, nullptr,
                       nullptr, stream);
 }
 
@@ -1437,8 +1486,8 @@ extern "C" int lgm_conv_yx_post(const LgmConvGeom* g, const float* y, int64_t y_
                                 void* stream) {
   if (int rc = post_check(post, "conv_yx_post")) return rc;
   if (int rc = check_geom(g)) return rc;
-  return with_post(post, x, x_pitch, (long)g->B * g->H * g->W, g->Cw, stream, [&] {
-    return conv_yx_impl(g, y, y_pitch, w, w_t, bias, res, res_pitch, x, x_pitch, workspace, workspace_bytes, nullptr,
+  return with_post(post, x, x_pitch, (long)g->B * g->H * g->W, g->Cw, stream, [&](CallCtx& ctx) {
+    return conv_yx_impl(ctx, g, y, y_pitch, w, w_t, bias, res, res_pitch, x, x_pitch, workspace, workspace_bytes, nullptr,
                         nullptr, stream);
   });
 }
@@ -1448,7 +1497,8 @@ extern "C" int lgm_conv_yx_stats(const LgmConvGeom* g, const float* y, int64_t y
                                  const float* w_t, float* x, int64_t x_pitch, void* workspace, int64_t workspace_bytes,
                                  float* stats, int* stats_tiles, void* stream) {
   LGM_REQUIRE(stats && stats_tiles, "conv_yx_stats: null statistics buffer");
-  return conv_yx_impl(g, y, y_pitch, w, w_t, nullptr, nullptr, 0, x, x_pitch, workspace, workspace_bytes, stats,
+  CallCtx ctx{};
+  return conv_yx_impl(ctx, g, y, y_pitch, w, w_t, nullptr, nullptr, 0, x, x_pitch, workspace, workspace_bytes, stats,
                       stats_tiles, stream);
 }
 
@@ -1460,21 +1510,6 @@ extern "C" int lgm_conv_yx_stats(const LgmConvGeom* g, const float* y, int64_t y
 namespace {
 
 constexpr int WBK = 64;  // pixels per chunk (32 MFMAs per wave between barriers)
-
-struct WgradArgs {
-  const float* y;  // [P, Nw] rows
-  const float* x;  // X-side NHWC
-  float* out;      // gw (splits == 1) or workspace [splits][Nw*Q + Nw]
-  float* bias_out; // gbias (splits == 1), workspace slab tail (splits > 1), or null
-  float beta;      // only for splits == 1
-  long slab;       // floats per split slab in the workspace
-  long y_pitch, x_pitch;
-  int B, H, W, Cw, Ho, Wo, Nw, KH, KW, stride, pad;
-  int P, Q;        // pixels, T*Cw
-  int tiles_m, tiles_n, splits, chunk;  // chunk = pixels per split (multiple of WBK)
-  int swz;         // stand-alone launches: XCD-aware block order (wgrad_kernel)
-  int lWo, lHo, lW, lH;                 // FAST: log2 of the (power-of-two) map sizes
-};
 
 // FAST: Ho, Wo, H, W powers of two, B*H*W < 2^24, byte offsets < 2^31: the pixel decode of the gather is shifts
 // and masks and every load is a raw buffer load (zero fill = an offset at the descriptor's range) - ~12 VALU
@@ -1735,6 +1770,9 @@ __global__ __launch_bounds__(256) void wgrad_group_kernel(const WgradArgs a, con
 // Per-thread queue of such launches.  Off unless the caller switches it on around a call (lgm_wgrad_queue_enable): only a
 // caller that will call lgm_wgrad_queue_flush before anything reads the gradients - and keeps the operands alive until
 // then - may let a launch wait (lgm_hip.nn.GradCtx does, for its deferred passes).
+// The one thread_local of this file: its entries outlive the call that pushed them (up to four layers' calls share a
+// launch) and Python switches it on and off between calls, so no entry point's stack can own it - unlike what ONE call
+// asks of its launch sites, which travels as an argument (CallCtx).
 struct WgradQueue {
   WgradArgs a[4];
   unsigned nb[4];
@@ -1864,8 +1902,8 @@ extern "C" int64_t lgm_conv_wgrad_workspace(const LgmConvGeom* g) {
   return (int64_t)splits * slab * (int64_t)sizeof(float);
 }
 
-static int conv_wgrad_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch, const float* x, int64_t x_pitch,
-                           float* gw, float* gbias, float beta, void* workspace, int64_t workspace_bytes,
+static int conv_wgrad_impl(CallCtx& ctx, const LgmConvGeom* g, const float* y, int64_t y_pitch, const float* x,
+                           int64_t x_pitch, float* gw, float* gbias, float beta, void* workspace, int64_t workspace_bytes,
                            int64_t* desc, void* stream) {
   if (int rc = check_geom(g)) return rc;
   LGM_REQUIRE(y && x && gw, "conv_wgrad: null pointer");
@@ -1912,6 +1950,7 @@ static int conv_wgrad_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch
   a.tiles_m = lgm_cdiv(a.Nw, 64);
   a.tiles_n = lgm_cdiv(a.Q, 64);
   hipStream_t s = (hipStream_t)stream;
+  PairRecord* const pr = ctx.pair;
   if (fastw4) {
     if (int rc = lgm_wino4_wgrad_launch(g, y, y_pitch, x, x_pitch, a.out, gbias ? 1 : 0, a.slab, a.splits, cpsw, totalw, s))
       return rc;
@@ -1939,12 +1978,11 @@ static int conv_wgrad_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch
     const bool big = fast && want_big && a.Nw % 128 == 0 && (long)(a.Nw / 128) * a.tiles_n * a.splits >= 512;
     lgm_note_kernel(big ? LGM_KNAME("wgrad_kernel<128, 64, 2, 1, true>")
                         : fast ? LGM_KNAME("wgrad_kernel<64, 64, 1, 1, true>") : LGM_KNAME("wgrad_kernel<64, 64, 1, 1, false>"));
-    static_assert(sizeof(WgradArgs) <= sizeof(t_pair.wg), "PairCtx::wg too small");
     a.swz = swz_on();
-    if (!big && fast && t_pair.active && !t_pair.rec_w) {       // launched by lgm_conv_bwd_pair, with the input gradient
-      memcpy(t_pair.wg, &a, sizeof(WgradArgs));
-      t_pair.wg_blocks = (unsigned)(a.tiles_m * a.tiles_n * a.splits);
-      t_pair.rec_w = true;
+    if (!big && fast && pr && !pr->rec_w) {          // launched by lgm_conv_bwd_pair, with the input gradient
+      pr->wg = a;
+      pr->wg_blocks = (unsigned)(a.tiles_m * a.tiles_n * a.splits);
+      pr->rec_w = true;
     } else if (big) {
       a.tiles_m = a.Nw / 128;
       hipLaunchKernelGGL((wgrad_kernel<128, 64, 2, 1, true>), dim3((unsigned)(a.tiles_m * a.tiles_n * a.splits)), dim3(256), 0, s, a);
@@ -1957,30 +1995,22 @@ static int conv_wgrad_impl(const LgmConvGeom* g, const float* y, int64_t y_pitch
     LGM_LAUNCH_CHECK();
   }
   const long n_b = gbias ? a.Nw : 0;
+  const SlabReduce red{true, (const float*)workspace, a.slab, gw, n_w, gbias, n_b, a.splits, beta};
   if (desc) {            // deferred: the caller reduces many layers' slabs with ONE lgm_wgrad_reduce_batch launch
-    union { float f; int64_t i; } bb;
-    bb.i = 0;
-    bb.f = beta;
-    desc[0] = (int64_t)(uintptr_t)workspace; desc[1] = a.slab; desc[2] = (int64_t)(uintptr_t)gw; desc[3] = n_w;
-    desc[4] = (int64_t)(uintptr_t)gbias; desc[5] = n_b; desc[6] = a.splits; desc[7] = bb.i;
+    red.describe(desc);
     return LGM_OK;
   }
   if (a.splits > 1) {
-    if (t_pair.active && t_pair.rec_w) {          // the kernel has not run yet: reduce after the pair launch
-      t_pair.red_w = true;
-      t_pair.w_ws = (const float*)workspace; t_pair.w_slab = a.slab; t_pair.w_gw = gw; t_pair.w_nw = n_w;
-      t_pair.w_gb = gbias; t_pair.w_nb = n_b; t_pair.w_splits = a.splits; t_pair.w_beta = beta;
+    if (pr && pr->rec_w) {                           // the kernel has not run yet: reduce after the pair launch
+      pr->red_w = red;
       return LGM_OK;
     }
-    const long groups = (n_w + n_b + 3) / 4;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)lgm_cdiv(groups, 64)), dim3(256), 0, s,
-                       (const float*)workspace, a.slab, gw, n_w, gbias, n_b, a.splits, beta);
-    LGM_LAUNCH_CHECK();
+    return red.launch(s);
   }
   return LGM_OK;
 }
 
-// the single-layer slab reducer for other translation units (linattn_fused.hip)
+// the single-layer slab reducer: every launch of wgrad_reduce_kernel, here and in linattn_fused.hip
 int lgm_wgrad_reduce_launch(const float* ws, long slab, float* gw, long n_w, float* gb, long n_b, int splits, float beta,
                             hipStream_t s) {
   const long groups = (n_w + n_b + 3) / 4;
@@ -2039,23 +2069,16 @@ extern "C" int lgm_conv3x3_wino_bwd(const LgmConvGeom* g, const float* gy, int64
                                     dgrad_ws_bytes, partial, (float*)wgrad_ws, gbias ? 1 : 0, slab, s))
     return rc;
   const long n_b = gbias ? g->Nw : 0;
+  const SlabReduce red{true, (const float*)wgrad_ws, slab, gw, n_w, gbias, n_b, splits, beta};
   if (desc) {
-    union { float f; int64_t i; } bb;
-    bb.i = 0;
-    bb.f = beta;
-    desc[0] = (int64_t)(uintptr_t)wgrad_ws; desc[1] = slab; desc[2] = (int64_t)(uintptr_t)gw; desc[3] = n_w;
-    desc[4] = (int64_t)(uintptr_t)gbias; desc[5] = n_b; desc[6] = splits; desc[7] = bb.i;
+    red.describe(desc);
     return LGM_OK;
   }
-  const long groups = (n_w + n_b + 3) / 4;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)lgm_cdiv(groups, 64)), dim3(256), 0, s, (const float*)wgrad_ws,
-                     slab, gw, n_w, gbias, n_b, splits, beta);
-  LGM_LAUNCH_CHECK();
-  return LGM_OK;
+  return red.launch(s);
 }
 
 // Backward of a generic layer (any geometry): weight / bias gradient AND input gradient.  When the dispatchers pick
-// the two kernels that can share a grid (see PairCtx) both run in ONE launch; otherwise this is exactly
+// the two kernels that can share a grid (see PairRecord) both run in ONE launch; otherwise this is exactly
 // lgm_conv_wgrad[_deferred] followed by lgm_conv_yx.  dgrad_ws and wgrad_ws must not overlap (the kernels run side by side).
 static int conv_bwd_pair_impl(const LgmConvGeom* g, const float* gy, int64_t gy_pitch, const float* x,
                               int64_t x_pitch, const float* w, const float* w_t, const float* res, int64_t res_pitch,
@@ -2064,26 +2087,15 @@ static int conv_bwd_pair_impl(const LgmConvGeom* g, const float* gy, int64_t gy_
                               const LgmPostOp* post, void* stream) {
   static const bool no_pair = lgm_env_set("LGM_NO_PAIR");   // A/B switch: separate launches
   hipStream_t s = (hipStream_t)stream;
-  t_pair = PairCtx{};
-  t_pair.active = !no_pair;
-  int rc = conv_wgrad_impl(g, gy, gy_pitch, x, x_pitch, gw, gbias, beta, wgrad_ws, wgrad_ws_bytes, desc, stream);
-  bool post_done = true;
-  if (rc == LGM_OK) {
-    // the post-op belongs to the input gradient only: parked for the duration of ITS dispatch (see with_post)
-    if (post && post->bn_tiles) *post->bn_tiles = 0;
-    t_post.post = post;
-    t_post.done = false;
-    rc = conv_yx_impl(g, gy, gy_pitch, w, w_t, nullptr, res, res_pitch, gx, gx_pitch, dgrad_ws, dgrad_ws_bytes, nullptr,
-                      nullptr, stream);
-    post_done = post == nullptr || t_post.done;
-    t_post.post = nullptr;
-    t_post.done = false;
-  }
-  const PairCtx c = t_pair;
-  t_pair = PairCtx{};
-  if (rc != LGM_OK) return rc;
-  WgradArgs wa;
-  memcpy(&wa, c.wg, sizeof(WgradArgs));
+  PairRecord c{};
+  CallCtx wctx{nullptr, false, no_pair ? nullptr : &c};
+  if (int rc = conv_wgrad_impl(wctx, g, gy, gy_pitch, x, x_pitch, gw, gbias, beta, wgrad_ws, wgrad_ws_bytes, desc, stream))
+    return rc;
+  if (post && post->bn_tiles) *post->bn_tiles = 0;
+  CallCtx ictx{post, false, wctx.pair};     // the post-op belongs to the input gradient only
+  if (int rc = conv_yx_impl(ictx, g, gy, gy_pitch, w, w_t, nullptr, res, res_pitch, gx, gx_pitch, dgrad_ws, dgrad_ws_bytes,
+                            nullptr, nullptr, stream))
+    return rc;
   // one launch only while both grids fit the chip together (67 KB of LDS per workgroup: two per CU): large layers keep
   // their own launches, where the input-gradient kernel alone gets four workgroups per CU (B = 128: 1 % slower paired)
   static const unsigned pair_max = (unsigned)lgm_env_int("LGM_PAIR_MAX", 512);
@@ -2098,46 +2110,27 @@ static int conv_bwd_pair_impl(const LgmConvGeom* g, const float* gy, int64_t gy_
       attr = pair_smem;
     }
     lgm_note_kernel(LGM_KNAME("gemm_bwd_pair_kernel"));
-    hipLaunchKernelGGL(gemm_bwd_pair_kernel, dim3(c.ig_blocks + c.wg_blocks), dim3(256), pair_smem, s, c.ig, wa,
+    hipLaunchKernelGGL(gemm_bwd_pair_kernel, dim3(c.ig_blocks + c.wg_blocks), dim3(256), pair_smem, s, c.ig, c.wg,
                        (int)c.ig_blocks);
   } else {
     if (c.rec_w && t_wq.on && desc) {
-      if (int r2 = wq_push(wa, c.wg_blocks, s)) return r2;
+      if (int r2 = wq_push(c.wg, c.wg_blocks, s)) return r2;
     } else if (c.rec_w) {
       lgm_note_kernel(LGM_KNAME("wgrad_kernel<64, 64, 1, 1, true>"));
-      hipLaunchKernelGGL((wgrad_kernel<64, 64, 1, 1, true>), dim3(c.wg_blocks), dim3(256), 0, s, wa);
+      hipLaunchKernelGGL((wgrad_kernel<64, 64, 1, 1, true>), dim3(c.wg_blocks), dim3(256), 0, s, c.wg);
     }
-    if (c.rec_i) {
-      IgemmArgs ia = c.ig;
-      t_pair = PairCtx{};                    // inactive: this time the launch site launches
-      if (int r2 = launch_igemm_t<MODE_YX, 64, 64, 1, 1, true>(ia, s)) return r2;
+    if (c.rec_i) {                         // prepared when it was recorded; once more for the name, then the launch
+      const size_t smem = prepare_igemm_t<MODE_YX, 64, 64, 1, 1, true>(c.ig);
+      if (int r2 = run_igemm_t<MODE_YX, 64, 64, 1, 1, true>(c.ig, smem, s)) return r2;
     }
   }
   LGM_LAUNCH_CHECK();
-  if (c.red_i) {
-    if (c.r_post) {
-      const long items = c.r_M * (c.r_N / 4);
-      hipLaunchKernelGGL(splitk_reduce_post_kernel, dim3((unsigned)lgm_cdiv(items, 256)), dim3(256), 0, s, c.r_ws,
-                         c.r_stride, c.r_splits, c.r_bias, c.r_res, c.r_res_pitch, c.r_out, c.r_out_pitch, c.r_M, c.r_N,
-                         c.r_act, c.r_slope, c.r_mask, c.r_mask_pitch, c.r_mask_slope);
-      LGM_LAUNCH_CHECK();
-    } else if (int r2 = lgm_splitk_reduce_launch(c.r_ws, c.r_stride, c.r_splits, c.r_bias, c.r_res, c.r_res_pitch, c.r_out,
-                                                 c.r_out_pitch, c.r_M, c.r_N, s)) {
-      return r2;
-    }
-  }
-  if (c.red_w) {
-    const long groups = (c.w_nw + c.w_nb + 3) / 4;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)lgm_cdiv(groups, 64)), dim3(256), 0, s, c.w_ws, c.w_slab, c.w_gw,
-                       c.w_nw, c.w_gb, c.w_nb, c.w_splits, c.w_beta);
-    LGM_LAUNCH_CHECK();
-  }
-  if (!post_done) {        // the input gradient took a path without an epilogue hook: one elementwise pass
-    const long M = (long)g->B * g->H * g->W;
-    hipLaunchKernelGGL(post_kernel, dim3((unsigned)lgm_cdiv(M * g->Cw, 256)), dim3(256), 0, s, gx, (long)gx_pitch, M, g->Cw,
-                       post->act, post->slope, post->mask, (long)post->mask_pitch, post->mask_slope);
-    LGM_LAUNCH_CHECK();
-  }
+  if (c.red_i.present)
+    if (int r2 = c.red_i.launch(s)) return r2;
+  if (c.red_w.present)
+    if (int r2 = c.red_w.launch(s)) return r2;
+  // the input gradient took a path without an epilogue hook: one elementwise pass
+  if (post && !ictx.post_done) return post_launch(post, gx, (long)gx_pitch, (long)g->B * g->H * g->W, g->Cw, s);
   return LGM_OK;
 }
 
@@ -2175,14 +2168,16 @@ extern "C" int lgm_wgrad_queue_flush(void) { return wq_launch(); }
 extern "C" int lgm_conv_wgrad(const LgmConvGeom* g, const float* y, int64_t y_pitch, const float* x,
                               int64_t x_pitch, float* gw, float* gbias, float beta, void* workspace,
                               int64_t workspace_bytes, void* stream) {
-  return conv_wgrad_impl(g, y, y_pitch, x, x_pitch, gw, gbias, beta, workspace, workspace_bytes, nullptr, stream);
+  CallCtx ctx{};
+  return conv_wgrad_impl(ctx, g, y, y_pitch, x, x_pitch, gw, gbias, beta, workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" int lgm_conv_wgrad_deferred(const LgmConvGeom* g, const float* y, int64_t y_pitch, const float* x,
                                        int64_t x_pitch, float* gw, float* gbias, float beta, void* workspace,
                                        int64_t workspace_bytes, int64_t* desc, void* stream) {
   LGM_REQUIRE(desc, "conv_wgrad_deferred: null descriptor");
-  return conv_wgrad_impl(g, y, y_pitch, x, x_pitch, gw, gbias, beta, workspace, workspace_bytes, desc, stream);
+  CallCtx ctx{};
+  return conv_wgrad_impl(ctx, g, y, y_pitch, x, x_pitch, gw, gbias, beta, workspace, workspace_bytes, desc, stream);
 }
 
 namespace {

@@ -1,10 +1,16 @@
 """GPU: every HIP op (through the C-ABI) against a plain fp32 CPU reference of the same op.
 Tolerances: fp32 results within 1e-4 relative (north_star); integer/index work bit-exact."""
 import math
+import os
+import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+if __name__ == "__main__":          # child process of the LGM_PAIR_MAX test: the package is not on the path yet
+    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(_root, "lightning-generative-models_amd"))
 
 pytestmark = pytest.mark.gpu
 
@@ -807,6 +813,92 @@ def test_generic_backward_pair_equals_separate_calls(dev, case, variant):
     assert rel(gw_oihw, torch.nn.grad.conv2d_weight(x, w.shape, gy, padding=k // 2)) < 1e-5
 
 
+def _pair_against_separate(dev, case, variant, mask_slope=None, queue=False):
+    """ops.conv_bwd_generic against ops.conv_wgrad + ops.conv_yx on one layer (torch.equal: the same kernel bodies run)
+    and against torch on the CPU; ``mask_slope``: with the backward mask of a saved activation as the input gradient's
+    post-op (0.0 ReLU, else LeakyReLU).  Returns the kernel noted last by the one call."""
+    from lgm_hip import ops
+    B, ci, co, hw, k = case
+    gen = torch.Generator().manual_seed(sum(case) + 5)
+    x = torch.randn(B, ci, hw, hw, generator=gen)
+    gy = torch.randn(B, co, hw, hw, generator=gen)
+    w = torch.randn(co, ci, k, k, generator=gen) / math.sqrt(ci * k * k)
+    xin = torch.randn(B, ci, hw, hw, generator=gen)          # the saved activation the mask is taken from
+    xd, gyd, wd, xind = nhwc(x, dev), nhwc(gy, dev), phys_weight(w, dev), nhwc(xin, dev)
+    wt = wd.permute(2, 1, 0).contiguous()
+    g = ops.make_geom(B, hw, hw, xd.shape[-1], gyd.shape[-1], k, k, 1, k // 2)
+    base = torch.randn(B, hw, hw, xd.shape[-1], generator=gen).to(dev)
+    mask = None if mask_slope is None else xind
+    post = lambda: None if mask is None else ops.make_post(0, 0.0, mask, mask_slope)
+    # ---- separate calls
+    gw_ref, gb_ref = torch.zeros_like(wd), torch.zeros(gyd.shape[-1], device=dev)
+    ops.conv_wgrad(g, gyd, xd, gw_ref.data_ptr(), 0.0, gb_ref.data_ptr())
+    gx_ref = base.clone()
+    ops.conv_yx(g, gyd, wd.data_ptr(), None, gx_ref if variant == "accumulate" else None, gx_ref, wt.data_ptr(),
+                post=post(), post_mask=mask)
+    # ---- one call
+    gw, gb = torch.zeros_like(wd), torch.zeros(gyd.shape[-1], device=dev)
+    gx = base.clone()
+    defer = [] if variant == "deferred" else None
+    ops.conv_bwd_generic(g, gyd, xd, wd.data_ptr(), wt.data_ptr(), gw.data_ptr(), 0.0, gb.data_ptr(), defer,
+                         gx if variant == "accumulate" else None, gx, post=post(), post_mask=mask, queue=queue)
+    kern = ops.lib()._dll.lgm_last_kernel().decode()
+    if queue:
+        ops.wgrad_queue_flush()
+    if defer:
+        ops.wgrad_reduce_batch(defer, dev)
+    assert torch.equal(gx, gx_ref), kern
+    assert torch.equal(gw, gw_ref) and torch.equal(gb, gb_ref), kern
+    ref = torch.nn.grad.conv2d_input(x.shape, w, gy, padding=k // 2) + (nchw(base, ci) if variant == "accumulate" else 0)
+    if mask_slope is not None:
+        ref = ref * torch.where(xin > 0, torch.ones_like(xin), torch.full_like(xin, mask_slope))
+    assert rel(nchw(gx, ci), ref) < 1e-5
+    gw_oihw = gw[:co, :, :ci].reshape(co, k, k, ci).permute(0, 3, 1, 2)
+    assert rel(gw_oihw, torch.nn.grad.conv2d_weight(x, w.shape, gy, padding=k // 2)) < 1e-5
+    return kern
+
+
+# the input gradient's post-op under the pair: in the held-back split-K reducer (32 tiles, 3 planes), in the paired kernel's
+# epilogue (K = 64: one plane), beside a held-back slab reducer (P = 512: 2 slabs), and on a 3x3 layer, whose input gradient
+# leaves the direct 3x3 kernel for the implicit GEMM when there is a post-op
+PAIR_POST_CASES = [(16, 512, 384, 4, 1), (2, 96, 64, 16, 1), (8, 256, 384, 8, 1), (4, 128, 32, 4, 3)]
+
+
+@pytest.mark.parametrize("case", PAIR_POST_CASES)
+@pytest.mark.parametrize("variant", ["plain", "accumulate", "deferred"])
+@pytest.mark.parametrize("mask_slope", [0.0, 0.2], ids=["relu", "lrelu"])
+def test_generic_backward_pair_with_post_op(dev, case, variant, mask_slope):
+    """lgm_conv_bwd_pair_post against lgm_conv_wgrad + lgm_conv_yx_post"""
+    B, ci, co, hw, k = case
+    kern = _pair_against_separate(dev, case, variant, mask_slope=mask_slope)
+    if variant != "deferred" and k == 1 and B * hw * hw <= 1024 and ci % 32 == 0 and co % 32 == 0:
+        assert kern == "gemm_bwd_pair_kernel", kern
+
+
+@pytest.mark.parametrize("queue", [True, False], ids=["queued", "at-once"])
+def test_generic_backward_pair_weight_gradient_alone_records(dev, queue):
+    """48 gathered channels are no multiple of 32: the input gradient is not uniform-tap and launches at once, the recorded
+    weight gradient follows on its own - queued in a deferred pass that asks for it, else as its own launch"""
+    _pair_against_separate(dev, (2, 96, 48, 16, 1), "deferred", queue=queue)
+
+
+def test_generic_backward_pair_both_record_without_sharing_a_launch():
+    """LGM_PAIR_MAX=0 (read once per process: a child): both halves record, each is launched alone"""
+    import subprocess
+    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--pair-max-child"], capture_output=True, text=True,
+                         env=dict(os.environ, LGM_PAIR_MAX="0"), timeout=300)
+    assert res.returncode == 0, res.stdout[-1000:] + res.stderr[-2000:]
+    assert res.stdout.strip().splitlines()[-1] == "pair-max-child ok", res.stdout[-1000:]
+
+
+def _pair_max_child():
+    assert os.environ.get("LGM_PAIR_MAX") == "0"
+    for variant in ("plain", "deferred"):
+        kern = _pair_against_separate(torch.device("cuda", 0), (16, 512, 384, 4, 1), variant)
+        assert kern == "igemm_kernel<1, 64, 64, 1, 1, true>", kern
+    print("pair-max-child ok")
+
+
 @pytest.mark.parametrize("B,layers", [(5, 2), (256, 2), (2, 4)])
 def test_vqvae_residual_stack_forward_in_one_launch(dev, B, layers):
     """lgm_resstack_fwd against the reference arithmetic (residual.py:5-43): per layer y = relu(conv3x3(cur)),
@@ -879,3 +971,8 @@ def test_time_embedding_in_one_launch(dev, dim, B, parity):
         ops.time_mlp_fwd(T[1:4].contiguous(), dim, 10000.0, W1.data_ptr(), B1.data_ptr(), W2.data_ptr(), B2.data_ptr(), td, *sub)
         for a, b in zip(sub, outs):
             assert torch.equal(a, b[1:4])
+
+
+if __name__ == "__main__":
+    assert sys.argv[1] == "--pair-max-child"
+    _pair_max_child()
