@@ -58,7 +58,9 @@ extern "C" {
                              *  lgm_lowres_cond, lgm_lowres_emb_fwd, lgm_sample_step_extent, lgm_dpm_step_extent,
                              *  lgm_distill_half_step, lgm_distill_target, lgm_slerp, lgm_slerp_span, lgm_slerp_partials,
                              *  lgm_edm_qsample, lgm_edm_qsample_sigma, lgm_edm_pre, lgm_edm_euler, lgm_edm_heun, lgm_fourier_emb_fwd,
-                             *  lgm_fourier_emb_bwd
+                             *  lgm_fourier_emb_bwd, lgm_mconv_xy, lgm_mconv_yx, lgm_mconv_wgrad, lgm_mconv_wgrad_workspace, lgm_mconv_zero_dead, lgm_gated_fwd, lgm_gated_bwd,
+                             *  lgm_softmax_xent_fwd, lgm_softmax_xent_bwd, lgm_pixelcnn_step, lgm_pixelcnn_step_workspace,
+                             *  lgm_categorical_draw
                              *  - a library that lacks a declared symbol fails to load) */
 #define LGM_OK 0
 #define LGM_ERR_INVALID (-1)
@@ -1308,6 +1310,64 @@ int lgm_edm_heun(const float* F, int64_t f_pitch, const float* xhat, const float
 int lgm_fourier_emb_fwd(const float* x, const float* weights, int B, int half, float* out, int64_t pitch, void* stream);
 int lgm_fourier_emb_bwd(const float* emb, int64_t pitch, const float* gemb, int64_t gpitch, int B, int half, float* gweights,
                         float beta, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Gated PixelCNN prior over the VQ-VAE's codes (csrc/pixelcnn.hip; reference models/generative/autoregressive/pixelcnn.py:
+ * MaskedConv2d :8-23, GatedBlock :26-45, PixelCNN :48-106).
+ * Masked convolutions: geometry as the convolution family's with stride 1, odd KH = KW and pad = KH / 2; NHWC fp32 operands
+ * with pitches (16-byte aligned, pitch % 4 == 0), weight [Nw][KH*KW][Cw].  A type-A / type-B mask keeps the taps whose
+ * row-major index kh KW + kw is below taps_live = (KH / 2) KW + KW / 2 + [type B] (24 / 25 of 49 for 7 x 7): the kernels stop
+ * at tap taps_live - 1 and NEVER read a weight at a tap index >= taps_live.  Exact fp32 on v_mfma_f32_32x32x2_f32; a wave
+ * owns its output tile's whole reduction in a fixed order; only the weight gradient splits its reduction, into runs of
+ * positions whose count follows from the geometry alone (2048 positions a run, at most 16), their slabs added in ascending
+ * order by a second launch.  No atomics: the same bits on every run and under every lgm_set_cu_margin.
+ * lgm_mconv_xy: y = conv_live(x, w) + bias (bias optional).  Launches mconv_xy_kernel.
+ * lgm_mconv_yx: gx = conv_live^T(gy, w) + res (res optional, may alias gx).  Launches mconv_yx_kernel.
+ * lgm_mconv_wgrad: gw[n][t][c] = beta gw + sum_m gy[m, n] x[m + d(t), c] for t < taps_live, positions in ascending order;
+ *   the dead taps receive exact zeros when beta == 0 and are left alone otherwise; gbias (optional) = beta gbias + sum_m gy.
+ *   Launches mconv_wgrad_kernel (+ mconv_wgrad_reduce_kernel, mconv_dead_zero_kernel, mconv_bias_grad_kernel).
+ * lgm_mconv_zero_dead: exact zeros into the taps >= taps_live of a weight gradient [Nw][KH*KW][Cw] that lgm_conv_wgrad wrote on
+ *   zero-masked weights (the route of a shape on which the generic kernel is the faster one).  Launches mconv_dead_zero_kernel.
+ * lgm_gated_fwd: y[m, h] = x[m, h] + tanh(a) sigmoid(b), (a, b) = pre[m, h], pre[m, H + h]; H % 4 == 0, 16-byte accesses.
+ * lgm_gated_bwd: (ga, gb) = (gy s (1 - t^2), gy t s (1 - s)) into lanes [0, H), [H, 2H) of gpre (which may be pre itself);
+ *   gx (optional) += gy.
+ * lgm_softmax_xent_fwd: per row m of logits [M, K]: lse[m] = log sum_k exp(l_k), loss_rows[m] = lse[m] - l[target[m]] (NaN for
+ *   a target outside [0, K)); mean (optional) = sum_m loss_rows[m] / M by ONE workgroup in a fixed order.  One wave per row.
+ * lgm_softmax_xent_bwd: glogits[m, k] = (exp(l_k - lse[m]) - [k == target[m]]) gloss[0] / M for k < K, 0 for K <= k < lanes.
+ * lgm_pixelcnn_step: one layer at the ONE position p = counter[0] (read on the device; outside [0, H W): nothing is written):
+ *   o[b, n] = bias[n] + sum_{t < taps_live} sum_c w[n][t][c] cache_in[b, p + d(t), c], zeros outside the map, one workgroup
+ *   row per tap into `workspace` (lgm_pixelcnn_step_workspace bytes), the taps' planes added in ascending order.  gate: the
+ *   result is cache_in[b, p, h] + tanh(o[b, h]) sigmoid(o[b, Nw / 2 + h]) (Nw / 2 lanes), else o (Nw lanes); out_at_p: `out` is a
+ *   [B, H, W, .] map written at p, else a [B, .] matrix.  taps_live = 1 on a 1 x 1 geometry is a plain 1 x 1 layer.
+ *   Launches pixelcnn_step_partial_kernel + pixelcnn_step_finish_kernel.
+ * lgm_categorical_draw: one wave per sample: e_k = exp(logits[b, k] / temperature - max); the class drawn is the first with
+ *   e_k > 0 whose cumulative sum (ascending classes, fixed order) exceeds u[b] sum_k e_k, else the last class with e_k > 0.  codes[b, p] =
+ *   the class (int64, codes [B, HW]); lanes [0, C) of xin[b, p] = codebook[class] (or float(class) when codebook is NULL);
+ *   advance: counter[0] += 1 behind the launch.  Launches categorical_draw_kernel.
+ * ------------------------------------------------------------------------------------- */
+int lgm_mconv_xy(const LgmConvGeom* g, int taps_live, const float* x, int64_t x_pitch, const float* w, const float* bias,
+                 float* y, int64_t y_pitch, void* stream);
+int lgm_mconv_yx(const LgmConvGeom* g, int taps_live, const float* gy, int64_t gy_pitch, const float* w, const float* res,
+                 int64_t res_pitch, float* gx, int64_t gx_pitch, void* stream);
+int64_t lgm_mconv_wgrad_workspace(const LgmConvGeom* g, int taps_live);   /* bytes of the slabs (0: one run) */
+int lgm_mconv_wgrad(const LgmConvGeom* g, int taps_live, const float* gy, int64_t gy_pitch, const float* x, int64_t x_pitch,
+                    float* gw, float* gbias, float beta, void* workspace, int64_t workspace_bytes, void* stream);
+int lgm_mconv_zero_dead(const LgmConvGeom* g, int taps_live, float* gw, void* stream);
+int lgm_gated_fwd(const float* x, int64_t x_pitch, const float* pre, int64_t pre_pitch, int64_t M, int H, float* y,
+                  int64_t y_pitch, void* stream);
+int lgm_gated_bwd(const float* gy, int64_t gy_pitch, const float* pre, int64_t pre_pitch, int64_t M, int H, float* gx,
+                  int64_t gx_pitch, float* gpre, int64_t gpre_pitch, void* stream);
+int lgm_softmax_xent_fwd(const float* logits, int64_t pitch, const int64_t* target, int64_t M, int K, float* loss_rows,
+                         float* lse, float* mean, void* stream);
+int lgm_softmax_xent_bwd(const float* logits, int64_t pitch, const int64_t* target, const float* lse, const float* gloss,
+                         int64_t M, int K, int lanes, float* glogits, int64_t g_pitch, void* stream);
+int64_t lgm_pixelcnn_step_workspace(const LgmConvGeom* g, int taps_live);
+int lgm_pixelcnn_step(const LgmConvGeom* g, int taps_live, int gate, const float* cache_in, int64_t in_pitch, const float* w,
+                      const float* bias, const int32_t* counter, float* out, int64_t out_pitch, int out_at_p, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+int lgm_categorical_draw(const float* logits, int64_t pitch, int B, int K, float temperature, const float* u,
+                         const float* codebook, int64_t cb_pitch, int C, int HW, int32_t* counter, int64_t* codes, float* xin,
+                         int64_t xin_pitch, int advance, void* stream);
 
 #ifdef __cplusplus
 }

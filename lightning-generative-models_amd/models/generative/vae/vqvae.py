@@ -170,6 +170,34 @@ class VQVAE(LightningModule):
         ops.nhwc_to_nchw(r["x_hat"], xh)
         return xh, r["out3"][0], r["out3"][1]
 
+    # ---- the two halves a prior over the codes needs (models/generative/autoregressive/pixelcnn.py) ------------------------
+    def quantize(self, x: torch.Tensor):
+        """x NCHW -> (q [B, h, w, D] NHWC codebook rows, idx [B, h, w] int64).  No tape and no EMA update, whatever the mode."""
+        self.prepare_hip(x.device)
+        B, C, H, W = x.shape
+        x4 = ops.new((B, H, W, _r4(C)), x)
+        ops.nchw_to_nhwc(x.detach().float().contiguous(), x4)
+        lat, _ = self.encoder.fwd(x4)
+        q, _, vq_saved = self.vector_quantizer.fwd(lat, False)
+        return q, vq_saved[2].view(lat.shape[:3])
+
+    def encode_codes(self, x: torch.Tensor) -> torch.Tensor:
+        """x NCHW -> the indices [B, h, w] (int64) of the nearest codebook rows of its latents."""
+        return self.quantize(x)[1]
+
+    def decode_codes(self, idx: torch.Tensor) -> torch.Tensor:
+        """idx [B, h, w] int64 -> images NCHW: codebook rows -> decoder -> tanh, the kernels ``forward`` runs."""
+        self.prepare_hip(idx.device)
+        B, h, w = idx.shape
+        cb = self.vector_quantizer.embedding.weight.detach()
+        q = cb.index_select(0, idx.reshape(-1)).contiguous().view(B, h, w, cb.shape[1])
+        pre, _ = self.decoder.fwd(q)
+        xh = ops.new(pre.shape, pre)
+        ops.act_fwd(pre, None, None, xh, ops.ACT_TANH)
+        out = ops.new((B, self.hparams.img_channels, pre.shape[1], pre.shape[2]), pre)
+        ops.nhwc_to_nchw(xh, out)
+        return out
+
     def _common_step(self, batch, batch_idx: int, split: str):
         x, _ = batch
         w = self.hparams.loss_weights
