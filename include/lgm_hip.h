@@ -1369,6 +1369,50 @@ int lgm_categorical_draw(const float* logits, int64_t pitch, int B, int K, float
                          const float* codebook, int64_t cb_pitch, int C, int HW, int32_t* counter, int64_t* codes, float* xin,
                          int64_t xin_pitch, int advance, void* stream);
 
+/* ---- Fully connected layers with few rows, and the MLP VAE's heads and loss (csrc/dense.hip; reference vae.py:15-215) -----
+ * Activations are row-major [B, pitch] float32; an OUTPUT has pitch >= round_up(C, 4) and its pad lanes [C, round_up(C, 4))
+ * are written 0; an INPUT needs pitch >= C only and may start at any 4-byte address (x.view(B, C S S) of an NCHW batch).
+ * Weights [N, K] in FlatParams' layout [Np][Kp] (16-byte aligned; padding rows are never read), vectors padded to 4.
+ * act: LGM_ACT_NONE, LGM_ACT_LRELU (slope) or LGM_ACT_TANH.  All sums have a fixed order that depends on the shape alone
+ * (not on lgm_cu_margin()); no atomics, no workgroup waits for another.  rc < 0 before any launch on a null pointer,
+ * B < 1, a pitch below the channel count, an unknown act or a workspace that is too small.
+ * lgm_dense_fwd   y = act(x W^T + bias) (bias may be NULL).  Launches dense_gemm_kernel (+ dense_reduce_kernel when the
+ *   reduction is split: lgm_dense_fwd_workspace(B, K, N) > 0 bytes of partial planes).
+ * lgm_dense_bwd   g = gy * act'(y) with act' read from the saved output y (LeakyReLU: y > 0 ? 1 : slope; tanh: 1 - y^2; y may
+ *   be NULL for LGM_ACT_NONE);  gb = beta gb + colsum(g) (gb may be NULL);  gx = g W (gx may be NULL: first layer) from wt, the
+ *   transposed copy [Kp][Np] of the weights;  gw = beta gw + g^T x.  Launches dense_g_kernel, dense_gemm_kernel
+ *   (+ dense_reduce_kernel), dense_gw_kernel.  16-byte aligned workspace of lgm_dense_bwd_workspace bytes.
+ * lgm_vae_head_fwd   mu = h Wmu^T + bmu, log_var = h Wlv^T + blv, z = mu + eps exp(log_var / 2) ([B][round_up(L, 4)] each,
+ *   eps [B][L]), kld_part[b] = sum_j 1 + log_var - mu^2 - exp(log_var) (j ascending).  One launch: vae_head_fwd_kernel.
+ * lgm_vae_head_bwd   with c = kld_weight gloss[0] / (B L): gmu = gz + c mu, glv = gz eps 0.5 exp(log_var / 2) +
+ *   c 0.5 (exp(log_var) - 1); gh = gmu Wmu + glv Wlv; the two heads' gw / gb = beta . + (as lgm_dense_bwd).  Launches
+ *   vae_head_g_kernel, vae_head_gh_kernel, 2 x dense_g_kernel, 2 x dense_gw_kernel.
+ * lgm_tanh_l1_fwd   xh = tanh(pre), row_part[b] = sum_d |xh - x|.   lgm_tanh_l1_bwd   gpre = sign(xh - x) (gloss[0] / (B D))
+ *   (1 - xh^2), sign(0) = 0.   lgm_vae_loss   vals3 = (recon + kld_weight kld, recon = sum(row_part) / (B D),
+ *   kld = -0.5 sum(kld_part) / (B L)), one wave, fixed order.
+ * ------------------------------------------------------------------------------------- */
+int64_t lgm_dense_fwd_workspace(int B, int K, int N);
+int lgm_dense_fwd(const float* x, int64_t x_pitch, const float* w, const float* bias, int B, int K, int N, int act,
+                  float slope, float* y, int64_t y_pitch, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t lgm_dense_bwd_workspace(int B, int K, int N, int need_gx);
+int lgm_dense_bwd(const float* gy, int64_t gy_pitch, const float* y, int64_t y_pitch, const float* x, int64_t x_pitch,
+                  const float* wt, int B, int K, int N, int act, float slope, float* gx, int64_t gx_pitch, float* gw,
+                  float* gb, float beta, void* workspace, int64_t workspace_bytes, void* stream);
+int lgm_vae_head_fwd(const float* h, int64_t h_pitch, const float* w_mu, const float* b_mu, const float* w_lv,
+                     const float* b_lv, const float* eps, int B, int K, int L, float* mu, float* log_var, float* z,
+                     float* kld_part, void* stream);
+int64_t lgm_vae_head_bwd_workspace(int B, int L);
+int lgm_vae_head_bwd(const float* gz, const float* mu, const float* log_var, const float* eps, const float* gloss,
+                     float kld_weight, const float* h, int64_t h_pitch, const float* w_mu, const float* w_lv, int B, int K,
+                     int L, float* gh, int64_t gh_pitch, float* gw_mu, float* gb_mu, float* gw_lv, float* gb_lv, float beta,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+int lgm_tanh_l1_fwd(const float* pre, int64_t pre_pitch, const float* x, int64_t x_pitch, int B, int D, float* xh,
+                    int64_t xh_pitch, float* row_part, void* stream);
+int lgm_tanh_l1_bwd(const float* xh, int64_t xh_pitch, const float* x, int64_t x_pitch, const float* gloss, int B, int D,
+                    float* gpre, int64_t gpre_pitch, void* stream);
+int lgm_vae_loss(const float* row_part, const float* kld_part, int B, int D, int L, float kld_weight, float* vals3,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

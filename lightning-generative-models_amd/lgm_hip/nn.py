@@ -373,6 +373,68 @@ class Linear(nn.Module):
             self._geoms[B] = g
         return g
 
+    # -- a layer of an MLP (few rows: the batch) on the dense kernels (csrc/dense.hip) -------------------------------------
+    def forward(self, x):
+        """Plain torch (autograd), for a module that also runs on the CPU; the HIP engine calls fwd / bwd."""
+        return torch.nn.functional.linear(x, self.weight, self.bias)
+
+    # Which kernels a layer runs, per direction: "dense" (csrc/dense.hip) or "generic" (the 1x1 convolution dispatcher on
+    # a [B, 1, 1, C] map, where the operands allow it: 16-byte aligned rows with a padded pitch, no tanh).  Defaults from
+    # profiles/r23_vae_bench.json, see DESIGN section 6; the tests run both.
+    fwd_route = "dense"
+    bwd_route = "dense"
+
+    @staticmethod
+    def _as_map(t, C):
+        """[B, >= C] -> the [B, 1, 1, r4(C)] view the convolution kernels take, or None when the rows do not allow it
+        (a padded pitch means the engine's activation contract: the pad lanes are zero)"""
+        Cp, p = _r4(C), ops.pitch(t)
+        if t.data_ptr() % 16 or p % 4 or p < Cp:
+            return None
+        return t.as_strided((t.shape[0], 1, 1, Cp), (p, p, p, 1))
+
+    def fwd(self, x, act=0, slope=0.0, out=None):
+        """y [B, r4(cout)] = act(x W^T + b), act in {none, LeakyReLU(slope), tanh} applied by the kernel's epilogue.
+        x [B, >= cin]: any row pitch and alignment (the flattened image batch is passed as it is)."""
+        fp = _flat(self.weight)
+        y = out if out is not None else ops.new((x.shape[0], _r4(self.cout)), x)
+        bias = fp.ptr(self.bias) if self.bias is not None else None
+        x4 = self._as_map(x, self.cin) if self.fwd_route == "generic" and act in (ops.ACT_NONE, ops.ACT_LRELU) else None
+        if x4 is not None:
+            ops.conv_xy(self.geom(x.shape[0]), x4, fp.ptr(self.weight), bias, None, self._as_map(y, self.cout),
+                        post=ops.make_post(act, slope))
+            return y
+        return ops.dense_fwd(x, fp.ptr(self.weight), bias, self.cin, self.cout, y, act, slope)
+
+    def bwd(self, gc: GradCtx, x, y, gy, act=0, slope=0.0, need_gx=True):
+        """gW, gb into the flat gradients; returns gx [B, r4(cin)] (None without need_gx).  ``y`` is the saved OUTPUT of
+        fwd: the activation's derivative is read from it, no mask is kept."""
+        fp = gc.flat
+        bw = gc.beta(self.weight)
+        gb = None
+        if self.bias is not None:
+            assert gc.beta(self.bias) == bw
+            gb = fp.gptr(self.bias)
+        gx = ops.new((x.shape[0], _r4(self.cin)), gy) if need_gx else None
+        wt = fp.tptr(self.weight) if need_gx else None
+        if need_gx and wt is None:
+            raise RuntimeError("Linear.bwd needs the transposed weight copy: build the GradCtx with transposed=True")
+        x4 = self._as_map(x, self.cin) if self.bwd_route == "generic" and act in (ops.ACT_NONE, ops.ACT_LRELU) else None
+        g4 = self._as_map(gy, self.cout) if x4 is not None else None
+        if g4 is not None:
+            geom = self.geom(x.shape[0])
+            if act != ops.ACT_NONE:               # g = gy * act'(y): LeakyReLU keeps the sign, so y stands in for its input
+                g = ops.new((x.shape[0], _r4(self.cout)), gy)
+                g4 = self._as_map(g, self.cout)
+                ops.act_bwd(self._as_map(y, self.cout), None, self._as_map(gy, self.cout), g4, False, act, slope)
+            if need_gx:
+                ops.conv_bwd_generic(geom, g4, x4, fp.ptr(self.weight), wt, fp.gptr(self.weight), bw, gb, None, None,
+                                     self._as_map(gx, self.cin))
+            else:
+                ops.conv_wgrad(geom, g4, x4, fp.gptr(self.weight), bw, gb)
+            return gx
+        return ops.dense_bwd(gy, y, x, wt, self.cin, self.cout, gx, fp.gptr(self.weight), gb, bw, act, slope)
+
 
 def linear_fwd(g, x2d, w_ptr, b_ptr, y2d):
     ops.conv_xy(g, x2d, w_ptr, b_ptr, None, y2d)

@@ -1651,6 +1651,72 @@ def fill(x, val):
     lib().lgm_fill(x.data_ptr(), x.numel(), val, stream())
 
 
+# ----------------------------------------------------------------------------------------
+# fully connected layers with few rows, the MLP VAE's heads and loss (csrc/dense.hip)
+# ----------------------------------------------------------------------------------------
+def _r4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def _ws_ptr(nbytes: int, device):
+    return (workspace(nbytes, device).data_ptr(), nbytes) if nbytes > 0 else (None, 0)
+
+
+def dense_fwd(x, w_ptr: int, bias_ptr: Optional[int], K: int, N: int, y, act: int = ACT_NONE, slope: float = 0.0):
+    """y [B, >= r4(N)] = act(x [B, >= K] W^T + bias), W in FlatParams' layout; x may be an unpadded, unaligned view"""
+    B = x.shape[0]
+    assert x.dim() == 2 and y.dim() == 2 and y.shape[0] == B and x.dtype == y.dtype == torch.float32
+    ws, nb = _ws_ptr(int(lib().lgm_dense_fwd_workspace(B, K, N)), x.device)
+    lib().lgm_dense_fwd(x.data_ptr(), pitch(x), w_ptr, bias_ptr, B, K, N, act, slope, y.data_ptr(), pitch(y), ws, nb, stream())
+    return y
+
+
+def dense_bwd(gy, y, x, wt_ptr: Optional[int], K: int, N: int, gx, gw_ptr: int, gb_ptr: Optional[int], beta: float,
+              act: int = ACT_NONE, slope: float = 0.0):
+    """g = gy * act'(y); gx (None: not wanted) = g W from the transposed weights; gw = beta gw + g^T x; gb likewise"""
+    B = x.shape[0]
+    ws, nb = _ws_ptr(int(lib().lgm_dense_bwd_workspace(B, K, N, 0 if gx is None else 1)), x.device)
+    lib().lgm_dense_bwd(gy.data_ptr(), pitch(gy), _p(y), 0 if y is None else pitch(y), x.data_ptr(), pitch(x), wt_ptr, B, K, N,
+                        act, slope, _p(gx), 0 if gx is None else pitch(gx), gw_ptr, gb_ptr, beta, ws, nb, stream())
+    return gx
+
+
+def vae_head_fwd(h, K: int, L: int, w_mu: int, b_mu: int, w_lv: int, b_lv: int, eps):
+    """-> (mu, log_var, z [B, r4(L)], kld_part [B]) from h [B, >= K] and eps [B, L]"""
+    B = h.shape[0]
+    assert eps.shape == (B, L) and eps.is_contiguous()
+    out = new((3, B, _r4(L)), h)
+    part = new((B,), h)
+    lib().lgm_vae_head_fwd(h.data_ptr(), pitch(h), w_mu, b_mu, w_lv, b_lv, eps.data_ptr(), B, K, L, out[0].data_ptr(),
+                           out[1].data_ptr(), out[2].data_ptr(), part.data_ptr(), stream())
+    return out[0], out[1], out[2], part
+
+
+def vae_head_bwd(gz, mu, log_var, eps, gloss, kld_weight: float, h, K: int, L: int, w_mu: int, w_lv: int, gh, gw_mu: int,
+                 gb_mu: int, gw_lv: int, gb_lv: int, beta: float):
+    B = h.shape[0]
+    assert gz.is_contiguous() and gz.shape == mu.shape == log_var.shape == (B, _r4(L))
+    ws, nb = _ws_ptr(int(lib().lgm_vae_head_bwd_workspace(B, L)), h.device)
+    lib().lgm_vae_head_bwd(gz.data_ptr(), mu.data_ptr(), log_var.data_ptr(), eps.data_ptr(), gloss.data_ptr(), kld_weight,
+                           h.data_ptr(), pitch(h), w_mu, w_lv, B, K, L, gh.data_ptr(), pitch(gh), gw_mu, gb_mu, gw_lv, gb_lv,
+                           beta, ws, nb, stream())
+    return gh
+
+
+def tanh_l1_fwd(pre, x, D: int, xh, row_part):
+    lib().lgm_tanh_l1_fwd(pre.data_ptr(), pitch(pre), x.data_ptr(), pitch(x), pre.shape[0], D, xh.data_ptr(), pitch(xh),
+                          row_part.data_ptr(), stream())
+
+
+def tanh_l1_bwd(xh, x, gloss, D: int, gpre):
+    lib().lgm_tanh_l1_bwd(xh.data_ptr(), pitch(xh), x.data_ptr(), pitch(x), gloss.data_ptr(), xh.shape[0], D, gpre.data_ptr(),
+                          pitch(gpre), stream())
+
+
+def vae_loss(row_part, kld_part, D: int, L: int, kld_weight: float, vals3):
+    lib().lgm_vae_loss(row_part.data_ptr(), kld_part.data_ptr(), row_part.numel(), D, L, kld_weight, vals3.data_ptr(), stream())
+
+
 from ._lib import on_selection_change as _on_selection_change  # noqa: E402
 
 _on_selection_change(clear_plan_caches)
