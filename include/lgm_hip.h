@@ -1412,6 +1412,46 @@ int lgm_tanh_l1_bwd(const float* xh, int64_t xh_pitch, const float* x, int64_t x
                     float* gpre, int64_t gpre_pitch, void* stream);
 int lgm_vae_loss(const float* row_part, const float* kld_part, int B, int D, int L, float kld_weight, float* vals3,
                  void* stream);
+/* lgm_dense_dgrad   the input gradient of lgm_dense_bwd alone (gx = (gy * act'(y)) W from wt; no gw, no gb): the sweep
+ *   through a network whose parameters are not being updated.  Same launches, same bits in gx; a workspace of
+ *   lgm_dense_bwd_workspace(B, K, N, 1) bytes. */
+int lgm_dense_dgrad(const float* gy, int64_t gy_pitch, const float* y, int64_t y_pitch, const float* wt, int B, int K, int N,
+                    int act, float slope, float* gx, int64_t gx_pitch, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+
+/* ---- BatchNorm1d over few rows and the MLP GAN's loss head (csrc/bn1d.hip; reference gan/gan.py:15-89, :258-308) ----------
+ * Activations as in the dense section: row-major [B, pitch] float32, an OUTPUT has pitch >= round_up(F, 4) and its pad lanes
+ * are written 0, an INPUT needs pitch >= F only and its pad lanes are never read.  gamma, beta, running_*, mean, rstd: [F].
+ * One launch each; one workgroup owns 32 columns and all B rows (lgm_bn1d_supported: 1 <= B <= 512).  Every sum has a fixed
+ * order that depends on (B, F) alone (not on lgm_cu_margin()); no atomics, no workgroup waits for another.
+ * act: LGM_ACT_NONE or LGM_ACT_LRELU (slope).  rc < 0 before any launch on a null pointer, an unsupported B, a pitch below
+ * the feature count, an unknown act, or training with B = 1.
+ * lgm_bn1d_fwd   training: mean = sum_b a / B, var = sum_b (a - mean)^2 / B (centred, from the rows held on chip),
+ *   rstd = 1 / sqrt(var + eps), running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with
+ *   var B / (B - 1);  eval (training = 0): mean = running_mean, rstd = 1 / sqrt(running_var + eps), nothing else is written
+ *   to the running statistics.  y = act(gamma ((a - mean) rstd) + beta); mean and rstd are outputs (the backward reads them).
+ * lgm_bn1d_bwd   g = gy * act'(y) (act' from the saved output y; y may be NULL for LGM_ACT_NONE), xhat = (a - mean) rstd,
+ *   s1 = sum_b g, s2 = sum_b g xhat;  gbeta = beta_acc gbeta + s1, ggamma = beta_acc ggamma + s2;
+ *   ga = (gamma rstd) ((g - s1 / B) - xhat (s2 / B)) - the backward of the training-mode forward.
+ * lgm_gan_bce_d   bce(s, t) = max(s, 0) - s t + log1p(exp(-|s|)).  vals5 = (mean_b bce(real, 1), mean_b bce(fake, 0), their
+ *   mean, mean real, mean fake); score vectors are column 0 of a [B, pitch] matrix.  One wave, fixed order.
+ * lgm_gan_bce_g   vals2 = (g_loss, mean s): loss_type 0 (non-saturating) mean bce(s, 1), 1 (min-max) -mean bce(s, 0).
+ * lgm_gan_bce_bwd  g_k[b][0] = (gloss[0] factor_k / B) (sigmoid(s_k[b]) - t_k), t_k in {0, 1}, lanes 1 .. 3 of the row 0;
+ *   k = 0 and, when s1 / g1 are given, k = 1 in the same launch (the discriminator loss: factors 0.5, targets 1 and 0).
+ * ------------------------------------------------------------------------------------- */
+int64_t lgm_bn1d_supported(int B, int F);
+int lgm_bn1d_fwd(const float* a, int64_t a_pitch, int B, int F, const float* gamma, const float* beta, float eps,
+                 float momentum, int training, int act, float slope, float* running_mean, float* running_var, float* y,
+                 int64_t y_pitch, float* mean, float* rstd, void* stream);
+int lgm_bn1d_bwd(const float* gy, int64_t gy_pitch, const float* y, int64_t y_pitch, const float* a, int64_t a_pitch,
+                 const float* mean, const float* rstd, const float* gamma, int B, int F, int act, float slope, float* ga,
+                 int64_t ga_pitch, float* ggamma, float* gbeta, float beta_acc, void* stream);
+int lgm_gan_bce_d(const float* real, int64_t real_pitch, const float* fake, int64_t fake_pitch, int B, float* vals5,
+                  void* stream);
+int lgm_gan_bce_g(const float* s, int64_t pitch, int B, int loss_type, float* vals2, void* stream);
+int lgm_gan_bce_bwd(const float* s0, int64_t s0_pitch, float t0, float factor0, float* g0, int64_t g0_pitch, const float* s1,
+                    int64_t s1_pitch, float t1, float factor1, float* g1, int64_t g1_pitch, int B, const float* gloss,
+                    void* stream);
 
 #ifdef __cplusplus
 }

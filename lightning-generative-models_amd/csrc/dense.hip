@@ -477,6 +477,29 @@ extern "C" int lgm_dense_bwd(const float* gy, int64_t gy_pitch, const float* y, 
   return launch_gw("dense_bwd", g, Np, x, (long)x_pitch, B, N, K, gw, beta, st);
 }
 
+// the input gradient alone (a sweep through a network whose parameters are not being updated): dense_g_kernel and
+// dense_gemm_kernel as lgm_dense_bwd launches them, the same bits in gx; workspace of lgm_dense_bwd_workspace(B, K, N, 1)
+extern "C" int lgm_dense_dgrad(const float* gy, int64_t gy_pitch, const float* y, int64_t y_pitch, const float* wt, int B, int K,
+                               int N, int act, float slope, float* gx, int64_t gx_pitch, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  LGM_REQUIRE(gy && gx && wt && workspace, "dense_dgrad: gy, gx, wt and a workspace required");
+  LGM_REQUIRE(B >= 1 && K >= 1 && N >= 1 && B <= DN_MAX_DIM && K <= DN_MAX_DIM && N <= DN_MAX_DIM, "dense_dgrad: B, K, N >= 1 required, got %d %d %d", B, K, N);
+  LGM_REQUIRE(act_ok(act), "dense_dgrad: act must be none, LeakyReLU or tanh, got %d", act);
+  LGM_REQUIRE(act == LGM_ACT_NONE || y, "dense_dgrad: the saved output y is required with an activation");
+  LGM_REQUIRE(gy_pitch >= N && (!y || y_pitch >= N), "dense_dgrad: pitches below the channel count %d", N);
+  LGM_REQUIRE(lgm_aligned16(wt) && gx_pitch >= r4(K),
+              "dense_dgrad: 16-byte aligned transposed weights [Kp][Np] and gx_pitch >= %d required", r4(K));
+  const int64_t need = lgm_dense_bwd_workspace(B, K, N, 1);
+  LGM_REQUIRE(workspace_bytes >= need && lgm_aligned16(workspace), "dense_dgrad: 16-byte aligned workspace of %ld bytes required",
+              (long)need);
+  hipStream_t st = (hipStream_t)stream;
+  const int Np = r4(N);
+  float* g = (float*)workspace;
+  const int rc = launch_g("dense_dgrad", gy, (long)gy_pitch, y, (long)y_pitch, B, N, act, slope, g, nullptr, 0.f, st);
+  if (rc) return rc;
+  return launch_gemm("dense_dgrad", g, Np, wt, Np, nullptr, B, K, N, LGM_ACT_NONE, 0.f, gx, (long)gx_pitch, g + (long)B * Np, st);
+}
+
 extern "C" int lgm_vae_head_fwd(const float* h, int64_t h_pitch, const float* w_mu, const float* b_mu, const float* w_lv,
                                 const float* b_lv, const float* eps, int B, int K, int L, float* mu, float* log_var, float* z,
                                 float* kld_part, void* stream) {

@@ -160,3 +160,93 @@ class BatchNorm2d(nn.Module):
                            sv.mean.data_ptr(), sv.rstd.data_ptr(), coef.data_ptr(), gn_bar.data_ptr(),
                            ops.pitch(gn_bar), a_bar.data_ptr(), ops.pitch(a_bar), rows, C, ops.stream())
         return gn_bar, a_bar
+
+
+class BatchNorm1d(BatchNorm2d):
+    """nn.BatchNorm1d over [B, F] rows of an MLP (parameters / buffers named as torch's, the host-side batch counter of
+    BatchNorm2d).  ``route`` selects the kernels: "rows" = csrc/bn1d.hip, one launch per direction with the whole batch on
+    chip (B <= ops.BN1D_MAX_ROWS); "generic" = the two-launch pairs above on the [B, 1, 1, r4(F)] view, which also take every
+    batch the rows kernels do not hold.  Default from profiles/r24_gan_bench.json; the tests run both."""
+
+    route = "rows"
+
+    def forward(self, x):
+        """Plain torch (autograd), for a module that also runs on the CPU; the HIP engine calls fwd / bwd."""
+        if self.training:
+            if x.shape[0] == 1:
+                raise ValueError("BatchNorm1d: train mode needs more than one row per feature, got a batch of 1")
+            _count_forward(self)
+        return torch.nn.functional.batch_norm(x, self.running_mean, self.running_var, self.weight, self.bias, self.training,
+                                              self.momentum, self.eps)
+
+    def _rows(self, B: int) -> bool:
+        return self.route == "rows" and B <= ops.BN1D_MAX_ROWS
+
+    def fwd(self, a, act: int = 0, slope: float = 0.0, training: bool = True):
+        """a [B, >= F] -> (y [B, r4(F)] = act(gamma xhat + beta), saved); act in {none, LeakyReLU(slope)}"""
+        from .nn import Linear
+        B, F = a.shape[0], self.channels
+        if training and B == 1:
+            raise ValueError("BatchNorm1d: train mode needs more than one row per feature, got a batch of 1")
+        fp = _flat(self.weight)
+        Fp = (F + 3) // 4 * 4
+        y = ops.new((B, Fp), a)
+        a4 = None if self._rows(B) else Linear._as_map(a, F)
+        if a4 is None and B > ops.BN1D_MAX_ROWS:          # rows the convolution kernels cannot view: a padded copy
+            pad = torch.zeros((B, Fp), dtype=torch.float32, device=a.device)
+            pad[:, :F].copy_(a[:, :F])
+            a, a4 = pad, Linear._as_map(pad, F)
+        st = torch.empty((2, Fp), dtype=torch.float32, device=a.device)
+        mean, rstd = st[0], st[1]
+        if a4 is None:
+            ops.bn1d_fwd(a, F, fp.ptr(self.weight), fp.ptr(self.bias), self.eps, self.momentum, training, act, slope,
+                         self.running_mean, self.running_var, y, mean, rstd)
+            if training:
+                _count_forward(self)
+            return y, BNSaved(a, mean, rstd)
+        L = ops.lib()
+        if training:
+            rm, rv = self.running_mean, self.running_var
+            if Fp != F:                                   # lgm_bn_stats updates r4(F) running statistics
+                rm, rv = torch.zeros(Fp, device=a.device), torch.ones(Fp, device=a.device)
+                rm[:F].copy_(self.running_mean)
+                rv[:F].copy_(self.running_var)
+            L.lgm_bn_stats(a4.data_ptr(), ops.pitch(a4), B, Fp, self.eps, self.momentum, mean.data_ptr(), rstd.data_ptr(),
+                           rm.data_ptr(), rv.data_ptr(), _ws(a4).data_ptr(), ops.stream())
+            if Fp != F:
+                self.running_mean.copy_(rm[:F])
+                self.running_var.copy_(rv[:F])
+            _count_forward(self)
+        else:
+            st.zero_()
+            mean[:F].copy_(self.running_mean)
+            rstd[:F].copy_((self.running_var + self.eps).rsqrt())
+        y4 = Linear._as_map(y, F)
+        L.lgm_bn_affine3(None, 0, None, 0, a4.data_ptr(), ops.pitch(a4), mean.data_ptr(), rstd.data_ptr(), None, None,
+                         fp.ptr(self.weight), fp.ptr(self.bias), y4.data_ptr(), ops.pitch(y4), 0, act, slope, B, Fp,
+                         ops.stream())
+        return y, BNSaved(a4, mean, rstd)
+
+    def bwd(self, gc: GradCtx, saved: BNSaved, y, gy, act: int = 0, slope: float = 0.0):
+        """ggamma, gbeta into the flat gradients; returns ga [B, r4(F)].  ``y`` is the saved OUTPUT of fwd: the activation's
+        derivative is read from it."""
+        from .nn import Linear
+        F = self.channels
+        a = saved.a
+        B = a.shape[0]
+        ga = ops.new((B, (F + 3) // 4 * 4), gy)
+        if a.dim() == 2:                                  # the rows kernels ran the forward
+            fp = gc.flat
+            beta = gc.beta(self.weight)
+            assert gc.beta(self.bias) == beta
+            return ops.bn1d_bwd(gy, y, a, F, saved.mean, saved.rstd, fp.ptr(self.weight), act, slope, ga,
+                                fp.gptr(self.weight), fp.gptr(self.bias), beta)
+        g4 = Linear._as_map(gy, F)
+        if g4 is None:
+            raise RuntimeError("BatchNorm1d.bwd (generic route): gy must be 16-byte aligned rows with a padded pitch")
+        if act != ops.ACT_NONE:                           # g = gy * act'(y): LeakyReLU keeps the sign, y stands in for its input
+            g = ops.new(ga.shape, gy)
+            ops.act_bwd(Linear._as_map(y, F), None, g4, Linear._as_map(g, F), False, act, slope)
+            g4 = Linear._as_map(g, F)
+        self.apply_T(saved, g4, gc, out=Linear._as_map(ga, F))
+        return ga

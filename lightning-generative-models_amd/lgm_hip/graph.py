@@ -15,7 +15,8 @@ backward pass runs in four phases, each of which makes one exchange bucket of th
 
 Collectives are never captured, the optimiser's step count lives on the host, and the RNG is torch's graph-safe
 Philox generator.  The arithmetic is identical to the eager path (same kernels, same order) - tested bit for bit.
-ModuleFastStep (VQ-VAE: one graph) and WGANFastStep (critic graph / generator graph) follow the same rules and keep
+ModuleFastStep (VQ-VAE: one graph), WGANFastStep (critic graph / generator graph) and GANFastStep (the MLP GAN: the work in
+front of and behind the D optimizer step, two graphs on one memory pool) follow the same rules and keep
 what they captured in a ``_Captured``: warm-up and capture leave the training state untouched (_TrainingState), also
 when capture fails.  Every step class falls back to eager launches when capture is not possible (``_eager_fallback``).
 ``accumulate > 1`` (DDPMFastStep, ModuleFastStep) leaves the captured graphs as they are: the micro-gradients are summed in one
@@ -668,5 +669,88 @@ class WGANFastStep:
         opt = self.d_opt if critic else self.g_opt
         opt.step()                                   # the counting proxy advances global_step (the schedule's clock)
         opt.zero_grad()
+        m.log_dict(logs, prog_bar=True, logger=True, sync_dist=self.world > 1)
+        return logs
+
+
+class GANFastStep:
+    """Fast step for the MLP GAN (manual optimisation, reference gan.py:144-174: one D update, then one G update on the SAME
+    ``x_hat``).  What runs in front of the D optimizer step - z ~ randn, G forward with its tape, D on the real and on the
+    fake batch, the BCE head, D's backward - and what runs behind it - D forward on that ``x_hat`` with the updated
+    weights, the BCE head, the input-gradient sweep through D, G's backward - are captured ONCE into two HIP graphs that
+    share one memory pool and one capture stream: the second reads the first's ``x_hat`` and generator tape where the first
+    left them.  The gradient exchange (N > 1: ONE all-reduce per update of the flat buffer that update wrote, 1/N folded
+    into the fused optimizer), the two optimizer kernels and logging stay on the host.  Warm-up and capture leave
+    parameters, running statistics, batch counters and the random stream untouched; eager launches in the same process when
+    capture is not possible or a batch has another shape."""
+
+    def __init__(self, model, opts, world: int = 1, use_graph: bool = True):
+        from .lightning import FlatGradSync
+        self.model, self.world = model, world
+        self.d_opt, self.g_opt = opts
+        for o in opts:
+            if world > 1:
+                getattr(o, "_opt", o).grad_scale = 1.0 / world
+        if world > 1:
+            model._grads_prescaled = True
+        self.sync = ({"d": FlatGradSync(model.D._flat, beside_backward=False),
+                      "g": FlatGradSync(model.G._flat, beside_backward=False)} if world > 1 else None)
+        self.use_graph = use_graph
+        self.captured = None      # (_Captured of the D phase: out = (x_hat, logs), _Captured of the G phase: out = logs)
+        self.mode = "eager"
+
+    # the two halves of a step, without exchange / optimizer step (what a graph holds)
+    def _d_phase(self, x):
+        m = self.model
+        x_hat = m.G.random_sample(x.size(0))
+        ld = m._calculate_d_loss(x, x_hat)
+        m.D._flat.zero_grad()
+        ld["d_loss"].backward()
+        return x_hat, ld
+
+    def _g_phase(self, x_hat):
+        m = self.model
+        lg = m._calculate_g_loss(x_hat)
+        m.G._flat.zero_grad()
+        lg["g_loss"].backward()
+        return lg
+
+    def _capture(self, x):
+        m = self.model
+        static = (x.clone(),)
+        state = _TrainingState([m], x.device)
+        try:
+            # the whole step eagerly (the second half consumes the first's tape: the halves cannot warm up apart)
+            _warm_up(lambda: self._g_phase(self._d_phase(static[0])[0]), 2)
+            ga, out_a, trace_a = _capture(lambda: self._d_phase(static[0]), 0)
+            gb, out_b, trace_b = _capture(lambda: self._g_phase(out_a[0]), 0, pool=ga.pool())
+            self.captured = (_Captured(ga, static, out_a, trace_a), _Captured(gb, (), out_b, trace_b))
+            self.mode = "hipGraph replay (D graph / G graph, one pool)"
+        except Exception as e:
+            self.captured = None
+            _eager_fallback(self, e)
+        finally:
+            state.restore()
+
+    def _update(self, key, opt):
+        if self.sync is not None:
+            sy = self.sync[key]
+            sy.ready(0, sy.flat.total)
+            sy.finish()
+        opt.step()
+        opt.zero_grad()
+
+    def step(self, batch, batch_idx: int = 0):
+        m = self.model
+        x = batch[0]
+        if self.use_graph and self.captured is None and m.training:
+            self._capture(x)
+        cap = self.captured
+        replay = cap is not None and cap[0].matches((x,))
+        x_hat, ld = cap[0].replay((x,)) if replay else self._d_phase(x)
+        self._update("d", self.d_opt)
+        lg = cap[1].replay(()) if replay else self._g_phase(x_hat)
+        self._update("g", self.g_opt)
+        logs = {f"train_{k}": v for k, v in {**ld, **lg}.items()}
         m.log_dict(logs, prog_bar=True, logger=True, sync_dist=self.world > 1)
         return logs

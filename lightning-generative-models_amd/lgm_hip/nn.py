@@ -435,6 +435,26 @@ class Linear(nn.Module):
             return gx
         return ops.dense_bwd(gy, y, x, wt, self.cin, self.cout, gx, fp.gptr(self.weight), gb, bw, act, slope)
 
+    def dgrad(self, y, gy, act=0, slope=0.0):
+        """gx [B, r4(cin)] = (gy * act'(y)) W alone - no parameter gradients: the sweep through a network that is not being
+        updated (a GAN's discriminator under the generator's loss).  The caller keeps the transposed weight copy current
+        (FlatParams.refresh_transposed)."""
+        fp = _flat(self.weight)
+        B = gy.shape[0]
+        gx = ops.new((B, _r4(self.cin)), gy)
+        g4 = self._as_map(gy, self.cout) if self.bwd_route == "generic" and act in (ops.ACT_NONE, ops.ACT_LRELU) else None
+        if g4 is not None:
+            if act != ops.ACT_NONE:
+                g = ops.new((B, _r4(self.cout)), gy)
+                ops.act_bwd(self._as_map(y, self.cout), None, g4, self._as_map(g, self.cout), False, act, slope)
+                g4 = self._as_map(g, self.cout)
+            ops.conv_yx(self.geom(B), g4, fp.ptr(self.weight), None, None, self._as_map(gx, self.cin), fp.tptr(self.weight))
+            return gx
+        wt = fp.tptr(self.weight)
+        if wt is None:
+            raise RuntimeError("Linear.dgrad needs the transposed weight copy (FlatParams.refresh_transposed)")
+        return ops.dense_dgrad(gy, y, wt, self.cin, self.cout, gx, act, slope)
+
 
 def linear_fwd(g, x2d, w_ptr, b_ptr, y2d):
     ops.conv_xy(g, x2d, w_ptr, b_ptr, None, y2d)

@@ -1717,6 +1717,58 @@ def vae_loss(row_part, kld_part, D: int, L: int, kld_weight: float, vals3):
     lib().lgm_vae_loss(row_part.data_ptr(), kld_part.data_ptr(), row_part.numel(), D, L, kld_weight, vals3.data_ptr(), stream())
 
 
+def dense_dgrad(gy, y, wt_ptr: int, K: int, N: int, gx, act: int = ACT_NONE, slope: float = 0.0):
+    """gx = (gy * act'(y)) W alone: the input gradient of dense_bwd without the parameter gradients"""
+    B = gy.shape[0]
+    ws, nb = _ws_ptr(int(lib().lgm_dense_bwd_workspace(B, K, N, 1)), gy.device)
+    lib().lgm_dense_dgrad(gy.data_ptr(), pitch(gy), _p(y), 0 if y is None else pitch(y), wt_ptr, B, K, N, act, slope,
+                          gx.data_ptr(), pitch(gx), ws, nb, stream())
+    return gx
+
+
+# ----------------------------------------------------------------------------------------
+# BatchNorm1d over few rows and the MLP GAN's loss head (csrc/bn1d.hip)
+# ----------------------------------------------------------------------------------------
+BN1D_MAX_ROWS = 512
+GAN_LOSS_TYPES = {"non-saturating": 0, "min-max": 1}
+
+
+def bn1d_fwd(a, F: int, gamma_ptr: int, beta_ptr: int, eps: float, momentum: float, training: bool, act: int, slope: float,
+             running_mean, running_var, y, mean, rstd):
+    """y [B, >= r4(F)] = act(gamma xhat + beta) over a [B, >= F]; mean, rstd [F] are written for the backward"""
+    lib().lgm_bn1d_fwd(a.data_ptr(), pitch(a), a.shape[0], F, gamma_ptr, beta_ptr, eps, momentum, 1 if training else 0, act,
+                       slope, running_mean.data_ptr(), running_var.data_ptr(), y.data_ptr(), pitch(y), mean.data_ptr(),
+                       rstd.data_ptr(), stream())
+    return y
+
+
+def bn1d_bwd(gy, y, a, F: int, mean, rstd, gamma_ptr: int, act: int, slope: float, ga, ggamma_ptr: int, gbeta_ptr: int,
+             beta_acc: float):
+    lib().lgm_bn1d_bwd(gy.data_ptr(), pitch(gy), _p(y), 0 if y is None else pitch(y), a.data_ptr(), pitch(a), mean.data_ptr(),
+                       rstd.data_ptr(), gamma_ptr, a.shape[0], F, act, slope, ga.data_ptr(), pitch(ga), ggamma_ptr, gbeta_ptr,
+                       beta_acc, stream())
+    return ga
+
+
+def gan_bce_d(s_real, s_fake, vals5):
+    """score vectors = column 0 of [B, pitch] matrices -> (d_loss_real, d_loss_fake, d_loss, mean real, mean fake)"""
+    B = s_real.shape[0]
+    assert s_fake.shape[0] == B and vals5.numel() >= 5
+    lib().lgm_gan_bce_d(s_real.data_ptr(), pitch(s_real), s_fake.data_ptr(), pitch(s_fake), B, vals5.data_ptr(), stream())
+    return vals5
+
+
+def gan_bce_g(s, loss_type: str, vals2):
+    lib().lgm_gan_bce_g(s.data_ptr(), pitch(s), s.shape[0], GAN_LOSS_TYPES[loss_type], vals2.data_ptr(), stream())
+    return vals2
+
+
+def gan_bce_bwd(gloss, s0, t0: float, f0: float, g0, s1=None, t1: float = 0.0, f1: float = 0.0, g1=None):
+    """g_k [B, 4] (column 0 live) = gloss f_k / B (sigmoid(s_k) - t_k), one launch for one or two score vectors"""
+    lib().lgm_gan_bce_bwd(s0.data_ptr(), pitch(s0), t0, f0, g0.data_ptr(), pitch(g0), _p(s1), 0 if s1 is None else pitch(s1),
+                          t1, f1, _p(g1), 0 if g1 is None else pitch(g1), s0.shape[0], gloss.data_ptr(), stream())
+
+
 from ._lib import on_selection_change as _on_selection_change  # noqa: E402
 
 _on_selection_change(clear_plan_caches)
