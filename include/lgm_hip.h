@@ -1373,7 +1373,7 @@ int lgm_categorical_draw(const float* logits, int64_t pitch, int B, int K, float
  * Activations are row-major [B, pitch] float32; an OUTPUT has pitch >= round_up(C, 4) and its pad lanes [C, round_up(C, 4))
  * are written 0; an INPUT needs pitch >= C only and may start at any 4-byte address (x.view(B, C S S) of an NCHW batch).
  * Weights [N, K] in FlatParams' layout [Np][Kp] (16-byte aligned; padding rows are never read), vectors padded to 4.
- * act: LGM_ACT_NONE, LGM_ACT_LRELU (slope) or LGM_ACT_TANH.  All sums have a fixed order that depends on the shape alone
+ * act: LGM_ACT_NONE, LGM_ACT_RELU, LGM_ACT_LRELU (slope) or LGM_ACT_TANH.  All sums have a fixed order that depends on the shape alone
  * (not on lgm_cu_margin()); no atomics, no workgroup waits for another.  rc < 0 before any launch on a null pointer,
  * B < 1, a pitch below the channel count, an unknown act or a workspace that is too small.
  * lgm_dense_fwd   y = act(x W^T + bias) (bias may be NULL).  Launches dense_gemm_kernel (+ dense_reduce_kernel when the
@@ -1452,6 +1452,37 @@ int lgm_gan_bce_g(const float* s, int64_t pitch, int B, int loss_type, float* va
 int lgm_gan_bce_bwd(const float* s0, int64_t s0_pitch, float t0, float factor0, float* g0, int64_t g0_pitch, const float* s1,
                     int64_t s1_pitch, float t1, float factor1, float* g1, int64_t g1_pitch, int B, const float* gloss,
                     void* stream);
+
+/* ---- The denoising autoencoder: corruption, tanh + squared error, loss (csrc/dae.hip; reference autoencoder/dae.py) -------
+ * Its Linear layers are lgm_dense_fwd / _bwd with LGM_ACT_RELU (the dense section accepts it: y = v > 0 ? v : +0, the
+ * derivative from the saved output y > 0 ? 1 : 0).  Activations as in the dense section: row-major [B, pitch] float32, an
+ * OUTPUT has pitch >= round_up(D, 4) and its pad lanes are written +0, an INPUT needs pitch >= D only, may start at any
+ * 4-byte address and its pad lanes are never read (16-byte accesses where every operand's base and pitch allow them, guarded
+ * scalar ones otherwise: the same bits).  No atomics, no workgroup waits for another, every sum in a fixed order that depends
+ * on (B, D) alone; no product is contracted into a sum.  B, D <= 2^20 and B round_up(D, 4) <= 2^31.  rc < 0 before any
+ * launch on a null pointer, B or D out of that range, a pitch below D, an output whose span of B rows shares a byte with an
+ * input's span, an unknown mode or a negative level.
+ * lgm_dae_corrupt        out = fl(x + fl(noise * level)): two roundings (torch's x + randn_like(x) * level).
+ * lgm_dae_corrupt_mask   the corruption is drawn in registers by Philox4x32-10 (csrc/lgm_philox.h) under the 64-bit key that
+ *   `key` (device, int64 [1]) holds when the kernel runs.  Element n = b D + d (the logical index), q = n >> 2:
+ *   w_s = philox(counter = (q lo, q hi, 0, 0))[n & 3], w_p = philox(counter = (q lo, q hi, 1, 0))[n & 3].
+ *   mode 0 (salt_and_pepper): out = w_p < thr ? 0 : (w_s < thr ? 1 : x), thr = lgm_dae_mask_threshold(0, level)
+ *     = min(2^32 - 1, floor(level / 2 * 2^32));  mode 1 (masking): out = w_s < thr ? 0 : x, thr = min(2^32 - 1,
+ *     floor(level * 2^32)).  Untouched elements keep x's bits.  lgm_dae_mask_threshold is host-only (-1: bad mode or level).
+ * lgm_dae_tanh_mse_fwd   xh = tanhf(pre), row_part[b] = sum_d (x - xh)^2.  (lgm_tanh_mse_fwd is the VQ-VAE's NHWC kernel.)
+ * lgm_dae_tanh_mse_bwd   gpre = ((2 gloss[0] / (B D)) (xh - x)) (1 - xh^2), gloss on the device; 0 where xh == x.
+ * lgm_dae_loss           vals[0] = sum_b row_part[b] / (B D): one wave, lane l adds rows l, l + 64, .., then a fixed tree.
+ * ------------------------------------------------------------------------------------- */
+int lgm_dae_corrupt(const float* x, int64_t x_pitch, const float* noise, int64_t noise_pitch, float level, int B, int D,
+                    float* out, int64_t out_pitch, void* stream);
+int64_t lgm_dae_mask_threshold(int mode, double level);
+int lgm_dae_corrupt_mask(const float* x, int64_t x_pitch, const int64_t* key, int mode, double level, int B, int D,
+                         float* out, int64_t out_pitch, void* stream);
+int lgm_dae_tanh_mse_fwd(const float* pre, int64_t pre_pitch, const float* x, int64_t x_pitch, int B, int D, float* xh,
+                         int64_t xh_pitch, float* row_part, void* stream);
+int lgm_dae_tanh_mse_bwd(const float* xh, int64_t xh_pitch, const float* x, int64_t x_pitch, const float* gloss, int B, int D,
+                         float* gpre, int64_t gpre_pitch, void* stream);
+int lgm_dae_loss(const float* row_part, int B, int D, float* vals, void* stream);
 
 #ifdef __cplusplus
 }

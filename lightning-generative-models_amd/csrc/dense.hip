@@ -12,7 +12,8 @@
 //   accumulators are summed through LDS in wave order; a split launch leaves one plane per slice and dense_reduce_kernel sums
 //   them in slice order and applies bias and activation.  The slice length depends on (M, No, R) alone - never on
 //   lgm_cu_margin() - and nothing is summed by an atomic: eager, replayed and repeated runs give equal bits.
-// dense_g_kernel            g = gy * act'(y) (act' read from the saved OUTPUT: LeakyReLU y > 0 ? 1 : slope, tanh 1 - y^2) and
+// dense_g_kernel            g = gy * act'(y) (act' read from the saved OUTPUT: LeakyReLU y > 0 ? 1 : slope, ReLU y > 0 ? 1 : 0,
+//   tanh 1 - y^2) and
 //   gb = beta gb + colsum(g): 16 columns x 16 row groups per workgroup, rows in ascending order inside a group, the groups in
 //   order through LDS.
 // dense_gw_kernel           gw[N, K] = beta gw + g^T x: one wave per 16 x 64 tile, the whole (short) reduction over the rows
@@ -30,6 +31,7 @@ constexpr int DN_SLOTS = 256;                                         // workgro
 __device__ __forceinline__ float dn_act(float v, int act, float slope) {
   if (act == LGM_ACT_LRELU) return v > 0.f ? v : v * slope;
   if (act == LGM_ACT_TANH) return tanhf(v);
+  if (act == LGM_ACT_RELU) return v > 0.f ? v : 0.f;
   return v;
 }
 
@@ -37,6 +39,7 @@ __device__ __forceinline__ float dn_dact(float y, int act, float slope) {
 #pragma clang fp contract(off)
   if (act == LGM_ACT_LRELU) return y > 0.f ? 1.f : slope;
   if (act == LGM_ACT_TANH) return 1.f - y * y;
+  if (act == LGM_ACT_RELU) return y > 0.f ? 1.f : 0.f;
   return 1.f;
 }
 
@@ -417,7 +420,7 @@ int launch_gw(const char* who, const float* g, long g_pitch, const float* x, lon
   return LGM_OK;
 }
 
-bool act_ok(int act) { return act == LGM_ACT_NONE || act == LGM_ACT_LRELU || act == LGM_ACT_TANH; }
+bool act_ok(int act) { return act == LGM_ACT_NONE || act == LGM_ACT_LRELU || act == LGM_ACT_TANH || act == LGM_ACT_RELU; }
 constexpr int DN_MAX_DIM = 1 << 20;
 
 }  // namespace
@@ -436,7 +439,7 @@ extern "C" int lgm_dense_fwd(const float* x, int64_t x_pitch, const float* w, co
   LGM_REQUIRE(B >= 1 && K >= 1 && N >= 1 && B <= DN_MAX_DIM && K <= DN_MAX_DIM && N <= DN_MAX_DIM, "dense_fwd: B, K, N >= 1 required, got %d %d %d", B, K, N);
   LGM_REQUIRE(x_pitch >= K && y_pitch >= r4(N), "dense_fwd: pitches below the channel counts (x %ld < %d or y %ld < %d)",
               (long)x_pitch, K, (long)y_pitch, r4(N));
-  LGM_REQUIRE(act_ok(act), "dense_fwd: act must be none, LeakyReLU or tanh, got %d", act);
+  LGM_REQUIRE(act_ok(act), "dense_fwd: act must be none, ReLU, LeakyReLU or tanh, got %d", act);
   LGM_REQUIRE(lgm_aligned16(w), "dense_fwd: 16-byte aligned weights required");
   LGM_REQUIRE((const void*)y != (const void*)x, "dense_fwd: y must not alias x");
   const int64_t need = gemm_workspace(B, N, K);
@@ -456,7 +459,7 @@ extern "C" int lgm_dense_bwd(const float* gy, int64_t gy_pitch, const float* y, 
                              float* gb, float beta, void* workspace, int64_t workspace_bytes, void* stream) {
   LGM_REQUIRE(gy && x && gw && workspace, "dense_bwd: gy, x, gw and a workspace required");
   LGM_REQUIRE(B >= 1 && K >= 1 && N >= 1 && B <= DN_MAX_DIM && K <= DN_MAX_DIM && N <= DN_MAX_DIM, "dense_bwd: B, K, N >= 1 required, got %d %d %d", B, K, N);
-  LGM_REQUIRE(act_ok(act), "dense_bwd: act must be none, LeakyReLU or tanh, got %d", act);
+  LGM_REQUIRE(act_ok(act), "dense_bwd: act must be none, ReLU, LeakyReLU or tanh, got %d", act);
   LGM_REQUIRE(act == LGM_ACT_NONE || y, "dense_bwd: the saved output y is required with an activation");
   LGM_REQUIRE(gy_pitch >= N && x_pitch >= K && (!y || y_pitch >= N), "dense_bwd: pitches below the channel counts");
   LGM_REQUIRE(!gx || (wt && lgm_aligned16(wt) && gx_pitch >= r4(K)),
@@ -484,7 +487,7 @@ extern "C" int lgm_dense_dgrad(const float* gy, int64_t gy_pitch, const float* y
                                int64_t workspace_bytes, void* stream) {
   LGM_REQUIRE(gy && gx && wt && workspace, "dense_dgrad: gy, gx, wt and a workspace required");
   LGM_REQUIRE(B >= 1 && K >= 1 && N >= 1 && B <= DN_MAX_DIM && K <= DN_MAX_DIM && N <= DN_MAX_DIM, "dense_dgrad: B, K, N >= 1 required, got %d %d %d", B, K, N);
-  LGM_REQUIRE(act_ok(act), "dense_dgrad: act must be none, LeakyReLU or tanh, got %d", act);
+  LGM_REQUIRE(act_ok(act), "dense_dgrad: act must be none, ReLU, LeakyReLU or tanh, got %d", act);
   LGM_REQUIRE(act == LGM_ACT_NONE || y, "dense_dgrad: the saved output y is required with an activation");
   LGM_REQUIRE(gy_pitch >= N && (!y || y_pitch >= N), "dense_dgrad: pitches below the channel count %d", N);
   LGM_REQUIRE(lgm_aligned16(wt) && gx_pitch >= r4(K),

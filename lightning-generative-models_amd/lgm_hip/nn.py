@@ -383,6 +383,13 @@ class Linear(nn.Module):
     # profiles/r23_vae_bench.json; the tests run both.
     fwd_route = "dense"
     bwd_route = "dense"
+    # what the 1x1 dispatcher has an epilogue and a backward mask for; a tanh layer runs on the dense kernels under either route
+    _GENERIC_ACTS = (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LRELU)
+    _ACTS = _GENERIC_ACTS + (ops.ACT_TANH,)
+
+    def _check_act(self, act, route):
+        if act not in self._ACTS:
+            raise ValueError(f"Linear on the {route!r} route: act must be none, ReLU, LeakyReLU or tanh, got {act}")
 
     @staticmethod
     def _as_map(t, C):
@@ -394,12 +401,13 @@ class Linear(nn.Module):
         return t.as_strided((t.shape[0], 1, 1, Cp), (p, p, p, 1))
 
     def fwd(self, x, act=0, slope=0.0, out=None):
-        """y [B, r4(cout)] = act(x W^T + b), act in {none, LeakyReLU(slope), tanh} applied by the kernel's epilogue.
+        """y [B, r4(cout)] = act(x W^T + b), act in {none, ReLU, LeakyReLU(slope), tanh} applied by the kernel's epilogue.
         x [B, >= cin]: any row pitch and alignment (the flattened image batch is passed as it is)."""
+        self._check_act(act, self.fwd_route)
         fp = _flat(self.weight)
         y = out if out is not None else ops.new((x.shape[0], _r4(self.cout)), x)
         bias = fp.ptr(self.bias) if self.bias is not None else None
-        x4 = self._as_map(x, self.cin) if self.fwd_route == "generic" and act in (ops.ACT_NONE, ops.ACT_LRELU) else None
+        x4 = self._as_map(x, self.cin) if self.fwd_route == "generic" and act in self._GENERIC_ACTS else None
         if x4 is not None:
             ops.conv_xy(self.geom(x.shape[0]), x4, fp.ptr(self.weight), bias, None, self._as_map(y, self.cout),
                         post=ops.make_post(act, slope))
@@ -409,6 +417,7 @@ class Linear(nn.Module):
     def bwd(self, gc: GradCtx, x, y, gy, act=0, slope=0.0, need_gx=True):
         """gW, gb into the flat gradients; returns gx [B, r4(cin)] (None without need_gx).  ``y`` is the saved OUTPUT of
         fwd: the activation's derivative is read from it, no mask is kept."""
+        self._check_act(act, self.bwd_route)
         fp = gc.flat
         bw = gc.beta(self.weight)
         gb = None
@@ -419,11 +428,11 @@ class Linear(nn.Module):
         wt = fp.tptr(self.weight) if need_gx else None
         if need_gx and wt is None:
             raise RuntimeError("Linear.bwd needs the transposed weight copy: build the GradCtx with transposed=True")
-        x4 = self._as_map(x, self.cin) if self.bwd_route == "generic" and act in (ops.ACT_NONE, ops.ACT_LRELU) else None
+        x4 = self._as_map(x, self.cin) if self.bwd_route == "generic" and act in self._GENERIC_ACTS else None
         g4 = self._as_map(gy, self.cout) if x4 is not None else None
         if g4 is not None:
             geom = self.geom(x.shape[0])
-            if act != ops.ACT_NONE:               # g = gy * act'(y): LeakyReLU keeps the sign, so y stands in for its input
+            if act != ops.ACT_NONE:               # g = gy * act'(y): (Leaky)ReLU keeps the sign, so y stands in for its input
                 g = ops.new((x.shape[0], _r4(self.cout)), gy)
                 g4 = self._as_map(g, self.cout)
                 ops.act_bwd(self._as_map(y, self.cout), None, self._as_map(gy, self.cout), g4, False, act, slope)
@@ -439,10 +448,11 @@ class Linear(nn.Module):
         """gx [B, r4(cin)] = (gy * act'(y)) W alone - no parameter gradients: the sweep through a network that is not being
         updated (a GAN's discriminator under the generator's loss).  The caller keeps the transposed weight copy current
         (FlatParams.refresh_transposed)."""
+        self._check_act(act, self.bwd_route)
         fp = _flat(self.weight)
         B = gy.shape[0]
         gx = ops.new((B, _r4(self.cin)), gy)
-        g4 = self._as_map(gy, self.cout) if self.bwd_route == "generic" and act in (ops.ACT_NONE, ops.ACT_LRELU) else None
+        g4 = self._as_map(gy, self.cout) if self.bwd_route == "generic" and act in self._GENERIC_ACTS else None
         if g4 is not None:
             if act != ops.ACT_NONE:
                 g = ops.new((B, _r4(self.cout)), gy)

@@ -1769,6 +1769,49 @@ def gan_bce_bwd(gloss, s0, t0: float, f0: float, g0, s1=None, t1: float = 0.0, f
                           t1, f1, _p(g1), 0 if g1 is None else pitch(g1), s0.shape[0], gloss.data_ptr(), stream())
 
 
+# ----------------------------------------------------------------------------------------
+# the denoising autoencoder's corruption, tanh + squared error and loss (csrc/dae.hip)
+# ----------------------------------------------------------------------------------------
+DAE_MASK_MODES = {"salt_and_pepper": 0, "masking": 1}
+
+
+def dae_corrupt(x, noise, level: float, out):
+    """out [B, >= r4(D)] = fl(x + fl(noise * level)) over x, noise [B, D] (any pitch and alignment)"""
+    B, D = x.shape
+    assert noise.shape == (B, D) and out.shape[0] == B and x.dtype == noise.dtype == out.dtype == torch.float32
+    lib().lgm_dae_corrupt(x.data_ptr(), pitch(x), noise.data_ptr(), pitch(noise), level, B, D, out.data_ptr(), pitch(out),
+                          stream())
+    return out
+
+
+def dae_mask_threshold(mode: str, level: float) -> int:
+    return int(lib().lgm_dae_mask_threshold(DAE_MASK_MODES[mode], level))
+
+
+def dae_corrupt_mask(x, key, mode: str, level: float, out):
+    """salt-and-pepper / masking noise over x [B, D] from Philox words under ``key`` (device int64 [1], read by the kernel)"""
+    B, D = x.shape
+    assert key.dtype == torch.int64 and key.numel() == 1 and key.device == x.device
+    assert out.shape[0] == B and x.dtype == out.dtype == torch.float32
+    lib().lgm_dae_corrupt_mask(x.data_ptr(), pitch(x), key.data_ptr(), DAE_MASK_MODES[mode], level, B, D, out.data_ptr(),
+                               pitch(out), stream())
+    return out
+
+
+def dae_tanh_mse_fwd(pre, x, D: int, xh, row_part):
+    lib().lgm_dae_tanh_mse_fwd(pre.data_ptr(), pitch(pre), x.data_ptr(), pitch(x), pre.shape[0], D, xh.data_ptr(), pitch(xh),
+                               row_part.data_ptr(), stream())
+
+
+def dae_tanh_mse_bwd(xh, x, gloss, D: int, gpre):
+    lib().lgm_dae_tanh_mse_bwd(xh.data_ptr(), pitch(xh), x.data_ptr(), pitch(x), gloss.data_ptr(), xh.shape[0], D,
+                               gpre.data_ptr(), pitch(gpre), stream())
+
+
+def dae_loss(row_part, D: int, vals):
+    lib().lgm_dae_loss(row_part.data_ptr(), row_part.numel(), D, vals.data_ptr(), stream())
+
+
 from ._lib import on_selection_change as _on_selection_change  # noqa: E402
 
 _on_selection_change(clear_plan_caches)
