@@ -1484,6 +1484,33 @@ int lgm_dae_tanh_mse_bwd(const float* xh, int64_t xh_pitch, const float* x, int6
                          float* gpre, int64_t gpre_pitch, void* stream);
 int lgm_dae_loss(const float* row_part, int B, int D, float* vals, void* stream);
 
+/* ---- The NICE flow: additive coupling, scaling layer, log-likelihood (csrc/nice.hip; reference flow/nice.py) ---------------
+ * The coupling nets' Linear layers are lgm_dense_fwd / _bwd with LGM_ACT_LRELU; their conditioning half and the gradient
+ * of the shifted half are pitched views of the state buffers.  Activations as in the dense section: row-major [B, pitch]
+ * float32; an output has pitch >= round_up(D, 4) and its pad lanes are written +0; an input needs pitch >= D, may start at
+ * any 4-byte address, and its pad lanes are never read.  16-byte accesses where every operand's base, pitch and lane offset
+ * allow them, guarded scalar ones otherwise: the same bits.  No atomics; every sum runs in a fixed order that depends on
+ * (B, D) alone; no product is contracted into a sum.  1 <= B, D <= 2^20 with B round_up(D, 4) <= 2^31.  rc < 0 before any
+ * launch on a null pointer, B or D out of that range, a slice outside [0, D), a pitch below its lane count, or an output
+ * whose span of B rows shares a byte with an input's span (lgm_nice_couple alone accepts out == x with equal pitches).
+ * lgm_nice_couple     out[b][d] = fl(x[b][d] + sign t[b][d - off]) for d in [off, off + n), x[b][d]'s bits elsewhere;
+ *   sign is +1 or -1; one rounding.  The forward, the inverse (sign = -1) and the backward (g[:, cond] += gx, in place).
+ * lgm_nice_scale_fwd  z = fl(h expf(reverse ? -log_scale[d] : log_scale[d])), row_part[b] = sum_d z^2: a thread adds the
+ *   elements of quads t, t + 256, .. in ascending d, then a fixed tree over the workgroup.  row_part may be NULL (the inverse).
+ * lgm_nice_loss       one wave.  vals3 = (loss, mean_ll, sum_d log_scale[d]), mean_ll = (-0.5 sum_b row_part[b]) / B -
+ *   fl(0.5 D log 2 pi); loss = -(mean_ll + sum) with exact, -(mean_ll - sum) (the reference's sign) without.
+ * lgm_nice_scale_bwd  c = gloss[0] / B (gloss on the device): gh = (c z) expf(log_scale[d]);
+ *   gls[d] = beta gls[d] + (sum_b (c z[b][d]) z[b][d] + (exact ? -gloss[0] : gloss[0])), b ascending from 0, any B; beta = 0
+ *   overwrites.  gls holds D floats; nothing is written beyond them.
+ * ------------------------------------------------------------------------------------- */
+int lgm_nice_couple(const float* x, int64_t x_pitch, const float* t, int64_t t_pitch, int B, int D, int off, int n, int sign,
+                    float* out, int64_t out_pitch, void* stream);
+int lgm_nice_scale_fwd(const float* h, int64_t h_pitch, const float* log_scale, int B, int D, int reverse, float* z,
+                       int64_t z_pitch, float* row_part, void* stream);
+int lgm_nice_loss(const float* row_part, const float* log_scale, int B, int D, int exact, float* vals3, void* stream);
+int lgm_nice_scale_bwd(const float* z, int64_t z_pitch, const float* log_scale, const float* gloss, int B, int D, int exact,
+                       float* gh, int64_t gh_pitch, float* gls, float beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

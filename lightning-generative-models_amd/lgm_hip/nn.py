@@ -400,23 +400,27 @@ class Linear(nn.Module):
             return None
         return t.as_strided((t.shape[0], 1, 1, Cp), (p, p, p, 1))
 
-    def fwd(self, x, act=0, slope=0.0, out=None):
+    def fwd(self, x, act=0, slope=0.0, out=None, x_sliced=False):
         """y [B, r4(cout)] = act(x W^T + b), act in {none, ReLU, LeakyReLU(slope), tanh} applied by the kernel's epilogue.
-        x [B, >= cin]: any row pitch and alignment (the flattened image batch is passed as it is)."""
+        x [B, >= cin]: any row pitch and alignment (the flattened image batch is passed as it is).  ``x_sliced``: x is a lane
+        slice of a wider buffer, so the lanes after cin hold other data, not zeros - the generic route, which reads whole
+        quads, takes it only when cin is a multiple of 4."""
         self._check_act(act, self.fwd_route)
         fp = _flat(self.weight)
         y = out if out is not None else ops.new((x.shape[0], _r4(self.cout)), x)
         bias = fp.ptr(self.bias) if self.bias is not None else None
-        x4 = self._as_map(x, self.cin) if self.fwd_route == "generic" and act in self._GENERIC_ACTS else None
+        generic = self.fwd_route == "generic" and act in self._GENERIC_ACTS and not (x_sliced and self.cin % 4)
+        x4 = self._as_map(x, self.cin) if generic else None
         if x4 is not None:
             ops.conv_xy(self.geom(x.shape[0]), x4, fp.ptr(self.weight), bias, None, self._as_map(y, self.cout),
                         post=ops.make_post(act, slope))
             return y
         return ops.dense_fwd(x, fp.ptr(self.weight), bias, self.cin, self.cout, y, act, slope)
 
-    def bwd(self, gc: GradCtx, x, y, gy, act=0, slope=0.0, need_gx=True):
+    def bwd(self, gc: GradCtx, x, y, gy, act=0, slope=0.0, need_gx=True, x_sliced=False, gy_sliced=False):
         """gW, gb into the flat gradients; returns gx [B, r4(cin)] (None without need_gx).  ``y`` is the saved OUTPUT of
-        fwd: the activation's derivative is read from it, no mask is kept."""
+        fwd: the activation's derivative is read from it, no mask is kept.  ``x_sliced`` / ``gy_sliced``: as in ``fwd``, for
+        x (cin lanes) and gy (cout lanes)."""
         self._check_act(act, self.bwd_route)
         fp = gc.flat
         bw = gc.beta(self.weight)
@@ -428,7 +432,9 @@ class Linear(nn.Module):
         wt = fp.tptr(self.weight) if need_gx else None
         if need_gx and wt is None:
             raise RuntimeError("Linear.bwd needs the transposed weight copy: build the GradCtx with transposed=True")
-        x4 = self._as_map(x, self.cin) if self.bwd_route == "generic" and act in self._GENERIC_ACTS else None
+        generic = self.bwd_route == "generic" and act in self._GENERIC_ACTS and not (x_sliced and self.cin % 4) and \
+            not (gy_sliced and self.cout % 4)
+        x4 = self._as_map(x, self.cin) if generic else None
         g4 = self._as_map(gy, self.cout) if x4 is not None else None
         if g4 is not None:
             geom = self.geom(x.shape[0])

@@ -1812,6 +1812,37 @@ def dae_loss(row_part, D: int, vals):
     lib().lgm_dae_loss(row_part.data_ptr(), row_part.numel(), D, vals.data_ptr(), stream())
 
 
+# ----------------------------------------------------------------------------------------
+# the NICE flow's additive coupling, scaling layer and log-likelihood (csrc/nice.hip)
+# ----------------------------------------------------------------------------------------
+def nice_couple(x, t, off: int, sign: int, out):
+    """out [B, >= r4(D)] = x [B, D] with lanes [off, off + n) shifted by sign * t [B, n]; ``out`` may be ``x`` itself"""
+    B, D = x.shape
+    assert t.shape[0] == B and out.shape[0] == B and x.dtype == t.dtype == out.dtype == torch.float32
+    lib().lgm_nice_couple(x.data_ptr(), pitch(x), t.data_ptr(), pitch(t), B, D, off, t.shape[1], sign, out.data_ptr(), pitch(out),
+                          stream())
+    return out
+
+
+def nice_scale_fwd(h, ls_ptr: int, D: int, reverse: bool, z, row_part=None):
+    """z [B, >= r4(D)] = h exp(+-log_scale); row_part [B] = sum_d z^2 where wanted"""
+    lib().lgm_nice_scale_fwd(h.data_ptr(), pitch(h), ls_ptr, h.shape[0], D, 1 if reverse else 0, z.data_ptr(), pitch(z),
+                             _p(row_part), stream())
+    return z
+
+
+def nice_loss(row_part, ls_ptr: int, D: int, exact: bool, vals3):
+    """vals3 = (loss, mean log-likelihood under N(0, I), sum of log_scale)"""
+    lib().lgm_nice_loss(row_part.data_ptr(), ls_ptr, row_part.numel(), D, 1 if exact else 0, vals3.data_ptr(), stream())
+    return vals3
+
+
+def nice_scale_bwd(z, ls_ptr: int, gloss, D: int, exact: bool, gh, gls_ptr: int, beta: float):
+    lib().lgm_nice_scale_bwd(z.data_ptr(), pitch(z), ls_ptr, gloss.data_ptr(), z.shape[0], D, 1 if exact else 0, gh.data_ptr(),
+                             pitch(gh), gls_ptr, beta, stream())
+    return gh
+
+
 from ._lib import on_selection_change as _on_selection_change  # noqa: E402
 
 _on_selection_change(clear_plan_caches)
